@@ -7,11 +7,14 @@ GENCODE-like transcriptome (58 k genes -> ~202 k transcripts, seed 7), K = 24, e
 config's 100 M reads at N = 1. Multi-GPU: one process per GPU, reads sharded by rank (weak scaling: every rank maps its own
 --steps x --batch reads), index replicated, one RCCL all-reduce of the class-count table at the end of the timed region.
 
-The default N = 1 run also times BASELINE.json's error-read configuration (config 5: K = 31, 1 % substitutions; the same
-transcriptome, its own index) for a few steps and reports it under the extra key `config5` (never `value`).
+A plain run sets up, warms up, times the steps, writes the last step's outputs if --dump-outputs is given, and prints the result
+line. Everything else is measured or checked only with --full: the parity sample against the oracle, the roofline and per-rank
+figures, the `cpu_baseline` leg, the host-to-host, FASTQ-text and per-call legs, and (N = 1) the other workloads under extra keys
+(never `value`): BASELINE.json's error-read configuration (config 5: K = 31, 1 % substitutions; the same transcriptome, its own
+index), config3r, config3k64 and config 2.
 
-The oracle (oracle/pa_oracle.c, a CPU port of the reference path) is used here only as (1) the parity checker of a sample and
-(2) the `cpu_baseline` leg; it is never part of the measured GPU path.
+The oracle (oracle/pa_oracle.c, a CPU port of the reference path) is used here only under --full, as (1) the parity checker of a
+sample and (2) the `cpu_baseline` leg; it is never part of the measured GPU path.
 """
 from __future__ import annotations
 
@@ -290,6 +293,48 @@ def roofline_of(run, ctr, stage_ms, step_ms):
             "algorithmic_bytes_per_read": bytes_per_read, "reads_per_launch": B, "requests": requests}
 
 
+DUMP_SAMPLE_READS = 1 << 18
+DUMP_SAMPLE_SEED = 20240613
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(env, run, out_dir):
+    """What pa_map_count_batch_device handed its caller after the timed steps, as float64 .npy files in out_dir (rank 0's reads):
+    counts = the class-count table accumulated over the timed steps; for a fixed, seeded sample of the last step's reads (sample_read =
+    their positions in the batch) their records (coverage, mismatches, mapped) and their classes as ids (class_offsets[n+1] + class_ids,
+    resolved from the index or the arena, so the arena's layout does not matter). The sample shrinks to its first reads if the ids
+    would push the files past DUMP_MAX_BYTES."""
+    pa, torch, np = env["pa"], env["torch"], env["np"]
+    os.makedirs(out_dir, exist_ok=True)
+    B = run.B
+    counts = run.counts.cpu().numpy().astype(np.float64)
+    n = min(B, DUMP_SAMPLE_READS)
+    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(B, n, replace=False)) if n < B else np.arange(B)
+    d_idx = torch.from_numpy(idx.astype(np.int64)).to(run.results.device)
+    res = run.results.view(B, 4).index_select(0, d_idx).cpu().numpy().view(np.uint32).reshape(-1).view(pa.RESULT_DTYPE).copy()
+    lens = res["class_len"].astype(np.int64)
+    budget = (DUMP_MAX_BYTES - counts.nbytes) // 8 - 5 * n - 1     # float64 entries left for the class ids
+    keep = int(np.searchsorted(np.cumsum(lens), budget, side="right"))
+    idx, res, lens = idx[:keep], res[:keep], lens[:keep]
+    # the arena ranges of the sampled reads whose class is no index class, gathered on the device into a small arena of their own
+    in_arena = ((res["class_off"] & pa.PA_CLASS_REF) == 0) & (lens > 0)
+    a_lens = np.where(in_arena, lens, 0)
+    a_new = np.concatenate([[0], np.cumsum(a_lens)])
+    total = int(a_new[-1])
+    pos = np.repeat(res["class_off"].astype(np.int64), a_lens) + np.arange(total) - np.repeat(a_new[:-1], a_lens)
+    if total and int(pos.max()) >= run.arena.numel():
+        raise SystemExit("--dump-outputs: a record of the last step points past the arena (%d >= %d)" % (int(pos.max()), run.arena.numel()))
+    sub = (run.arena.index_select(0, torch.from_numpy(pos).to(run.arena.device)).cpu().numpy().view(np.uint32) if total
+            else np.zeros(0, np.uint32))
+    res["class_off"] = np.where(in_arena, a_new[:-1], res["class_off"]).astype(np.uint32)
+    coff, cids = pa.gather_classes(res, sub, run.host)
+    arrays = {"counts": counts, "sample_read": idx, "coverage": res["coverage"], "mismatches": res["mismatches"] & 0x7FFFFFFF,
+              "mapped": res["mismatches"] >> 31, "class_offsets": coff, "class_ids": cids}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+    log("outputs of the last step: %d count-table entries, %d of %d reads, %d class ids -> %s" % (len(counts), keep, B, len(cids), out_dir))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -298,12 +343,16 @@ def main() -> None:
     ap.add_argument("--batch", type=int, default=0, help="reads per step per GPU (default: the batch BASELINE.json quotes for the workload: "
                     "100 M reads for configs 3/5, 10 M for config 2)")
     ap.add_argument("--workload", default="config3", choices=sorted(WORKLOADS))
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target duration of the CPU baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the host-to-host leg (pinned tiles -> records on the host), an extra report at N=1")
-    ap.add_argument("--no-ingest", action="store_true", help="skip the FASTQ-text leg (pa_process_reads / pa_record_stream_* on a bounded sample), an extra report at N=1")
-    ap.add_argument("--ingest-reads", type=int, default=8_000_000, help="reads of the FASTQ-text leg")
-    ap.add_argument("--no-config5", action="store_true", help="skip the extra config-5 measurement of the default N=1 run")
+    ap.add_argument("--full", action="store_true", help="also run the checks and extra reports after the timed steps: parity sample, roofline, "
+                    "per-rank figures, CPU baseline, host-to-host / FASTQ-text / per-call legs and the other workloads (the --no-* options below skip some)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the timed path returned in its last step as DIR/<name>.npy "
+                    "(float64): the class-count table and, for a fixed seeded sample of the step's reads, their records and class ids")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target duration of the CPU baseline sample (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="(--full) skip the host-to-host leg (pinned tiles -> records on the host), an extra report at N=1")
+    ap.add_argument("--no-ingest", action="store_true", help="(--full) skip the FASTQ-text leg (pa_process_reads / pa_record_stream_* on a bounded sample), an extra report at N=1")
+    ap.add_argument("--ingest-reads", type=int, default=8_000_000, help="reads of the FASTQ-text leg (--full)")
+    ap.add_argument("--no-config5", action="store_true", help="(--full) skip the other workloads of the N=1 run (config 5, config3r, config3k64, config 2)")
     ap.add_argument("--separate-count", action="store_true", help="class counts from the stored records (pa_counts_accumulate_device) instead of the key streams")
     ap.add_argument("--index-cache", default="", help="optional path to save/load the host index container")
     ap.add_argument("--cpu-build", action="store_true", help="build the index with the CPU builder instead of the GPU builder")
@@ -385,21 +434,23 @@ def main() -> None:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
 
+    total_reads = K * B * n_gpus
+    value = total_reads / elapsed
+    counts_host = run.counts.cpu().numpy()
+    assert os.environ.get("PA_MAP_ABLATE") or int(counts_host.sum()) == total_reads, "count table does not add up: %d vs %d" % (int(counts_host.sum()), total_reads)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(env, run, args.dump_outputs)
+
     # every rank's own kernel times travel to rank 0 (north_star: reads/s AND HBM GB/s at every N): mean mapping-kernel, resolve,
     # count and whole-step device time per rank
     n_t = max(len(map_ms), 1)
     mine = [sum(m[0] for m in map_ms) / n_t, sum(m[1] for m in map_ms) / n_t, sum(m[2] for m in map_ms) / n_t, sum(step_ms) / max(len(step_ms), 1)]
     per_rank = [mine]
-    if dist is not None:
+    if dist is not None and args.full:
         t = torch.tensor(mine, dtype=torch.float64, device=dev if backend == "nccl" else "cpu")   # (the gloo rehearsal gathers on the host)
         gathered = [torch.zeros_like(t) for _ in range(world)]
         dist.all_gather(gathered, t)
         per_rank = [g.tolist() for g in gathered]
-
-    total_reads = K * B * n_gpus
-    value = total_reads / elapsed
-    counts_host = run.counts.cpu().numpy()
-    assert os.environ.get("PA_MAP_ABLATE") or int(counts_host.sum()) == total_reads, "count table does not add up: %d vs %d" % (int(counts_host.sum()), total_reads)
 
     st, k, read_len = run.st, wl["k"], wl["read_len"]
     out = {
@@ -417,7 +468,7 @@ def main() -> None:
     # ---- SURVEY §8d's wall-clock leg (extra keys, never `value`): the same batch from PINNED HOST tiles to per-read records +
     # count table back on the host. Chunks alternate between streams of the one index handle: H2D of chunk i+1 and D2H
     # of chunk i-1 overlap the kernel of chunk i; the link (PCIe Gen5 x16, 63 GB/s per direction), not the kernel, bounds it.
-    if n_gpus == 1 and not args.no_e2e:
+    if args.full and n_gpus == 1 and not args.no_e2e:
         try:
             out.update(host_to_host_leg(env, run))
         except Exception as e:   # the leg is a report, not the benchmark: never lose the bench line over it
@@ -426,21 +477,21 @@ def main() -> None:
 
     # ---- the drop-in entry points on this round's code, extra keys: FASTQ text -> Debug tuples through
     # pa_process_reads (a path) and pa_record_stream_* (records pushed by the caller), with the host stages' seconds ----
-    if n_gpus == 1 and rank == 0 and not args.no_ingest and args.workload == "config3":
+    if args.full and n_gpus == 1 and rank == 0 and not args.no_ingest and args.workload == "config3":
         try:
             out.update(ingest_leg(env, run, args.ingest_reads))
         except Exception as e:   # an extra report: never lose the bench line over it
             log("ingest leg failed: %r" % (e,))
             out["ingest_error"] = repr(e)
 
-    if n_gpus == 1 and rank == 0 and not args.no_ingest and args.workload == "config3":
+    if args.full and n_gpus == 1 and rank == 0 and not args.no_ingest and args.workload == "config3":
         try:
             out.update(per_call_leg(env, run))
         except Exception as e:   # an extra report: never lose the bench line over it
             log("per-call leg failed: %r" % (e,))
             out["per_call_error"] = repr(e)
 
-    if rank == 0:
+    if args.full and rank == 0:
         # ---- checker + CPU baseline (oracle = C port of the reference path), outside the timed region ----
         ncpu = usable_cpus()
         sample_n = 200_000
@@ -479,7 +530,7 @@ def main() -> None:
     # K = 31, 1 % substitutions), the headline's robustness to real graph structure (config3r: repeat families, low-complexity tracts) and the
     # the other k of the reference's CLI (config3k64: two-word k-mers) and the one index built from real gene structure (config 2: gencode_small)
     # at the headline's 100 M reads per launch
-    if n_gpus == 1 and rank == 0 and args.workload == "config3" and not args.no_config5 and not args.batch:
+    if args.full and n_gpus == 1 and rank == 0 and args.workload == "config3" and not args.no_config5 and not args.batch:
         buffers = run.buffers
         run.aligner = None
         run.host = None

@@ -51,3 +51,53 @@ def test_committed_bench_line_has_the_contract_fields(name):
         assert "index_build_s" in line["config"] and "kernel_ms_steps" in r and len(r["kernel_ms_steps"]) == line["steps"]
         if "config3" in name:
             assert line["e2e_reads_per_s"] > 0 and 0 < line["e2e_pcie_frac"] < 1
+
+
+def test_dump_outputs_resolves_every_class_and_repeats(small_index, tmp_path, monkeypatch):
+    """bench.dump_outputs on hand-made records (CPU tensors in place of the device buffers): a seeded sample of the reads, each read's class
+    read back as ids whether it is an index class (by reference) or a range of the arena, and the same files from a second call"""
+    from types import SimpleNamespace
+
+    import numpy as np
+    import torch
+    import helpers
+    pa = helpers.pa
+    host = small_index(24)
+    a = host.arrays()
+    off, ids, nc = a["ec_offset"].astype(np.int64), a["ec_ids"], int(a["num_classes"])
+    rng = np.random.default_rng(3)
+    B = 60
+    arena = rng.integers(0, 5000, 700).astype(np.uint32)
+    res = np.zeros(B, pa.RESULT_DTYPE)
+    want = []
+    for i in range(B):
+        if i % 3 == 0:                                        # unmapped
+            want.append(np.zeros(0, np.uint32))
+            continue
+        if i % 3 == 1:                                        # an index class, returned by reference
+            c = int(rng.integers(0, nc))
+            res[i]["class_off"], res[i]["class_len"] = pa.PA_CLASS_REF | c, off[c + 1] - off[c]
+            want.append(ids[off[c]:off[c + 1]])
+        else:                                                 # an intersection: ids in the arena
+            o, n = int(rng.integers(0, 680)), int(rng.integers(1, 20))
+            res[i]["class_off"], res[i]["class_len"] = o, n
+            want.append(arena[o:o + n])
+        res[i]["coverage"], res[i]["mismatches"] = 100 + i, pa.PA_MAPPED_BIT | (i % 3)
+    run = SimpleNamespace(B=B, host=host, counts=torch.arange(nc + 3, dtype=torch.int64),
+                          results=torch.from_numpy(res.view(np.int32).copy()), arena=torch.from_numpy(arena.view(np.int32).copy()))
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_READS", 25)
+    env = dict(pa=pa, torch=torch, np=np)
+    bench.dump_outputs(env, run, str(tmp_path / "a"))
+    bench.dump_outputs(env, run, str(tmp_path / "b"))
+    names = ("counts", "sample_read", "coverage", "mismatches", "mapped", "class_offsets", "class_ids")
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    for n in names:
+        assert got[n].dtype == np.float64 and np.array_equal(got[n], np.load(tmp_path / "b" / (n + ".npy"))), n
+    assert np.array_equal(got["counts"], np.arange(nc + 3))
+    sample = got["sample_read"].astype(np.int64)
+    assert len(sample) == 25 and np.all(np.diff(sample) > 0) and 0 <= sample[0] and sample[-1] < B
+    coff = got["class_offsets"].astype(np.int64)
+    assert len(coff) == 26 and coff[-1] == len(got["class_ids"])
+    for j, r in enumerate(sample):
+        assert np.array_equal(got["class_ids"][coff[j]:coff[j + 1]], want[r].astype(np.float64)), r
+        assert got["coverage"][j] == res[r]["coverage"] and got["mapped"][j] == (r % 3 != 0) and got["mismatches"][j] == r % 3

@@ -53,7 +53,7 @@ def test_bench_under_torchrun_reduces_through_the_product(ranks):
     not the torch.distributed spare) and count every read of every rank"""
     if _gpus() < ranks:
         pytest.skip("needs %d GPUs" % ranks)
-    out = _torchrun(ranks, helpers.ROOT / "bench.py", "--gpus", ranks, "--steps", 2, "--warmup", 1, "--workload", "config2", "--batch", 2_000_000)
+    out = _torchrun(ranks, helpers.ROOT / "bench.py", "--gpus", ranks, "--steps", 2, "--warmup", 1, "--workload", "config2", "--batch", 2_000_000, "--full")
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == ranks and line["rccl_ranks"] == ranks and "pa_counts_allreduce" in line["config"]["parallelism"]
@@ -66,7 +66,7 @@ def test_bench_two_ranks_on_one_gpu_rehearsal():
     gather of every rank's kernel times and the whole-job value are the code the driver's N > 1 runs take"""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", PA_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           str(helpers.ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "config2", "--batch", "2000000"]
+           str(helpers.ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "config2", "--batch", "2000000", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=str(helpers.ROOT))
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

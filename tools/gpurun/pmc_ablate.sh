@@ -1,6 +1,6 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/abl; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
 for a in 0 2 1; do
-  B="env PA_MAP_ABLATE=$a python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-e2e"
+  B="env PA_MAP_ABLATE=$a python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-e2e"
   timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/f$a -- $B > $O/f$a.log 2>&1
   timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/w$a -- $B > $O/w$a.log 2>&1
 done

@@ -8,7 +8,7 @@ rocprofv3 --list-avail 2>/dev/null | grep -o "\b\(TA\|TCP\|TD\|SQ\|TCC\|GRBM\)_[
 envs=""; flags=""
 for tok in "$@"; do case "$tok" in --*) flags="$flags $tok";; *=*) envs="$envs $tok";; *) flags="$flags $tok";; esac; done
 envs=$(echo "$envs" | sed "s#PA_PRODUCT_SO=tools#PA_PRODUCT_SO=$R/tools#")
-B="env $envs python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-e2e --no-config5 $flags"
+B="env $envs python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-e2e --no-config5 $flags"
 run() { name=$1; shift; timeout 600 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $O/$name -- $B > $O/$name.log 2>&1; echo "$name rc=$?"; }
 run pmc_ta1 TA_TA_BUSY_sum TA_BUSY_avr TA_BUSY_max GRBM_GUI_ACTIVE
 #run pmc_ta2 (hangs rocprofv3 on this pool) TA_ADDR_STALLED_BY_TC_CYCLES_sum TA_ADDR_STALLED_BY_TD_CYCLES_sum TA_DATA_STALLED_BY_TC_CYCLES_sum TA_FLAT_READ_WAVEFRONTS_sum

@@ -9,7 +9,7 @@ for wl in $WLS; do
   extra=""
   [ "$wl" = "config2" ] && extra="--batch 100000000"
   cd /tmp && export TMPDIR=/tmp
-  B="python $R/bench.py --workload $wl $extra --steps 5 --warmup 1 --no-cpu-baseline --no-e2e --no-config5 --no-ingest"
+  B="python $R/bench.py --full --workload $wl $extra --steps 5 --warmup 1 --no-cpu-baseline --no-e2e --no-config5 --no-ingest"
   $B > $O/bench.json 2> $O/bench.err; cut -c1-200 $O/bench.json
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- $B > $O/trace.log 2>&1; echo "$wl trace rc=$?"
   run() { name=$1; shift; timeout 600 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $O/$name -- $B > $O/$name.log 2>&1; echo "$wl $name rc=$?"; }

@@ -7,9 +7,9 @@ mkdir -p $O
 cd $R
 python -m pytest tests -m gpu -q 2>&1 | tail -2 > $O/pytest_gpu.txt; cat $O/pytest_gpu.txt
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids | tail -1
-timeout 900 python bench.py --index-cache /tmp/g.idx 2> $O/bench.err > $O/bench.json; cat $O/bench.json | cut -c1-300
+timeout 900 python bench.py --full --index-cache /tmp/g.idx 2> $O/bench.err > $O/bench.json; cat $O/bench.json | cut -c1-300
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --index-cache /tmp/g.idx"
+B="python $R/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --index-cache /tmp/g.idx"
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- $B > $O/trace.log 2>&1; echo "trace rc=$?"
 run() { name=$1; shift; timeout 400 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $O/$name -- $B > $O/$name.log 2>&1; echo "$name rc=$?"; }
 run pmc_fetch FETCH_SIZE

@@ -5,7 +5,7 @@ mkdir -p gpurun_out
 for ratio in 0 0.5; do
   for wl in config3; do
     echo "== $wl ratio $ratio"
-    PA_ANCHOR_RATIO=$ratio PA_PRODUCT_SO=tools/baseline/knobs.so PA_MAP_STATS=1 python bench.py --workload $wl --no-cpu-baseline --no-e2e --no-config5 --no-ingest --steps 3 --warmup 1 2> /tmp/stats.err | python -c "
+    PA_ANCHOR_RATIO=$ratio PA_PRODUCT_SO=tools/baseline/knobs.so PA_MAP_STATS=1 python bench.py --full --workload $wl --no-cpu-baseline --no-e2e --no-config5 --no-ingest --steps 3 --warmup 1 2> /tmp/stats.err | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('value=%.3e ms_step=%.3f kernel_ms=%.3f' % (d['value'], d['ms_per_step'], d['roofline']['kernel_ms']))"
     grep "pa map stats" /tmp/stats.err | sed -n 2p

@@ -8,7 +8,7 @@ python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids | t
 bash tools/gpurun/profile_r05.sh ${tag}_config3 config3
 bash tools/gpurun/profile_r05.sh ${tag}_config5 config5
 python tools/make_latest_pmc.py config3=gpurun_out/${tag}_config3/pmc.txt config5=gpurun_out/${tag}_config5/pmc.txt && cp profiles/latest_pmc.json $O/latest_pmc.json
-timeout 1500 python bench.py 2> $O/bench.err > $O/bench.json; cut -c1-1500 $O/bench.json
+timeout 1500 python bench.py --full 2> $O/bench.err > $O/bench.json; cut -c1-1500 $O/bench.json
 for wl in config5 config2 config3k64; do
-  timeout 900 python bench.py --workload $wl --no-e2e 2> gpurun_out/${tag}_bench_$wl.err > gpurun_out/${tag}_bench_$wl.json; cut -c1-300 gpurun_out/${tag}_bench_$wl.json
+  timeout 900 python bench.py --full --workload $wl --no-e2e 2> $O/bench_$wl.err > $O/bench_$wl.json; cut -c1-300 $O/bench_$wl.json
 done

@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${tag}_insts; mkdir -p $O; cd /tmp; export T
 i=0
 for so in "" "$@"; do
   for wl in config3 config5; do
-    B="env ${so:+PA_PRODUCT_SO=$R/$so} python $R/bench.py --workload $wl --steps 3 --warmup 1 --no-cpu-baseline --no-e2e --no-config5 --no-ingest"
+    B="env ${so:+PA_PRODUCT_SO=$R/$so} python $R/bench.py --full --workload $wl --steps 3 --warmup 1 --no-cpu-baseline --no-e2e --no-config5 --no-ingest"
     timeout 600 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY --output-format csv -d $O/p${i}_$wl -- $B > $O/p${i}_$wl.log 2>&1
     timeout 600 rocprofv3 --kernel-trace --pmc SQ_INSTS SQ_INSTS_BRANCH SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR GRBM_GUI_ACTIVE --output-format csv -d $O/q${i}_$wl -- $B > $O/q${i}_$wl.log 2>&1
     echo "build=${so:-HEAD} $wl" >> $O/index.txt; echo "p${i}_$wl q${i}_$wl" >> $O/index.txt

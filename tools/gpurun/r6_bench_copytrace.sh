@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/bench_copytrace
 rm -rf $O
-rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O -o t -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-config5 --no-e2e > $O.json 2> $O.err
+rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O -o t -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-config5 --no-e2e > $O.json 2> $O.err
 python - <<PY
 import csv, glob, collections
 ks = glob.glob("$O/**/*kernel_trace.csv", recursive=True); cs = glob.glob("$O/**/*memory_copy_trace.csv", recursive=True)

@@ -10,7 +10,7 @@ done
 done
 for pin in "" 1; do
   echo "== bench.py, PA_INGEST_NO_PIN=$pin"
-  PA_INGEST_NO_PIN=$pin PA_VERBOSE=1 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-config5 2> /tmp/err.txt | python -c "
+  PA_INGEST_NO_PIN=$pin PA_VERBOSE=1 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-config5 2> /tmp/err.txt | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ingest']['runs_Mreads_per_s'], d['ingest']['stages'], d['ingest'].get('two_lanes_one_gpu_reads_per_s'), 'e2e', d.get('e2e',{}).get('runs_ms'))"
   grep "windows to" /tmp/err.txt | cut -c1-120

@@ -12,7 +12,7 @@ done
 done
 for one in "" 1 "" 1; do
   echo "== bench.py, PA_INGEST_ONE_STREAM=$one"
-  PA_INGEST_ONE_STREAM=$one python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-config5 --no-e2e 2> /tmp/err.txt | python -c "
+  PA_INGEST_ONE_STREAM=$one python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-config5 --no-e2e 2> /tmp/err.txt | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ingest']['runs_Mreads_per_s'], d['ingest']['stages'], d['ingest'].get('two_lanes_one_gpu_reads_per_s'), d['ingest']['record_stream']['reads_per_s'])"
 done
