@@ -55,17 +55,24 @@ struct LaunchCtx {
     std::mutex mu;
     DevBuf ctl;      // [0..7] arena_top (u64), [8..11] status, [12..15] tile counter, [16..] statistics, [448..455] novel results listed, [456..463] count keys handed out
     DevBuf spill, trace, novel;
-    DevBuf keys, keys_sorted, keys_ctl;   // class-count launches: the waves' key streams (+ one key per deferred read), the keys partitioned by range, histograms / cursors (count_sort.hip)
+    DevBuf keys, keys_sorted, keys_ctl;   // class-count launches: the waves' key streams (+ one key per deferred read), the keys partitioned by bin inside tiles, where the runs lie (count_sort.hip)
     DevBuf defer;                          // reads whose class is looked up by content after the launch (resolve.hip): 32 bytes each, sized for every read
     uint32_t last_grid = 0;
     uint64_t last_arena_cap = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;   // before the map kernel / after it / after the resolve kernel / after the count kernels of the last launch (pa_index_set_timing)
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;   // before the map kernel / after it / after the resolve kernel (on `side`) / after the count kernels of the last launch (pa_index_set_timing)
     bool timed = false;
+    // class-count launches with a partitioned table: pa_resolve_kernel runs on `side` while the caller's stream partitions the map kernel's
+    // keys (fork: the map kernel is done; join: resolve is done). Owned here: it lives and dies with the context of the caller's stream.
+    hipStream_t side = nullptr;
+    hipEvent_t fork = nullptr, join = nullptr;
     void release() {
+        if (side) (void)hipStreamSynchronize(side);
         for (DevBuf* b : {&ctl, &spill, &trace, &novel, &keys, &keys_sorted, &keys_ctl, &defer}) b->release();
-        for (hipEvent_t e : {ev0, ev1, ev2, ev3})
+        for (hipEvent_t e : {ev0, ev1, ev2, ev3, fork, join})
             if (e) (void)hipEventDestroy(e);
-        ev0 = ev1 = ev2 = ev3 = nullptr;
+        ev0 = ev1 = ev2 = ev3 = fork = join = nullptr;
+        if (side) (void)hipStreamDestroy(side);
+        side = nullptr;
         timed = false;
     }
 };
@@ -470,9 +477,11 @@ static int map_launch_locked(pa_index* idx, LaunchCtx* cx, const uint64_t* d_til
     p.defer_cap = defer_cap;
     p.keys_cap = 0;
     uint64_t keys_cap = 0;
-    if (d_counts) {   // the waves' key streams (4.3 bytes per read), one key per deferred read behind them, and the keys partitioned by range (4 bytes per read)
+    if (d_counts) {   // the waves' key streams (4.3 bytes per read), one key per deferred read behind them, and the keys partitioned by bin (2 bytes per key)
         keys_cap = key_stream_capacity(n_reads, grid * (PA_MAP_BLOCK / 64));
-        if ((rc = cx->keys.ensure((keys_cap + defer_cap) * 4)) || (rc = cx->keys_sorted.ensure((n_reads + 64) * 4)) || (rc = cx->keys_ctl.ensure(count_keys_ctl_bytes(counts_len)))) return rc;
+        size_t sorted_bytes = 0, ctl_bytes = 0;
+        count_keys_scratch(counts_len, n_reads, keys_cap, defer_cap, &sorted_bytes, &ctl_bytes);
+        if ((rc = cx->keys.ensure((keys_cap + defer_cap) * 4)) || (rc = cx->keys_sorted.ensure(sorted_bytes)) || (rc = cx->keys_ctl.ensure(ctl_bytes))) return rc;
         p.keys = cx->keys.as<uint32_t>();
         p.keys_top = cx->ctl.as<unsigned long long>() + 57;
         p.keys_cap = keys_cap;
@@ -510,14 +519,35 @@ static int map_launch_locked(pa_index* idx, LaunchCtx* cx, const uint64_t* d_til
     const int e = launch_map_pool(p, grid, lds, stream);
     if (e) return fail(PA_ERR_HIP, "map launch (grid %u, lds %zu): %s", grid, lds, hipGetErrorString((hipError_t)e));
     if (timing) { HIP_TRY(hipEventRecord(cx->ev1, stream)); cx->timed = true; }
+    // resolve and the partition of the map kernel's keys need only the map kernel: with a partitioned table they run side by side
+    // (resolve on cx->side); the partition of the deferred reads' keys, the count kernel and the overflow table wait for both
+    const bool overlap = d_counts && count_keys_partitioned(counts_len, n_reads);
+    hipStream_t rs = stream;
+    if (overlap) {
+        if (!cx->side) {
+            HIP_TRY(hipStreamCreateWithFlags(&cx->side, hipStreamNonBlocking));
+            HIP_TRY(hipEventCreateWithFlags(&cx->fork, hipEventDisableTiming));
+            HIP_TRY(hipEventCreateWithFlags(&cx->join, hipEventDisableTiming));
+        }
+        HIP_TRY(hipEventRecord(cx->fork, stream));
+        HIP_TRY(hipStreamWaitEvent(cx->side, cx->fork, 0));
+        rs = cx->side;
+    }
     {
-        const int e1 = launch_resolve(p, defer_cap, keys_cap, idx->num_cus, stream);
+        const int e1 = launch_resolve(p, defer_cap, keys_cap, idx->num_cus, rs);
         if (e1) return fail(PA_ERR_HIP, "resolve launch: %s", hipGetErrorString((hipError_t)e1));
     }
-    if (timing) HIP_TRY(hipEventRecord(cx->ev2, stream));
+    if (timing) HIP_TRY(hipEventRecord(cx->ev2, rs));
+    if (overlap) {
+        HIP_TRY(hipEventRecord(cx->join, rs));
+        const int e2 = launch_count_keys(p.keys, p.keys_top, keys_cap, p.defer_top, defer_cap, cx->keys_sorted.as<uint32_t>(), cx->keys_ctl.as<uint32_t>(),
+                                         reinterpret_cast<unsigned long long*>(d_counts), counts_len, idx->num_cus, stream, n_reads, 0);
+        if (e2) return fail(PA_ERR_HIP, "count launch: %s", hipGetErrorString((hipError_t)e2));
+        HIP_TRY(hipStreamWaitEvent(stream, cx->join, 0));
+    }
     if (d_counts) {
         const int e2 = launch_count_keys(p.keys, p.keys_top, keys_cap, p.defer_top, defer_cap, cx->keys_sorted.as<uint32_t>(), cx->keys_ctl.as<uint32_t>(),
-                                         reinterpret_cast<unsigned long long*>(d_counts), counts_len, idx->num_cus, stream, n_reads);
+                                         reinterpret_cast<unsigned long long*>(d_counts), counts_len, idx->num_cus, stream, n_reads, 1);
         if (e2) return fail(PA_ERR_HIP, "count launch: %s", hipGetErrorString((hipError_t)e2));
         if (ovf) {
             rc = overflow_after_map(ovf, p.novel_list, p.novel_ctr, p.novel_cap, d_arena, stream);

@@ -72,12 +72,16 @@ uint32_t pool_max_slots();              // slots a wave can schedule
 size_t pool_lds_bytes(uint32_t wpr, uint32_t slots);
 int launch_map_pool(const MapParams& p, uint32_t grid, size_t lds_bytes, hipStream_t stream);
 int pool_kernel_occupancy(size_t lds_bytes, int* blocks_per_cu);
-// count_sort.hip: the key streams of a launch -> counts[counts_len] += (keys partitioned by range, counted in LDS). `sorted` holds
-// n_reads u32 and `ctl` count_keys_ctl_bytes() of scratch; both may be reused once the stream has passed these kernels.
-uint64_t key_stream_capacity(uint64_t n_reads, uint32_t nwaves);
-size_t count_keys_ctl_bytes(uint64_t counts_len);                  // bytes of `ctl`   // u32 entries `keys` must hold for a launch of nwaves waves
+// count_sort.hip: the key streams of a launch -> counts[counts_len] += (keys partitioned by bin inside tiles, counted in LDS). Pass 0
+// partitions the map kernel's chunks [0, *keys_top) and needs only the map kernel (it may run while pa_resolve_kernel appends the
+// deferred reads' keys behind them); pass 1, after resolve, does the rest. `sorted` / `ctl` hold count_keys_scratch() bytes (none
+// when the table is counted without a partition); both may be reused once the stream has passed pass 1.
+uint64_t key_stream_capacity(uint64_t n_reads, uint32_t nwaves);   // u32 entries `keys` must hold for a launch of nwaves waves
+bool count_keys_partitioned(uint64_t counts_len, uint64_t n_reads);  // pass 0 launches anything
+void count_keys_scratch(uint64_t counts_len, uint64_t n_reads, uint64_t keys_cap, uint64_t extra_cap, size_t* sorted_bytes, size_t* ctl_bytes);
 int launch_count_keys(const uint32_t* keys, const unsigned long long* keys_top, uint64_t keys_cap, const unsigned long long* extra_top, uint64_t extra_cap,
-                      uint32_t* sorted, uint32_t* ctl, unsigned long long* counts, uint64_t counts_len, int num_cus, hipStream_t stream, uint64_t n_reads);
+                      uint32_t* sorted, uint32_t* ctl, unsigned long long* counts, uint64_t counts_len, int num_cus, hipStream_t stream, uint64_t n_reads,
+                      uint32_t pass);
 // resolve.hip: the deferred content lookups of a launch (records by reference / in the arena, count keys into keys_b, colours, novel list)
 uint64_t defer_capacity(uint64_t n_reads, uint32_t nwaves);   // 32-byte entries `defer` must hold
 int launch_resolve(const MapParams& p, uint64_t defer_cap, uint64_t keys_cap, int num_cus, hipStream_t stream);
