@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include "hip_buffer.hpp"
 #include "kernel_utils.hpp"
 #include "kernels.hpp"
 #include "pa_common.hpp"
@@ -43,38 +44,32 @@ int barcode_counts(const DevIndexView& ix, const uint32_t* class_table, uint64_t
     *n_entries = 0;
     if (n == 0) return PA_OK;
     if (n > 0x7FFFFFFFull) return fail(PA_ERR_UNSUPPORTED, "at most 2^31-1 reads per call");
-    unsigned long long *keys_in = nullptr, *keys_sorted = nullptr;
-    unsigned int* d_runs = nullptr;
-    void* tmp = nullptr;
-    auto done = [&](int rc) {
-        for (void* p : {(void*)keys_in, (void*)keys_sorted, (void*)d_runs, tmp})
-            if (p) (void)hipFree(p);
-        return rc;
-    };
-#define TRY_(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return done(fail(PA_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_))); } while (0)
-    TRY_(hipMalloc(&keys_in, n * 8));
-    TRY_(hipMalloc(&keys_sorted, n * 8));
-    TRY_(hipMalloc(&d_runs, 4));
+    DeviceBuffer<unsigned long long> keys_in, keys_sorted;
+    DeviceBuffer<unsigned int> d_runs;
+    DeviceBuffer<uint8_t> tmp;
+    int e = keys_in.alloc(n);
+    if (e == PA_OK) e = keys_sorted.alloc(n);
+    if (e == PA_OK) e = d_runs.alloc(1);
+    if (e != PA_OK) return e;
     hipLaunchKernelGGL(pa_barcode_keys_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, d_results, d_arena, d_barcode, n, ix, class_table,
-                       class_table_size, keys_in);
-    TRY_(hipGetLastError());
+                       class_table_size, keys_in.get());
+    PA_HIP_TRY(hipGetLastError());
     uint32_t col_bits = 1;
     while (col_bits < 32 && (1ull << col_bits) < (uint64_t)ix.num_classes + 3) ++col_bits;
     const int end_bit = (int)(32 + (barcode_bits ? (barcode_bits > 32 ? 32 : barcode_bits) : 32));
     size_t sort_bytes = 0, rle_bytes = 0;
     // only the bits that can differ are sorted: the column's low bits and the barcode's
-    TRY_(hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, keys_in, keys_sorted, (int)n, 0, end_bit, stream));
-    TRY_(hipcub::DeviceRunLengthEncode::Encode(nullptr, rle_bytes, keys_sorted, (unsigned long long*)d_keys, d_vals, d_runs, (int)n, stream));
-    TRY_(hipMalloc(&tmp, sort_bytes > rle_bytes ? sort_bytes : rle_bytes));
+    PA_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, keys_in.get(), keys_sorted.get(), (int)n, 0, end_bit, stream));
+    PA_HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(nullptr, rle_bytes, keys_sorted.get(), (unsigned long long*)d_keys, d_vals, d_runs.get(), (int)n, stream));
+    if ((e = tmp.alloc(sort_bytes > rle_bytes ? sort_bytes : rle_bytes)) != PA_OK) return e;
     (void)col_bits;
-    TRY_(hipcub::DeviceRadixSort::SortKeys(tmp, sort_bytes, keys_in, keys_sorted, (int)n, 0, end_bit, stream));
-    TRY_(hipcub::DeviceRunLengthEncode::Encode(tmp, rle_bytes, keys_sorted, (unsigned long long*)d_keys, d_vals, d_runs, (int)n, stream));
+    PA_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(tmp.get(), sort_bytes, keys_in.get(), keys_sorted.get(), (int)n, 0, end_bit, stream));
+    PA_HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(tmp.get(), rle_bytes, keys_sorted.get(), (unsigned long long*)d_keys, d_vals, d_runs.get(), (int)n, stream));
     unsigned int runs = 0;
-    TRY_(hipMemcpyAsync(&runs, d_runs, 4, hipMemcpyDeviceToHost, stream));
-    TRY_(hipStreamSynchronize(stream));
-#undef TRY_
+    PA_HIP_TRY(hipMemcpyAsync(&runs, d_runs.get(), 4, hipMemcpyDeviceToHost, stream));
+    PA_HIP_TRY(hipStreamSynchronize(stream));
     *n_entries = runs;
-    return done(PA_OK);
+    return PA_OK;
 }
 
 }  // namespace pa

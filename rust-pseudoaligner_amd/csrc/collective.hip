@@ -15,17 +15,12 @@
 #include <mutex>
 #include <vector>
 
+#include "hip_buffer.hpp"
 #include "kernel_utils.hpp"
 #include "kernels.hpp"
 #include "pa_common.hpp"
 
 using namespace pa;
-
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t _e = (expr);                                                                         \
-        if (_e != hipSuccess) return fail(PA_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e));  \
-    } while (0)
 
 // ------------------------------------------------------------------------------------------------ overflow table
 // Device layout: open addressing over `cap` slots (power of two):
@@ -37,11 +32,11 @@ using namespace pa;
 struct pa_overflow {
     int device = 0;
     uint64_t cap = 0, pool_cap = 0;
-    unsigned long long* d_keys = nullptr;
-    uint32_t* d_meta = nullptr;
-    uint32_t* d_pool = nullptr;
-    unsigned long long* d_ctl = nullptr;   // [0] pool top, [1] status, [2] export cursor, [3] entries
-    uint32_t* d_export = nullptr;          // serialised records (export_cap u32)
+    DeviceBuffer<unsigned long long> d_keys;
+    DeviceBuffer<uint32_t> d_meta;
+    DeviceBuffer<uint32_t> d_pool;
+    DeviceBuffer<unsigned long long> d_ctl;   // [0] pool top, [1] status, [2] export cursor, [3] entries
+    DeviceBuffer<uint32_t> d_export;          // serialised records (export_cap u32)
     uint64_t export_cap = 0;
     std::vector<uint32_t> h_export, h_merged;
     std::mutex mu;
@@ -207,19 +202,19 @@ int rccl_ready() {
 struct pa_comm {
     int device = 0, nranks = 1, rank = 0;
     ncclComm_t comm = nullptr;
-    unsigned long long* d_scalar = nullptr;   // two u64 for the size / status exchange of the overflow gather
+    DeviceBuffer<unsigned long long> d_scalar;   // two u64 for the size / status exchange of the overflow gather
 };
 
 // hooks for device_index.hip: what the map launch needs to know about an attached overflow table
 namespace pa {
 
-void overflow_launch_params(pa_overflow* o, MapParams& p) { p.novel_status = o->d_ctl + 1; }
+void overflow_launch_params(pa_overflow* o, MapParams& p) { p.novel_status = o->d_ctl.get() + 1; }
 
 // files the novel results a launch listed (per stream: device_index.hip) in the table; same stream, right behind the launch
 int overflow_after_map(pa_overflow* o, const uint32_t* novel_list, const unsigned long long* novel_ctr, uint64_t novel_cap, const uint32_t* d_arena,
                        hipStream_t stream) {
-    hipLaunchKernelGGL(pa_overflow_insert_kernel, dim3(1024), dim3(256), 0, stream, novel_list, novel_ctr, novel_cap, d_arena, o->d_keys, o->d_meta,
-                       o->d_pool, o->d_ctl, o->cap, o->pool_cap);
+    hipLaunchKernelGGL(pa_overflow_insert_kernel, dim3(1024), dim3(256), 0, stream, novel_list, novel_ctr, novel_cap, d_arena, o->d_keys.get(), o->d_meta.get(),
+                       o->d_pool.get(), o->d_ctl.get(), o->cap, o->pool_cap);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(PA_ERR_HIP, "overflow insert launch: %s", hipGetErrorString(e));
     return PA_OK;
@@ -237,7 +232,7 @@ int pa_overflow_create(int device, uint64_t max_classes, uint64_t max_ids, pa_ov
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(PA_ERR_NO_DEVICE, "no HIP device available; this library has no CPU fallback");
     if (device < 0 || device >= n) return fail(PA_ERR_INVALID_ARG, "device %d out of range (have %d)", device, n);
     if (max_ids > 0xFFFFFFF0ull) return fail(PA_ERR_UNSUPPORTED, "at most 2^32-16 ids in an overflow table");
-    HIP_TRY(hipSetDevice(device));
+    PA_HIP_TRY(hipSetDevice(device));
     pa_overflow* o = new (std::nothrow) pa_overflow();
     if (!o) return fail(PA_ERR_OOM, "out of memory");
     o->device = device;
@@ -246,14 +241,15 @@ int pa_overflow_create(int device, uint64_t max_classes, uint64_t max_ids, pa_ov
     o->cap = cap;
     o->pool_cap = max_ids;
     o->export_cap = 2 + 3 * cap + max_ids;   // a record per table slot: whatever the table can hold can be exported (TABLE_FULL / POOL_FULL are the only limits)
-    hipError_t e = hipMalloc(&o->d_keys, cap * 8);
-    if (e == hipSuccess) e = hipMalloc(&o->d_meta, cap * OVF_META_WORDS * 4);
-    if (e == hipSuccess) e = hipMalloc(&o->d_pool, max_ids * 4);
-    if (e == hipSuccess) e = hipMalloc(&o->d_ctl, 64);
-    if (e == hipSuccess) e = hipMalloc(&o->d_export, o->export_cap * 4);
-    if (e == hipSuccess) e = hipMemset(o->d_keys, 0, cap * 8);
-    if (e == hipSuccess) e = hipMemset(o->d_meta, 0, cap * OVF_META_WORDS * 4);
-    if (e == hipSuccess) e = hipMemset(o->d_ctl, 0, 64);
+    int rc = o->d_keys.alloc(cap);
+    if (rc == PA_OK) rc = o->d_meta.alloc(cap * OVF_META_WORDS);
+    if (rc == PA_OK) rc = o->d_pool.alloc(max_ids);
+    if (rc == PA_OK) rc = o->d_ctl.alloc(8);
+    if (rc == PA_OK) rc = o->d_export.alloc(o->export_cap);
+    if (rc != PA_OK) { pa_overflow_destroy(o); return rc; }
+    hipError_t e = hipMemset(o->d_keys.get(), 0, cap * 8);
+    if (e == hipSuccess) e = hipMemset(o->d_meta.get(), 0, cap * OVF_META_WORDS * 4);
+    if (e == hipSuccess) e = hipMemset(o->d_ctl.get(), 0, 64);
     if (e != hipSuccess) {
         pa_overflow_destroy(o);
         return fail(PA_ERR_OOM, "overflow table (%llu slots, %llu ids): %s", (unsigned long long)cap, (unsigned long long)max_ids, hipGetErrorString(e));
@@ -265,41 +261,39 @@ int pa_overflow_create(int device, uint64_t max_classes, uint64_t max_ids, pa_ov
 void pa_overflow_destroy(pa_overflow* o) {
     if (!o) return;
     (void)hipSetDevice(o->device);
-    for (void* p : {(void*)o->d_keys, (void*)o->d_meta, (void*)o->d_pool, (void*)o->d_ctl, (void*)o->d_export})
-        if (p) (void)hipFree(p);
     delete o;
 }
 
 int pa_overflow_reset(pa_overflow* o, void* stream) {
     if (!o) return fail(PA_ERR_INVALID_ARG, "null argument");
     std::lock_guard<std::mutex> g(o->mu);
-    HIP_TRY(hipSetDevice(o->device));
+    PA_HIP_TRY(hipSetDevice(o->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemsetAsync(o->d_keys, 0, o->cap * 8, st));
-    HIP_TRY(hipMemsetAsync(o->d_meta, 0, o->cap * OVF_META_WORDS * 4, st));
-    HIP_TRY(hipMemsetAsync(o->d_ctl, 0, 64, st));
+    PA_HIP_TRY(hipMemsetAsync(o->d_keys.get(), 0, o->cap * 8, st));
+    PA_HIP_TRY(hipMemsetAsync(o->d_meta.get(), 0, o->cap * OVF_META_WORDS * 4, st));
+    PA_HIP_TRY(hipMemsetAsync(o->d_ctl.get(), 0, 64, st));
     return PA_OK;
 }
 
 // serialise the table on the device; *n_words = words used (header included). Leaves the records in o->d_export.
 static int export_locked(pa_overflow* o, hipStream_t st, uint64_t* n_words) {
-    HIP_TRY(hipSetDevice(o->device));
-    HIP_TRY(hipMemsetAsync(o->d_export, 0, 8, st));
+    PA_HIP_TRY(hipSetDevice(o->device));
+    PA_HIP_TRY(hipMemsetAsync(o->d_export.get(), 0, 8, st));
     const unsigned long long two = 2;
-    HIP_TRY(hipMemcpyAsync(o->d_ctl + 2, &two, 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(pa_overflow_export_kernel, dim3((uint32_t)((o->cap + 255) / 256)), dim3(256), 0, st, o->d_keys, o->d_meta, o->d_pool, o->d_ctl,
-                       o->cap, o->d_export, o->export_cap);
-    HIP_TRY(hipGetLastError());
+    PA_HIP_TRY(hipMemcpyAsync(o->d_ctl.get() + 2, &two, 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(pa_overflow_export_kernel, dim3((uint32_t)((o->cap + 255) / 256)), dim3(256), 0, st, o->d_keys.get(), o->d_meta.get(), o->d_pool.get(), o->d_ctl.get(),
+                       o->cap, o->d_export.get(), o->export_cap);
+    PA_HIP_TRY(hipGetLastError());
     unsigned long long ctl[4];
-    HIP_TRY(hipMemcpyAsync(ctl, o->d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    PA_HIP_TRY(hipMemcpyAsync(ctl, o->d_ctl.get(), sizeof ctl, hipMemcpyDeviceToHost, st));
+    PA_HIP_TRY(hipStreamSynchronize(st));
     if (ctl[1] & OVF_STATUS_LIST_FULL) return fail(PA_ERR_ARENA_FULL, "overflow: more novel results in one launch than its list holds");
     if (ctl[1] & OVF_STATUS_TABLE_FULL) return fail(PA_ERR_ARENA_FULL, "overflow table full: more than %llu distinct novel classes", (unsigned long long)(o->cap / 2));
     if (ctl[1] & OVF_STATUS_POOL_FULL) return fail(PA_ERR_ARENA_FULL, "overflow id pool full: %llu ids needed, %llu available", ctl[0], (unsigned long long)o->pool_cap);
     if (ctl[1] & OVF_STATUS_EXPORT_FULL) return fail(PA_ERR_INTERNAL, "overflow export buffer too small");
     const uint32_t words = (uint32_t)ctl[2];
-    HIP_TRY(hipMemcpyAsync(o->d_export + 1, &words, 4, hipMemcpyHostToDevice, st));   // header word 1 = words used
-    HIP_TRY(hipStreamSynchronize(st));
+    PA_HIP_TRY(hipMemcpyAsync(o->d_export.get() + 1, &words, 4, hipMemcpyHostToDevice, st));   // header word 1 = words used
+    PA_HIP_TRY(hipStreamSynchronize(st));
     *n_words = ctl[2];
     return PA_OK;
 }
@@ -312,7 +306,7 @@ int pa_overflow_fetch(pa_overflow* o, void* stream, const uint32_t** words, uint
     const int rc = export_locked(o, st, &nw);
     if (rc != PA_OK) return rc;
     o->h_export.resize(nw);
-    HIP_TRY(hipMemcpy(o->h_export.data(), o->d_export, nw * 4, hipMemcpyDeviceToHost));
+    PA_HIP_TRY(hipMemcpy(o->h_export.data(), o->d_export.get(), nw * 4, hipMemcpyDeviceToHost));
     const uint32_t* one[1] = {o->h_export.data()};
     const int rc2 = merge_serialised(one, &nw, 1, o->h_merged);   // canonical order, duplicate entries folded
     if (rc2 != PA_OK) return rc2;
@@ -350,7 +344,7 @@ int pa_comm_create(int device, int nranks, int rank, const uint8_t id[128], pa_c
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(PA_ERR_NO_DEVICE, "no HIP device available; this library has no CPU fallback");
     if (device < 0 || device >= n) return fail(PA_ERR_INVALID_ARG, "device %d out of range (have %d)", device, n);
-    HIP_TRY(hipSetDevice(device));
+    PA_HIP_TRY(hipSetDevice(device));
     pa_comm* c = new (std::nothrow) pa_comm();
     if (!c) return fail(PA_ERR_OOM, "out of memory");
     c->device = device;
@@ -360,7 +354,7 @@ int pa_comm_create(int device, int nranks, int rank, const uint8_t id[128], pa_c
     memcpy(u.internal, id, 128);
     ncclResult_t r = rccl().CommInitRank(&c->comm, nranks, u, rank);
     if (r != 0) { delete c; return fail(PA_ERR_HIP, "ncclCommInitRank(%d of %d): %s", rank, nranks, rccl().GetErrorString(r)); }
-    if (hipMalloc(&c->d_scalar, 16) != hipSuccess) { rccl().CommDestroy(c->comm); delete c; return fail(PA_ERR_OOM, "hipMalloc"); }
+    if (const int e = c->d_scalar.alloc(2)) { rccl().CommDestroy(c->comm); delete c; return e; }
     *out = c;
     return PA_OK;
 }
@@ -369,7 +363,6 @@ void pa_comm_destroy(pa_comm* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->comm) rccl().CommDestroy(c->comm);
-    if (c->d_scalar) (void)hipFree(c->d_scalar);
     delete c;
 }
 
@@ -379,7 +372,7 @@ int pa_comm_size(const pa_comm* c) { return c ? c->nranks : 1; }
 int pa_counts_allreduce(pa_index* idx, uint64_t* d_counts, pa_comm* comm, void* stream) {
     if (!idx || !d_counts) return fail(PA_ERR_INVALID_ARG, "null argument");
     if (!comm) return PA_OK;   // one GPU: the local table is the global one
-    HIP_TRY(hipSetDevice(comm->device));
+    PA_HIP_TRY(hipSetDevice(comm->device));
     NCCL_TRY(rccl().AllReduce(d_counts, d_counts, (size_t)pa_counts_len(idx), ncclUint64, ncclSum, comm->comm, static_cast<hipStream_t>(stream)));
     return PA_OK;
 }
@@ -409,11 +402,11 @@ int pa_overflow_allgather(pa_overflow* o, pa_comm* comm, void* stream, const uin
             mine[1] = (unsigned long long)(-PA_ERR_HIP);
         };
         note(hipSetDevice(comm->device), "hipSetDevice");
-        note(hipMemcpyAsync(comm->d_scalar, mine, 16, hipMemcpyHostToDevice, st), "hipMemcpyAsync(status)");
-        if (rc_local == PA_ERR_HIP) (void)hipMemcpyAsync(comm->d_scalar, mine, 16, hipMemcpyHostToDevice, st);   // (the status, if the device still takes it)
-        const ncclResult_t r = rccl().AllReduce(comm->d_scalar, comm->d_scalar, 2, ncclUint64, ncclMax, comm->comm, st);
+        note(hipMemcpyAsync(comm->d_scalar.get(), mine, 16, hipMemcpyHostToDevice, st), "hipMemcpyAsync(status)");
+        if (rc_local == PA_ERR_HIP) (void)hipMemcpyAsync(comm->d_scalar.get(), mine, 16, hipMemcpyHostToDevice, st);   // (the status, if the device still takes it)
+        const ncclResult_t r = rccl().AllReduce(comm->d_scalar.get(), comm->d_scalar.get(), 2, ncclUint64, ncclMax, comm->comm, st);
         if (r != 0 && rc_local == PA_OK) { rc_local = PA_ERR_HIP; why_local = std::string("ncclAllReduce: ") + rccl().GetErrorString(r); }
-        note(hipMemcpyAsync(most, comm->d_scalar, 16, hipMemcpyDeviceToHost, st), "hipMemcpyAsync(result)");
+        note(hipMemcpyAsync(most, comm->d_scalar.get(), 16, hipMemcpyDeviceToHost, st), "hipMemcpyAsync(result)");
         note(hipStreamSynchronize(st), "hipStreamSynchronize");
     };
     unsigned long long mine[2] = {rc_local == PA_OK ? nw : 0ull, (unsigned long long)(rc_local == PA_OK ? 0 : -rc_local)}, most[2] = {0, 0};
@@ -424,27 +417,24 @@ int pa_overflow_allgather(pa_overflow* o, pa_comm* comm, void* stream, const uin
     const uint64_t len = most[0];
     // send buffer of the common length (the largest table), zero padded: independent of this rank's own export capacity. A rank that
     // cannot allocate it says so in a second exchange, so that no rank enters the gather alone
-    uint32_t *d_send = nullptr, *d_all = nullptr;
-    hipError_t e = hipMalloc(&d_send, (size_t)len * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_all, (size_t)len * 4 * comm->nranks);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_send, o->d_export, (size_t)nw * 4, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess && len > nw) e = hipMemsetAsync(d_send + nw, 0, (size_t)(len - nw) * 4, st);
+    DeviceBuffer<uint32_t> d_send, d_all;
+    hipError_t e = d_send.alloc(len) || d_all.alloc((size_t)len * comm->nranks) ? hipErrorOutOfMemory : hipSuccess;
+    if (e == hipSuccess) e = hipMemcpyAsync(d_send.get(), o->d_export.get(), (size_t)nw * 4, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && len > nw) e = hipMemsetAsync(d_send.get() + nw, 0, (size_t)(len - nw) * 4, st);
     if (e != hipSuccess) { rc_local = PA_ERR_OOM; why_local = std::string("overflow gather buffers: ") + hipGetErrorString(e); }
     unsigned long long mine2[2] = {0ull, (unsigned long long)(rc_local == PA_OK ? 0 : -rc_local)}, most2[2] = {0, 0};
     exchange(mine2, most2);
     if (rc_local != PA_OK || most2[1] != 0) {
-        (void)hipFree(d_send);
-        (void)hipFree(d_all);
         if (rc_local != PA_OK) return fail(rc_local, "%s (%llu words x %d ranks)", why_local.c_str(), (unsigned long long)len, comm->nranks);
         return fail(-(int)most2[1], "overflow gather: another rank could not allocate its gather buffers (status %d there); no rank merged anything", -(int)most2[1]);
     }
-    ncclResult_t r = rccl().AllGather(d_send, d_all, (size_t)len, ncclUint32, comm->comm, st);
-    if (r != 0) { (void)hipFree(d_send); (void)hipFree(d_all); return fail(PA_ERR_HIP, "ncclAllGather: %s", rccl().GetErrorString(r)); }
+    ncclResult_t r = rccl().AllGather(d_send.get(), d_all.get(), (size_t)len, ncclUint32, comm->comm, st);
+    if (r != 0) return fail(PA_ERR_HIP, "ncclAllGather: %s", rccl().GetErrorString(r));
     std::vector<uint32_t> all((size_t)len * comm->nranks);
-    e = hipMemcpyAsync(all.data(), d_all, all.size() * 4, hipMemcpyDeviceToHost, st);
+    e = hipMemcpyAsync(all.data(), d_all.get(), all.size() * 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(d_send);
-    (void)hipFree(d_all);
+    d_send.release();
+    d_all.release();
     if (e != hipSuccess) return fail(PA_ERR_HIP, "overflow gather copy: %s", hipGetErrorString(e));
     std::vector<const uint32_t*> bufs(comm->nranks);
     std::vector<uint64_t> sizes(comm->nranks, len);

@@ -3,6 +3,9 @@
 #include <vector>
 
 #include "device_layout.hpp"
+#ifdef __HIPCC__   // (device_fill_index: the rest of this header is also compiled without HIP, tests/emu)
+#include "hip_buffer.hpp"
+#endif
 
 namespace pa {
 
@@ -35,8 +38,10 @@ struct FlatDevice {
 // `nbuckets` 0, node_kcum is filled.
 int flatten_for_device(const pa_flat_index& f, int threads, FlatDevice& out, bool device_dict = false);
 
+#ifdef __HIPCC__
 // index_fill.hip: dictionary fill (CAS into the bucket lines) and verification (duplicate k-mers, probe distance) on the
-// device, from chain blocks already resident in HBM. Allocates *d_table (hipMalloc) and sets *nbuckets.
-int device_fill_index(const FlatDevice& fd, void* d_blobs, void** d_table, uint64_t* nbuckets);
+// device, from chain blocks already resident in HBM. Hands the dictionary back in `table` (left as it was on failure) and sets *nbuckets.
+int device_fill_index(const FlatDevice& fd, const uint8_t* d_blobs, DeviceBuffer<uint32_t>& table, uint64_t* nbuckets);
+#endif
 
 }  // namespace pa

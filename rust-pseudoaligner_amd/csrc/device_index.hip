@@ -12,6 +12,7 @@
 #include <thread>
 
 #include "device_flatten.hpp"
+#include "hip_buffer.hpp"
 #include "kernels.hpp"
 #include "lane_steps.hpp"
 #include "pa_common.hpp"
@@ -19,29 +20,21 @@
 
 using namespace pa;
 
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t _e = (expr);                                                                         \
-        if (_e != hipSuccess) return fail(PA_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e));  \
-    } while (0)
-
 namespace {
 
-struct DevBuf {   // grow-only device scratch
-    void* p = nullptr;
-    size_t bytes = 0;
-    int ensure(size_t need) {
-        if (need <= bytes) return PA_OK;
-        if (p) { hipError_t e = hipFree(p); p = nullptr; bytes = 0; if (e != hipSuccess) return fail(PA_ERR_HIP, "hipFree: %s", hipGetErrorString(e)); }
-        const size_t want = need + need / 4 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) { p = nullptr; return fail(PA_ERR_OOM, "hipMalloc(%zu): %s", want, hipGetErrorString(e)); }
-        bytes = want;
-        return PA_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
+using Scratch = DeviceBuffer<uint8_t>;
+
+// grow-only device scratch: a quarter more than asked for (and 256 bytes) when it has to grow
+int grow(Scratch& b, size_t need) { return b.reserve(need, need + need / 4 + 256); }
+
+// n elements to a new device buffer (16 bytes when there are none)
+template <class T> int upload(DeviceBuffer<T>& dst, const T* src, size_t n) {
+    const int e = dst.alloc(n ? n : 16 / sizeof(T));
+    if (e != PA_OK) return e;
+    if (n) PA_HIP_TRY(hipMemcpy(dst.get(), src, n * sizeof(T), hipMemcpyHostToDevice));
+    return PA_OK;
+}
+template <class T> int upload(DeviceBuffer<T>& dst, const std::vector<T>& src) { return upload(dst, src.data(), src.size()); }
 
 uint64_t list_hash_host(const uint32_t* v, uint32_t n) {   // must equal list_hash_dev (kernel_utils.hpp)
     uint64_t h = 0x243f6a8885a308d3ull ^ n;
@@ -53,10 +46,10 @@ uint64_t list_hash_host(const uint32_t* v, uint32_t n) {   // must equal list_ha
 
 struct LaunchCtx {
     std::mutex mu;
-    DevBuf ctl;      // [0..7] arena_top (u64), [8..11] status, [12..15] tile counter, [16..] statistics, [448..455] novel results listed, [456..463] count keys handed out
-    DevBuf spill, trace, novel;
-    DevBuf keys, keys_sorted, keys_ctl;   // class-count launches: the waves' key streams (+ one key per deferred read), the keys partitioned by bin inside tiles, where the runs lie (count_sort.hip)
-    DevBuf defer;                          // reads whose class is looked up by content after the launch (resolve.hip): 32 bytes each, sized for every read
+    Scratch ctl;      // [0..7] arena_top (u64), [8..11] status, [12..15] tile counter, [16..] statistics, [448..455] novel results listed, [456..463] count keys handed out
+    Scratch spill, trace, novel;
+    Scratch keys, keys_sorted, keys_ctl;   // class-count launches: the waves' key streams (+ one key per deferred read), the keys partitioned by bin inside tiles, where the runs lie (count_sort.hip)
+    Scratch defer;                         // reads whose class is looked up by content after the launch (resolve.hip): 32 bytes each, sized for every read
     uint32_t last_grid = 0;
     uint64_t last_arena_cap = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;   // before the map kernel / after it / after the resolve kernel (on `side`) / after the count kernels of the last launch (pa_index_set_timing)
@@ -67,7 +60,7 @@ struct LaunchCtx {
     hipEvent_t fork = nullptr, join = nullptr;
     void release() {
         if (side) (void)hipStreamSynchronize(side);
-        for (DevBuf* b : {&ctl, &spill, &trace, &novel, &keys, &keys_sorted, &keys_ctl, &defer}) b->release();
+        for (Scratch* b : {&ctl, &spill, &trace, &novel, &keys, &keys_sorted, &keys_ctl, &defer}) b->release();
         for (hipEvent_t e : {ev0, ev1, ev2, ev3, fork, join})
             if (e) (void)hipEventDestroy(e);
         ev0 = ev1 = ev2 = ev3 = fork = join = nullptr;
@@ -81,8 +74,9 @@ struct pa_index {
     int device = 0;
     int num_cus = 0;
     DevIndexView dv{};
-    void *d_table = nullptr, *d_blobs = nullptr, *d_ledge = nullptr, *d_seg_g = nullptr, *d_seg_nid = nullptr, *d_ec = nullptr, *d_class_ref = nullptr, *d_class_len = nullptr,
-         *d_class_table = nullptr, *d_wtable = nullptr;
+    DeviceBuffer<uint32_t> d_table, d_ledge, d_seg_nid, d_ec, d_class_ref, d_class_len, d_class_table, d_wtable;
+    DeviceBuffer<uint8_t> d_blobs;
+    DeviceBuffer<uint64_t> d_seg_g;
     uint64_t class_table_size = 0;
     pa_index_stats stats{};
     // per-launch scratch: one context per stream the caller launches on, so that launches on different streams (from one or
@@ -93,7 +87,7 @@ struct pa_index {
     bool timing = false;          // pa_index_set_timing: HIP events around the map kernel of every launch
     std::mutex hmu;               // the host-buffer convenience path (b_* below) is one batch at a time
     // host-buffer convenience path
-    DevBuf b_ascii, b_offsets, b_tiles, b_lens, b_results, b_arena, b_colour, b_nodes, b_nodes_len;
+    Scratch b_ascii, b_offsets, b_tiles, b_lens, b_results, b_arena, b_colour, b_nodes, b_nodes_len;
     std::vector<uint32_t> h_class_ids;
     std::vector<uint32_t> h_ec, h_class_ref, h_class_len;
     // every index class rendered once as the reference prints it between the brackets ("1, 5, 9"): text of class c =
@@ -103,7 +97,8 @@ struct pa_index {
     std::vector<uint64_t> h_class_text_off;
     std::vector<char> h_class_text;
     std::vector<uint32_t> h_arena;
-    void *d_class_text_off = nullptr, *d_class_text = nullptr;   // device copy of the rendered classes (uploaded on first use, under `mu`)
+    DeviceBuffer<uint64_t> d_class_text_off;   // device copy of the rendered classes (uploaded on first use, under `mu`)
+    DeviceBuffer<uint8_t> d_class_text;
     // parked by fastq.cpp / record_stream.cpp between calls (guarded by `mu`): the buffer sets of up to four lanes (pa_process_reads_multi with the
     // handle listed several times, concurrent callers)
     std::vector<std::pair<void*, void (*)(void*)>> ingest_caches;
@@ -125,13 +120,7 @@ static int use_device(int device) {
         return fail(PA_ERR_NO_DEVICE, "no HIP device available (%s); this library has no CPU fallback",
                     e == hipSuccess ? "device count is 0" : hipGetErrorString(e));
     if (device < 0 || device >= n) return fail(PA_ERR_INVALID_ARG, "device %d out of range (have %d)", device, n);
-    HIP_TRY(hipSetDevice(device));
-    return PA_OK;
-}
-
-static int upload(const void* src, size_t bytes, void** dst) {
-    HIP_TRY(hipMalloc(dst, bytes ? bytes : 16));
-    if (bytes) HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+    PA_HIP_TRY(hipSetDevice(device));
     return PA_OK;
 }
 
@@ -199,20 +188,14 @@ int index_device_class_text(pa_index* idx, const uint64_t** d_off, const uint8_t
     const char* txt = nullptr;
     index_host_class_text(idx, &off, &txt);
     std::lock_guard<std::mutex> g(idx->mu);
-    if (!idx->d_class_text) {
+    if (!idx->d_class_text.get()) {   // (d_class_text is uploaded last: it is there only when both are)
         if (hipSetDevice(idx->device) != hipSuccess) return fail(PA_ERR_HIP, "hipSetDevice failed");
-        void *a = nullptr, *b = nullptr;
-        const size_t nb = idx->h_class_text.size(), no = idx->h_class_text_off.size() * 8;
-        if (hipMalloc(&a, no ? no : 16) != hipSuccess || hipMalloc(&b, nb ? nb : 16) != hipSuccess) { if (a) (void)hipFree(a); return fail(PA_ERR_OOM, "hipMalloc for the rendered class table"); }
-        if (hipMemcpy(a, off, no, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(b, txt, nb, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(a); (void)hipFree(b);
-            return fail(PA_ERR_HIP, "upload of the rendered class table failed");
-        }
-        idx->d_class_text_off = a;
-        idx->d_class_text = b;
+        int e = upload(idx->d_class_text_off, off, idx->h_class_text_off.size());
+        if (e == PA_OK) e = upload(idx->d_class_text, reinterpret_cast<const uint8_t*>(txt), idx->h_class_text.size());
+        if (e != PA_OK) return e;
     }
-    *d_off = static_cast<const uint64_t*>(idx->d_class_text_off);
-    *d_text = static_cast<const uint8_t*>(idx->d_class_text);
+    *d_off = idx->d_class_text_off.get();
+    *d_text = idx->d_class_text.get();
     return PA_OK;
 }
 void* index_take_ingest_cache(pa_index* idx) {
@@ -255,19 +238,13 @@ void index_put_ingest_cache(pa_index* idx, void* cache, void (*free_fn)(void*)) 
 void pa_index_destroy(pa_index* idx) {
     if (!idx) return;
     (void)hipSetDevice(idx->device);
-    for (void* p : {idx->d_table, idx->d_blobs, idx->d_ledge, idx->d_seg_g, idx->d_seg_nid, idx->d_ec, idx->d_class_ref, idx->d_class_len, idx->d_class_table, idx->d_wtable,
-                    idx->d_class_text_off, idx->d_class_text})
-        if (p) (void)hipFree(p);
     {   // (releases their streams' contexts)
         std::vector<std::pair<void*, void (*)(void*)>> parked;
         { std::lock_guard<std::mutex> g(idx->mu); parked.swap(idx->ingest_caches); parked.insert(parked.end(), idx->host_pipes.begin(), idx->host_pipes.end()); idx->host_pipes.clear(); }
         for (auto& c : parked) c.second(c.first);
     }
     for (auto& kv : idx->ctxs) kv.second->release();
-    for (DevBuf* b : {&idx->b_ascii, &idx->b_offsets, &idx->b_tiles, &idx->b_lens, &idx->b_results,
-                      &idx->b_arena, &idx->b_colour, &idx->b_nodes, &idx->b_nodes_len})
-        b->release();
-    delete idx;
+    delete idx;   // (the index's own buffers, with its device current)
 }
 
 int pa_index_create(const pa_flat_index* flat, int device, pa_index** out) {
@@ -297,31 +274,31 @@ int pa_index_create(const pa_flat_index* flat, int device, pa_index** out) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) idx->num_cus = prop.multiProcessorCount;
     if (idx->num_cus <= 0) idx->num_cus = 256;
-    rc = upload(fd.blobs.data(), fd.blobs.size(), &idx->d_blobs);
-    if (rc == PA_OK) rc = upload(fd.ledge.data(), fd.ledge.size() * 4, &idx->d_ledge);
-    if (rc == PA_OK) rc = device_fill_index(fd, idx->d_blobs, &idx->d_table, &fd.nbuckets);
-    if (rc == PA_OK) rc = upload(fd.seg_g.data(), fd.seg_g.size() * 8, &idx->d_seg_g);
-    if (rc == PA_OK) rc = upload(fd.seg_nid.data(), fd.seg_nid.size() * 4, &idx->d_seg_nid);
-    if (rc == PA_OK) rc = upload(fd.ec.data(), fd.ec.size() * 4, &idx->d_ec);
-    if (rc == PA_OK) rc = upload(fd.class_ref.data(), fd.class_ref.size() * 4, &idx->d_class_ref);
-    if (rc == PA_OK) rc = upload(fd.class_len.data(), fd.class_len.size() * 4, &idx->d_class_len);
-    if (rc == PA_OK) rc = upload(ctab.data(), ctab.size() * 4, &idx->d_class_table);
-    if (rc == PA_OK) rc = upload(fd.wtable.data(), fd.wtable.size() * 4, &idx->d_wtable);
+    rc = upload(idx->d_blobs, fd.blobs);
+    if (rc == PA_OK) rc = upload(idx->d_ledge, fd.ledge);
+    if (rc == PA_OK) rc = device_fill_index(fd, idx->d_blobs.get(), idx->d_table, &fd.nbuckets);
+    if (rc == PA_OK) rc = upload(idx->d_seg_g, fd.seg_g);
+    if (rc == PA_OK) rc = upload(idx->d_seg_nid, fd.seg_nid);
+    if (rc == PA_OK) rc = upload(idx->d_ec, fd.ec);
+    if (rc == PA_OK) rc = upload(idx->d_class_ref, fd.class_ref);
+    if (rc == PA_OK) rc = upload(idx->d_class_len, fd.class_len);
+    if (rc == PA_OK) rc = upload(idx->d_class_table, ctab);
+    if (rc == PA_OK) rc = upload(idx->d_wtable, fd.wtable);
     if (rc != PA_OK) { pa_index_destroy(idx); return rc; }
     idx->class_table_size = ctab.size();
     idx->dv = fd.host_view();
-    idx->dv.table = static_cast<const uint32_t*>(idx->d_table);
-    idx->dv.blobs = static_cast<const uint8_t*>(idx->d_blobs);
-    idx->dv.ledge = static_cast<const uint32_t*>(idx->d_ledge);
-    idx->dv.seg_g = static_cast<const uint64_t*>(idx->d_seg_g);
-    idx->dv.seg_nid = static_cast<const uint32_t*>(idx->d_seg_nid);
+    idx->dv.table = idx->d_table.get();
+    idx->dv.blobs = idx->d_blobs.get();
+    idx->dv.ledge = idx->d_ledge.get();
+    idx->dv.seg_g = idx->d_seg_g.get();
+    idx->dv.seg_nid = idx->d_seg_nid.get();
     idx->h_ec = fd.ec;   // host copy of the class table: pa_map_batch resolves by-reference classes from it
     idx->h_class_ref = fd.class_ref;
     idx->h_class_len = fd.class_len;
-    idx->dv.ec = static_cast<const uint32_t*>(idx->d_ec);
-    idx->dv.class_ref = static_cast<const uint32_t*>(idx->d_class_ref);
-    idx->dv.class_len = static_cast<const uint32_t*>(idx->d_class_len);
-    idx->dv.wtable = static_cast<const uint32_t*>(idx->d_wtable);
+    idx->dv.ec = idx->d_ec.get();
+    idx->dv.class_ref = idx->d_class_ref.get();
+    idx->dv.class_len = idx->d_class_len.get();
+    idx->dv.wtable = idx->d_wtable.get();
     // a dictionary beyond the Infinity Cache (256 MB) is streamed past the caches (ld_stream): every line of it is used once per probe,
     // and left to itself it evicts the chain blocks, which every read comes back to
     idx->dv.stream_nt = (fd.k <= 32 && fd.nbuckets * BUCKET_WORDS * 4 > (512ull << 20)) ? 1u : 0u;   // (the two-word dictionary's probe is four loads of one line: slower with the hint)
@@ -371,7 +348,7 @@ size_t pa_tiles_words(uint64_t n_reads, uint32_t words_per_read) { return (size_
 int pa_encode_reads_device(const pa_index* idx, const uint8_t* d_ascii, const uint64_t* d_offsets, uint64_t n_reads,
                            uint32_t words_per_read, uint64_t* d_tiles, uint32_t* d_lens, void* stream) {
     if (!idx || !d_ascii || !d_offsets || !d_tiles || !d_lens || words_per_read == 0) return fail(PA_ERR_INVALID_ARG, "null argument");
-    HIP_TRY(hipSetDevice(idx->device));
+    PA_HIP_TRY(hipSetDevice(idx->device));
     const int e = launch_encode(d_ascii, d_offsets, n_reads, words_per_read, d_tiles, d_lens, static_cast<hipStream_t>(stream));
     if (e) return fail(PA_ERR_HIP, "encode launch: %s", hipGetErrorString((hipError_t)e));
     return PA_OK;
@@ -421,7 +398,7 @@ static int ctx_of(pa_index* idx, hipStream_t stream, std::shared_ptr<LaunchCtx>*
     if (it == idx->ctxs.end()) {
         std::shared_ptr<LaunchCtx> c(new (std::nothrow) LaunchCtx());
         if (!c) return fail(PA_ERR_OOM, "out of memory");
-        const int rc = c->ctl.ensure(1024);
+        const int rc = grow(c->ctl, 1024);
         if (rc != PA_OK) return rc;
         it = idx->ctxs.emplace(stream, std::move(c)).first;
     }
@@ -446,10 +423,10 @@ static int map_launch_locked(pa_index* idx, LaunchCtx* cx, const uint64_t* d_til
         if ((size_t)grid * per_block > budget) grid = (uint32_t)std::max<size_t>(1, budget / per_block);
     }
     const size_t lanes = (size_t)grid * (PA_MAP_BLOCK / 64) * slots;
-    rc = cx->spill.ensure(lanes * spill_cap * 4);
+    rc = grow(cx->spill, lanes * spill_cap * 4);
     if (rc != PA_OK) return rc;
-    if (d_nodes) { rc = cx->trace.ensure(lanes * spill_cap * 4); if (rc != PA_OK) return rc; }
-    HIP_TRY(hipMemsetAsync(cx->ctl.p, 0, 512, stream));
+    if (d_nodes) { rc = grow(cx->trace, lanes * spill_cap * 4); if (rc != PA_OK) return rc; }
+    PA_HIP_TRY(hipMemsetAsync(cx->ctl.get(), 0, 512, stream));
     MapParams p{};
     p.ix = idx->dv;
     p.tiles = d_tiles;
@@ -471,7 +448,7 @@ static int map_launch_locked(pa_index* idx, LaunchCtx* cx, const uint64_t* d_til
     const uint64_t counts_len = (uint64_t)idx->stats.num_classes + 3;
     // reads whose class has to be looked up by content are resolved after the launch (resolve.hip): 32 bytes per read in the worst case
     const uint64_t defer_cap = defer_capacity(n_reads, grid * (PA_MAP_BLOCK / 64));
-    if ((rc = cx->defer.ensure(defer_cap * 32))) return rc;
+    if ((rc = grow(cx->defer, defer_cap * 32))) return rc;
     p.defer = cx->defer.as<uint32_t>();
     p.defer_top = cx->ctl.as<unsigned long long>() + 58;
     p.defer_cap = defer_cap;
@@ -481,13 +458,13 @@ static int map_launch_locked(pa_index* idx, LaunchCtx* cx, const uint64_t* d_til
         keys_cap = key_stream_capacity(n_reads, grid * (PA_MAP_BLOCK / 64));
         size_t sorted_bytes = 0, ctl_bytes = 0;
         count_keys_scratch(counts_len, n_reads, keys_cap, defer_cap, &sorted_bytes, &ctl_bytes);
-        if ((rc = cx->keys.ensure((keys_cap + defer_cap) * 4)) || (rc = cx->keys_sorted.ensure(sorted_bytes)) || (rc = cx->keys_ctl.ensure(ctl_bytes))) return rc;
+        if ((rc = grow(cx->keys, (keys_cap + defer_cap) * 4)) || (rc = grow(cx->keys_sorted, sorted_bytes)) || (rc = grow(cx->keys_ctl, ctl_bytes))) return rc;
         p.keys = cx->keys.as<uint32_t>();
         p.keys_top = cx->ctl.as<unsigned long long>() + 57;
         p.keys_cap = keys_cap;
         p.counts = reinterpret_cast<unsigned long long*>(d_counts);
     }
-    p.class_table = static_cast<const uint32_t*>(idx->d_class_table);
+    p.class_table = idx->d_class_table.get();
     p.class_table_size = idx->class_table_size;
     p.pool_slots = slots;
     p.dbg = env_int("PA_MAP_STATS", 0) ? cx->ctl.as<unsigned long long>() + 2 : nullptr;
@@ -496,7 +473,7 @@ static int map_launch_locked(pa_index* idx, LaunchCtx* cx, const uint64_t* d_til
     { std::lock_guard<std::mutex> g(idx->mu); ovf = idx->ovf; }
     if (d_counts && ovf) {   // novel results of this launch are listed (per stream) for the overflow table
         const uint64_t want = n_reads + 64;   // every read can end in a novel class: the list never overflows
-        rc = cx->novel.ensure(want * 8);
+        rc = grow(cx->novel, want * 8);
         if (rc != PA_OK) return rc;
         p.novel_list = cx->novel.as<uint32_t>();
         p.novel_ctr = cx->ctl.as<unsigned long long>() + 56;
@@ -513,37 +490,37 @@ static int map_launch_locked(pa_index* idx, LaunchCtx* cx, const uint64_t* d_til
     bool timing = false;
     { std::lock_guard<std::mutex> g(idx->mu); timing = idx->timing; }
     if (timing) {
-        if (!cx->ev0) { HIP_TRY(hipEventCreate(&cx->ev0)); HIP_TRY(hipEventCreate(&cx->ev1)); HIP_TRY(hipEventCreate(&cx->ev2)); HIP_TRY(hipEventCreate(&cx->ev3)); }
-        HIP_TRY(hipEventRecord(cx->ev0, stream));
+        if (!cx->ev0) { PA_HIP_TRY(hipEventCreate(&cx->ev0)); PA_HIP_TRY(hipEventCreate(&cx->ev1)); PA_HIP_TRY(hipEventCreate(&cx->ev2)); PA_HIP_TRY(hipEventCreate(&cx->ev3)); }
+        PA_HIP_TRY(hipEventRecord(cx->ev0, stream));
     }
     const int e = launch_map_pool(p, grid, lds, stream);
     if (e) return fail(PA_ERR_HIP, "map launch (grid %u, lds %zu): %s", grid, lds, hipGetErrorString((hipError_t)e));
-    if (timing) { HIP_TRY(hipEventRecord(cx->ev1, stream)); cx->timed = true; }
+    if (timing) { PA_HIP_TRY(hipEventRecord(cx->ev1, stream)); cx->timed = true; }
     // resolve and the partition of the map kernel's keys need only the map kernel: with a partitioned table they run side by side
     // (resolve on cx->side); the partition of the deferred reads' keys, the count kernel and the overflow table wait for both
     const bool overlap = d_counts && count_keys_partitioned(counts_len, n_reads);
     hipStream_t rs = stream;
     if (overlap) {
         if (!cx->side) {
-            HIP_TRY(hipStreamCreateWithFlags(&cx->side, hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&cx->fork, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&cx->join, hipEventDisableTiming));
+            PA_HIP_TRY(hipStreamCreateWithFlags(&cx->side, hipStreamNonBlocking));
+            PA_HIP_TRY(hipEventCreateWithFlags(&cx->fork, hipEventDisableTiming));
+            PA_HIP_TRY(hipEventCreateWithFlags(&cx->join, hipEventDisableTiming));
         }
-        HIP_TRY(hipEventRecord(cx->fork, stream));
-        HIP_TRY(hipStreamWaitEvent(cx->side, cx->fork, 0));
+        PA_HIP_TRY(hipEventRecord(cx->fork, stream));
+        PA_HIP_TRY(hipStreamWaitEvent(cx->side, cx->fork, 0));
         rs = cx->side;
     }
     {
         const int e1 = launch_resolve(p, defer_cap, keys_cap, idx->num_cus, rs);
         if (e1) return fail(PA_ERR_HIP, "resolve launch: %s", hipGetErrorString((hipError_t)e1));
     }
-    if (timing) HIP_TRY(hipEventRecord(cx->ev2, rs));
+    if (timing) PA_HIP_TRY(hipEventRecord(cx->ev2, rs));
     if (overlap) {
-        HIP_TRY(hipEventRecord(cx->join, rs));
+        PA_HIP_TRY(hipEventRecord(cx->join, rs));
         const int e2 = launch_count_keys(p.keys, p.keys_top, keys_cap, p.defer_top, defer_cap, cx->keys_sorted.as<uint32_t>(), cx->keys_ctl.as<uint32_t>(),
                                          reinterpret_cast<unsigned long long*>(d_counts), counts_len, idx->num_cus, stream, n_reads, 0);
         if (e2) return fail(PA_ERR_HIP, "count launch: %s", hipGetErrorString((hipError_t)e2));
-        HIP_TRY(hipStreamWaitEvent(stream, cx->join, 0));
+        PA_HIP_TRY(hipStreamWaitEvent(stream, cx->join, 0));
     }
     if (d_counts) {
         const int e2 = launch_count_keys(p.keys, p.keys_top, keys_cap, p.defer_top, defer_cap, cx->keys_sorted.as<uint32_t>(), cx->keys_ctl.as<uint32_t>(),
@@ -554,7 +531,7 @@ static int map_launch_locked(pa_index* idx, LaunchCtx* cx, const uint64_t* d_til
             if (rc != PA_OK) return rc;
         }
     }
-    if (timing) HIP_TRY(hipEventRecord(cx->ev3, stream));
+    if (timing) PA_HIP_TRY(hipEventRecord(cx->ev3, stream));
     return PA_OK;
 }
 
@@ -562,12 +539,12 @@ static int map_finish_locked(pa_index* idx, LaunchCtx* cx, hipStream_t stream, u
     // (the control block comes back ON the launch's stream: a plain hipMemcpy runs on the null stream and waits for every other stream
     // of the process — a caller that copies its next batch in on another stream meanwhile would find this call waiting for that copy)
     struct { unsigned long long top; uint32_t status; uint32_t pad; } ctl;
-    HIP_TRY(hipMemcpyAsync(&ctl, cx->ctl.p, 16, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
+    PA_HIP_TRY(hipMemcpyAsync(&ctl, cx->ctl.get(), 16, hipMemcpyDeviceToHost, stream));
+    PA_HIP_TRY(hipStreamSynchronize(stream));
     if (env_int("PA_MAP_STATS", 0)) {
         constexpr uint32_t NS = ST_COUNT + 4;   // ST_NSTAT of map_pool.hip: one entry per state, the dual iterations, the forward step in three parts
         unsigned long long d[3 * NS];
-        HIP_TRY(hipMemcpy(d, cx->ctl.as<unsigned long long>() + 2, sizeof d, hipMemcpyDeviceToHost));
+        PA_HIP_TRY(hipMemcpy(d, cx->ctl.as<unsigned long long>() + 2, sizeof d, hipMemcpyDeviceToHost));
         static const char* names[NS] = {"refill", "seek", "fwd", "left", "pick+pop", "store+push", "fin_light", "fin_scan", "fin_coop", "fin_bits", "fin_mask", "fwd+seek", "fwd:issue", "fwd:wait", "fwd:wait+compute"};
         fprintf(stderr, "[pa map stats] grid=%u", cx->last_grid);
         for (uint32_t i = 0; i < NS; ++i)
@@ -575,7 +552,7 @@ static int map_finish_locked(pa_index* idx, LaunchCtx* cx, hipStream_t stream, u
                 fprintf(stderr, " %s: %llu iters x %.1f lanes, %.0f ticks/iter;", names[i], d[i], (double)d[NS + i] / (double)d[i],
                         (double)d[2 * NS + i] / (double)d[i]);
         unsigned long long tops[2];
-        HIP_TRY(hipMemcpy(tops, cx->ctl.as<unsigned long long>() + 57, sizeof tops, hipMemcpyDeviceToHost));
+        PA_HIP_TRY(hipMemcpy(tops, cx->ctl.as<unsigned long long>() + 57, sizeof tops, hipMemcpyDeviceToHost));
         fprintf(stderr, " key stream %llu entries, deferred stream %llu entries\n", tops[0], tops[1]);
     }
     // the counter includes every wave's partly used chunk and may run past the caller's arena without any allocation having
@@ -617,7 +594,7 @@ int pa_map_batch_device(pa_index* idx, const uint64_t* d_tiles, const uint32_t* 
     const int rc0 = ctx_of(idx, static_cast<hipStream_t>(stream), &cx);
     if (rc0 != PA_OK) return rc0;
     std::lock_guard<std::mutex> g(cx->mu);
-    HIP_TRY(hipSetDevice(idx->device));
+    PA_HIP_TRY(hipSetDevice(idx->device));
     return map_launch_locked(idx, cx.get(), d_tiles, d_lens, n_reads, words_per_read, allowed_mismatches, d_results, d_arena, arena_cap, d_colour,
                              nullptr, nullptr, nullptr, static_cast<hipStream_t>(stream));
 }
@@ -630,7 +607,7 @@ int pa_map_count_batch_device(pa_index* idx, const uint64_t* d_tiles, const uint
     const int rc0 = ctx_of(idx, static_cast<hipStream_t>(stream), &cx);
     if (rc0 != PA_OK) return rc0;
     std::lock_guard<std::mutex> g(cx->mu);
-    HIP_TRY(hipSetDevice(idx->device));
+    PA_HIP_TRY(hipSetDevice(idx->device));
     return map_launch_locked(idx, cx.get(), d_tiles, d_lens, n_reads, words_per_read, allowed_mismatches, d_results, d_arena, arena_cap, nullptr,
                              d_counts, nullptr, nullptr, static_cast<hipStream_t>(stream));
 }
@@ -641,7 +618,7 @@ int pa_map_count_batch_uniform_device(pa_index* idx, const uint64_t* d_tiles, ui
     if (!idx || !d_counts || (n_reads && (!d_tiles || !d_results || !d_arena))) return fail(PA_ERR_INVALID_ARG, "null argument");
     if (read_len == 0 || read_len > PA_MAX_READ_LEN || read_len > 32ull * words_per_read)
         return fail(PA_ERR_INVALID_ARG, "read_len %u does not fit %u words per read (or exceeds %u bases)", read_len, words_per_read, PA_MAX_READ_LEN);
-    HIP_TRY(hipSetDevice(idx->device));
+    PA_HIP_TRY(hipSetDevice(idx->device));
     std::shared_ptr<LaunchCtx> cx;
     int rc = ctx_of(idx, static_cast<hipStream_t>(stream), &cx);
     if (rc != PA_OK) return rc;
@@ -656,7 +633,7 @@ int pa_map_finish(pa_index* idx, void* stream, uint64_t* arena_used, uint64_t* a
     const int rc0 = ctx_of(idx, static_cast<hipStream_t>(stream), &cx);
     if (rc0 != PA_OK) return rc0;
     std::lock_guard<std::mutex> g(cx->mu);
-    HIP_TRY(hipSetDevice(idx->device));
+    PA_HIP_TRY(hipSetDevice(idx->device));
     return map_finish_locked(idx, cx.get(), static_cast<hipStream_t>(stream), arena_used, arena_needed);
 }
 
@@ -674,8 +651,8 @@ int pa_map_kernel_ms(pa_index* idx, void* stream, float* ms) {
     if (rc0 != PA_OK) return rc0;
     std::lock_guard<std::mutex> g(cx->mu);
     if (!cx->timed) return fail(PA_ERR_INVALID_ARG, "no timed launch on this stream (pa_index_set_timing before the launch)");
-    HIP_TRY(hipEventSynchronize(cx->ev1));
-    HIP_TRY(hipEventElapsedTime(ms, cx->ev0, cx->ev1));
+    PA_HIP_TRY(hipEventSynchronize(cx->ev1));
+    PA_HIP_TRY(hipEventElapsedTime(ms, cx->ev0, cx->ev1));
     return PA_OK;
 }
 
@@ -686,10 +663,10 @@ int pa_map_stage_ms(pa_index* idx, void* stream, float ms[3]) {
     if (rc0 != PA_OK) return rc0;
     std::lock_guard<std::mutex> g(cx->mu);
     if (!cx->timed) return fail(PA_ERR_INVALID_ARG, "no timed launch on this stream (pa_index_set_timing before the launch)");
-    HIP_TRY(hipEventSynchronize(cx->ev3));
-    HIP_TRY(hipEventElapsedTime(&ms[0], cx->ev0, cx->ev1));
-    HIP_TRY(hipEventElapsedTime(&ms[1], cx->ev1, cx->ev2));
-    HIP_TRY(hipEventElapsedTime(&ms[2], cx->ev2, cx->ev3));
+    PA_HIP_TRY(hipEventSynchronize(cx->ev3));
+    PA_HIP_TRY(hipEventElapsedTime(&ms[0], cx->ev0, cx->ev1));
+    PA_HIP_TRY(hipEventElapsedTime(&ms[1], cx->ev1, cx->ev2));
+    PA_HIP_TRY(hipEventElapsedTime(&ms[2], cx->ev2, cx->ev3));
     return PA_OK;
 }
 
@@ -731,7 +708,7 @@ static int map_batch_host(pa_index* idx, const HostReads& in, uint64_t n, uint32
     const int rc0 = ctx_of(idx, nullptr, &cx);
     if (rc0 != PA_OK) return rc0;
     std::lock_guard<std::mutex> g(cx->mu);
-    HIP_TRY(hipSetDevice(idx->device));
+    PA_HIP_TRY(hipSetDevice(idx->device));
     uint64_t maxlen = 1;
     for (uint64_t i = 0; i < n; ++i) {
         if (packed) {
@@ -747,8 +724,8 @@ static int map_batch_host(pa_index* idx, const HostReads& in, uint64_t n, uint32
     const uint32_t wpr = pa_words_per_read((uint32_t)maxlen);
     hipStream_t st = nullptr;
     int rc;
-    if ((rc = idx->b_tiles.ensure(pa_tiles_words(n, wpr) * 8 + 8)) || (rc = idx->b_lens.ensure((n + 64) * 4)) ||
-        (rc = idx->b_results.ensure((n + 1) * sizeof(pa_read_result))))
+    if ((rc = grow(idx->b_tiles, pa_tiles_words(n, wpr) * 8 + 8)) || (rc = grow(idx->b_lens, (n + 64) * 4)) ||
+        (rc = grow(idx->b_results, (n + 1) * sizeof(pa_read_result))))
         return rc;
     if (n == 0) { if (class_offsets) class_offsets[0] = 0; if (class_ids) *class_ids = nullptr; return PA_OK; }
     if (packed) {   // the words go into the tile layout on the host (bases beyond a read's length cleared, as the encoder leaves them)
@@ -764,31 +741,31 @@ static int map_batch_host(pa_index* idx, const HostReads& in, uint64_t n, uint32
                 dst[(uint64_t)j * 64] = v;
             }
         }
-        HIP_TRY(hipMemcpyAsync(idx->b_tiles.p, tiles.data(), tiles.size() * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(idx->b_lens.p, in.lens, n * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));   // (`tiles` is pageable and dies with this block)
+        PA_HIP_TRY(hipMemcpyAsync(idx->b_tiles.get(), tiles.data(), tiles.size() * 8, hipMemcpyHostToDevice, st));
+        PA_HIP_TRY(hipMemcpyAsync(idx->b_lens.get(), in.lens, n * 4, hipMemcpyHostToDevice, st));
+        PA_HIP_TRY(hipStreamSynchronize(st));   // (`tiles` is pageable and dies with this block)
     } else {
         const uint64_t total_ascii = in.offsets[n] - in.offsets[0];
-        if ((rc = idx->b_ascii.ensure(total_ascii + 64)) || (rc = idx->b_offsets.ensure((n + 1) * 8))) return rc;
+        if ((rc = grow(idx->b_ascii, total_ascii + 64)) || (rc = grow(idx->b_offsets, (n + 1) * 8))) return rc;
         std::vector<uint64_t> rel(n + 1);
         for (uint64_t i = 0; i <= n; ++i) rel[i] = in.offsets[i] - in.offsets[0];
-        HIP_TRY(hipMemcpyAsync(idx->b_ascii.p, in.ascii + in.offsets[0], total_ascii, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(idx->b_offsets.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
+        PA_HIP_TRY(hipMemcpyAsync(idx->b_ascii.get(), in.ascii + in.offsets[0], total_ascii, hipMemcpyHostToDevice, st));
+        PA_HIP_TRY(hipMemcpyAsync(idx->b_offsets.get(), rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
         int e = launch_encode(idx->b_ascii.as<uint8_t>(), idx->b_offsets.as<uint64_t>(), n, wpr, idx->b_tiles.as<uint64_t>(),
                               idx->b_lens.as<uint32_t>(), st);
         if (e) return fail(PA_ERR_HIP, "encode launch: %s", hipGetErrorString((hipError_t)e));
-        HIP_TRY(hipStreamSynchronize(st));   // (`rel` is pageable and dies with this block)
+        PA_HIP_TRY(hipStreamSynchronize(st));   // (`rel` is pageable and dies with this block)
     }
     const uint32_t spill_cap = spill_cap_of(wpr);
     uint32_t *d_nodes = nullptr, *d_nodes_len = nullptr;
     if (nodes_flat) {
-        if ((rc = idx->b_nodes.ensure(n * spill_cap * 4)) || (rc = idx->b_nodes_len.ensure(n * 4))) return rc;
+        if ((rc = grow(idx->b_nodes, n * spill_cap * 4)) || (rc = grow(idx->b_nodes_len, n * 4))) return rc;
         d_nodes = idx->b_nodes.as<uint32_t>();
         d_nodes_len = idx->b_nodes_len.as<uint32_t>();
     }
     uint64_t cap = pa_map_arena_hint(idx, n), used = 0, need = 0;
     for (int attempt = 0;; ++attempt) {
-        if ((rc = idx->b_arena.ensure(cap * 4))) return rc;
+        if ((rc = grow(idx->b_arena, cap * 4))) return rc;
         rc = map_launch_locked(idx, cx.get(), idx->b_tiles.as<uint64_t>(), idx->b_lens.as<uint32_t>(), n, wpr, allowed,
                                idx->b_results.as<pa_read_result>(), idx->b_arena.as<uint32_t>(), cap, nullptr, nullptr, d_nodes, d_nodes_len, st);
         if (rc != PA_OK) return rc;
@@ -797,9 +774,9 @@ static int map_batch_host(pa_index* idx, const HostReads& in, uint64_t n, uint32
         if (rc != PA_OK) return rc;
         break;
     }
-    HIP_TRY(hipMemcpy(results, idx->b_results.p, n * sizeof(pa_read_result), hipMemcpyDeviceToHost));
+    PA_HIP_TRY(hipMemcpy(results, idx->b_results.get(), n * sizeof(pa_read_result), hipMemcpyDeviceToHost));
     idx->h_arena.resize(used + 1);
-    if (used) HIP_TRY(hipMemcpy(idx->h_arena.data(), idx->b_arena.p, used * 4, hipMemcpyDeviceToHost));
+    if (used) PA_HIP_TRY(hipMemcpy(idx->h_arena.data(), idx->b_arena.get(), used * 4, hipMemcpyDeviceToHost));
     if (class_offsets || class_ids) {
         uint64_t total = 0;
         for (uint64_t i = 0; i < n; ++i) total += results[i].class_len;
@@ -821,8 +798,8 @@ static int map_batch_host(pa_index* idx, const HostReads& in, uint64_t n, uint32
     }
     if (nodes_flat) {
         std::vector<uint32_t> hn(n * (size_t)spill_cap), hl(n);
-        HIP_TRY(hipMemcpy(hn.data(), d_nodes, hn.size() * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(hl.data(), d_nodes_len, n * 4, hipMemcpyDeviceToHost));
+        PA_HIP_TRY(hipMemcpy(hn.data(), d_nodes, hn.size() * 4, hipMemcpyDeviceToHost));
+        PA_HIP_TRY(hipMemcpy(hl.data(), d_nodes_len, n * 4, hipMemcpyDeviceToHost));
         for (uint64_t i = 0; i < n; ++i) {
             nodes_len[i] = hl[i];
             const uint32_t m = std::min(std::min(hl[i], spill_cap), nodes_stride_cap);
@@ -925,8 +902,8 @@ int pa_map_batch_nodes(pa_index* idx, const uint8_t* ascii, const uint64_t* offs
 int pa_counts_by_barcode_device(pa_index* idx, const pa_read_result* d_results, const uint32_t* d_arena, const uint32_t* d_barcode, uint64_t n_reads,
                                 uint32_t barcode_bits, uint64_t* d_keys, uint32_t* d_vals, uint64_t* n_entries, void* stream) {
     if (!idx || !n_entries || (n_reads && (!d_results || !d_arena || !d_barcode || !d_keys || !d_vals))) return fail(PA_ERR_INVALID_ARG, "null argument");
-    HIP_TRY(hipSetDevice(idx->device));
-    return barcode_counts(idx->dv, static_cast<const uint32_t*>(idx->d_class_table), idx->class_table_size, d_results, d_arena, d_barcode, n_reads,
+    PA_HIP_TRY(hipSetDevice(idx->device));
+    return barcode_counts(idx->dv, idx->d_class_table.get(), idx->class_table_size, d_results, d_arena, d_barcode, n_reads,
                           barcode_bits, d_keys, d_vals, n_entries, static_cast<hipStream_t>(stream));
 }
 
@@ -944,8 +921,8 @@ uint64_t pa_counts_len(const pa_index* idx) { return idx ? (uint64_t)idx->stats.
 int pa_counts_accumulate_device(pa_index* idx, const pa_read_result* d_results, const uint32_t* d_arena, const uint32_t* d_colour,
                                 uint64_t n_reads, uint64_t* d_counts, void* stream) {
     if (!idx || !d_results || !d_arena || !d_counts) return fail(PA_ERR_INVALID_ARG, "null argument");
-    HIP_TRY(hipSetDevice(idx->device));
-    const int e = launch_count(d_results, d_arena, d_colour, n_reads, idx->dv, static_cast<const uint32_t*>(idx->d_class_table),
+    PA_HIP_TRY(hipSetDevice(idx->device));
+    const int e = launch_count(d_results, d_arena, d_colour, n_reads, idx->dv, idx->d_class_table.get(),
                                idx->class_table_size, reinterpret_cast<unsigned long long*>(d_counts), static_cast<hipStream_t>(stream));
     if (e) return fail(PA_ERR_HIP, "count launch: %s", hipGetErrorString((hipError_t)e));
     return PA_OK;
@@ -954,9 +931,9 @@ int pa_counts_accumulate_device(pa_index* idx, const pa_read_result* d_results, 
 // ---- synthetic reads on the device ----
 struct pa_txome_device {
     int device;
-    void *d_packed, *d_tx_start, *d_cum;
     uint32_t num_tx, read_len;
     uint64_t total;
+    DeviceBuffer<uint64_t> d_packed, d_tx_start, d_cum;
 };
 
 int pa_txome_upload(const pa_txome* t, uint32_t read_len, int device, pa_txome_device** out) {
@@ -966,10 +943,10 @@ int pa_txome_upload(const pa_txome* t, uint32_t read_len, int device, pa_txome_d
     std::vector<uint64_t> cum;
     synth::build_cum(t->t.tx_start.data(), t->t.num_tx(), read_len, cum);
     if (cum.back() == 0) return fail(PA_ERR_INVALID_ARG, "no transcript is at least %u bases long", read_len);
-    pa_txome_device* d = new pa_txome_device{device, nullptr, nullptr, nullptr, t->t.num_tx(), read_len, cum.back()};
-    rc = upload(t->t.packed.data(), t->t.packed.size() * 8, &d->d_packed);
-    if (rc == PA_OK) rc = upload(t->t.tx_start.data(), t->t.tx_start.size() * 8, &d->d_tx_start);
-    if (rc == PA_OK) rc = upload(cum.data(), cum.size() * 8, &d->d_cum);
+    pa_txome_device* d = new pa_txome_device{device, t->t.num_tx(), read_len, cum.back()};
+    rc = upload(d->d_packed, t->t.packed);
+    if (rc == PA_OK) rc = upload(d->d_tx_start, t->t.tx_start);
+    if (rc == PA_OK) rc = upload(d->d_cum, cum);
     if (rc != PA_OK) { pa_txome_device_destroy(d); return rc; }
     *out = d;
     return PA_OK;
@@ -978,8 +955,6 @@ int pa_txome_upload(const pa_txome* t, uint32_t read_len, int device, pa_txome_d
 void pa_txome_device_destroy(pa_txome_device* t) {
     if (!t) return;
     (void)hipSetDevice(t->device);
-    for (void* p : {t->d_packed, t->d_tx_start, t->d_cum})
-        if (p) (void)hipFree(p);
     delete t;
 }
 
@@ -987,9 +962,8 @@ int pa_simulate_reads_device(const pa_txome_device* t, uint64_t seed, uint32_t s
                              uint32_t words_per_read, uint64_t* d_tiles, uint32_t* d_lens, void* stream) {
     if (!t || !d_tiles || !d_lens) return fail(PA_ERR_INVALID_ARG, "null argument");
     if (words_per_read < (t->read_len + 31) / 32) return fail(PA_ERR_INVALID_ARG, "words_per_read too small");
-    HIP_TRY(hipSetDevice(t->device));
-    const int e = launch_simulate(static_cast<const uint64_t*>(t->d_packed), static_cast<const uint64_t*>(t->d_tx_start),
-                                  static_cast<const uint64_t*>(t->d_cum), t->num_tx, t->total, t->read_len, seed, sub_rate_ppm, first_read,
+    PA_HIP_TRY(hipSetDevice(t->device));
+    const int e = launch_simulate(t->d_packed.get(), t->d_tx_start.get(), t->d_cum.get(), t->num_tx, t->total, t->read_len, seed, sub_rate_ppm, first_read,
                                   n_reads, words_per_read, d_tiles, d_lens, static_cast<hipStream_t>(stream));
     if (e) return fail(PA_ERR_HIP, "simulate launch: %s", hipGetErrorString((hipError_t)e));
     return PA_OK;
@@ -999,17 +973,17 @@ int pa_simulate_reads_device(const pa_txome_device* t, uint64_t seed, uint32_t s
 int pa_event_create(void** ev) {
     if (!ev) return fail(PA_ERR_INVALID_ARG, "null argument");
     hipEvent_t e;
-    HIP_TRY(hipEventCreate(&e));
+    PA_HIP_TRY(hipEventCreate(&e));
     *ev = e;
     return PA_OK;
 }
-int pa_event_record(void* ev, void* stream) { HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(ev), static_cast<hipStream_t>(stream))); return PA_OK; }
+int pa_event_record(void* ev, void* stream) { PA_HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(ev), static_cast<hipStream_t>(stream))); return PA_OK; }
 int pa_event_elapsed_ms(void* start, void* stop, float* ms) {
-    HIP_TRY(hipEventSynchronize(static_cast<hipEvent_t>(stop)));
-    HIP_TRY(hipEventElapsedTime(ms, static_cast<hipEvent_t>(start), static_cast<hipEvent_t>(stop)));
+    PA_HIP_TRY(hipEventSynchronize(static_cast<hipEvent_t>(stop)));
+    PA_HIP_TRY(hipEventElapsedTime(ms, static_cast<hipEvent_t>(start), static_cast<hipEvent_t>(stop)));
     return PA_OK;
 }
-int pa_event_destroy(void* ev) { HIP_TRY(hipEventDestroy(static_cast<hipEvent_t>(ev))); return PA_OK; }
+int pa_event_destroy(void* ev) { PA_HIP_TRY(hipEventDestroy(static_cast<hipEvent_t>(ev))); return PA_OK; }
 
 int pa_device_malloc(int device, size_t bytes, void** out) {
     if (!out) return fail(PA_ERR_INVALID_ARG, "null argument");
@@ -1019,20 +993,20 @@ int pa_device_malloc(int device, size_t bytes, void** out) {
     if (e != hipSuccess) return fail(PA_ERR_OOM, "hipMalloc(%zu): %s", bytes, hipGetErrorString(e));
     return PA_OK;
 }
-int pa_device_free(void* p) { if (p) HIP_TRY(hipFree(p)); return PA_OK; }
+int pa_device_free(void* p) { if (p) PA_HIP_TRY(hipFree(p)); return PA_OK; }
 int pa_memcpy_h2d(void* dst, const void* src, size_t bytes, void* stream) {
-    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, static_cast<hipStream_t>(stream)));
+    PA_HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, static_cast<hipStream_t>(stream)));
     return PA_OK;
 }
 int pa_memcpy_d2h(void* dst, const void* src, size_t bytes, void* stream) {
-    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, static_cast<hipStream_t>(stream)));
-    HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    PA_HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, static_cast<hipStream_t>(stream)));
+    PA_HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
     return PA_OK;
 }
 int pa_memset_device(void* dst, int value, size_t bytes, void* stream) {
-    HIP_TRY(hipMemsetAsync(dst, value, bytes, static_cast<hipStream_t>(stream)));
+    PA_HIP_TRY(hipMemsetAsync(dst, value, bytes, static_cast<hipStream_t>(stream)));
     return PA_OK;
 }
-int pa_stream_synchronize(void* stream) { HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream))); return PA_OK; }
+int pa_stream_synchronize(void* stream) { PA_HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream))); return PA_OK; }
 
 }  // extern "C"

@@ -127,8 +127,6 @@ void for_each_newline(const char* d, uint64_t from, uint64_t to, F&& fn) {
         if (d[i] == '\n' && !fn(i)) return;
 }
 
-#define HIP_OK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(PA_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
-
 // The parallel scan finds records by counting lines, four to a record. A file that does not have that shape — sequence or
 // qualities wrapped over several lines, which bio's fastq::Reader (the reference's reader) accepts — is first rewritten
 // into it by this sequential reader: header line '@...', sequence lines up to the line that starts with '+', then as many
@@ -691,7 +689,7 @@ struct TextPipe {
             if (e != PA_OK) return e;
             uint64_t cum = 0, bucket = 0;
             while (next_report <= w.first_read + c.n) {   // :497-503: the counts of exactly the first 10^6 m reads
-                if (bucket < FLAG_BUCKETS) cum += c.h_tot[1 + bucket];
+                if (bucket < FLAG_BUCKETS) cum += c.h_tot.get()[1 + bucket];
                 ++bucket;
                 fprintf(stderr, "\rDone Mapping %llu reads w/ Rate: %s", (unsigned long long)next_report,
                         rust_f32((float)(flagged + cum) * 100.0f / (float)next_report).c_str());
@@ -700,7 +698,7 @@ struct TextPipe {
             }
             flagged += c.flagged;
             reported += c.n;
-            l.text_job[w.slot] = writer.push(c.h_text, c.text_bytes);
+            l.text_job[w.slot] = writer.push(c.h_text.get(), c.text_bytes);
             wins.pop_front();
         }
         return PA_OK;
@@ -838,18 +836,18 @@ int process_reads_impl(pa_index* const* idxs, int nidx, const char* fastq_path, 
             const double t0 = TextPipe::now();
             if (hipEventSynchronize(c.ev_info) != hipSuccess) return fail(PA_ERR_HIP, "waiting for the FASTQ scan failed");
             tp.t_wait += TextPipe::now() - t0;
-            if (!c.h_info->overflow) break;
+            if (!c.h_info.get()->overflow) break;
             if (attempt == 2) return fail(PA_ERR_INTERNAL, "FASTQ scan: line table too small after regrowing");
             ++tp.rescans;   // more lines than guessed (short reads): grow the line table, fill it again from the counts already there
-            if ((e = window_ensure_scan(c, c.h_info->lines)) != PA_OK) return e;
+            if ((e = window_ensure_scan(c, c.h_info.get()->lines)) != PA_OK) return e;
             if ((e = window_scan_enqueue(c, true, l.scan)) != PA_OK) return e;
         }
-        if (c.h_info->odd) return WIN_ODD;
-        if (c.h_info->n == 0) return WIN_EMPTY;
-        if (c.h_info->max_seq > PA_MAX_READ_LEN) return fail(PA_ERR_UNSUPPORTED, "read longer than %u bases", PA_MAX_READ_LEN);
-        c.n = c.h_info->n;
-        c.wpr = pa_words_per_read(c.h_info->max_seq ? c.h_info->max_seq : 1);
-        rec_start = pending.from + c.h_info->consumed;
+        if (c.h_info.get()->odd) return WIN_ODD;
+        if (c.h_info.get()->n == 0) return WIN_EMPTY;
+        if (c.h_info.get()->max_seq > PA_MAX_READ_LEN) return fail(PA_ERR_UNSUPPORTED, "read longer than %u bases", PA_MAX_READ_LEN);
+        c.n = c.h_info.get()->n;
+        c.wpr = pa_words_per_read(c.h_info.get()->max_seq ? c.h_info.get()->max_seq : 1);
+        rec_start = pending.from + c.h_info.get()->consumed;
         tp.wins.push_back(pending);
         ++tp.gpu_windows;
         return tp.launch(tp.wins.back());
@@ -870,7 +868,7 @@ int process_reads_impl(pa_index* const* idxs, int nidx, const char* fastq_path, 
         if (e != PA_OK) return e;
         p.l = &tp.lane_of(id);
         if ((e = window_ensure_raw(*p.c, WINDOW_HEAD_ROOM + p.main_len)) != PA_OK) return e;
-        tp.read_begin(read_to, p.main_len, p.c->h_raw + WINDOW_HEAD_ROOM);
+        tp.read_begin(read_to, p.main_len, p.c->h_raw.get() + WINDOW_HEAD_ROOM);
         read_to += p.main_len;
         p.active = true;
         return PA_OK;
@@ -896,7 +894,7 @@ int process_reads_impl(pa_index* const* idxs, int nidx, const char* fastq_path, 
         for (size_t o = 0; o < lanes.size() && lane_serial; ++o)
             if (&lanes[o] != &l && lanes[o].device == l.device && lanes[o].last_h2d && hipStreamWaitEvent(l.copy, lanes[o].last_h2d, 0) != hipSuccess) { rc = fail(PA_ERR_HIP, "hipStreamWaitEvent failed"); break; }
         if (rc != PA_OK) break;
-        if (hipMemcpyAsync((uint8_t*)c.d_raw + WINDOW_HEAD_ROOM, c.h_raw + WINDOW_HEAD_ROOM, main_len, hipMemcpyHostToDevice, l.copy) != hipSuccess ||
+        if (hipMemcpyAsync(c.d_raw.get() + WINDOW_HEAD_ROOM, c.h_raw.get() + WINDOW_HEAD_ROOM, main_len, hipMemcpyHostToDevice, l.copy) != hipSuccess ||
             hipEventRecord(c.ev_h2d, l.copy) != hipSuccess) { rc = fail(PA_ERR_HIP, "copy of a text window to the GPU failed"); break; }
         l.last_h2d = c.ev_h2d;
         if (verbose) (void)hipEventRecord(vt1[id % 8], l.copy);
@@ -921,8 +919,8 @@ int process_reads_impl(pa_index* const* idxs, int nidx, const char* fastq_path, 
         }
         t0 = TextPipe::now();
         if (head) {
-            if ((rc = tp.read_small(rec_start, head, c.h_raw + WINDOW_HEAD_ROOM - head)) != PA_OK) break;
-            if (hipMemcpyAsync((uint8_t*)c.d_raw + WINDOW_HEAD_ROOM - head, c.h_raw + WINDOW_HEAD_ROOM - head, head, hipMemcpyHostToDevice, l.scan) != hipSuccess) { rc = fail(PA_ERR_HIP, "copy of a window's head failed"); break; }
+            if ((rc = tp.read_small(rec_start, head, c.h_raw.get() + WINDOW_HEAD_ROOM - head)) != PA_OK) break;
+            if (hipMemcpyAsync(c.d_raw.get() + WINDOW_HEAD_ROOM - head, c.h_raw.get() + WINDOW_HEAD_ROOM - head, head, hipMemcpyHostToDevice, l.scan) != hipSuccess) { rc = fail(PA_ERR_HIP, "copy of a window's head failed"); break; }
         }
         tp.t_read += TextPipe::now() - t0; t0 = TextPipe::now();
         c.raw_begin = WINDOW_HEAD_ROOM - head;
@@ -985,7 +983,7 @@ int process_reads_impl(pa_index* const* idxs, int nidx, const char* fastq_path, 
                     const int ntask = (int)std::max<uint64_t>(1, std::min<uint64_t>((bytes + PIECE - 1) / PIECE, 1u << 20));
                     pool.run(ntask, [&](int t) {
                         const uint64_t a = bytes * (uint64_t)t / (uint64_t)ntask, b = bytes * (uint64_t)(t + 1) / (uint64_t)ntask;
-                        memcpy(c.h_raw + WINDOW_HEAD_ROOM + a, src + a, (size_t)(b - a));
+                        memcpy(c.h_raw.get() + WINDOW_HEAD_ROOM + a, src + a, (size_t)(b - a));
                     });
                 }
                 const int T4 = pool.size() * 4;
@@ -996,7 +994,7 @@ int process_reads_impl(pa_index* const* idxs, int nidx, const char* fastq_path, 
                         const RecPos& r = rp[i0 + i];
                         const uint64_t seq_off = std::min<uint64_t>(r.start + r.hdr + 1, ws.size);
                         const uint32_t seq_len = (uint32_t)std::min<uint64_t>(r.seq_len, ws.size - seq_off);
-                        c.h_rec[i] = make_uint4((uint32_t)(WINDOW_HEAD_ROOM + r.start + 1 - first), r.id_len, (uint32_t)(WINDOW_HEAD_ROOM + seq_off - first), seq_len);
+                        c.h_rec.get()[i] = make_uint4((uint32_t)(WINDOW_HEAD_ROOM + r.start + 1 - first), r.id_len, (uint32_t)(WINDOW_HEAD_ROOM + seq_off - first), seq_len);
                         mx = std::max(mx, seq_len);
                     }
                     tmax[(size_t)t] = mx;
@@ -1006,8 +1004,8 @@ int process_reads_impl(pa_index* const* idxs, int nidx, const char* fastq_path, 
                 tp.t_read += TextPipe::now() - t0;
                 if (maxlen > PA_MAX_READ_LEN) { rc = fail(PA_ERR_UNSUPPORTED, "read longer than %u bases", PA_MAX_READ_LEN); break; }
                 // (the copies ride on the lane's kernel stream: this path is bound by the host's scan, not by the link)
-                if (hipMemcpyAsync((uint8_t*)c.d_raw + WINDOW_HEAD_ROOM, c.h_raw + WINDOW_HEAD_ROOM, bytes, hipMemcpyHostToDevice, l.stream) != hipSuccess ||
-                    hipMemcpyAsync(c.d_rec, c.h_rec, n * sizeof(uint4), hipMemcpyHostToDevice, l.stream) != hipSuccess) { rc = fail(PA_ERR_HIP, "copy of a text window to the GPU failed"); break; }
+                if (hipMemcpyAsync(c.d_raw.get() + WINDOW_HEAD_ROOM, c.h_raw.get() + WINDOW_HEAD_ROOM, bytes, hipMemcpyHostToDevice, l.stream) != hipSuccess ||
+                    hipMemcpyAsync(c.d_rec.get(), c.h_rec.get(), n * sizeof(uint4), hipMemcpyHostToDevice, l.stream) != hipSuccess) { rc = fail(PA_ERR_HIP, "copy of a text window to the GPU failed"); break; }
                 c.raw_begin = WINDOW_HEAD_ROOM;
                 c.raw_end = WINDOW_HEAD_ROOM + bytes;
                 c.n = n;

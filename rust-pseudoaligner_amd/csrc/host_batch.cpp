@@ -9,21 +9,24 @@
 #include <new>
 #include <vector>
 
+#include "hip_buffer.hpp"
 #include "pa_common.hpp"
 
 using namespace pa;
 
 namespace {
 
-#define HB_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(PA_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
-
 constexpr int MAX_STREAMS = 8;
 
 struct Stage {   // one chunk in flight
     hipStream_t stream = nullptr;
-    void *d_tiles = nullptr, *d_lens = nullptr, *d_res = nullptr, *d_arena = nullptr, *d_compact = nullptr, *d_packed = nullptr, *d_pw = nullptr, *d_scr = nullptr;
-    uint64_t cap_reads = 0, arena_cap = 0, tiles_words = 0;
-    size_t scr_bytes = 0;
+    DeviceBuffer<uint64_t> tiles;
+    DeviceBuffer<uint32_t> lens;
+    DeviceBuffer<pa_read_result> res;
+    DeviceBuffer<uint64_t> compact, pw;
+    DeviceBuffer<uint8_t> scr;
+    DeviceBuffer<uint32_t> arena, packed;
+    uint64_t cap_reads = 0, arena_cap = 0;
     hipEvent_t ev_in = nullptr, ev_out = nullptr, ev_back = nullptr;   // the chunk's tiles have arrived | its outputs are ready on the device | ... and on the host
     int64_t busy = -1;   // the chunk whose outputs are on their way
 };
@@ -34,9 +37,8 @@ struct HostPipe {
     Stage st[MAX_STREAMS];
     // dedicated copy streams (A/B in knobs builds: see run())
     hipStream_t s_in = nullptr, s_back = nullptr, s_in2 = nullptr;
-    void* d_counts = nullptr;
-    uint64_t counts_len = 0;
-    unsigned long long* h_pw = nullptr;   // pinned: words of every stage's packed classes
+    DeviceBuffer<uint64_t> counts;
+    PinnedBuffer<unsigned long long> h_pw;   // words of every stage's packed classes
     static void destroy(void* p) {
         HostPipe* h = static_cast<HostPipe*>(p);
         (void)hipSetDevice(h->device);
@@ -46,65 +48,46 @@ struct HostPipe {
             for (hipEvent_t e : {s.ev_in, s.ev_out, s.ev_back})
                 if (e) (void)hipEventDestroy(e);
             if (s.stream) { (void)hipStreamSynchronize(s.stream); if (h->idx) (void)pa_index_release_stream(h->idx, s.stream); (void)hipStreamDestroy(s.stream); }
-            for (void* q : {s.d_tiles, s.d_lens, s.d_res, s.d_arena, s.d_compact, s.d_packed, s.d_pw, s.d_scr})
-                if (q) (void)hipFree(q);
         }
-        if (h->d_counts) (void)hipFree(h->d_counts);
-        if (h->h_pw) (void)hipHostFree(h->h_pw);
-        delete h;
+        delete h;   // (the buffers, with the device still current)
     }
 };
 
-int stage_ensure(pa_index* idx, Stage& s, uint64_t chunk, uint32_t wpr, bool lens) {
+int stage_ensure(pa_index* idx, Stage& s, uint64_t chunk, uint32_t wpr) {
     if (!s.stream) {
-        HB_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-        HB_HIP(hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming));
-        HB_HIP(hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming));
-        HB_HIP(hipEventCreateWithFlags(&s.ev_back, hipEventDisableTiming));
+        PA_HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+        PA_HIP_TRY(hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming));
+        PA_HIP_TRY(hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming));
+        PA_HIP_TRY(hipEventCreateWithFlags(&s.ev_back, hipEventDisableTiming));
     }
-    const uint64_t tw = pa_tiles_words(chunk, wpr);
-    if (tw > s.tiles_words) {
-        if (s.d_tiles) (void)hipFree(s.d_tiles);
-        s.d_tiles = nullptr; s.tiles_words = 0;
-        HB_HIP(hipMalloc(&s.d_tiles, tw * 8 + 64));
-        s.tiles_words = tw;
-    }
+    const uint64_t tw = pa_tiles_words(chunk, wpr) + 8;   // (64 spare bytes)
+    int e = s.tiles.reserve(tw, tw);
+    if (e != PA_OK) return e;
     if (chunk > s.cap_reads) {
-        for (void** q : {&s.d_lens, &s.d_res, &s.d_compact, &s.d_scr}) { if (*q) (void)hipFree(*q); *q = nullptr; }
         s.cap_reads = 0;
-        HB_HIP(hipMalloc(&s.d_lens, chunk * 4 + 64));
-        HB_HIP(hipMalloc(&s.d_res, chunk * sizeof(pa_read_result)));
-        HB_HIP(hipMalloc(&s.d_compact, chunk * 8));
-        s.scr_bytes = pa_compact_scratch_bytes(chunk);
-        HB_HIP(hipMalloc(&s.d_scr, s.scr_bytes));
+        s.lens.release(); s.res.release(); s.compact.release(); s.scr.release();
+        if ((e = s.lens.alloc(chunk + 16)) || (e = s.res.alloc(chunk)) || (e = s.compact.alloc(chunk)) || (e = s.scr.alloc(pa_compact_scratch_bytes(chunk)))) return e;
         s.cap_reads = chunk;
     }
-    (void)lens;
     const uint64_t hint = pa_map_arena_hint(idx, chunk);
     if (hint > s.arena_cap) {
-        for (void** q : {&s.d_arena, &s.d_packed}) { if (*q) (void)hipFree(*q); *q = nullptr; }
         s.arena_cap = 0;
-        HB_HIP(hipMalloc(&s.d_arena, hint * 4));
-        HB_HIP(hipMalloc(&s.d_packed, hint * 4));
+        s.arena.release(); s.packed.release();
+        if ((e = s.arena.alloc(hint)) || (e = s.packed.alloc(hint))) return e;
         s.arena_cap = hint;
     }
-    if (!s.d_pw) HB_HIP(hipMalloc(&s.d_pw, 8));
-    return PA_OK;
+    return s.pw.reserve(1, 1);
 }
 
 int run(pa_index* idx, HostPipe& hp, const uint64_t* h_tiles, const uint32_t* h_lens, uint32_t uniform_len, uint64_t n, uint32_t wpr, uint32_t allowed, uint64_t* h_compact,
         uint32_t* h_packed, uint64_t packed_cap, uint64_t* packed_words, uint64_t* h_counts, uint64_t chunk, int ns) {
     const uint64_t counts_len = pa_counts_len(idx);
-    if (counts_len > hp.counts_len) {
-        if (hp.d_counts) (void)hipFree(hp.d_counts);
-        hp.d_counts = nullptr; hp.counts_len = 0;
-        HB_HIP(hipMalloc(&hp.d_counts, counts_len * 8));
-        hp.counts_len = counts_len;
-    }
-    if (!hp.h_pw) HB_HIP(hipHostMalloc((void**)&hp.h_pw, MAX_STREAMS * 8, hipHostMallocDefault));
-    if (!hp.s_in) HB_HIP(hipStreamCreateWithFlags(&hp.s_in, hipStreamNonBlocking));
-    if (!hp.s_back) HB_HIP(hipStreamCreateWithFlags(&hp.s_back, hipStreamNonBlocking));
-    if (!hp.s_in2) HB_HIP(hipStreamCreateWithFlags(&hp.s_in2, hipStreamNonBlocking));
+    int rc = hp.counts.reserve(counts_len, counts_len);
+    if (rc == PA_OK) rc = hp.h_pw.reserve(MAX_STREAMS, MAX_STREAMS);
+    if (rc != PA_OK) return rc;
+    if (!hp.s_in) PA_HIP_TRY(hipStreamCreateWithFlags(&hp.s_in, hipStreamNonBlocking));
+    if (!hp.s_back) PA_HIP_TRY(hipStreamCreateWithFlags(&hp.s_back, hipStreamNonBlocking));
+    if (!hp.s_in2) PA_HIP_TRY(hipStreamCreateWithFlags(&hp.s_in2, hipStreamNonBlocking));
     // Where the copies run — measured (tools/bench_e2e.py, 100 M reads of config 3, same box, profiles/r06_e2e_copy_streams.txt): every copy on its chunk's OWN stream,
     // nothing else: 76 - 113 ms, different from call to call — with several copies of one direction queued at once the runtime runs some of them as blit KERNELS
     // (rocprofv3: 8 - 16 of the 50 tile copies, 1.4 - 4 ms each against 1.4 ms by DMA). The same streams with every copy BACK waiting for the one before it
@@ -113,56 +96,54 @@ int run(pa_index* idx, HostPipe& hp, const uint64_t* h_tiles, const uint32_t* h_
     // arrangements stay selectable in knobs builds only.
     const int in_mode = knob_int("PA_HB_IN", 0), back_mode = knob_int("PA_HB_BACK", 2);   // in: 0 = the chunk's own stream, 1 = one copy stream, 2 = two alternating, 3 = own stream, one at a time; back: 0 = own stream, 1 = one copy stream, 2 = own stream, one at a time
     for (int k = 0; k < ns; ++k) {
-        const int e = stage_ensure(idx, hp.st[k], chunk, wpr, h_lens != nullptr);
-        if (e != PA_OK) return e;
+        if ((rc = stage_ensure(idx, hp.st[k], chunk, wpr)) != PA_OK) return rc;
         hp.st[k].busy = -1;
     }
-    HB_HIP(hipMemsetAsync(hp.d_counts, 0, counts_len * 8, hp.st[0].stream));
-    HB_HIP(hipStreamSynchronize(hp.st[0].stream));
+    PA_HIP_TRY(hipMemsetAsync(hp.counts.get(), 0, counts_len * 8, hp.st[0].stream));
+    PA_HIP_TRY(hipStreamSynchronize(hp.st[0].stream));
     const uint64_t n_chunks = (n + chunk - 1) / chunk;
     uint64_t off = 0;
-    int rc = PA_OK;
     for (uint64_t c = 0; c < n_chunks + (uint64_t)ns && rc == PA_OK; ++c) {
         const int k = (int)(c % (uint64_t)ns);
         Stage& s = hp.st[k];
         if (s.busy >= 0) {   // the chunk launched ns chunks ago: its packed classes follow its records to the host
             uint64_t used = 0, need = 0;
             if ((rc = pa_map_finish(idx, s.stream, &used, &need)) != PA_OK) break;
-            HB_HIP(hipEventSynchronize(s.ev_back));   // (its records and the length of its packed stream have arrived)
-            const uint64_t words = hp.h_pw[k];
+            PA_HIP_TRY(hipEventSynchronize(s.ev_back));   // (its records and the length of its packed stream have arrived)
+            const uint64_t words = hp.h_pw.get()[k];
             if (off + words > packed_cap || words > s.arena_cap) { rc = fail(PA_ERR_ARENA_FULL, "packed classes: %llu words so far, room for %llu", (unsigned long long)(off + words), (unsigned long long)packed_cap); break; }
             const hipStream_t sb0 = back_mode == 1 ? hp.s_back : s.stream;
-            if (words) HB_HIP(hipMemcpyAsync(h_packed + off, s.d_packed, words * 4, hipMemcpyDeviceToHost, sb0));
-            HB_HIP(hipEventRecord(s.ev_back, sb0));                 // (the stage's d_packed is rewritten only behind this copy)
-            HB_HIP(hipStreamWaitEvent(s.stream, s.ev_back, 0));
+            if (words) PA_HIP_TRY(hipMemcpyAsync(h_packed + off, s.packed.get(), words * 4, hipMemcpyDeviceToHost, sb0));
+            PA_HIP_TRY(hipEventRecord(s.ev_back, sb0));                 // (the stage's d_packed is rewritten only behind this copy)
+            PA_HIP_TRY(hipStreamWaitEvent(s.stream, s.ev_back, 0));
             off += words;
             s.busy = -1;
         }
         if (c < n_chunks) {
             const uint64_t lo = c * chunk, nn = std::min<uint64_t>(chunk, n - lo);   // chunk is a multiple of 64: tile aligned
             const hipStream_t si = (in_mode == 0 || in_mode == 3) ? s.stream : (in_mode == 2 && (c & 1)) ? hp.s_in2 : hp.s_in;
-            if (in_mode == 3 && c > 0) HB_HIP(hipStreamWaitEvent(si, hp.st[(int)((c - 1) % (uint64_t)ns)].ev_in, 0));   // one copy to the GPU at a time, each on its chunk's own stream
-            HB_HIP(hipMemcpyAsync(s.d_tiles, h_tiles + (lo / 64) * wpr * 64, pa_tiles_words(nn, wpr) * 8, hipMemcpyHostToDevice, si));
-            if (h_lens) HB_HIP(hipMemcpyAsync(s.d_lens, h_lens + lo, nn * 4, hipMemcpyHostToDevice, si));
-            HB_HIP(hipEventRecord(s.ev_in, si));
-            HB_HIP(hipStreamWaitEvent(s.stream, s.ev_in, 0));
+            if (in_mode == 3 && c > 0) PA_HIP_TRY(hipStreamWaitEvent(si, hp.st[(int)((c - 1) % (uint64_t)ns)].ev_in, 0));   // one copy to the GPU at a time, each on its chunk's own stream
+            PA_HIP_TRY(hipMemcpyAsync(s.tiles.get(), h_tiles + (lo / 64) * wpr * 64, pa_tiles_words(nn, wpr) * 8, hipMemcpyHostToDevice, si));
+            if (h_lens) PA_HIP_TRY(hipMemcpyAsync(s.lens.get(), h_lens + lo, nn * 4, hipMemcpyHostToDevice, si));
+            PA_HIP_TRY(hipEventRecord(s.ev_in, si));
+            PA_HIP_TRY(hipStreamWaitEvent(s.stream, s.ev_in, 0));
             if (h_lens)
-                rc = pa_map_count_batch_device(idx, (const uint64_t*)s.d_tiles, (const uint32_t*)s.d_lens, nn, wpr, allowed, (pa_read_result*)s.d_res, (uint32_t*)s.d_arena, s.arena_cap,
-                                               (uint64_t*)hp.d_counts, s.stream);
+                rc = pa_map_count_batch_device(idx, s.tiles.get(), s.lens.get(), nn, wpr, allowed, s.res.get(), s.arena.get(), s.arena_cap,
+                                               hp.counts.get(), s.stream);
             else
-                rc = pa_map_count_batch_uniform_device(idx, (const uint64_t*)s.d_tiles, uniform_len, nn, wpr, allowed, (pa_read_result*)s.d_res, (uint32_t*)s.d_arena, s.arena_cap,
-                                                       (uint64_t*)hp.d_counts, s.stream);
+                rc = pa_map_count_batch_uniform_device(idx, s.tiles.get(), uniform_len, nn, wpr, allowed, s.res.get(), s.arena.get(), s.arena_cap,
+                                                       hp.counts.get(), s.stream);
             if (rc != PA_OK) break;
-            rc = pa_results_compact_device(idx, (const pa_read_result*)s.d_res, (const uint32_t*)s.d_arena, s.arena_cap, nn, (uint64_t*)s.d_compact, (uint32_t*)s.d_packed, s.arena_cap,
-                                           (uint64_t*)s.d_pw, s.d_scr, s.scr_bytes, s.stream);
+            rc = pa_results_compact_device(idx, s.res.get(), s.arena.get(), s.arena_cap, nn, s.compact.get(), s.packed.get(), s.arena_cap,
+                                           s.pw.get(), s.scr.get(), s.scr.size(), s.stream);
             if (rc != PA_OK) break;
-            HB_HIP(hipEventRecord(s.ev_out, s.stream));
+            PA_HIP_TRY(hipEventRecord(s.ev_out, s.stream));
             const hipStream_t sb = back_mode == 1 ? hp.s_back : s.stream;
-            HB_HIP(hipStreamWaitEvent(sb, s.ev_out, 0));
-            if (back_mode == 2 && c > 0) HB_HIP(hipStreamWaitEvent(sb, hp.st[(int)((c - 1) % (uint64_t)ns)].ev_back, 0));   // one copy back at a time
-            HB_HIP(hipMemcpyAsync(h_compact + lo, s.d_compact, nn * 8, hipMemcpyDeviceToHost, sb));
-            HB_HIP(hipMemcpyAsync(hp.h_pw + k, s.d_pw, 8, hipMemcpyDeviceToHost, sb));
-            HB_HIP(hipEventRecord(s.ev_back, sb));
+            PA_HIP_TRY(hipStreamWaitEvent(sb, s.ev_out, 0));
+            if (back_mode == 2 && c > 0) PA_HIP_TRY(hipStreamWaitEvent(sb, hp.st[(int)((c - 1) % (uint64_t)ns)].ev_back, 0));   // one copy back at a time
+            PA_HIP_TRY(hipMemcpyAsync(h_compact + lo, s.compact.get(), nn * 8, hipMemcpyDeviceToHost, sb));
+            PA_HIP_TRY(hipMemcpyAsync(hp.h_pw.get() + k, s.pw.get(), 8, hipMemcpyDeviceToHost, sb));
+            PA_HIP_TRY(hipEventRecord(s.ev_back, sb));
             s.busy = (int64_t)c;
         }
     }
@@ -172,8 +153,8 @@ int run(pa_index* idx, HostPipe& hp, const uint64_t* h_tiles, const uint32_t* h_
         if (hp.st[k].stream) (void)hipStreamSynchronize(hp.st[k].stream);   // (also on the error path: nothing of this call is in flight when it returns)
     if (rc != PA_OK) return rc;
     if (h_counts) {
-        HB_HIP(hipMemcpyAsync(h_counts, hp.d_counts, counts_len * 8, hipMemcpyDeviceToHost, hp.st[0].stream));
-        HB_HIP(hipStreamSynchronize(hp.st[0].stream));
+        PA_HIP_TRY(hipMemcpyAsync(h_counts, hp.counts.get(), counts_len * 8, hipMemcpyDeviceToHost, hp.st[0].stream));
+        PA_HIP_TRY(hipStreamSynchronize(hp.st[0].stream));
     }
     if (packed_words) *packed_words = off;
     return PA_OK;

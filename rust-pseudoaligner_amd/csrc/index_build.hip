@@ -35,6 +35,7 @@
 #include <numeric>
 #include <unordered_map>
 
+#include "hip_buffer.hpp"
 #include "lane_steps.hpp"
 #include "pa_common.hpp"
 
@@ -43,25 +44,10 @@ namespace {
 
 constexpr uint32_t NONE32 = 0xFFFFFFFFu;
 
-struct DBuf {   // device allocation that frees itself
-    void* p = nullptr;
-    size_t bytes = 0;
-    DBuf() = default;
-    DBuf(const DBuf&) = delete;
-    DBuf& operator=(const DBuf&) = delete;
-    ~DBuf() { release(); }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-    hipError_t alloc(size_t n) {
-        release();
-        if (n == 0) n = 16;
-        const hipError_t e = hipMalloc(&p, n);
-        if (e == hipSuccess) bytes = n;
-        return e;
-    }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
+using Bytes = DeviceBuffer<uint8_t>;
 
-#define IB_HIP(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(PA_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
+// a device temporary of n bytes (16 when n is 0); freed when it goes out of scope
+int dalloc(Bytes& b, size_t n) { return b.alloc(n ? n : 16); }
 
 // ---- k-mers of one or two words on the device ----
 template <class KT> struct DKmer;
@@ -360,44 +346,44 @@ struct Stage {   // PA_VERBOSE: stage times (device work is synchronised at each
 template <class K, class V>
 int sort_pairs(const K* kin, K* kout, const V* vin, V* vout, uint64_t n, uint32_t begin_bit, uint32_t end_bit) {
     size_t bytes = 0;
-    IB_HIP(rocprim::radix_sort_pairs(nullptr, bytes, kin, kout, vin, vout, (size_t)n, begin_bit, end_bit, (hipStream_t) nullptr));
-    DBuf tmp;
-    IB_HIP(tmp.alloc(bytes));
-    IB_HIP(rocprim::radix_sort_pairs(tmp.p, bytes, kin, kout, vin, vout, (size_t)n, begin_bit, end_bit, (hipStream_t) nullptr));
-    IB_HIP(hipStreamSynchronize(nullptr));   // tmp is freed on return
+    PA_HIP_TRY(rocprim::radix_sort_pairs(nullptr, bytes, kin, kout, vin, vout, (size_t)n, begin_bit, end_bit, (hipStream_t) nullptr));
+    Bytes tmp;
+    if (const int e_ = dalloc(tmp, bytes)) return e_;
+    PA_HIP_TRY(rocprim::radix_sort_pairs(tmp.get(), bytes, kin, kout, vin, vout, (size_t)n, begin_bit, end_bit, (hipStream_t) nullptr));
+    PA_HIP_TRY(hipStreamSynchronize(nullptr));   // tmp is freed on return
     return PA_OK;
 }
 template <class T>
 int scan_incl(const T* in, T* out, uint64_t n) {
     size_t bytes = 0;
-    IB_HIP(rocprim::inclusive_scan(nullptr, bytes, in, out, (size_t)n, rocprim::plus<T>(), (hipStream_t) nullptr));
-    DBuf tmp;
-    IB_HIP(tmp.alloc(bytes));
-    IB_HIP(rocprim::inclusive_scan(tmp.p, bytes, in, out, (size_t)n, rocprim::plus<T>(), (hipStream_t) nullptr));
-    IB_HIP(hipStreamSynchronize(nullptr));
+    PA_HIP_TRY(rocprim::inclusive_scan(nullptr, bytes, in, out, (size_t)n, rocprim::plus<T>(), (hipStream_t) nullptr));
+    Bytes tmp;
+    if (const int e_ = dalloc(tmp, bytes)) return e_;
+    PA_HIP_TRY(rocprim::inclusive_scan(tmp.get(), bytes, in, out, (size_t)n, rocprim::plus<T>(), (hipStream_t) nullptr));
+    PA_HIP_TRY(hipStreamSynchronize(nullptr));
     return PA_OK;
 }
 template <class T>
 int scan_excl(const T* in, T* out, uint64_t n) {
     size_t bytes = 0;
-    IB_HIP(rocprim::exclusive_scan(nullptr, bytes, in, out, T(0), (size_t)n, rocprim::plus<T>(), (hipStream_t) nullptr));
-    DBuf tmp;
-    IB_HIP(tmp.alloc(bytes));
-    IB_HIP(rocprim::exclusive_scan(tmp.p, bytes, in, out, T(0), (size_t)n, rocprim::plus<T>(), (hipStream_t) nullptr));
-    IB_HIP(hipStreamSynchronize(nullptr));
+    PA_HIP_TRY(rocprim::exclusive_scan(nullptr, bytes, in, out, T(0), (size_t)n, rocprim::plus<T>(), (hipStream_t) nullptr));
+    Bytes tmp;
+    if (const int e_ = dalloc(tmp, bytes)) return e_;
+    PA_HIP_TRY(rocprim::exclusive_scan(tmp.get(), bytes, in, out, T(0), (size_t)n, rocprim::plus<T>(), (hipStream_t) nullptr));
+    PA_HIP_TRY(hipStreamSynchronize(nullptr));
     return PA_OK;
 }
 // indices i in [0, n) with flags[i] != 0, ascending
 int select_flagged(const uint32_t* flags, uint64_t n, uint32_t* out, uint32_t* count_host) {
-    DBuf cnt;
-    IB_HIP(cnt.alloc(8));
+    Bytes cnt;
+    if (const int e_ = dalloc(cnt, 8)) return e_;
     size_t bytes = 0;
     rocprim::counting_iterator<uint32_t> it(0);
-    IB_HIP(rocprim::select(nullptr, bytes, it, flags, out, cnt.as<uint32_t>(), (size_t)n, (hipStream_t) nullptr));
-    DBuf tmp;
-    IB_HIP(tmp.alloc(bytes));
-    IB_HIP(rocprim::select(tmp.p, bytes, it, flags, out, cnt.as<uint32_t>(), (size_t)n, (hipStream_t) nullptr));
-    IB_HIP(hipMemcpy(count_host, cnt.p, 4, hipMemcpyDeviceToHost));
+    PA_HIP_TRY(rocprim::select(nullptr, bytes, it, flags, out, cnt.as<uint32_t>(), (size_t)n, (hipStream_t) nullptr));
+    Bytes tmp;
+    if (const int e_ = dalloc(tmp, bytes)) return e_;
+    PA_HIP_TRY(rocprim::select(tmp.get(), bytes, it, flags, out, cnt.as<uint32_t>(), (size_t)n, (hipStream_t) nullptr));
+    PA_HIP_TRY(hipMemcpy(count_host, cnt.get(), 4, hipMemcpyDeviceToHost));
     return PA_OK;
 }
 
@@ -424,86 +410,86 @@ int build_graph_device_t(const uint64_t* packed_in, const uint64_t* tx_start, ui
     const uint32_t P = 1u << logp;
 
     const uint64_t nwords = (total_bases + 31) / 32;
-    DBuf d_packed, d_txs, d_kcum;
-    IB_HIP(d_packed.alloc((nwords + 3) * 8));
-    IB_HIP(hipMemset(d_packed.p, 0, (nwords + 3) * 8));
-    IB_HIP(hipMemcpy(d_packed.p, packed_in, nwords * 8, hipMemcpyHostToDevice));
-    IB_HIP(d_txs.alloc(((size_t)num_tx + 1) * 8));
-    IB_HIP(hipMemcpy(d_txs.p, tx_start, ((size_t)num_tx + 1) * 8, hipMemcpyHostToDevice));
-    IB_HIP(d_kcum.alloc(((size_t)num_tx + 1) * 8));
-    IB_HIP(hipMemcpy(d_kcum.p, kcum.data(), ((size_t)num_tx + 1) * 8, hipMemcpyHostToDevice));
+    Bytes d_packed, d_txs, d_kcum;
+    if (const int e_ = dalloc(d_packed, (nwords + 3) * 8)) return e_;
+    PA_HIP_TRY(hipMemset(d_packed.get(), 0, (nwords + 3) * 8));
+    PA_HIP_TRY(hipMemcpy(d_packed.get(), packed_in, nwords * 8, hipMemcpyHostToDevice));
+    if (const int e_ = dalloc(d_txs, ((size_t)num_tx + 1) * 8)) return e_;
+    PA_HIP_TRY(hipMemcpy(d_txs.get(), tx_start, ((size_t)num_tx + 1) * 8, hipMemcpyHostToDevice));
+    if (const int e_ = dalloc(d_kcum, ((size_t)num_tx + 1) * 8)) return e_;
+    PA_HIP_TRY(hipMemcpy(d_kcum.get(), kcum.data(), ((size_t)num_tx + 1) * 8, hipMemcpyHostToDevice));
 
     // ---- 1 + 2. records, sorted by k-mer ----
-    DBuf keys, vals;
+    Bytes keys, vals;
     {
-        DBuf keys0, vals0;
-        IB_HIP(keys0.alloc(N * sizeof(KT)));
-        IB_HIP(vals0.alloc(N * 4));
-        IB_HIP(keys.alloc(N * sizeof(KT)));
-        IB_HIP(vals.alloc(N * 4));
+        Bytes keys0, vals0;
+        if (const int e_ = dalloc(keys0, N * sizeof(KT))) return e_;
+        if (const int e_ = dalloc(vals0, N * 4)) return e_;
+        if (const int e_ = dalloc(keys, N * sizeof(KT))) return e_;
+        if (const int e_ = dalloc(vals, N * 4)) return e_;
         hipLaunchKernelGGL(pa_ib_enum_kernel<KT>, grid_of(total_bases), dim3(256), 0, nullptr, d_packed.as<uint64_t>(), d_txs.as<uint64_t>(), d_kcum.as<uint64_t>(),
                            num_tx, total_bases, k, keys0.as<KT>(), vals0.as<uint32_t>());
-        IB_HIP(hipGetLastError());
+        PA_HIP_TRY(hipGetLastError());
         stage.mark("enumerate k-mers");
         const int rc = sort_pairs(keys0.as<KT>(), keys.as<KT>(), vals0.as<uint32_t>(), vals.as<uint32_t>(), N, 0, 2 * k);
         if (rc != PA_OK) return rc;
         stage.mark("radix sort");
     }
     // ---- 3. segments ----
-    DBuf seg;
-    IB_HIP(seg.alloc(N * 4));
+    Bytes seg;
+    if (const int e_ = dalloc(seg, N * 4)) return e_;
     {
-        DBuf head;
-        IB_HIP(head.alloc(N * 4));
+        Bytes head;
+        if (const int e_ = dalloc(head, N * 4)) return e_;
         hipLaunchKernelGGL(pa_ib_heads_kernel<KT>, grid_of(N), dim3(256), 0, nullptr, keys.as<KT>(), N, head.as<uint32_t>());
-        IB_HIP(hipGetLastError());
+        PA_HIP_TRY(hipGetLastError());
         const int rc = scan_incl(head.as<uint32_t>(), seg.as<uint32_t>(), N);
         if (rc != PA_OK) return rc;
     }
     uint32_t D = 0;
-    IB_HIP(hipMemcpy(&D, seg.as<uint32_t>() + (N - 1), 4, hipMemcpyDeviceToHost));
-    DBuf dkmer, dfirst, dexts, dcnt, dhash, coltmp, run_first;
-    IB_HIP(dkmer.alloc((size_t)D * sizeof(KT)));
-    IB_HIP(dfirst.alloc((size_t)D * 4));
-    IB_HIP(dexts.alloc((size_t)D * 4));
-    IB_HIP(dcnt.alloc((size_t)D * 4));
-    IB_HIP(dhash.alloc((size_t)D * 8));
-    IB_HIP(coltmp.alloc((size_t)D * 4));
-    IB_HIP(hipMemset(dexts.p, 0, (size_t)D * 4));
-    IB_HIP(hipMemset(dcnt.p, 0, (size_t)D * 4));
+    PA_HIP_TRY(hipMemcpy(&D, seg.as<uint32_t>() + (N - 1), 4, hipMemcpyDeviceToHost));
+    Bytes dkmer, dfirst, dexts, dcnt, dhash, coltmp, run_first;
+    if (const int e_ = dalloc(dkmer, (size_t)D * sizeof(KT))) return e_;
+    if (const int e_ = dalloc(dfirst, (size_t)D * 4)) return e_;
+    if (const int e_ = dalloc(dexts, (size_t)D * 4)) return e_;
+    if (const int e_ = dalloc(dcnt, (size_t)D * 4)) return e_;
+    if (const int e_ = dalloc(dhash, (size_t)D * 8)) return e_;
+    if (const int e_ = dalloc(coltmp, (size_t)D * 4)) return e_;
+    PA_HIP_TRY(hipMemset(dexts.get(), 0, (size_t)D * 4));
+    PA_HIP_TRY(hipMemset(dcnt.get(), 0, (size_t)D * 4));
     // ---- 4. colours: runs of equal set hash, verified by content ----
     uint32_t C = 0;
     uint64_t seed = 0x243f6a8885a308d3ull;
     for (int attempt = 0;; ++attempt) {
-        IB_HIP(hipMemset(dhash.p, 0, (size_t)D * 8));
+        PA_HIP_TRY(hipMemset(dhash.get(), 0, (size_t)D * 8));
         hipLaunchKernelGGL(pa_ib_segment_kernel<KT>, grid_of(N), dim3(256), 0, nullptr, keys.as<KT>(), vals.as<uint32_t>(), seg.as<uint32_t>(), N, seed,
                            dkmer.as<KT>(), dfirst.as<uint32_t>(), attempt == 0 ? dexts.as<uint32_t>() : nullptr, attempt == 0 ? dcnt.as<uint32_t>() : nullptr,
                            dhash.as<unsigned long long>());
-        IB_HIP(hipGetLastError());
-        DBuf hs, ds0, ds, rid, rh;
-        IB_HIP(hs.alloc((size_t)D * 8));
-        IB_HIP(ds0.alloc((size_t)D * 4));
-        IB_HIP(ds.alloc((size_t)D * 4));
-        IB_HIP(rid.alloc((size_t)D * 4));
-        IB_HIP(rh.alloc((size_t)D * 4));
+        PA_HIP_TRY(hipGetLastError());
+        Bytes hs, ds0, ds, rid, rh;
+        if (const int e_ = dalloc(hs, (size_t)D * 8)) return e_;
+        if (const int e_ = dalloc(ds0, (size_t)D * 4)) return e_;
+        if (const int e_ = dalloc(ds, (size_t)D * 4)) return e_;
+        if (const int e_ = dalloc(rid, (size_t)D * 4)) return e_;
+        if (const int e_ = dalloc(rh, (size_t)D * 4)) return e_;
         hipLaunchKernelGGL(pa_ib_iota_kernel, grid_of(D), dim3(256), 0, nullptr, ds0.as<uint32_t>(), (uint64_t)D);
         { const int rc = sort_pairs(dhash.as<unsigned long long>(), hs.as<unsigned long long>(), ds0.as<uint32_t>(), ds.as<uint32_t>(), D, 0, 64); if (rc != PA_OK) return rc; }
         hipLaunchKernelGGL(pa_ib_runheads_kernel, grid_of(D), dim3(256), 0, nullptr, hs.as<unsigned long long>(), (uint64_t)D, rh.as<uint32_t>());
-        IB_HIP(hipGetLastError());
+        PA_HIP_TRY(hipGetLastError());
         { const int rc = scan_incl(rh.as<uint32_t>(), rid.as<uint32_t>(), D); if (rc != PA_OK) return rc; }
-        IB_HIP(hipMemcpy(&C, rid.as<uint32_t>() + (D - 1), 4, hipMemcpyDeviceToHost));
-        IB_HIP(run_first.alloc((size_t)C * 4));
+        PA_HIP_TRY(hipMemcpy(&C, rid.as<uint32_t>() + (D - 1), 4, hipMemcpyDeviceToHost));
+        if (const int e_ = dalloc(run_first, (size_t)C * 4)) return e_;
         hipLaunchKernelGGL(pa_ib_runs_kernel, grid_of(D), dim3(256), 0, nullptr, ds.as<uint32_t>(), rid.as<uint32_t>(), (uint64_t)D, run_first.as<uint32_t>(),
                            coltmp.as<uint32_t>());
-        IB_HIP(hipGetLastError());
-        DBuf mism;
-        IB_HIP(mism.alloc(4));
-        IB_HIP(hipMemset(mism.p, 0, 4));
+        PA_HIP_TRY(hipGetLastError());
+        Bytes mism;
+        if (const int e_ = dalloc(mism, 4)) return e_;
+        PA_HIP_TRY(hipMemset(mism.get(), 0, 4));
         hipLaunchKernelGGL(pa_ib_verify_kernel, grid_of(D), dim3(256), 0, nullptr, vals.as<uint32_t>(), dfirst.as<uint32_t>(), dcnt.as<uint32_t>(), coltmp.as<uint32_t>(),
                            run_first.as<uint32_t>(), (uint64_t)D, N, mism.as<uint32_t>());
-        IB_HIP(hipGetLastError());
+        PA_HIP_TRY(hipGetLastError());
         uint32_t bad = 0;
-        IB_HIP(hipMemcpy(&bad, mism.p, 4, hipMemcpyDeviceToHost));
+        PA_HIP_TRY(hipMemcpy(&bad, mism.get(), 4, hipMemcpyDeviceToHost));
         if (bad == 0) break;
         if (attempt == 3) return fail(PA_ERR_INTERNAL, "colour interning: set hashes kept colliding (%u k-mers)", bad);
         seed = pa_mix64(seed + attempt + 1);   // two different id lists shared a hash: take another hash
@@ -513,21 +499,21 @@ int build_graph_device_t(const uint64_t* packed_in, const uint64_t* tx_start, ui
     std::vector<unsigned long long> loff((size_t)C + 1, 0);
     std::vector<uint32_t> lids;
     {
-        DBuf llen, d_off, d_ids;
-        IB_HIP(llen.alloc(((size_t)C + 1) * 8));
-        IB_HIP(d_off.alloc(((size_t)C + 1) * 8));
-        IB_HIP(hipMemset(llen.p, 0, ((size_t)C + 1) * 8));
+        Bytes llen, d_off, d_ids;
+        if (const int e_ = dalloc(llen, ((size_t)C + 1) * 8)) return e_;
+        if (const int e_ = dalloc(d_off, ((size_t)C + 1) * 8)) return e_;
+        PA_HIP_TRY(hipMemset(llen.get(), 0, ((size_t)C + 1) * 8));
         hipLaunchKernelGGL(pa_ib_listlen_kernel, grid_of(C), dim3(256), 0, nullptr, run_first.as<uint32_t>(), dcnt.as<uint32_t>(), (uint64_t)C, llen.as<unsigned long long>());
-        IB_HIP(hipGetLastError());
+        PA_HIP_TRY(hipGetLastError());
         { const int rc = scan_excl(llen.as<unsigned long long>(), d_off.as<unsigned long long>(), (uint64_t)C + 1); if (rc != PA_OK) return rc; }
-        IB_HIP(hipMemcpy(loff.data(), d_off.p, ((size_t)C + 1) * 8, hipMemcpyDeviceToHost));
+        PA_HIP_TRY(hipMemcpy(loff.data(), d_off.get(), ((size_t)C + 1) * 8, hipMemcpyDeviceToHost));
         const uint64_t nids = loff[C];
-        IB_HIP(d_ids.alloc(nids * 4));
+        if (const int e_ = dalloc(d_ids, nids * 4)) return e_;
         hipLaunchKernelGGL(pa_ib_listwrite_kernel, grid_of(C), dim3(256), 0, nullptr, vals.as<uint32_t>(), dfirst.as<uint32_t>(), run_first.as<uint32_t>(),
                            d_off.as<unsigned long long>(), (uint64_t)C, (uint64_t)D, N, d_ids.as<uint32_t>());
-        IB_HIP(hipGetLastError());
+        PA_HIP_TRY(hipGetLastError());
         lids.resize(nids);
-        IB_HIP(hipMemcpy(lids.data(), d_ids.p, nids * 4, hipMemcpyDeviceToHost));
+        PA_HIP_TRY(hipMemcpy(lids.data(), d_ids.get(), nids * 4, hipMemcpyDeviceToHost));
     }
     if (C >= NONE32) return fail(PA_ERR_UNSUPPORTED, "too many equivalence classes");
     std::vector<uint32_t> lorder(C), remap(C);
@@ -544,53 +530,53 @@ int build_graph_device_t(const uint64_t* packed_in, const uint64_t* tx_start, ui
     }
     // the occurrence records are no longer needed
     keys.release(); vals.release(); seg.release(); dhash.release(); dfirst.release(); run_first.release(); dcnt.release();
-    DBuf dcol;
+    Bytes dcol;
     {
-        DBuf d_remap;
-        IB_HIP(d_remap.alloc((size_t)C * 4));
-        IB_HIP(hipMemcpy(d_remap.p, remap.data(), (size_t)C * 4, hipMemcpyHostToDevice));
-        IB_HIP(dcol.alloc((size_t)D * 4));
+        Bytes d_remap;
+        if (const int e_ = dalloc(d_remap, (size_t)C * 4)) return e_;
+        PA_HIP_TRY(hipMemcpy(d_remap.get(), remap.data(), (size_t)C * 4, hipMemcpyHostToDevice));
+        if (const int e_ = dalloc(dcol, (size_t)D * 4)) return e_;
         hipLaunchKernelGGL(pa_ib_colour_kernel, grid_of(D), dim3(256), 0, nullptr, coltmp.as<uint32_t>(), d_remap.as<uint32_t>(), (uint64_t)D, dcol.as<uint32_t>());
-        IB_HIP(hipGetLastError());
-        IB_HIP(hipStreamSynchronize(nullptr));
+        PA_HIP_TRY(hipGetLastError());
+        PA_HIP_TRY(hipStreamSynchronize(nullptr));
     }
     coltmp.release();
     stage.mark("class numbering");
 
     // ---- 5 + 6. joins, pointer jumping ----
-    DBuf succ, pd;
-    IB_HIP(succ.alloc((size_t)D * 4));
-    IB_HIP(pd.alloc((size_t)D * 8));
+    Bytes succ, pd;
+    if (const int e_ = dalloc(succ, (size_t)D * 4)) return e_;
+    if (const int e_ = dalloc(pd, (size_t)D * 8)) return e_;
     hipLaunchKernelGGL(pa_ib_links_kernel<KT>, grid_of(D), dim3(256), 0, nullptr, dkmer.as<KT>(), dexts.as<uint32_t>(), dcol.as<uint32_t>(), D, k, succ.as<uint32_t>(),
                        pd.as<unsigned long long>());
-    IB_HIP(hipGetLastError());
+    PA_HIP_TRY(hipGetLastError());
     stage.mark("joins");
     {
-        DBuf cnt;
-        IB_HIP(cnt.alloc(4));
+        Bytes cnt;
+        if (const int e_ = dalloc(cnt, 4)) return e_;
         uint32_t prev = NONE32;
         for (int round = 0; round < 40; ++round) {
-            IB_HIP(hipMemset(cnt.p, 0, 4));
+            PA_HIP_TRY(hipMemset(cnt.get(), 0, 4));
             const uint32_t jump_blocks = (uint32_t)std::min<uint64_t>(((uint64_t)D + 255) / 256, 8192);
             hipLaunchKernelGGL(pa_ib_jump_kernel, dim3(jump_blocks), dim3(256), 0, nullptr, pd.as<unsigned long long>(), D, cnt.as<uint32_t>());
-            IB_HIP(hipGetLastError());
+            PA_HIP_TRY(hipGetLastError());
             uint32_t now = 0;
-            IB_HIP(hipMemcpy(&now, cnt.p, 4, hipMemcpyDeviceToHost));
+            PA_HIP_TRY(hipMemcpy(&now, cnt.get(), 4, hipMemcpyDeviceToHost));
             if (now == 0 || now == prev) break;   // only the members of pure cycles keep moving
             prev = now;
         }
     }
     stage.mark("pointer jumping");
     // ---- 7. nodes ----
-    DBuf is_start, is_cyclic, starts, cyc;
-    IB_HIP(is_start.alloc((size_t)D * 4));
-    IB_HIP(is_cyclic.alloc((size_t)D * 4));
+    Bytes is_start, is_cyclic, starts, cyc;
+    if (const int e_ = dalloc(is_start, (size_t)D * 4)) return e_;
+    if (const int e_ = dalloc(is_cyclic, (size_t)D * 4)) return e_;
     hipLaunchKernelGGL(pa_ib_classify_kernel, grid_of(D), dim3(256), 0, nullptr, pd.as<unsigned long long>(), D, is_start.as<uint32_t>(), is_cyclic.as<uint32_t>());
-    IB_HIP(hipGetLastError());
-    IB_HIP(starts.alloc((size_t)D * 4));
+    PA_HIP_TRY(hipGetLastError());
+    if (const int e_ = dalloc(starts, (size_t)D * 4)) return e_;
     uint32_t ns = 0, ncyc = 0;
     { const int rc = select_flagged(is_start.as<uint32_t>(), D, starts.as<uint32_t>(), &ns); if (rc != PA_OK) return rc; }
-    IB_HIP(cyc.alloc((size_t)D * 4));
+    if (const int e_ = dalloc(cyc, (size_t)D * 4)) return e_;
     { const int rc = select_flagged(is_cyclic.as<uint32_t>(), D, cyc.as<uint32_t>(), &ncyc); if (rc != PA_OK) return rc; }
     is_start.release();
     if (ns >= NONE32) return fail(PA_ERR_UNSUPPORTED, "too many nodes");
@@ -600,62 +586,62 @@ int build_graph_device_t(const uint64_t* packed_in, const uint64_t* tx_start, ui
     std::vector<uint64_t> h_seq;
     uint64_t nbases = 0;
     if (ns) {
-        DBuf pkey, pkey2, order, node_of, nlen, nlen64, nstart, nexts, ncol, seq;
-        IB_HIP(pkey.alloc((size_t)ns * 4));
-        IB_HIP(pkey2.alloc((size_t)ns * 4));
-        IB_HIP(order.alloc((size_t)ns * 4));
+        Bytes pkey, pkey2, order, node_of, nlen, nlen64, nstart, nexts, ncol, seq;
+        if (const int e_ = dalloc(pkey, (size_t)ns * 4)) return e_;
+        if (const int e_ = dalloc(pkey2, (size_t)ns * 4)) return e_;
+        if (const int e_ = dalloc(order, (size_t)ns * 4)) return e_;
         hipLaunchKernelGGL(pa_ib_partkey_kernel<KT>, grid_of(ns), dim3(256), 0, nullptr, dkmer.as<KT>(), starts.as<uint32_t>(), ns, logp, pkey.as<uint32_t>());
-        IB_HIP(hipGetLastError());
+        PA_HIP_TRY(hipGetLastError());
         // the first k-mers are in k-mer order; a STABLE sort by partition gives (partition, k-mer) order
         { const int rc = sort_pairs(pkey.as<uint32_t>(), pkey2.as<uint32_t>(), starts.as<uint32_t>(), order.as<uint32_t>(), ns, 0, logp); if (rc != PA_OK) return rc; }
-        IB_HIP(node_of.alloc((size_t)D * 4));
+        if (const int e_ = dalloc(node_of, (size_t)D * 4)) return e_;
         hipLaunchKernelGGL(pa_ib_nodeof_kernel, grid_of(ns), dim3(256), 0, nullptr, order.as<uint32_t>(), ns, node_of.as<uint32_t>());
-        IB_HIP(hipGetLastError());
-        IB_HIP(nlen.alloc((size_t)ns * 4));
-        IB_HIP(nlen64.alloc(((size_t)ns + 1) * 8));
-        IB_HIP(nstart.alloc(((size_t)ns + 1) * 8));
-        IB_HIP(nexts.alloc(ns));
-        IB_HIP(ncol.alloc((size_t)ns * 4));
-        IB_HIP(hipMemset(nlen64.p, 0, ((size_t)ns + 1) * 8));
+        PA_HIP_TRY(hipGetLastError());
+        if (const int e_ = dalloc(nlen, (size_t)ns * 4)) return e_;
+        if (const int e_ = dalloc(nlen64, ((size_t)ns + 1) * 8)) return e_;
+        if (const int e_ = dalloc(nstart, ((size_t)ns + 1) * 8)) return e_;
+        if (const int e_ = dalloc(nexts, ns)) return e_;
+        if (const int e_ = dalloc(ncol, (size_t)ns * 4)) return e_;
+        PA_HIP_TRY(hipMemset(nlen64.get(), 0, ((size_t)ns + 1) * 8));
         hipLaunchKernelGGL(pa_ib_tails_kernel, grid_of(D), dim3(256), 0, nullptr, pd.as<unsigned long long>(), succ.as<uint32_t>(), is_cyclic.as<uint32_t>(),
                            node_of.as<uint32_t>(), dexts.as<uint32_t>(), dcol.as<uint32_t>(), D, k, nlen.as<uint32_t>(), nlen64.as<unsigned long long>(),
                            nexts.as<uint8_t>(), ncol.as<uint32_t>());
-        IB_HIP(hipGetLastError());
+        PA_HIP_TRY(hipGetLastError());
         { const int rc = scan_excl(nlen64.as<unsigned long long>(), nstart.as<unsigned long long>(), (uint64_t)ns + 1); if (rc != PA_OK) return rc; }
-        IB_HIP(hipMemcpy(h_start.data(), nstart.p, ((size_t)ns + 1) * 8, hipMemcpyDeviceToHost));
+        PA_HIP_TRY(hipMemcpy(h_start.data(), nstart.get(), ((size_t)ns + 1) * 8, hipMemcpyDeviceToHost));
         nbases = h_start[ns];
         const uint64_t sw = (nbases + 31) / 32 + 2;
-        IB_HIP(seq.alloc(sw * 8));
-        IB_HIP(hipMemset(seq.p, 0, sw * 8));
+        if (const int e_ = dalloc(seq, sw * 8)) return e_;
+        PA_HIP_TRY(hipMemset(seq.get(), 0, sw * 8));
         hipLaunchKernelGGL(pa_ib_seq_kernel<KT>, grid_of(D), dim3(256), 0, nullptr, dkmer.as<KT>(), pd.as<unsigned long long>(), is_cyclic.as<uint32_t>(),
                            node_of.as<uint32_t>(), nstart.as<unsigned long long>(), D, k, seq.as<unsigned long long>());
-        IB_HIP(hipGetLastError());
+        PA_HIP_TRY(hipGetLastError());
         h_seq.resize(sw);
-        IB_HIP(hipMemcpy(h_seq.data(), seq.p, sw * 8, hipMemcpyDeviceToHost));
-        IB_HIP(hipMemcpy(h_len.data(), nlen.p, (size_t)ns * 4, hipMemcpyDeviceToHost));
-        IB_HIP(hipMemcpy(h_col.data(), ncol.p, (size_t)ns * 4, hipMemcpyDeviceToHost));
-        IB_HIP(hipMemcpy(h_exts.data(), nexts.p, ns, hipMemcpyDeviceToHost));
+        PA_HIP_TRY(hipMemcpy(h_seq.data(), seq.get(), sw * 8, hipMemcpyDeviceToHost));
+        PA_HIP_TRY(hipMemcpy(h_len.data(), nlen.get(), (size_t)ns * 4, hipMemcpyDeviceToHost));
+        PA_HIP_TRY(hipMemcpy(h_col.data(), ncol.get(), (size_t)ns * 4, hipMemcpyDeviceToHost));
+        PA_HIP_TRY(hipMemcpy(h_exts.data(), nexts.get(), ns, hipMemcpyDeviceToHost));
     }
     stage.mark("nodes + sequences");
     // ---- pure cycles: walked on the host in (partition, k-mer) order, exactly as dbg_build.cpp does after its start walks ----
     struct CycNode { std::vector<uint32_t> bases; uint32_t colour; uint8_t exts; };
     std::vector<CycNode> cyc_nodes;
     if (ncyc) {
-        DBuf ck, ce, cc, cs;
-        IB_HIP(ck.alloc((size_t)ncyc * sizeof(KT)));
-        IB_HIP(ce.alloc((size_t)ncyc * 4));
-        IB_HIP(cc.alloc((size_t)ncyc * 4));
-        IB_HIP(cs.alloc((size_t)ncyc * 4));
+        Bytes ck, ce, cc, cs;
+        if (const int e_ = dalloc(ck, (size_t)ncyc * sizeof(KT))) return e_;
+        if (const int e_ = dalloc(ce, (size_t)ncyc * 4)) return e_;
+        if (const int e_ = dalloc(cc, (size_t)ncyc * 4)) return e_;
+        if (const int e_ = dalloc(cs, (size_t)ncyc * 4)) return e_;
         hipLaunchKernelGGL(pa_ib_gather_kernel<KT>, grid_of(ncyc), dim3(256), 0, nullptr, cyc.as<uint32_t>(), ncyc, dkmer.as<KT>(), dexts.as<uint32_t>(),
                            dcol.as<uint32_t>(), succ.as<uint32_t>(), ck.as<KT>(), ce.as<uint32_t>(), cc.as<uint32_t>(), cs.as<uint32_t>());
-        IB_HIP(hipGetLastError());
+        PA_HIP_TRY(hipGetLastError());
         std::vector<uint32_t> which(ncyc), ce_h(ncyc), cc_h(ncyc), cs_h(ncyc);
         std::vector<KT> ck_h(ncyc);
-        IB_HIP(hipMemcpy(which.data(), cyc.p, (size_t)ncyc * 4, hipMemcpyDeviceToHost));
-        IB_HIP(hipMemcpy(ck_h.data(), ck.p, (size_t)ncyc * sizeof(KT), hipMemcpyDeviceToHost));
-        IB_HIP(hipMemcpy(ce_h.data(), ce.p, (size_t)ncyc * 4, hipMemcpyDeviceToHost));
-        IB_HIP(hipMemcpy(cc_h.data(), cc.p, (size_t)ncyc * 4, hipMemcpyDeviceToHost));
-        IB_HIP(hipMemcpy(cs_h.data(), cs.p, (size_t)ncyc * 4, hipMemcpyDeviceToHost));
+        PA_HIP_TRY(hipMemcpy(which.data(), cyc.get(), (size_t)ncyc * 4, hipMemcpyDeviceToHost));
+        PA_HIP_TRY(hipMemcpy(ck_h.data(), ck.get(), (size_t)ncyc * sizeof(KT), hipMemcpyDeviceToHost));
+        PA_HIP_TRY(hipMemcpy(ce_h.data(), ce.get(), (size_t)ncyc * 4, hipMemcpyDeviceToHost));
+        PA_HIP_TRY(hipMemcpy(cc_h.data(), cc.get(), (size_t)ncyc * 4, hipMemcpyDeviceToHost));
+        PA_HIP_TRY(hipMemcpy(cs_h.data(), cs.get(), (size_t)ncyc * 4, hipMemcpyDeviceToHost));
         std::unordered_map<uint32_t, uint32_t> local;   // k-mer index -> position in the gathered arrays
         local.reserve(ncyc * 2);
         for (uint32_t i = 0; i < ncyc; ++i) local[which[i]] = i;
@@ -720,7 +706,7 @@ int build_graph_device(const uint64_t* packed, const uint64_t* tx_start, uint32_
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(PA_ERR_NO_DEVICE, "no HIP device: the GPU index builder needs one");
     if (device < 0 || device >= ndev) return fail(PA_ERR_INVALID_ARG, "device %d out of range (%d devices)", device, ndev);
-    IB_HIP(hipSetDevice(device));
+    PA_HIP_TRY(hipSetDevice(device));
     try {
         return k <= 32 ? build_graph_device_t<uint64_t>(packed, tx_start, num_tx, k, out) : build_graph_device_t<u128>(packed, tx_start, num_tx, k, out);
     } catch (const std::bad_alloc&) {

@@ -17,13 +17,12 @@
 
 #include "device_flatten.hpp"
 #include "dict_slots.hpp"
+#include "hip_buffer.hpp"
 #include "lane_steps.hpp"
 #include "pa_common.hpp"
 
 namespace pa {
 namespace {
-
-#define FILL_HIP(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(PA_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
 
 __device__ __forceinline__ uint64_t win32(const uint64_t* w, uint32_t pos) {
     const uint32_t i = pos >> 5, s = (pos & 31) * 2;
@@ -158,25 +157,19 @@ __global__ __launch_bounds__(256) void pa_fill_verify_kernel(const uint8_t* __re
 }
 
 template <class KT>
-int fill_t(const FlatDevice& fd, void* d_blobs, void** d_table, uint64_t* nbuckets_out) {
+int fill_t(const FlatDevice& fd, const uint8_t* d_blobs, DeviceBuffer<uint32_t>& table_out, uint64_t* nbuckets_out) {
     const uint32_t N = fd.num_nodes, k = fd.k;
     const uint64_t nk = fd.num_kmers;
-    *d_table = nullptr;
-    void *d_handle = nullptr, *d_node_s = nullptr, *d_kcum = nullptr, *d_flags = nullptr;
-    auto done = [&](int rc) {
-        for (void* p : {d_handle, d_node_s, d_kcum, d_flags})
-            if (p) (void)hipFree(p);
-        if (rc != PA_OK && *d_table) { (void)hipFree(*d_table); *d_table = nullptr; }
-        return rc;
-    };
-#define FILL_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return done(fail(PA_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_))); } while (0)
-    FILL_TRY(hipMalloc(&d_handle, (size_t)(N ? N : 1) * 4));
-    FILL_TRY(hipMalloc(&d_node_s, (size_t)(N ? N : 1) * 4));
-    FILL_TRY(hipMalloc(&d_kcum, ((size_t)N + 1) * 8));
-    FILL_TRY(hipMalloc(&d_flags, 16));
-    if (N) FILL_TRY(hipMemcpy(d_handle, fd.handle.data(), (size_t)N * 4, hipMemcpyHostToDevice));
-    if (N) FILL_TRY(hipMemcpy(d_node_s, fd.node_s.data(), (size_t)N * 4, hipMemcpyHostToDevice));
-    FILL_TRY(hipMemcpy(d_kcum, fd.node_kcum.data(), ((size_t)N + 1) * 8, hipMemcpyHostToDevice));
+    DeviceBuffer<uint32_t> table, d_handle, d_node_s, d_flags;
+    DeviceBuffer<uint64_t> d_kcum;
+    int e = d_handle.alloc(N ? N : 1);
+    if (e == PA_OK) e = d_node_s.alloc(N ? N : 1);
+    if (e == PA_OK) e = d_kcum.alloc((size_t)N + 1);
+    if (e == PA_OK) e = d_flags.alloc(4);
+    if (e != PA_OK) return e;
+    if (N) PA_HIP_TRY(hipMemcpy(d_handle.get(), fd.handle.data(), (size_t)N * 4, hipMemcpyHostToDevice));
+    if (N) PA_HIP_TRY(hipMemcpy(d_node_s.get(), fd.node_s.data(), (size_t)N * 4, hipMemcpyHostToDevice));
+    PA_HIP_TRY(hipMemcpy(d_kcum.get(), fd.node_kcum.data(), ((size_t)N + 1) * 8, hipMemcpyHostToDevice));
     uint64_t nbuckets = 0;
     double load0 = FillOps<KT>::LOAD;
     {   // a device short of memory gets the denser table (it costs 4 % of the mapping rate, device_layout.hpp, not the index)
@@ -187,39 +180,36 @@ int fill_t(const FlatDevice& fd, void* d_blobs, void** d_table, uint64_t* nbucke
     if (const char* v = knob_str("PA_DICT_LOAD")) { const double x = atof(v); if (x > 0.01 && x <= 0.95) load0 = x; }   // A/B runs only
     for (double load = load0;; load *= 0.75) {
         nbuckets = std::max<uint64_t>(1, (uint64_t)((double)nk / (FillOps<KT>::SLOTS * load)) + 1);
-        if (nbuckets >= 0xFFFFFFFFull) return done(fail(PA_ERR_UNSUPPORTED, "dictionary exceeds 2^32 buckets"));
-        if (*d_table) { (void)hipFree(*d_table); *d_table = nullptr; }
-        const hipError_t em = hipMalloc(d_table, nbuckets * BUCKET_WORDS * 4);
-        if (em != hipSuccess) { *d_table = nullptr; return done(fail(PA_ERR_OOM, "hipMalloc(%llu) for the dictionary: %s", (unsigned long long)(nbuckets * BUCKET_WORDS * 4), hipGetErrorString(em))); }
-        FILL_TRY(hipMemsetAsync(*d_table, 0xFF, nbuckets * BUCKET_WORDS * 4, nullptr));   // empty slots, no flags (NO_HANDLE in every word)
+        if (nbuckets >= 0xFFFFFFFFull) return fail(PA_ERR_UNSUPPORTED, "dictionary exceeds 2^32 buckets");
+        if ((e = table.alloc(nbuckets * BUCKET_WORDS)) != PA_OK) return e;
+        PA_HIP_TRY(hipMemsetAsync(table.get(), 0xFF, nbuckets * BUCKET_WORDS * 4, nullptr));   // empty slots, no flags (NO_HANDLE in every word)
         const uint32_t init[4] = {NO_HANDLE, 0u, NO_HANDLE, NO_HANDLE};
-        FILL_TRY(hipMemcpy(d_flags, init, 16, hipMemcpyHostToDevice));
+        PA_HIP_TRY(hipMemcpy(d_flags.get(), init, 16, hipMemcpyHostToDevice));
         if (nk) {
             const dim3 grid((uint32_t)((nk + 255) / 256));
             for (int pass = 0; pass < (sizeof(KT) == 8 ? 2 : 1); ++pass) {   // (stream order is the barrier between the passes)
-                hipLaunchKernelGGL(pa_fill_insert_kernel<KT>, grid, dim3(256), 0, nullptr, static_cast<const uint8_t*>(d_blobs), static_cast<const uint32_t*>(d_handle),
-                                   static_cast<const uint32_t*>(d_node_s), static_cast<const uint64_t*>(d_kcum), N, nk, k, static_cast<uint32_t*>(*d_table), (uint32_t)nbuckets, pass);
-                FILL_TRY(hipGetLastError());
+                hipLaunchKernelGGL(pa_fill_insert_kernel<KT>, grid, dim3(256), 0, nullptr, d_blobs, d_handle.get(), d_node_s.get(), d_kcum.get(), N, nk, k,
+                                   table.get(), (uint32_t)nbuckets, pass);
+                PA_HIP_TRY(hipGetLastError());
             }
-            hipLaunchKernelGGL(pa_fill_verify_kernel<KT>, grid, dim3(256), 0, nullptr, static_cast<const uint8_t*>(d_blobs), static_cast<const uint32_t*>(d_handle),
-                               static_cast<const uint32_t*>(d_node_s), static_cast<const uint64_t*>(d_kcum), N, nk, k, static_cast<const uint32_t*>(*d_table), (uint32_t)nbuckets,
-                               static_cast<uint32_t*>(d_flags));
-            FILL_TRY(hipGetLastError());
+            hipLaunchKernelGGL(pa_fill_verify_kernel<KT>, grid, dim3(256), 0, nullptr, d_blobs, d_handle.get(), d_node_s.get(), d_kcum.get(), N, nk, k,
+                               table.get(), (uint32_t)nbuckets, d_flags.get());
+            PA_HIP_TRY(hipGetLastError());
         }
         uint32_t flags[4];
-        FILL_TRY(hipMemcpy(flags, d_flags, 16, hipMemcpyDeviceToHost));
-        if (flags[0] != NO_HANDLE) return done(fail(PA_ERR_FORMAT, "a k-mer of node %u occurs twice in the graph", flags[0]));
+        PA_HIP_TRY(hipMemcpy(flags, d_flags.get(), 16, hipMemcpyDeviceToHost));
+        if (flags[0] != NO_HANDLE) return fail(PA_ERR_FORMAT, "a k-mer of node %u occurs twice in the graph", flags[0]);
         if (!flags[1]) break;   // else: some key sits further from home than the kernel follows; a larger table
     }
-#undef FILL_TRY
     *nbuckets_out = nbuckets;
-    return done(PA_OK);
+    table_out = std::move(table);
+    return PA_OK;
 }
 
 }  // namespace
 
-int device_fill_index(const FlatDevice& fd, void* d_blobs, void** d_table, uint64_t* nbuckets) {
-    return fd.k <= 32 ? fill_t<uint64_t>(fd, d_blobs, d_table, nbuckets) : fill_t<u128>(fd, d_blobs, d_table, nbuckets);
+int device_fill_index(const FlatDevice& fd, const uint8_t* d_blobs, DeviceBuffer<uint32_t>& table, uint64_t* nbuckets) {
+    return fd.k <= 32 ? fill_t<uint64_t>(fd, d_blobs, table, nbuckets) : fill_t<u128>(fd, d_blobs, table, nbuckets);
 }
 
 }  // namespace pa

@@ -16,13 +16,12 @@
 #include <thread>
 #include <vector>
 
+#include "hip_buffer.hpp"
 #include "kernels.hpp"
 #include "pa_common.hpp"
 
 namespace pa {
 namespace ingest {
-
-#define PA_INGEST_HIP_OK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(PA_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
 
 // persistent worker threads; run(n, fn) executes fn(0..n-1) on them (and on the caller) and returns when all are done
 class Pool {
@@ -128,25 +127,31 @@ struct Record {   // one record inside a text (the mapped FASTQ file, or the byt
 
 
 struct BatchCtx {   // pinned host buffers + device buffers of one batch in flight
-    void *d_tiles = nullptr, *d_lens = nullptr, *d_results = nullptr, *d_arena = nullptr;
+    DeviceBuffer<uint64_t> d_tiles;
+    DeviceBuffer<uint32_t> d_lens, d_arena;
+    DeviceBuffer<pa_read_result> d_results;
     // (a) record stream: the batch's sequences as the records hold them (ASCII, back to back) and their offsets: the 2-bit packing into
     // tiles runs on the GPU (pa_encode_reads_device), the host only gathers the bytes into pinned memory
-    uint8_t* h_ascii = nullptr;
-    uint64_t* h_soff = nullptr;
-    void *d_ascii = nullptr, *d_soff = nullptr;
-    size_t ascii_cap = 0, ascii_bytes = 0, soff_cap = 0;
+    PinnedBuffer<uint8_t> h_ascii;
+    PinnedBuffer<uint64_t> h_soff;
+    DeviceBuffer<uint8_t> d_ascii;
+    DeviceBuffer<uint64_t> d_soff;
+    size_t ascii_bytes = 0, soff_cap = 0;
     // ... and the ids (record.id(), :456) for the render kernels (render.hip), which write the batch's output tuples: lengths, offsets
     // (d_off[n] = bytes of the whole text), the text itself, and its copy in pinned memory
-    uint8_t* h_ids = nullptr;
-    uint64_t* h_idoff = nullptr;
-    void *d_ids = nullptr, *d_idoff = nullptr, *d_len = nullptr, *d_off = nullptr, *d_scan = nullptr, *d_flag = nullptr, *d_text = nullptr;
-    unsigned long long* h_tot = nullptr;   // pinned {text bytes, flagged reads by bucket [PA_RENDER_FLAG_BUCKETS]}: bucket 0 = the reads before flag_mark, bucket j = the j-th million behind it
-    char* h_text = nullptr;
-    size_t ids_cap = 0, ids_bytes = 0, scan_bytes = 0, text_cap = 0, text_bytes = 0;
+    PinnedBuffer<uint8_t> h_ids;
+    PinnedBuffer<uint64_t> h_idoff;
+    DeviceBuffer<uint8_t> d_ids, d_scan, d_text;
+    DeviceBuffer<uint64_t> d_idoff, d_off;
+    DeviceBuffer<uint32_t> d_len;
+    DeviceBuffer<unsigned long long> d_flag;
+    PinnedBuffer<unsigned long long> h_tot;   // {text bytes, flagged reads by bucket [PA_RENDER_FLAG_BUCKETS]}: bucket 0 = the reads before flag_mark, bucket j = the j-th million behind it
+    PinnedBuffer<char> h_text;
+    size_t ids_bytes = 0, scan_bytes = 0, text_bytes = 0;
     size_t text_guess = 0, spec_bytes = 0;   // the text's expected length (from the batch before) and what was rendered + fetched ahead of knowing it
     uint64_t flagged = 0, flag_mark = 0;
     hipEvent_t ev_text = nullptr;
-    size_t tiles_bytes = 0, arena_entries = 0, reads_cap = 0;
+    size_t reads_cap = 0;
     std::vector<Record> recs;
     uint64_t first = 0, n = 0;
     uint32_t wpr = 1;
@@ -155,26 +160,26 @@ struct BatchCtx {   // pinned host buffers + device buffers of one batch in flig
     // for text the GPU scan does not take (the end of the file, wrapped records), by the host's scan (h_rec). Sequences and ids are
     // then read in place: no gather, no second copy
     bool in_place = false;
-    uint8_t* h_raw = nullptr;
-    void* d_raw = nullptr;
-    size_t raw_cap = 0;
+    PinnedBuffer<uint8_t> h_raw;
+    DeviceBuffer<uint8_t> d_raw;
     uint64_t raw_begin = 0, raw_end = 0;   // the window's bytes are [raw_begin, raw_end) of h_raw / d_raw
-    void *d_chunk = nullptr, *d_first = nullptr, *d_fq_tmp = nullptr, *d_ls = nullptr, *d_rec = nullptr, *d_info = nullptr;
-    size_t chunk_cap = 0, fq_tmp_bytes = 0, ls_cap = 0, rec_cap = 0, h_rec_cap = 0;
-    uint4* h_rec = nullptr;
-    FqInfo* h_info = nullptr;
+    DeviceBuffer<uint32_t> d_chunk, d_first, d_ls;
+    DeviceBuffer<uint8_t> d_fq_tmp;
+    DeviceBuffer<uint4> d_rec;
+    DeviceBuffer<FqInfo> d_info;
+    size_t chunk_cap = 0, fq_tmp_bytes = 0;
+    PinnedBuffer<uint4> h_rec;
+    PinnedBuffer<FqInfo> h_info;
     hipEvent_t ev_h2d = nullptr, ev_info = nullptr;
     // the tuples' way back on a stream of its own (the lane's; not owned here): the next window's kernels do not queue behind 14 MB of text going to the host
     hipStream_t back = nullptr;
     hipEvent_t ev_render = nullptr;
     bool text_on_back = false;
+    // the text buffers' size (d_text is allocated after h_text: it is empty unless both are there)
+    size_t text_cap() const { return d_text.size(); }
     void release() {
-        for (void* p : {(void*)h_ascii, (void*)h_soff, (void*)h_ids, (void*)h_idoff, (void*)h_tot, (void*)h_text, (void*)h_raw, (void*)h_rec, (void*)h_info})
-            if (p) (void)hipHostFree(p);
         for (hipEvent_t e : {ev_text, ev_h2d, ev_info, ev_render})
             if (e) (void)hipEventDestroy(e);
-        for (void* p : {d_tiles, d_lens, d_results, d_arena, d_ascii, d_soff, d_ids, d_idoff, d_len, d_off, d_scan, d_flag, d_text, d_raw, d_chunk, d_first, d_fq_tmp, d_ls, d_rec, d_info})
-            if (p) (void)hipFree(p);
         *this = BatchCtx();
     }
 };
@@ -182,75 +187,44 @@ struct BatchCtx {   // pinned host buffers + device buffers of one batch in flig
 // pinned host + device buffers of a batch of n reads of wpr words (grow-only; cap_reads: the size to allocate when growing)
 inline int batch_ensure(pa_index* idx, BatchCtx& c, uint64_t n, uint32_t wpr, uint64_t cap_reads) {
     cap_reads = std::max<uint64_t>(n, cap_reads);
-    const size_t tb = pa_tiles_words(n, wpr) * 8 + 8;
-    if (tb > c.tiles_bytes || !c.d_tiles) {   // (the tiles only exist on the device: pa_encode_reads_device writes them)
-        const size_t want = pa_tiles_words(cap_reads, wpr) * 8 + 8;
-        if (c.d_tiles) (void)hipFree(c.d_tiles);
-        c.d_tiles = nullptr;
-        c.tiles_bytes = 0;
-        PA_INGEST_HIP_OK(hipMalloc(&c.d_tiles, want));
-        c.tiles_bytes = want;
-    }
+    int e = c.d_tiles.reserve(pa_tiles_words(n, wpr) + 1, pa_tiles_words(cap_reads, wpr) + 1);   // (the tiles only exist on the device: pa_encode_reads_device writes them)
+    if (e != PA_OK) return e;
     if (n + 64 > c.reads_cap) {
         const size_t cap = cap_reads + 64;
-        for (void** q : {&c.d_lens, &c.d_results, &c.d_len, &c.d_off, &c.d_scan}) { if (*q) (void)hipFree(*q); *q = nullptr; }
         c.reads_cap = 0;
-        PA_INGEST_HIP_OK(hipMalloc(&c.d_lens, cap * 4));
-        PA_INGEST_HIP_OK(hipMalloc(&c.d_results, cap * sizeof(pa_read_result)));
-        PA_INGEST_HIP_OK(hipMalloc(&c.d_len, (cap + 1) * 4));
-        PA_INGEST_HIP_OK(hipMalloc(&c.d_off, (cap + 1) * 8));
+        c.d_lens.release(); c.d_results.release(); c.d_len.release(); c.d_off.release(); c.d_scan.release();
         c.scan_bytes = render_scan_bytes(cap);
-        PA_INGEST_HIP_OK(hipMalloc(&c.d_scan, c.scan_bytes ? c.scan_bytes : 16));
+        if ((e = c.d_lens.alloc(cap)) || (e = c.d_results.alloc(cap)) || (e = c.d_len.alloc(cap + 1)) || (e = c.d_off.alloc(cap + 1)) ||
+            (e = c.d_scan.alloc(c.scan_bytes ? c.scan_bytes : 16)))
+            return e;
         c.reads_cap = cap;
     }
-    if (!c.h_tot) {
-        PA_INGEST_HIP_OK(hipHostMalloc((void**)&c.h_tot, (1 + PA_RENDER_FLAG_BUCKETS) * 8, hipHostMallocDefault));
-        PA_INGEST_HIP_OK(hipMalloc(&c.d_flag, PA_RENDER_FLAG_BUCKETS * 8));
-        PA_INGEST_HIP_OK(hipEventCreateWithFlags(&c.ev_text, hipEventDisableTiming | hipEventBlockingSync));
+    if (!c.h_tot.get()) {
+        if ((e = c.h_tot.alloc(1 + PA_RENDER_FLAG_BUCKETS)) || (e = c.d_flag.alloc(PA_RENDER_FLAG_BUCKETS))) return e;
+        PA_HIP_TRY(hipEventCreateWithFlags(&c.ev_text, hipEventDisableTiming | hipEventBlockingSync));
     }
     if (!c.in_place) {   // gathered ids and sequences (record stream)
         if (n + 64 > c.soff_cap) {
             const size_t cap = cap_reads + 64;
-            if (c.h_soff) (void)hipHostFree(c.h_soff);
-            if (c.h_idoff) (void)hipHostFree(c.h_idoff);
-            for (void** q : {&c.d_soff, &c.d_idoff}) { if (*q) (void)hipFree(*q); *q = nullptr; }
-            c.h_soff = nullptr; c.h_idoff = nullptr;
             c.soff_cap = 0;
-            PA_INGEST_HIP_OK(hipHostMalloc((void**)&c.h_soff, (cap + 1) * 8, hipHostMallocDefault));
-            PA_INGEST_HIP_OK(hipHostMalloc((void**)&c.h_idoff, (cap + 1) * 8, hipHostMallocDefault));
-            PA_INGEST_HIP_OK(hipMalloc(&c.d_soff, (cap + 1) * 8));
-            PA_INGEST_HIP_OK(hipMalloc(&c.d_idoff, (cap + 1) * 8));
+            c.h_soff.release(); c.h_idoff.release(); c.d_soff.release(); c.d_idoff.release();
+            if ((e = c.h_soff.alloc(cap + 1)) || (e = c.h_idoff.alloc(cap + 1)) || (e = c.d_soff.alloc(cap + 1)) || (e = c.d_idoff.alloc(cap + 1))) return e;
             c.soff_cap = cap;
         }
-        if (c.ids_bytes + 64 > c.ids_cap) {
+        // (h_* then d_*: the device buffer is empty unless both are there)
+        if (c.ids_bytes + 64 > c.d_ids.size()) {
             const size_t want = std::max<size_t>(c.ids_bytes + c.ids_bytes / 8 + 4096, (size_t)cap_reads * 16);
-            if (c.h_ids) (void)hipHostFree(c.h_ids);
-            if (c.d_ids) (void)hipFree(c.d_ids);
-            c.h_ids = nullptr; c.d_ids = nullptr;
-            c.ids_cap = 0;
-            PA_INGEST_HIP_OK(hipHostMalloc((void**)&c.h_ids, want, hipHostMallocDefault));
-            PA_INGEST_HIP_OK(hipMalloc(&c.d_ids, want));
-            c.ids_cap = want;
+            c.d_ids.release();
+            if ((e = c.h_ids.alloc(want)) || (e = c.d_ids.alloc(want))) return e;
         }
-        if (c.ascii_bytes + 64 > c.ascii_cap) {   // (ascii_bytes: set by the caller before this call — the sum of the batch's sequence lengths)
+        if (c.ascii_bytes + 64 > c.d_ascii.size()) {   // (ascii_bytes: set by the caller before this call — the sum of the batch's sequence lengths)
             const size_t want = std::max<size_t>(c.ascii_bytes + c.ascii_bytes / 8 + 4096, (size_t)cap_reads * 32ull * wpr / 2);
-            if (c.h_ascii) (void)hipHostFree(c.h_ascii);
-            if (c.d_ascii) (void)hipFree(c.d_ascii);
-            c.h_ascii = nullptr; c.d_ascii = nullptr;
-            c.ascii_cap = 0;
-            PA_INGEST_HIP_OK(hipHostMalloc((void**)&c.h_ascii, want, hipHostMallocDefault));
-            PA_INGEST_HIP_OK(hipMalloc(&c.d_ascii, want));
-            c.ascii_cap = want;
+            c.d_ascii.release();
+            if ((e = c.h_ascii.alloc(want)) || (e = c.d_ascii.alloc(want))) return e;
         }
     }
     const uint64_t hint = pa_map_arena_hint(idx, n);
-    if (hint > c.arena_entries) {
-        if (c.d_arena) (void)hipFree(c.d_arena);
-        c.d_arena = nullptr;
-        PA_INGEST_HIP_OK(hipMalloc(&c.d_arena, hint * 4));
-        c.arena_entries = hint;
-    }
-    return PA_OK;
+    return c.d_arena.reserve(hint, hint);
 }
 
 // The batch's sequences (at text + rec.seq_off) gathered back to back into pinned memory, with their offsets: what the GPU packs
@@ -278,16 +252,16 @@ inline void batch_gather_ascii(Pool& pool, BatchCtx& c, const char* text, const 
         uint64_t o = ps[(size_t)t], io = pi[(size_t)t];
         for (uint64_t i = c.n * (uint64_t)t / ntask; i < c.n * (uint64_t)(t + 1) / ntask; ++i) {
             const Record& rec = c.recs[i];
-            c.h_soff[i] = o;
-            memcpy(c.h_ascii + o, text + rec.seq_off, rec.seq_len);
+            c.h_soff.get()[i] = o;
+            memcpy(c.h_ascii.get() + o, text + rec.seq_off, rec.seq_len);
             o += rec.seq_len;
-            c.h_idoff[i] = io;
-            memcpy(c.h_ids + io, text + rec.id_off, rec.id_len);
+            c.h_idoff.get()[i] = io;
+            memcpy(c.h_ids.get() + io, text + rec.id_off, rec.id_len);
             io += rec.id_len;
         }
     });
-    c.h_soff[c.n] = c.ascii_bytes;
-    c.h_idoff[c.n] = c.ids_bytes;
+    c.h_soff.get()[c.n] = c.ascii_bytes;
+    c.h_idoff.get()[c.n] = c.ids_bytes;
 }
 
 // the GPU leg of a batch, asynchronous on `stream`: tiles H2D -> index.map_read for every read (:451) -> records D2H
@@ -334,48 +308,31 @@ constexpr uint64_t WINDOW_HEAD_ROOM = 1ull << 20;   // bytes in front of a windo
 
 // pinned + device copy of a window of up to `bytes` bytes (grow-only; 64 spare bytes: the scan kernels load whole 16-byte groups)
 inline int window_ensure_raw(BatchCtx& c, uint64_t bytes) {
-    if (bytes + 64 <= c.raw_cap) return PA_OK;
     const size_t want = (size_t)bytes + 64;
-    if (c.h_raw) (void)hipHostFree(c.h_raw);
-    if (c.d_raw) (void)hipFree(c.d_raw);
-    c.h_raw = nullptr; c.d_raw = nullptr;
-    c.raw_cap = 0;
-    PA_INGEST_HIP_OK(hipHostMalloc((void**)&c.h_raw, want, hipHostMallocDefault));
-    PA_INGEST_HIP_OK(hipMalloc(&c.d_raw, want));
-    c.raw_cap = want;
-    return PA_OK;
+    if (want <= c.d_raw.size()) return PA_OK;   // (h_raw then d_raw: d_raw is empty unless both are there)
+    c.d_raw.release();
+    int e = c.h_raw.alloc(want);
+    return e != PA_OK ? e : c.d_raw.alloc(want);
 }
 inline int window_ensure_events(BatchCtx& c) {
-    if (!c.ev_h2d) PA_INGEST_HIP_OK(hipEventCreateWithFlags(&c.ev_h2d, hipEventDisableTiming));
+    if (!c.ev_h2d) PA_HIP_TRY(hipEventCreateWithFlags(&c.ev_h2d, hipEventDisableTiming));
     // (blocking: the thread that waits for a window's scan sleeps — the pool's workers are reading the next window on every CPU of the quota, and a spinning
     // waiter on top of them gets the whole process throttled)
-    if (!c.ev_info) PA_INGEST_HIP_OK(hipEventCreateWithFlags(&c.ev_info, hipEventDisableTiming | hipEventBlockingSync));
-    if (!c.ev_render) PA_INGEST_HIP_OK(hipEventCreateWithFlags(&c.ev_render, hipEventDisableTiming));
-    if (!c.h_info) {
-        PA_INGEST_HIP_OK(hipHostMalloc((void**)&c.h_info, sizeof(FqInfo), hipHostMallocDefault));
-        PA_INGEST_HIP_OK(hipMalloc(&c.d_info, sizeof(FqInfo)));
+    if (!c.ev_info) PA_HIP_TRY(hipEventCreateWithFlags(&c.ev_info, hipEventDisableTiming | hipEventBlockingSync));
+    if (!c.ev_render) PA_HIP_TRY(hipEventCreateWithFlags(&c.ev_render, hipEventDisableTiming));
+    if (!c.h_info.get()) {
+        int e = c.h_info.alloc(1);
+        if (e == PA_OK) e = c.d_info.alloc(1);
+        if (e != PA_OK) return e;
     }
     return PA_OK;
 }
 // records of a window: room for `recs` of them on the device (and in pinned memory when the host fills them in)
 inline int window_ensure_recs(BatchCtx& c, uint64_t recs, bool host_side) {
-    if (recs + 1 > c.rec_cap) {
-        const size_t want = (size_t)(recs + recs / 8 + 1024);
-        if (c.d_rec) (void)hipFree(c.d_rec);
-        c.d_rec = nullptr;
-        c.rec_cap = 0;
-        PA_INGEST_HIP_OK(hipMalloc(&c.d_rec, want * sizeof(uint4)));
-        c.rec_cap = want;
-    }
-    if (host_side && recs + 1 > c.h_rec_cap) {
-        const size_t want = (size_t)(recs + recs / 8 + 1024);
-        if (c.h_rec) (void)hipHostFree(c.h_rec);
-        c.h_rec = nullptr;
-        c.h_rec_cap = 0;
-        PA_INGEST_HIP_OK(hipHostMalloc((void**)&c.h_rec, want * sizeof(uint4), hipHostMallocDefault));
-        c.h_rec_cap = want;
-    }
-    return PA_OK;
+    const size_t want = (size_t)(recs + recs / 8 + 1024);
+    int e = c.d_rec.reserve(recs + 1, want);
+    if (e == PA_OK && host_side) e = c.h_rec.reserve(recs + 1, want);
+    return e;
 }
 // scratch of the GPU scan of the window [raw_begin, raw_end): chunk counts and prefixes, line starts for `lines` lines (0: a guess from the
 // window's size — FASTQ of 150-base reads has a line break per 79 bytes, of 60-base reads per 36)
@@ -385,32 +342,23 @@ inline int window_ensure_scan(BatchCtx& c, uint64_t lines) {
     const uint32_t chunks = fq_chunks(c.raw_begin, c.raw_end);
     if ((size_t)chunks + 1 > c.chunk_cap) {
         const size_t want = (size_t)chunks + chunks / 8 + 64;
-        for (void** q : {&c.d_chunk, &c.d_first, &c.d_fq_tmp}) { if (*q) (void)hipFree(*q); *q = nullptr; }
         c.chunk_cap = 0;
-        PA_INGEST_HIP_OK(hipMalloc(&c.d_chunk, want * 4));
-        PA_INGEST_HIP_OK(hipMalloc(&c.d_first, want * 4));
+        c.d_chunk.release(); c.d_first.release(); c.d_fq_tmp.release();
         c.fq_tmp_bytes = fq_scan_tmp_bytes((uint32_t)want);
-        PA_INGEST_HIP_OK(hipMalloc(&c.d_fq_tmp, c.fq_tmp_bytes ? c.fq_tmp_bytes : 16));
+        if ((e = c.d_chunk.alloc(want)) || (e = c.d_first.alloc(want)) || (e = c.d_fq_tmp.alloc(c.fq_tmp_bytes ? c.fq_tmp_bytes : 16))) return e;
         c.chunk_cap = want;
     }
     const uint64_t need = lines ? lines + 8 : (c.raw_end - c.raw_begin) / 32 + 1024;
-    if (need > c.ls_cap) {
-        const size_t want = (size_t)(need + need / 8);
-        if (c.d_ls) (void)hipFree(c.d_ls);
-        c.d_ls = nullptr;
-        c.ls_cap = 0;
-        PA_INGEST_HIP_OK(hipMalloc(&c.d_ls, want * 4));
-        c.ls_cap = want;
-    }
-    return window_ensure_recs(c, c.ls_cap / 4, false);
+    if ((e = c.d_ls.reserve(need, need + need / 8))) return e;
+    return window_ensure_recs(c, c.d_ls.size() / 4, false);
 }
 // the window's records found on the GPU, asynchronous on `stream`: c.h_info is valid once c.ev_info has passed
 inline int window_scan_enqueue(BatchCtx& c, bool rescan, hipStream_t stream) {
-    const int k = launch_fq_scan((const uint8_t*)c.d_raw, c.raw_begin, c.raw_end, (uint32_t*)c.d_chunk, (uint32_t*)c.d_first, c.d_fq_tmp, c.fq_tmp_bytes, (uint32_t*)c.d_ls, c.ls_cap,
-                                 (uint4*)c.d_rec, c.rec_cap, (FqInfo*)c.d_info, rescan, stream);
+    const int k = launch_fq_scan(c.d_raw.get(), c.raw_begin, c.raw_end, c.d_chunk.get(), c.d_first.get(), c.d_fq_tmp.get(), c.fq_tmp_bytes, c.d_ls.get(), c.d_ls.size(),
+                                 c.d_rec.get(), c.d_rec.size(), c.d_info.get(), rescan, stream);
     if (k) return fail(PA_ERR_HIP, "FASTQ scan: %s", hipGetErrorString((hipError_t)k));
-    PA_INGEST_HIP_OK(hipMemcpyAsync(c.h_info, c.d_info, sizeof(FqInfo), hipMemcpyDeviceToHost, stream));
-    PA_INGEST_HIP_OK(hipEventRecord(c.ev_info, stream));
+    PA_HIP_TRY(hipMemcpyAsync(c.h_info.get(), c.d_info.get(), sizeof(FqInfo), hipMemcpyDeviceToHost, stream));
+    PA_HIP_TRY(hipEventRecord(c.ev_info, stream));
     return PA_OK;
 }
 
@@ -418,49 +366,49 @@ inline int window_scan_enqueue(BatchCtx& c, bool rescan, hipStream_t stream) {
 // lengths + scan (d_off[n] = the text's bytes, copied to h_tot with the number of flagged reads), then — when buffers exist — the
 // bytes and their copy to pinned memory, c.spec_bytes of them: a guess from the batch before (the host only learns the exact length
 // when the batch is finished; a text that turns out longer is rendered again by batch_finish)
-inline const uint8_t* batch_id_bytes(const BatchCtx& c) { return (const uint8_t*)(c.in_place ? c.d_raw : c.d_ids); }
-inline const uint4* batch_rec(const BatchCtx& c) { return c.in_place ? (const uint4*)c.d_rec : nullptr; }
+inline const uint8_t* batch_id_bytes(const BatchCtx& c) { return c.in_place ? c.d_raw.get() : c.d_ids.get(); }
+inline const uint4* batch_rec(const BatchCtx& c) { return c.in_place ? c.d_rec.get() : nullptr; }
 inline int batch_render_enqueue(pa_index* idx, BatchCtx& c, hipStream_t stream) {
     const uint64_t* d_cls_off = nullptr;
     const uint8_t* d_cls_txt = nullptr;
     int e = index_device_class_text(idx, &d_cls_off, &d_cls_txt);
     if (e != PA_OK) return e;
-    PA_INGEST_HIP_OK(hipMemsetAsync(c.d_flag, 0, PA_RENDER_FLAG_BUCKETS * 8, stream));
-    int k = launch_render_len((const pa_read_result*)c.d_results, (const uint32_t*)c.d_arena, batch_id_bytes(c), (const uint64_t*)c.d_idoff, batch_rec(c), d_cls_off, d_cls_txt, c.n,
-                              c.arena_entries, c.flag_mark, (uint32_t*)c.d_len, (uint64_t*)c.d_off, (unsigned long long*)c.d_flag, c.d_scan, c.scan_bytes, stream);
+    PA_HIP_TRY(hipMemsetAsync(c.d_flag.get(), 0, PA_RENDER_FLAG_BUCKETS * 8, stream));
+    int k = launch_render_len(c.d_results.get(), c.d_arena.get(), batch_id_bytes(c), c.d_idoff.get(), batch_rec(c), d_cls_off, d_cls_txt, c.n,
+                              c.d_arena.size(), c.flag_mark, c.d_len.get(), c.d_off.get(), c.d_flag.get(), c.d_scan.get(), c.scan_bytes, stream);
     if (k) return fail(PA_ERR_HIP, "render (lengths): %s", hipGetErrorString((hipError_t)k));
-    PA_INGEST_HIP_OK(hipMemcpyAsync(c.h_tot, (const uint64_t*)c.d_off + c.n, 8, hipMemcpyDeviceToHost, stream));
-    PA_INGEST_HIP_OK(hipMemcpyAsync(c.h_tot + 1, c.d_flag, PA_RENDER_FLAG_BUCKETS * 8, hipMemcpyDeviceToHost, stream));
+    PA_HIP_TRY(hipMemcpyAsync(c.h_tot.get(), c.d_off.get() + c.n, 8, hipMemcpyDeviceToHost, stream));
+    PA_HIP_TRY(hipMemcpyAsync(c.h_tot.get() + 1, c.d_flag.get(), PA_RENDER_FLAG_BUCKETS * 8, hipMemcpyDeviceToHost, stream));
     c.spec_bytes = 0;
-    if (c.text_cap && c.text_guess) {
-        c.spec_bytes = std::min(c.text_cap, c.text_guess);
-        k = launch_render_write((const pa_read_result*)c.d_results, (const uint32_t*)c.d_arena, batch_id_bytes(c), (const uint64_t*)c.d_idoff, batch_rec(c), d_cls_off, d_cls_txt, c.n,
-                                c.arena_entries, (const uint64_t*)c.d_off, (uint8_t*)c.d_text, c.spec_bytes, stream);
+    if (c.text_cap() && c.text_guess) {
+        c.spec_bytes = std::min(c.text_cap(), c.text_guess);
+        k = launch_render_write(c.d_results.get(), c.d_arena.get(), batch_id_bytes(c), c.d_idoff.get(), batch_rec(c), d_cls_off, d_cls_txt, c.n,
+                                c.d_arena.size(), c.d_off.get(), c.d_text.get(), c.spec_bytes, stream);
         if (k) return fail(PA_ERR_HIP, "render (text): %s", hipGetErrorString((hipError_t)k));
         c.text_on_back = c.back && c.ev_render;
         if (c.text_on_back) {
-            PA_INGEST_HIP_OK(hipEventRecord(c.ev_render, stream));
-            PA_INGEST_HIP_OK(hipStreamWaitEvent(c.back, c.ev_render, 0));
+            PA_HIP_TRY(hipEventRecord(c.ev_render, stream));
+            PA_HIP_TRY(hipStreamWaitEvent(c.back, c.ev_render, 0));
         }
-        PA_INGEST_HIP_OK(hipMemcpyAsync(c.h_text, c.d_text, c.spec_bytes, hipMemcpyDeviceToHost, c.text_on_back ? c.back : stream));
+        PA_HIP_TRY(hipMemcpyAsync(c.h_text.get(), c.d_text.get(), c.spec_bytes, hipMemcpyDeviceToHost, c.text_on_back ? c.back : stream));
     }
     return PA_OK;
 }
 
 inline int batch_launch(pa_index* idx, BatchCtx& c, hipStream_t stream) {
     if (c.in_place) {   // sequences and ids are read where they lie in the window's text (already in HBM, records in d_rec)
-        const int k = launch_encode_rec((const uint8_t*)c.d_raw, (const uint4*)c.d_rec, c.n, c.wpr, (uint64_t*)c.d_tiles, (uint32_t*)c.d_lens, stream);   // :450
+        const int k = launch_encode_rec(c.d_raw.get(), c.d_rec.get(), c.n, c.wpr, c.d_tiles.get(), c.d_lens.get(), stream);   // :450
         if (k) return fail(PA_ERR_HIP, "encode launch: %s", hipGetErrorString((hipError_t)k));
     } else {
-        PA_INGEST_HIP_OK(hipMemcpyAsync(c.d_ascii, c.h_ascii, c.ascii_bytes, hipMemcpyHostToDevice, stream));
-        PA_INGEST_HIP_OK(hipMemcpyAsync(c.d_soff, c.h_soff, (c.n + 1) * 8, hipMemcpyHostToDevice, stream));
-        PA_INGEST_HIP_OK(hipMemcpyAsync(c.d_ids, c.h_ids, c.ids_bytes, hipMemcpyHostToDevice, stream));
-        PA_INGEST_HIP_OK(hipMemcpyAsync(c.d_idoff, c.h_idoff, (c.n + 1) * 8, hipMemcpyHostToDevice, stream));
-        const int e0 = pa_encode_reads_device(idx, (const uint8_t*)c.d_ascii, (const uint64_t*)c.d_soff, c.n, c.wpr, (uint64_t*)c.d_tiles, (uint32_t*)c.d_lens, stream);   // :450
+        PA_HIP_TRY(hipMemcpyAsync(c.d_ascii.get(), c.h_ascii.get(), c.ascii_bytes, hipMemcpyHostToDevice, stream));
+        PA_HIP_TRY(hipMemcpyAsync(c.d_soff.get(), c.h_soff.get(), (c.n + 1) * 8, hipMemcpyHostToDevice, stream));
+        PA_HIP_TRY(hipMemcpyAsync(c.d_ids.get(), c.h_ids.get(), c.ids_bytes, hipMemcpyHostToDevice, stream));
+        PA_HIP_TRY(hipMemcpyAsync(c.d_idoff.get(), c.h_idoff.get(), (c.n + 1) * 8, hipMemcpyHostToDevice, stream));
+        const int e0 = pa_encode_reads_device(idx, c.d_ascii.get(), c.d_soff.get(), c.n, c.wpr, c.d_tiles.get(), c.d_lens.get(), stream);   // :450
         if (e0 != PA_OK) return e0;
     }
-    const int e = pa_map_batch_device(idx, (const uint64_t*)c.d_tiles, (const uint32_t*)c.d_lens, c.n, c.wpr, PA_DEFAULT_ALLOWED_MISMATCHES,
-                                      (pa_read_result*)c.d_results, (uint32_t*)c.d_arena, c.arena_entries, nullptr, stream);
+    const int e = pa_map_batch_device(idx, c.d_tiles.get(), c.d_lens.get(), c.n, c.wpr, PA_DEFAULT_ALLOWED_MISMATCHES,
+                                      c.d_results.get(), c.d_arena.get(), c.d_arena.size(), nullptr, stream);
     if (e != PA_OK) return e;
     return batch_render_enqueue(idx, c, stream);   // (the records stay on the device: the render kernels read them there)
 }
@@ -471,46 +419,38 @@ inline int batch_finish(pa_index* idx, BatchCtx& c, hipStream_t stream) {
     uint64_t used = 0, need = 0;
     int e = pa_map_finish(idx, stream, &used, &need);
     for (int attempt = 0; e == PA_ERR_ARENA_FULL && attempt < 3; ++attempt) {
-        if (c.d_arena) (void)hipFree(c.d_arena);
-        c.d_arena = nullptr;
-        c.arena_entries = need + need / 8 + 4096;
-        PA_INGEST_HIP_OK(hipMalloc(&c.d_arena, c.arena_entries * 4));
+        if ((e = c.d_arena.alloc(need + need / 8 + 4096)) != PA_OK) return e;
         e = batch_launch(idx, c, stream);
         if (e == PA_OK) e = pa_map_finish(idx, stream, &used, &need);
     }
     if (e != PA_OK) return e;
     // (pa_map_finish synchronised the stream: the lengths — and the speculative text, if any — have arrived)
-    c.text_bytes = (size_t)c.h_tot[0];
+    c.text_bytes = (size_t)c.h_tot.get()[0];
     c.flagged = 0;
-    for (uint32_t j = 0; j < PA_RENDER_FLAG_BUCKETS; ++j) c.flagged += c.h_tot[1 + j];
+    for (uint32_t j = 0; j < PA_RENDER_FLAG_BUCKETS; ++j) c.flagged += c.h_tot.get()[1 + j];
     c.text_guess = c.text_bytes + c.text_bytes / 8 + (64 << 10);
     bool on_back = c.text_on_back && c.spec_bytes != 0;
     if (c.text_bytes > c.spec_bytes) {   // no guess yet (first batches) or a text longer than guessed: size the buffers, write it, fetch it
-        if (on_back) { PA_INGEST_HIP_OK(hipStreamSynchronize(c.back)); on_back = false; }   // (the copy of the guessed part is not left in flight beside this one)
-        if (c.text_bytes + 64 > c.text_cap) {
+        if (on_back) { PA_HIP_TRY(hipStreamSynchronize(c.back)); on_back = false; }   // (the copy of the guessed part is not left in flight beside this one)
+        if (c.text_bytes + 64 > c.text_cap()) {
             const size_t want = c.text_bytes + c.text_bytes / 4 + (1 << 20);
-            if (c.h_text) (void)hipHostFree(c.h_text);
-            if (c.d_text) (void)hipFree(c.d_text);
-            c.h_text = nullptr; c.d_text = nullptr;
-            c.text_cap = 0;
-            PA_INGEST_HIP_OK(hipHostMalloc((void**)&c.h_text, want, hipHostMallocDefault));
-            PA_INGEST_HIP_OK(hipMalloc(&c.d_text, want));
-            c.text_cap = want;
+            c.d_text.release();
+            if ((e = c.h_text.alloc(want)) || (e = c.d_text.alloc(want))) return e;
         }
         const uint64_t* d_cls_off = nullptr;
         const uint8_t* d_cls_txt = nullptr;
         if ((e = index_device_class_text(idx, &d_cls_off, &d_cls_txt)) != PA_OK) return e;
-        const int k = launch_render_write((const pa_read_result*)c.d_results, (const uint32_t*)c.d_arena, batch_id_bytes(c), (const uint64_t*)c.d_idoff, batch_rec(c), d_cls_off, d_cls_txt, c.n,
-                                          c.arena_entries, (const uint64_t*)c.d_off, (uint8_t*)c.d_text, c.text_cap, stream);
+        const int k = launch_render_write(c.d_results.get(), c.d_arena.get(), batch_id_bytes(c), c.d_idoff.get(), batch_rec(c), d_cls_off, d_cls_txt, c.n,
+                                          c.d_arena.size(), c.d_off.get(), c.d_text.get(), c.text_cap(), stream);
         if (k) return fail(PA_ERR_HIP, "render (text): %s", hipGetErrorString((hipError_t)k));
-        if (c.text_bytes) PA_INGEST_HIP_OK(hipMemcpyAsync(c.h_text, c.d_text, c.text_bytes, hipMemcpyDeviceToHost, stream));
+        if (c.text_bytes) PA_HIP_TRY(hipMemcpyAsync(c.h_text.get(), c.d_text.get(), c.text_bytes, hipMemcpyDeviceToHost, stream));
     }
-    PA_INGEST_HIP_OK(hipEventRecord(c.ev_text, on_back ? c.back : stream));
+    PA_HIP_TRY(hipEventRecord(c.ev_text, on_back ? c.back : stream));
     return PA_OK;
 }
 // the batch's tuples have arrived in c.h_text[0 .. c.text_bytes)
 inline int batch_text_wait(BatchCtx& c) {
-    PA_INGEST_HIP_OK(hipEventSynchronize(c.ev_text));
+    PA_HIP_TRY(hipEventSynchronize(c.ev_text));
     return PA_OK;
 }
 

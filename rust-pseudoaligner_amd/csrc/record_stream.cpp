@@ -102,7 +102,7 @@ int render(pa_record_stream* s, int k) {
         const size_t total = c.text_bytes;
         s->pool->run(P, [&](int t) {
             const size_t a = total * (size_t)t / P, b = total * (size_t)(t + 1) / P;
-            memcpy(dst + a, c.h_text + a, b - a);
+            memcpy(dst + a, c.h_text.get() + a, b - a);
         });
         buf.len = total;
         s->outq.push_back(std::move(buf));
