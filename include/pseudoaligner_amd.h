@@ -414,6 +414,52 @@ int pa_counts_by_barcode_device(pa_index* idx, const pa_read_result* d_results, 
                                 const uint32_t* d_barcode, uint64_t n_reads, uint32_t barcode_bits, uint64_t* d_keys,
                                 uint32_t* d_vals, uint64_t* n_entries, void* stream);
 
+/* ---------------- single-cell UMI count matrix (10x Chromium: R1 = cell barcode + UMI, R2 = cDNA) ----------------
+ * R1 bases [0, bc_len) are the barcode, [bc_len, bc_len + umi_len) the UMI (both lengths 1..16); only the bytes A C G T are bases, any other
+ * byte is an N. Per read, in this order:
+ *   barcode   in the whitelist: exact; else (no N) the one whitelist barcode among its 3 bc_len single substitutions, or (exactly one N)
+ *             the one among the 4 bases at the N; none, several or two Ns: invalid. An R1 shorter than bc_len + umi_len: invalid
+ *   UMI       an N drops the read; else packed 2 bits per base, first base most significant (integer order = string order)
+ *   gene      R2 mapped as map_read maps it (PA_DEFAULT_ALLOWED_MISMATCHES); confidently mapped = mapped, non-empty class whose
+ *             transcripts (tx_gene) all belong to one gene; everything else drops
+ * Per (cell, gene), with n(u) = reads of UMI u: every UMI moves to the greatest of {u} and its Hamming-1 neighbours present in the
+ * group, ordered by (n, UMI value) — one step, not transitive. Per (cell, corrected UMI) across genes the gene with strictly the most
+ * reads keeps the molecule (a tie drops it everywhere). Matrix entry (cell, gene) = distinct surviving UMIs.
+ * The molecule key packs cell | gene | UMI in 64 bits: bits(n_whitelist - 1) + bits(num_genes - 1) + 2 umi_len > 64 is PA_ERR_UNSUPPORTED.
+ * stats[PA_CELL_STATS]: [0] reads, [1] barcode exact, [2] barcode corrected, [3] barcode invalid, [4] UMI invalid, [5] not confidently
+ * mapped, [6] reads counted, [7] UMIs corrected (moved), [8] molecules lost to gene conflicts, [9] UMIs in the matrix (after finish);
+ * [0] = [3] + [4] + [5] + [6] and [1] + [2] = [4] + [5] + [6]. */
+#define PA_CELL_STATS 10
+typedef struct pa_cell_counter pa_cell_counter;
+/* The counter of one run on idx's GPU. h: the host index idx was created from (its classes give the per-class gene table; class
+ * numbering must be idx's), tx_gene[pa_host_index_num_transcripts(h)] < num_genes (pa_host_index_genes gives the reference's),
+ * whitelist: n_whitelist * bc_len bytes, no separators, line i = cell i. Every argument is checked before any device call. */
+int pa_cell_counter_create(pa_index* idx, const pa_host_index* h, const uint32_t* tx_gene, uint32_t num_genes,
+                           const char* whitelist, uint64_t n_whitelist, uint32_t bc_len, uint32_t umi_len, pa_cell_counter** out);
+/* One batch: d_results / d_arena as pa_map_batch_device left them for the R2s, d_r1 the R1s (ASCII, back to back, d_r1_offsets[n+1];
+ * only the first bc_len + umi_len bytes of each are read). Call any number of times: molecules are collapsed over the whole run.
+ * Synchronous on `stream`. PA_ERR_INVALID_ARG after finish. */
+int pa_cell_counter_add_device(pa_cell_counter* c, const pa_read_result* d_results, const uint32_t* d_arena,
+                               const uint8_t* d_r1, const uint64_t* d_r1_offsets, uint64_t n_reads, void* stream);
+/* UMI correction + gene conflicts + count (synchronous); *n_entries = non-zero matrix entries. */
+int pa_cell_counter_finish(pa_cell_counter* c, uint64_t* n_entries);
+/* the matrix after finish, sorted by (cell, gene): cell / gene / umis [n_entries] (cap < n_entries: PA_ERR_BUFFER_TOO_SMALL) */
+int pa_cell_counter_matrix(const pa_cell_counter* c, uint32_t* cell, uint32_t* gene, uint32_t* umis, uint64_t cap);
+int pa_cell_counter_stats(const pa_cell_counter* c, uint64_t stats[PA_CELL_STATS]);
+void pa_cell_counter_destroy(pa_cell_counter* c);
+/* Barcode whitelist file (plain or gzip'ed, LF or CRLF, one barcode per line) -> out[n * bc_len] (no separators). out NULL: only *n.
+ * PA_ERR_FORMAT naming the line for a wrong length, a non-ACGT byte or a duplicate; cap (barcodes) < n: PA_ERR_BUFFER_TOO_SMALL. Host only. */
+int pa_whitelist_load(const char* path, uint32_t bc_len, char* out, uint64_t cap, uint64_t* n);
+/* The whole chain from files: R1 / R2 FASTQ (acceptance rules of pa_process_reads, gzip included; equal record counts and equal
+ * record.id() after a trailing "/1" or "/2" is cut, else PA_ERR_FORMAT with the record number), the whitelist file, genes from
+ * pa_host_index_genes(h) -> out_dir/matrix.mtx (MatrixMarket coordinate integer general: genes x cells, 1-based "gene cell umis"
+ * sorted by cell then gene), out_dir/barcodes.tsv (the whitelist barcodes with at least one UMI, in whitelist order = the columns),
+ * out_dir/features.tsv ("name\tname\tGene Expression" for every gene). stats may be NULL. Batches of about 2 M pairs; the next batch
+ * is read while the GPU maps and counts the one before. pa_process_reads_stage_seconds then reports this call's stages:
+ * [0] scan, [1] gather, [2] waiting for the mapping, [3] launch, [4] counting (add_device + finish), [5] writing, [6] whole, [7] pairs. */
+int pa_count_cells(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const char* whitelist_path,
+                   uint32_t bc_len, uint32_t umi_len, const char* out_dir, int num_threads, uint64_t stats[PA_CELL_STATS]);
+
 /* ---------------- novel classes + the reduction over GPUs ---------------- */
 /* The dense table counts every result that is no index class in ONE slot (counts[num_classes]). A pa_overflow keeps WHICH
  * id sets those were, keyed by content, on the GPU: attach one to an index and every pa_map_count_batch_device launch files

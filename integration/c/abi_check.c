@@ -88,6 +88,28 @@ int main(int argc, char** argv) {
                starts[1] > starts[0] + hdr[0] + sq[0]);
     }
 
+    {   /* single-cell counting, host side: the whitelist file and argument checks that come before any device call */
+        uint64_t nwl = 0;
+        char wlb[4 * 4];
+        FILE* f;
+        snprintf(path, sizeof path, "%s/abi_check_whitelist.txt", dir);
+        f = fopen(path, "w");
+        if (f) { fputs("ACGT\r\nTTTT\nGGCA\n", f); fclose(f); }
+        EXPECT(pa_whitelist_load(path, 4, NULL, 0, &nwl) == PA_OK && nwl == 3);
+        EXPECT(pa_whitelist_load(path, 4, wlb, 4, &nwl) == PA_OK && memcmp(wlb, "ACGTTTTTGGCA", 12) == 0);
+        EXPECT(pa_whitelist_load(path, 5, NULL, 0, &nwl) == PA_ERR_FORMAT);
+        pa_cell_counter* cc = NULL;
+        uint64_t cst[PA_CELL_STATS], nent = 0;
+        EXPECT(pa_cell_counter_create(NULL, h, tx_gene, ngenes, "ACGT", 1, 4, 4, &cc) == PA_ERR_INVALID_ARG && cc == NULL);
+        EXPECT(pa_cell_counter_create(NULL, h, tx_gene, ngenes, "ACGT", 1, 0, 4, &cc) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_cell_counter_add_device(NULL, NULL, NULL, NULL, NULL, 0, NULL) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_cell_counter_finish(NULL, &nent) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_cell_counter_matrix(NULL, NULL, NULL, NULL, 0) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_cell_counter_stats(NULL, cst) == PA_ERR_INVALID_ARG);
+        pa_cell_counter_destroy(NULL);
+        EXPECT(pa_count_cells(NULL, h, fastq, fastq, path, 4, 4, dir, 1, cst) == PA_ERR_INVALID_ARG);
+    }
+
     pa_txome *tx = NULL, *tx2 = NULL, *tx3 = NULL;
     EXPECT(pa_txome_synthesize(50, 120, 7, &tx) == PA_OK);
     {   /* the same genes with repeat families and low-complexity tracts in their last exons */
@@ -313,6 +335,31 @@ int main(int argc, char** argv) {
                                                (uint32_t*)d_vals, &cells, NULL) == PA_OK && cells >= 4 && cells <= nsim);
             EXPECT(pa_device_free(d_bc) == PA_OK && pa_device_free(d_keys) == PA_OK && pa_device_free(d_vals) == PA_OK);
             free(bc);
+        }
+        {   /* single-cell UMI counts: the toy reads as R2, R1 = a whitelisted barcode + UMI per read; then the file-level entry (the
+               FASTQ as both R1 and R2: its reads' first 8 bases are barcode + UMI, most of them invalid) */
+            pa_cell_counter* cc = NULL;
+            const char wl[] = "ACGTTGCA";
+            uint8_t* r1 = (uint8_t*)malloc(nsim * 8);
+            uint64_t* r1o = (uint64_t*)malloc((nsim + 1) * 8);
+            void *d_r1 = NULL, *d_r1o = NULL;
+            for (uint64_t i = 0; i <= nsim; ++i) r1o[i] = i * 8;
+            for (uint64_t i = 0; i < nsim; ++i) { memcpy(r1 + i * 8, (i & 1) ? "ACGT" : "TGCA", 4); memcpy(r1 + i * 8 + 4, "ACGTACGT" + (i % 4), 4); }
+            EXPECT(pa_cell_counter_create(idx, h, tx_gene, ngenes, wl, 2, 4, 4, &cc) == PA_OK && cc);
+            EXPECT(pa_device_malloc(0, nsim * 8, &d_r1) == PA_OK && pa_device_malloc(0, (nsim + 1) * 8, &d_r1o) == PA_OK);
+            EXPECT(pa_memcpy_h2d(d_r1, r1, nsim * 8, NULL) == PA_OK && pa_memcpy_h2d(d_r1o, r1o, (nsim + 1) * 8, NULL) == PA_OK);
+            EXPECT(pa_cell_counter_add_device(cc, (const pa_read_result*)d_res, (const uint32_t*)d_arena, (const uint8_t*)d_r1, (const uint64_t*)d_r1o, nsim, NULL) == PA_OK);
+            uint64_t nent = 0, cst[PA_CELL_STATS];
+            EXPECT(pa_cell_counter_finish(cc, &nent) == PA_OK && nent >= 1);
+            uint32_t *mc = (uint32_t*)calloc(nent + 1, 4), *mg = (uint32_t*)calloc(nent + 1, 4), *mu = (uint32_t*)calloc(nent + 1, 4);
+            EXPECT(pa_cell_counter_matrix(cc, mc, mg, mu, nent) == PA_OK && mc[0] <= 1 && mu[0] >= 1);
+            EXPECT(pa_cell_counter_stats(cc, cst) == PA_OK && cst[0] == nsim && cst[0] == cst[3] + cst[4] + cst[5] + cst[6] && cst[1] == nsim);
+            EXPECT(pa_cell_counter_add_device(cc, (const pa_read_result*)d_res, (const uint32_t*)d_arena, (const uint8_t*)d_r1, (const uint64_t*)d_r1o, nsim, NULL) == PA_ERR_INVALID_ARG);
+            pa_cell_counter_destroy(cc);
+            free(mc); free(mg); free(mu); free(r1); free(r1o);
+            EXPECT(pa_device_free(d_r1) == PA_OK && pa_device_free(d_r1o) == PA_OK);
+            snprintf(path, sizeof path, "%s/abi_check_whitelist.txt", dir);
+            EXPECT(pa_count_cells(idx, h, fastq, fastq, path, 4, 4, dir, 2, cst) == PA_OK && cst[0] == nreads && cst[0] == cst[3] + cst[4] + cst[5] + cst[6]);
         }
         uint64_t* h_counts = (uint64_t*)calloc(counts_len, 8);
         EXPECT(pa_memcpy_d2h(h_counts, d_counts, counts_len * 8, NULL) == PA_OK);

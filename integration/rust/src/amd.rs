@@ -168,6 +168,32 @@ pub fn process_reads_path<K: Kmer + Sync + Send, P: AsRef<Path> + Debug, Q: AsRe
     Ok(())
 }
 
+/// Single-cell UMI counts from files (pa_count_cells): a 10x run's R1 (cell barcode + UMI) and R2 (cDNA) FASTQ and its barcode
+/// whitelist -> `out_dir`/matrix.mtx, barcodes.tsv, features.tsv. `index_file`: the index as `pa_host_index_save` wrote it (it keeps the
+/// transcript -> gene names the matrix rows need; the reference's `Pseudoaligner` does too, but the flat interchange does not carry them).
+/// 10x v3: bc_len 16, umi_len 12; v2: 16, 10. Returns the ten counters of PA_CELL_STATS.
+pub fn count_cells<P: AsRef<Path>>(index_file: P, r1_fastq: P, r2_fastq: P, whitelist: P, out_dir: P, bc_len: u32, umi_len: u32,
+                                   num_threads: usize, device: i32) -> Result<[u64; PA_CELL_STATS], Error> {
+    let cstr = |p: &P| CString::new(p.as_ref().to_string_lossy().into_owned());
+    let (ix, r1, r2, wl, out) = (cstr(&index_file)?, cstr(&r1_fastq)?, cstr(&r2_fastq)?, cstr(&whitelist)?, cstr(&out_dir)?);
+    let mut h = std::ptr::null_mut();
+    check(unsafe { pa_host_index_load(ix.as_ptr(), &mut h) })?;
+    let mut view: PaFlatIndex = unsafe { std::mem::zeroed() };
+    let mut idx = std::ptr::null_mut();
+    let mut rc = unsafe { pa_host_index_view(h, &mut view) };
+    if rc >= 0 { rc = unsafe { pa_index_create(&view, device, &mut idx) }; }
+    let mut stats = [0u64; PA_CELL_STATS];
+    if rc >= 0 {
+        rc = unsafe { pa_count_cells(idx, h, r1.as_ptr(), r2.as_ptr(), wl.as_ptr(), bc_len, umi_len, out.as_ptr(), num_threads as i32, stats.as_mut_ptr()) };
+    }
+    let result = check(rc).map(|_| stats);   // (the message is read before the handles go)
+    unsafe {
+        if !idx.is_null() { pa_index_destroy(idx); }
+        pa_host_index_destroy(h);
+    }
+    result
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // Drop-in entry points with the reference's EXACT signatures. The GPU copy of an index is made on first use and cached by the
 // CONTENT of the `Pseudoaligner`: k, node / class / transcript counts and a fingerprint of EVERY base of every node, every node's

@@ -8,6 +8,7 @@ use std::os::raw::{c_char, c_int, c_void};
 pub const PA_OK: c_int = 0;
 pub const PA_ERR_ARENA_FULL: c_int = -7;
 pub const PA_ERR_BUFFER_TOO_SMALL: c_int = -10;
+pub const PA_CELL_STATS: usize = 10;
 pub const PA_MAPPED_BIT: u32 = 0x8000_0000;
 pub const PA_CLASS_REF: u32 = 0x8000_0000;
 pub const PA_MAX_ARENA_ENTRIES: u64 = 0x7FFF_FFFF;
@@ -62,6 +63,8 @@ extern "C" {
     pub fn pa_host_index_save(h: *const PaHostIndex, path: *const c_char) -> c_int;
     pub fn pa_host_index_compare(a: *const PaHostIndex, b: *const PaHostIndex, max_kmers: u64, report: *mut c_char, report_cap: usize) -> c_int;
     pub fn pa_host_index_destroy(h: *mut PaHostIndex);
+    pub fn pa_host_index_load(path: *const c_char, out: *mut *mut PaHostIndex) -> c_int;
+    pub fn pa_host_index_view(h: *const PaHostIndex, view: *mut PaFlatIndex) -> c_int;
 
     // map_read / process_reads
     pub fn pa_map_batch(idx: *mut PaIndex, ascii: *const u8, offsets: *const u64, n_reads: u64, allowed_mismatches: u32,
@@ -89,6 +92,11 @@ extern "C" {
                             n_reads: *mut u64, n_flagged: *mut u64) -> c_int;
     pub fn pa_process_reads_multi(idx: *const *mut PaIndex, n_idx: c_int, fastq_path: *const c_char, out_path: *const c_char, num_threads: c_int,
                                   n_reads: *mut u64, n_flagged: *mut u64) -> c_int;
+    // single-cell UMI count matrix from paired FASTQ (R1 = barcode + UMI, R2 = cDNA) and a whitelist; stats: u64[PA_CELL_STATS]. The
+    // device-batch counter (pa_cell_counter_*) is bound in amd_cells_ffi.rs
+    pub fn pa_whitelist_load(path: *const c_char, bc_len: u32, out: *mut c_char, cap: u64, n: *mut u64) -> c_int;
+    pub fn pa_count_cells(idx: *mut PaIndex, h: *const PaHostIndex, r1_path: *const c_char, r2_path: *const c_char, whitelist_path: *const c_char,
+                          bc_len: u32, umi_len: u32, out_dir: *const c_char, num_threads: c_int, stats: *mut u64) -> c_int;
     pub fn pa_fastq_scan_host(fastq_path: *const c_char, num_threads: c_int, n_records: *mut u64, starts: *mut u64, header_len: *mut u32,
                               seq_len: *mut u32, capacity: u64, text_kind: *mut c_int) -> c_int;
 

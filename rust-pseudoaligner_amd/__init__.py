@@ -22,7 +22,8 @@ from ._ffi import (PA_DEFAULT_ALLOWED_MISMATCHES, PA_ERR_ARENA_FULL, PA_MAPPED_B
 
 __all__ = ["HostIndex", "Txome", "Pseudoaligner", "build_index", "process_reads", "process_reads_multi", "PaError", "lib", "concat_reads",
            "gather_classes", "unpack_compact", "unpack_tiles", "RESULT_DTYPE", "PA_MAPPED_BIT", "PA_DEFAULT_ALLOWED_MISMATCHES",
-           "PA_READ_COVERAGE_THRESHOLD", "PA_CLASS_REF", "Overflow", "Comm", "parse_overflow", "serialise_overflow", "overflow_merge"]
+           "PA_READ_COVERAGE_THRESHOLD", "PA_CLASS_REF", "Overflow", "Comm", "parse_overflow", "serialise_overflow", "overflow_merge",
+           "CellCounter", "load_whitelist"]
 
 PA_CLASS_REF = 0x80000000
 RESULT_DTYPE = np.dtype([("coverage", "<u4"), ("mismatches", "<u4"), ("class_off", "<u4"), ("class_len", "<u4")])
@@ -452,6 +453,15 @@ class Pseudoaligner:
         check(lib().pa_counts_by_barcode_device(self._h, d_results, d_arena, d_barcode, n_reads, barcode_bits, d_keys, d_vals, C.byref(n), stream or None))
         return n.value
 
+    def count_cells(self, host_index: HostIndex, r1: str, r2: str, whitelist: str, out_dir: str, bc_len: int = 16, umi_len: int = 12,
+                    num_threads: int = 0) -> dict:
+        """The single-cell chain from files (pa_count_cells): paired R1 (barcode + UMI) / R2 (cDNA) FASTQ and a barcode whitelist ->
+        out_dir/matrix.mtx, barcodes.tsv, features.tsv (UMI counts, cells x genes). Returns the stats (CellCounter.stats)."""
+        st = np.zeros(_ffi.PA_CELL_STATS, np.uint64)
+        check(lib().pa_count_cells(self._h, host_index._h, str(r1).encode(), str(r2).encode(), str(whitelist).encode(), bc_len, umi_len,
+                                   str(out_dir).encode(), num_threads, st.ctypes.data))
+        return dict(zip(_ffi.CELL_STAT_NAMES, (int(x) for x in st)))
+
     def set_overflow(self, overflow: Optional["Overflow"]) -> None:
         """attach the table that remembers WHICH novel classes the fused count launches met (None detaches)"""
         check(lib().pa_index_set_overflow(self._h, overflow._h if overflow else None))
@@ -471,6 +481,58 @@ class Pseudoaligner:
         try:
             if self._h:
                 lib().pa_index_destroy(self._h)
+                self._h = vp()
+        except Exception:
+            pass
+
+
+def load_whitelist(path: str, bc_len: int) -> List[str]:
+    """pa_whitelist_load: the barcodes of a whitelist file (plain or gzip'ed), line i = cell i"""
+    n = C.c_uint64()
+    check(lib().pa_whitelist_load(str(path).encode(), bc_len, None, 0, C.byref(n)))
+    buf = C.create_string_buffer(max(n.value * bc_len, 1))
+    check(lib().pa_whitelist_load(str(path).encode(), bc_len, buf, n.value, C.byref(n)))
+    raw = buf.raw[: n.value * bc_len].decode()
+    return [raw[i * bc_len:(i + 1) * bc_len] for i in range(n.value)]
+
+
+class CellCounter:
+    """Single-cell UMI counter on the index's GPU (pa_cell_counter): feed it device-resident batches (the mapping's records of the
+    R2s + the R1s), then finish() and read the (cell, gene) -> UMIs matrix."""
+
+    def __init__(self, aligner: "Pseudoaligner", host_index: HostIndex, tx_gene, num_genes: int, whitelist: Sequence[str],
+                 bc_len: int = 16, umi_len: int = 12):
+        self._h = vp()
+        tg = np.ascontiguousarray(tx_gene, np.uint32)
+        wl = "".join(whitelist).encode()
+        self._aligner = aligner   # the index outlives the counter
+        check(lib().pa_cell_counter_create(aligner._h if aligner is not None else None, host_index._h if host_index is not None else None,
+                                           tg.ctypes.data, num_genes, wl, len(whitelist), bc_len, umi_len, C.byref(self._h)))
+
+    def add_device(self, d_results: int, d_arena: int, d_r1: int, d_r1_offsets: int, n_reads: int, stream: int = 0) -> None:
+        check(lib().pa_cell_counter_add_device(self._h, d_results, d_arena, d_r1, d_r1_offsets, n_reads, stream or None))
+
+    def finish(self) -> int:
+        n = C.c_uint64()
+        check(lib().pa_cell_counter_finish(self._h, C.byref(n)))
+        return n.value
+
+    def matrix(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(cell, gene, umis) after finish, sorted by (cell, gene)"""
+        n = self.finish()
+        cell, gene, umis = (np.zeros(max(n, 1), np.uint32) for _ in range(3))
+        check(lib().pa_cell_counter_matrix(self._h, cell.ctypes.data, gene.ctypes.data, umis.ctypes.data, n))
+        return cell[:n], gene[:n], umis[:n]
+
+    def stats(self) -> dict:
+        st = np.zeros(_ffi.PA_CELL_STATS, np.uint64)
+        check(lib().pa_cell_counter_stats(self._h, st.ctypes.data))
+        return dict(zip(_ffi.CELL_STAT_NAMES, (int(x) for x in st)))
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib().pa_cell_counter_destroy(self._h)
                 self._h = vp()
         except Exception:
             pass

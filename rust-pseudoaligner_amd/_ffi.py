@@ -10,9 +10,15 @@ u8p, u32p, u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uin
 vp = C.c_void_p
 
 PA_OK = 0
+PA_ERR_INVALID_ARG = -1
+PA_ERR_FORMAT = -3
 PA_ERR_NO_DEVICE = -4
 PA_ERR_ARENA_FULL = -7
+PA_ERR_UNSUPPORTED = -8
 PA_ERR_BUFFER_TOO_SMALL = -10
+PA_CELL_STATS = 10
+CELL_STAT_NAMES = ("reads", "barcode_exact", "barcode_corrected", "barcode_invalid", "umi_invalid", "not_confidently_mapped", "reads_counted",
+                   "umis_corrected", "molecules_lost_to_conflicts", "umis_in_matrix")
 PA_MAPPED_BIT = 0x80000000
 PA_DEFAULT_ALLOWED_MISMATCHES = 2
 PA_READ_COVERAGE_THRESHOLD = 32
@@ -114,6 +120,14 @@ SIGNATURES = {
     "pa_counts_len": (C.c_uint64, [vp]),
     "pa_counts_accumulate_device": (C.c_int, [vp, vp, vp, vp, C.c_uint64, vp, vp]),
     "pa_counts_by_barcode_device": (C.c_int, [vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, u64p, vp]),
+    "pa_cell_counter_create": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
+    "pa_cell_counter_add_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint64, vp]),
+    "pa_cell_counter_finish": (C.c_int, [vp, u64p]),
+    "pa_cell_counter_matrix": (C.c_int, [vp, vp, vp, vp, C.c_uint64]),
+    "pa_cell_counter_stats": (C.c_int, [vp, vp]),
+    "pa_cell_counter_destroy": (None, [vp]),
+    "pa_whitelist_load": (C.c_int, [C.c_char_p, C.c_uint32, vp, C.c_uint64, u64p]),
+    "pa_count_cells": (C.c_int, [vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, vp]),
     "pa_overflow_create": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.POINTER(vp)]),
     "pa_overflow_destroy": (None, [vp]),
     "pa_overflow_reset": (C.c_int, [vp, vp]),

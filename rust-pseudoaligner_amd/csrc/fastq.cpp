@@ -35,6 +35,7 @@
 #include <memory>
 #include <mutex>
 #include <thread>
+#include <unordered_set>
 
 #include "ingest.hpp"
 #include "pa_common.hpp"
@@ -1098,4 +1099,387 @@ extern "C" int pa_process_reads_stage_seconds(double out[PA_INGEST_STAGES]) {
     if (!out) return fail(PA_ERR_INVALID_ARG, "null argument");
     memcpy(out, pa::ingest::last_stage_seconds(), sizeof(double) * PA_INGEST_STAGES);
     return PA_OK;
+}
+
+// ---- single-cell counting from files: the barcode whitelist and the paired-FASTQ driver of pa_cell_counter ----
+
+extern "C" int pa_whitelist_load(const char* path, uint32_t bc_len, char* out, uint64_t cap, uint64_t* n) {
+    if (!path || !n) return fail(PA_ERR_INVALID_ARG, "null argument");
+    if (bc_len < 1 || bc_len > 16) return fail(PA_ERR_INVALID_ARG, "barcode length %u: must be 1..16", bc_len);
+    *n = 0;
+    gzFile g = gzopen(path, "rb");   // (plain text reads through as it is)
+    if (!g) return fail(PA_ERR_IO, "cannot open %s: %s", path, strerror(errno));
+    std::vector<char> text;
+    {
+        char buf[1 << 16];
+        for (;;) {
+            const int got = gzread(g, buf, sizeof buf);
+            if (got < 0) { int e = 0; const char* why = gzerror(g, &e); const int rc = fail(PA_ERR_FORMAT, "%s: corrupt gzip stream: %s", path, why); gzclose(g); return rc; }
+            if (got == 0) break;
+            text.insert(text.end(), buf, buf + got);
+        }
+    }
+    gzclose(g);
+    std::vector<uint32_t> seen;   // packed barcodes (first base most significant) of the lines so far, for the duplicate check
+    uint64_t count = 0, line = 0;
+    for (size_t p = 0; p < text.size();) {
+        const char* nl = (const char*)memchr(text.data() + p, '\n', text.size() - p);
+        size_t e = nl ? (size_t)(nl - text.data()) : text.size();
+        const size_t next = nl ? e + 1 : text.size();
+        if (e > p && text[e - 1] == '\r') --e;
+        ++line;
+        if (e - p != bc_len) return fail(PA_ERR_FORMAT, "%s: line %llu has %zu bytes, a barcode has %u", path, (unsigned long long)line, e - p, bc_len);
+        uint32_t bc = 0;
+        for (size_t j = p; j < e; ++j) {
+            const char c = text[j];
+            const uint32_t b = c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u;
+            if (b > 3) return fail(PA_ERR_FORMAT, "%s: line %llu: byte %zu is not A, C, G or T", path, (unsigned long long)line, j - p + 1);
+            bc = (bc << 2) | b;
+        }
+        if (out && count < cap) memcpy(out + count * bc_len, text.data() + p, bc_len);
+        seen.push_back(bc);
+        ++count;
+        p = next;
+    }
+    std::vector<uint64_t> order(seen.size());
+    for (uint64_t i = 0; i < order.size(); ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) { return seen[a] != seen[b] ? seen[a] < seen[b] : a < b; });
+    for (uint64_t i = 1; i < order.size(); ++i)
+        if (seen[order[i]] == seen[order[i - 1]])
+            return fail(PA_ERR_FORMAT, "%s: line %llu repeats the barcode of line %llu", path, (unsigned long long)order[i] + 1, (unsigned long long)order[i - 1] + 1);
+    *n = count;
+    if (out && cap < count) return fail(PA_ERR_BUFFER_TOO_SMALL, "%s holds %llu barcodes, room for %llu", path, (unsigned long long)count, (unsigned long long)cap);
+    return PA_OK;
+}
+
+namespace {
+
+// one FASTQ file of the pair, a window of records at a time (host memory follows the window, not the file; gzip is inflated whole)
+struct PairCursor {
+    const char* path = nullptr;
+    FastqText text;
+    std::unique_ptr<WindowScan> ws;
+    std::vector<RecPos> rec;
+    std::vector<std::vector<uint32_t>> brk;
+    uint64_t at = 0, before = 0;   // next record of the window, records of the windows before it
+    int open(const char* p) {
+        path = p;
+        const int rc = open_fastq(p, text);
+        if (rc == PA_OK) ws.reset(new WindowScan(text));
+        return rc;
+    }
+    // records left in the window (0: the file has ended); the window before is given up
+    int ready(Pool& pool, uint64_t& left) {
+        if (at >= ws->nrec) {
+            before += ws->nrec;
+            at = 0;
+            const int rc = ws->next(path, before, pool, rec, brk);
+            if (rc != PA_OK) return rc;
+        }
+        left = ws->nrec - at;
+        return PA_OK;
+    }
+    const char* id(uint64_t i, uint32_t& len) const {   // record.id() with a trailing "/1" or "/2" cut
+        const RecPos& r = rec[i];
+        const char* s = ws->base + r.start + 1;
+        len = r.id_len;
+        if (len >= 2 && s[len - 2] == '/' && (s[len - 1] == '1' || s[len - 1] == '2')) len -= 2;
+        return s;
+    }
+    const char* seq(uint64_t i) const { return ws->base + rec[i].start + rec[i].hdr + 1; }
+};
+
+struct CellBatch {   // one batch of pairs: R2 (all of it) and the R1 prefixes, pinned + on the device, and the mapping's outputs
+    PinnedBuffer<uint8_t> h_r2, h_r1;
+    PinnedBuffer<uint64_t> h_r2off, h_r1off;
+    DeviceBuffer<uint8_t> d_r2, d_r1;
+    DeviceBuffer<uint64_t> d_r2off, d_r1off, d_tiles;
+    DeviceBuffer<uint32_t> d_lens, d_arena;
+    DeviceBuffer<pa_read_result> d_results;
+    uint64_t n = 0, r2_bytes = 0, r1_bytes = 0;
+    uint32_t max_len = 0;
+};
+
+// grow a pinned buffer to `want` elements, keeping the first `keep`
+template <class T>
+int grow_pinned(PinnedBuffer<T>& b, size_t want, size_t keep) {
+    if (want <= b.size()) return PA_OK;
+    PinnedBuffer<T> nb;
+    const int e = nb.alloc(std::max(want, b.size() + b.size() / 2));
+    if (e != PA_OK) return e;
+    if (keep) memcpy(nb.get(), b.get(), keep * sizeof(T));
+    b = std::move(nb);
+    return PA_OK;
+}
+
+double secs_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+
+// the batch's GPU leg up to the mapping: copies, encode, map (asynchronous on s)
+int cell_batch_map(pa_index* idx, CellBatch& b, hipStream_t s) {
+    const uint32_t wpr = pa_words_per_read(std::max(1u, b.max_len));
+    int e = PA_OK;
+    if ((e = b.d_r2.reserve(b.r2_bytes + 64, b.h_r2.size())) || (e = b.d_r1.reserve(b.r1_bytes + 64, b.h_r1.size())) ||
+        (e = b.d_r2off.reserve(b.n + 1, b.h_r2off.size())) || (e = b.d_r1off.reserve(b.n + 1, b.h_r1off.size())) ||
+        (e = b.d_tiles.reserve(pa_tiles_words(b.n, wpr) + 1, pa_tiles_words(b.n, wpr) + 1)) || (e = b.d_lens.reserve(b.n + 64, b.h_r1off.size())) ||
+        (e = b.d_results.reserve(b.n + 64, b.h_r1off.size())))
+        return e;
+    const uint64_t hint = pa_map_arena_hint(idx, b.n);
+    if ((e = b.d_arena.reserve(hint, hint)) != PA_OK) return e;
+    PA_HIP_TRY(hipMemcpyAsync(b.d_r2.get(), b.h_r2.get(), b.r2_bytes, hipMemcpyHostToDevice, s));
+    PA_HIP_TRY(hipMemcpyAsync(b.d_r2off.get(), b.h_r2off.get(), (b.n + 1) * 8, hipMemcpyHostToDevice, s));
+    PA_HIP_TRY(hipMemcpyAsync(b.d_r1.get(), b.h_r1.get(), b.r1_bytes, hipMemcpyHostToDevice, s));
+    PA_HIP_TRY(hipMemcpyAsync(b.d_r1off.get(), b.h_r1off.get(), (b.n + 1) * 8, hipMemcpyHostToDevice, s));
+    if ((e = pa_encode_reads_device(idx, b.d_r2.get(), b.d_r2off.get(), b.n, wpr, b.d_tiles.get(), b.d_lens.get(), s)) != PA_OK) return e;
+    return pa_map_batch_device(idx, b.d_tiles.get(), b.d_lens.get(), b.n, wpr, PA_DEFAULT_ALLOWED_MISMATCHES, b.d_results.get(), b.d_arena.get(),
+                               b.d_arena.size(), nullptr, s);
+}
+
+// waits for the mapping (regrowing the arena as pa_map_finish asks), then counts the batch
+int cell_batch_count(pa_index* idx, pa_cell_counter* counter, CellBatch& b, hipStream_t s, double* st) {
+    auto t0 = std::chrono::steady_clock::now();
+    uint64_t used = 0, need = 0;
+    int e = pa_map_finish(idx, s, &used, &need);
+    for (int attempt = 0; e == PA_ERR_ARENA_FULL && attempt < 3; ++attempt) {
+        if ((e = b.d_arena.alloc(need + need / 8 + 4096)) != PA_OK) return e;
+        const uint32_t wpr = pa_words_per_read(std::max(1u, b.max_len));
+        e = pa_map_batch_device(idx, b.d_tiles.get(), b.d_lens.get(), b.n, wpr, PA_DEFAULT_ALLOWED_MISMATCHES, b.d_results.get(), b.d_arena.get(),
+                                b.d_arena.size(), nullptr, s);
+        if (e == PA_OK) e = pa_map_finish(idx, s, &used, &need);
+    }
+    st[2] += secs_since(t0);
+    if (e != PA_OK) return e;
+    t0 = std::chrono::steady_clock::now();
+    e = pa_cell_counter_add_device(counter, b.d_results.get(), b.d_arena.get(), b.d_r1.get(), b.d_r1off.get(), b.n, s);
+    st[4] += secs_since(t0);
+    return e;
+}
+
+int write_text(const std::string& path, const std::string& text) {
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) return fail(PA_ERR_IO, "cannot create %s: %s", path.c_str(), strerror(errno));
+    const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
+    if (fclose(f) != 0 || !ok) return fail(PA_ERR_IO, "cannot write %s", path.c_str());
+    return PA_OK;
+}
+
+int count_cells_impl(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const char* whitelist_path, uint32_t bc_len,
+                     uint32_t umi_len, const char* out_dir, int num_threads, uint64_t* stats) {
+    const auto t_call = std::chrono::steady_clock::now();
+    double* st = last_stage_seconds();
+    for (int j = 0; j < PA_INGEST_STAGES; ++j) st[j] = 0.0;
+    if (!idx || !h || !r1_path || !r2_path || !whitelist_path || !out_dir) return fail(PA_ERR_INVALID_ARG, "null argument");
+    if (bc_len < 1 || bc_len > 16 || umi_len < 1 || umi_len > 16) return fail(PA_ERR_INVALID_ARG, "barcode length %u / UMI length %u: both must be 1..16", bc_len, umi_len);
+    struct stat sd;
+    if (stat(out_dir, &sd) != 0 || !S_ISDIR(sd.st_mode)) return fail(PA_ERR_IO, "%s is no directory", out_dir);
+    uint64_t n_wl = 0;
+    int rc = pa_whitelist_load(whitelist_path, bc_len, nullptr, 0, &n_wl);
+    if (rc != PA_OK) return rc;
+    std::vector<char> wl((size_t)n_wl * bc_len + 1);
+    if ((rc = pa_whitelist_load(whitelist_path, bc_len, wl.data(), n_wl, &n_wl)) != PA_OK) return rc;
+    const uint32_t ntx = pa_host_index_num_transcripts(h);
+    std::vector<uint32_t> tx_gene(ntx ? ntx : 1);
+    uint32_t num_genes = 0;
+    if ((rc = pa_host_index_genes(h, tx_gene.data(), &num_genes)) != PA_OK) return rc;
+    pa_cell_counter* counter = nullptr;
+    if ((rc = pa_cell_counter_create(idx, h, tx_gene.data(), num_genes, wl.data(), n_wl, bc_len, umi_len, &counter)) != PA_OK) return rc;
+    std::unique_ptr<pa_cell_counter, void (*)(pa_cell_counter*)> own(counter, pa_cell_counter_destroy);
+    const uint32_t prefix = bc_len + umi_len;
+
+    PairCursor f1, f2;
+    if ((rc = f1.open(r1_path)) != PA_OK || (rc = f2.open(r2_path)) != PA_OK) return rc;
+    Pool pool(num_threads < 1 ? usable_threads() : num_threads);
+    uint64_t batch_pairs = DEFAULT_BATCH_READS;
+    if (const char* v = getenv("PA_INGEST_BATCH")) { const long long x = atoll(v); if (x >= 1) batch_pairs = (uint64_t)x; }
+    hipStream_t s = nullptr;
+    PA_HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    struct StreamGuard { pa_index* idx; hipStream_t s; ~StreamGuard() { (void)hipStreamSynchronize(s); (void)pa_index_release_stream(idx, s); (void)hipStreamDestroy(s); } } guard{idx, s};
+    CellBatch batches[2];
+    const int ntask = pool.size() * 4;
+    std::vector<uint64_t> part((size_t)ntask + 1), part1((size_t)ntask + 1);
+    std::vector<uint32_t> part_max((size_t)ntask);
+    uint64_t pairs = 0;
+    bool in_flight = false, ended = false;
+    int cur = 0;
+    // gather the next batch into batches[cur]: whole windows' worth of pairs, each piece copied before its window is given up
+    auto gather = [&](CellBatch& b) -> int {
+        b.n = 0; b.r2_bytes = 0; b.r1_bytes = 0; b.max_len = 0;
+        int e = PA_OK;
+        if ((e = grow_pinned(b.h_r2off, batch_pairs + 1, 0)) || (e = grow_pinned(b.h_r1off, batch_pairs + 1, 0)) ||
+            (e = grow_pinned(b.h_r1, (size_t)batch_pairs * prefix + 64, 0)))
+            return e;
+        while (b.n < batch_pairs) {
+            uint64_t left1 = 0, left2 = 0;
+            auto t0 = std::chrono::steady_clock::now();
+            if ((e = f1.ready(pool, left1)) != PA_OK || (e = f2.ready(pool, left2)) != PA_OK) return e;
+            st[0] += secs_since(t0);
+            if (left1 == 0 || left2 == 0) {
+                if (left1 != left2)
+                    return fail(PA_ERR_FORMAT, "%s has more records than %s: record %llu has no mate", left1 ? r1_path : r2_path, left1 ? r2_path : r1_path,
+                                (unsigned long long)(pairs + b.n));
+                ended = true;
+                break;
+            }
+            t0 = std::chrono::steady_clock::now();
+            const uint64_t m = std::min(std::min(left1, left2), batch_pairs - b.n);
+            const uint64_t a1 = f1.at, a2 = f2.at, base = b.n;
+            std::atomic<uint64_t> bad{~0ull};
+            pool.run(ntask, [&](int t) {   // R2 and R1-prefix bytes per task, ids compared on the way
+                uint64_t sum2 = 0, sum1 = 0;
+                uint32_t mx = 0;
+                for (uint64_t i = m * (uint64_t)t / ntask; i < m * (uint64_t)(t + 1) / ntask; ++i) {
+                    uint32_t l1, l2;
+                    const char* id1 = f1.id(a1 + i, l1);
+                    const char* id2 = f2.id(a2 + i, l2);
+                    if (l1 != l2 || memcmp(id1, id2, l1) != 0) {
+                        uint64_t first = bad.load();
+                        while (i < first && !bad.compare_exchange_weak(first, i)) {}
+                    }
+                    const uint32_t len = f2.rec[a2 + i].seq_len;
+                    sum2 += len;
+                    sum1 += std::min(f1.rec[a1 + i].seq_len, prefix);
+                    mx = std::max(mx, len);
+                }
+                part[(size_t)t + 1] = sum2;
+                part1[(size_t)t + 1] = sum1;
+                part_max[(size_t)t] = mx;
+            });
+            if (bad.load() != ~0ull)
+                return fail(PA_ERR_FORMAT, "record %llu: the ids of %s and %s differ", (unsigned long long)(pairs + base + bad.load()), r1_path, r2_path);
+            part[0] = b.r2_bytes;
+            part1[0] = b.r1_bytes;
+            for (int t = 0; t < ntask; ++t) {
+                part[(size_t)t + 1] += part[(size_t)t];
+                part1[(size_t)t + 1] += part1[(size_t)t];
+                b.max_len = std::max(b.max_len, part_max[(size_t)t]);
+            }
+            if ((e = grow_pinned(b.h_r2, part[(size_t)ntask] + 64, b.r2_bytes)) != PA_OK) return e;
+            pool.run(ntask, [&](int t) {   // all of R2, the first bc_len + umi_len bytes of R1
+                uint64_t o2 = part[(size_t)t], o1 = part1[(size_t)t];
+                for (uint64_t i = m * (uint64_t)t / ntask; i < m * (uint64_t)(t + 1) / ntask; ++i) {
+                    const uint32_t len2 = f2.rec[a2 + i].seq_len;
+                    b.h_r2off.get()[base + i] = o2;
+                    memcpy(b.h_r2.get() + o2, f2.seq(a2 + i), len2);
+                    o2 += len2;
+                    const uint32_t len1 = std::min(f1.rec[a1 + i].seq_len, prefix);
+                    b.h_r1off.get()[base + i] = o1;
+                    memcpy(b.h_r1.get() + o1, f1.seq(a1 + i), len1);
+                    o1 += len1;
+                }
+            });
+            b.r1_bytes = part1[(size_t)ntask];
+            b.r2_bytes = part[(size_t)ntask];
+            b.n += m;
+            f1.at += m;
+            f2.at += m;
+            st[1] += secs_since(t0);
+        }
+        b.h_r2off.get()[b.n] = b.r2_bytes;
+        b.h_r1off.get()[b.n] = b.r1_bytes;
+        return PA_OK;
+    };
+    for (;;) {
+        CellBatch& b = batches[cur];
+        b.n = 0;
+        rc = ended ? PA_OK : gather(b);   // (while the batch before is on the GPU)
+        if (rc != PA_OK) break;
+        if (in_flight) {
+            if ((rc = cell_batch_count(idx, counter, batches[cur ^ 1], s, st)) != PA_OK) break;
+            in_flight = false;
+        }
+        if (b.n == 0) break;
+        const auto t0 = std::chrono::steady_clock::now();
+        if ((rc = cell_batch_map(idx, b, s)) != PA_OK) break;
+        st[3] += secs_since(t0);
+        pairs += b.n;
+        in_flight = true;
+        cur ^= 1;
+    }
+    f1.text.release();
+    f2.text.release();
+    if (rc != PA_OK) return rc;
+    auto t0 = std::chrono::steady_clock::now();
+    uint64_t entries = 0;
+    if ((rc = pa_cell_counter_finish(counter, &entries)) != PA_OK) return rc;
+    st[4] += secs_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    std::vector<uint32_t> cell(entries), gene(entries), umis(entries);
+    if ((rc = pa_cell_counter_matrix(counter, cell.data(), gene.data(), umis.data(), entries)) != PA_OK) return rc;
+    // columns: the cells with at least one UMI, in whitelist order (the matrix is sorted by cell)
+    std::string bc_text, mtx;
+    std::vector<uint32_t> column(entries);
+    uint32_t cols = 0;
+    for (uint64_t i = 0; i < entries; ++i) {
+        if (i == 0 || cell[i] != cell[i - 1]) {
+            bc_text.append(wl.data() + (size_t)cell[i] * bc_len, bc_len);
+            bc_text.push_back('\n');
+            ++cols;
+        }
+        column[i] = cols;
+    }
+    char head[96];
+    snprintf(head, sizeof head, "%%%%MatrixMarket matrix coordinate integer general\n%u %u %llu\n", num_genes, cols, (unsigned long long)entries);
+    // "gene cell umis" lines, rendered in pieces on the pool (a matrix has millions of entries; one formatted print per line cost
+    // most of the call)
+    auto put_u32 = [](char* p, uint32_t v) {   // decimal digits of v at p; returns the end
+        char tmp[10];
+        int n = 0;
+        do { tmp[n++] = (char)('0' + v % 10); v /= 10; } while (v);
+        while (n) *p++ = tmp[--n];
+        return p;
+    };
+    const int pieces = std::max(1, std::min<int>(pool.size() * 4, (int)(entries / 4096) + 1));
+    std::vector<std::string> piece((size_t)pieces);
+    pool.run(pieces, [&](int t) {
+        const uint64_t a = entries * (uint64_t)t / pieces, b = entries * (uint64_t)(t + 1) / pieces;
+        std::string& o = piece[(size_t)t];
+        o.resize((size_t)(b - a) * 33);
+        char* p = &o[0];
+        for (uint64_t i = a; i < b; ++i) {
+            p = put_u32(p, gene[i] + 1); *p++ = ' ';
+            p = put_u32(p, column[i]); *p++ = ' ';
+            p = put_u32(p, umis[i]); *p++ = '\n';
+        }
+        o.resize((size_t)(p - o.data()));
+    });
+    mtx = head;
+    size_t mtx_len = mtx.size();
+    for (const std::string& x : piece) mtx_len += x.size();
+    mtx.reserve(mtx_len);
+    for (const std::string& x : piece) mtx += x;
+    // gene names numbered as pa_host_index_genes numbers them (first appearance in transcript order), built once: the name lookup
+    // of the C ABI rebuilds that table on every call
+    std::string features;
+    {
+        std::unordered_set<std::string> seen;
+        for (const std::string& g : h->h.tx_genes) {
+            if (!seen.insert(g).second) continue;
+            features += g;
+            features += '\t';
+            features += g;
+            features += "\tGene Expression\n";
+        }
+        if (seen.size() != num_genes) return fail(PA_ERR_INTERNAL, "%zu gene names for %u genes", seen.size(), num_genes);
+    }
+    const std::string dir(out_dir);
+    if ((rc = write_text(dir + "/matrix.mtx", mtx)) != PA_OK || (rc = write_text(dir + "/barcodes.tsv", bc_text)) != PA_OK ||
+        (rc = write_text(dir + "/features.tsv", features)) != PA_OK)
+        return rc;
+    st[5] = secs_since(t0);
+    if (stats) (void)pa_cell_counter_stats(counter, stats);
+    st[6] = secs_since(t_call);
+    st[7] = (double)pairs;
+    return PA_OK;
+}
+
+}  // namespace
+
+extern "C" int pa_count_cells(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const char* whitelist_path, uint32_t bc_len,
+                              uint32_t umi_len, const char* out_dir, int num_threads, uint64_t stats[PA_CELL_STATS]) {
+    try {
+        return count_cells_impl(idx, h, r1_path, r2_path, whitelist_path, bc_len, umi_len, out_dir, num_threads, stats);
+    } catch (const std::bad_alloc&) {
+        return fail(PA_ERR_OOM, "out of host memory in pa_count_cells");
+    } catch (const std::exception& ex) {
+        return fail(PA_ERR_INTERNAL, "pa_count_cells: %s", ex.what());
+    }
 }
