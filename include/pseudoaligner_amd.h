@@ -460,6 +460,42 @@ int pa_whitelist_load(const char* path, uint32_t bc_len, char* out, uint64_t cap
 int pa_count_cells(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const char* whitelist_path,
                    uint32_t bc_len, uint32_t umi_len, const char* out_dir, int num_threads, uint64_t stats[PA_CELL_STATS]);
 
+/* ---------------- transcript abundances: EM over the class-count table (bulk RNA-seq) ----------------
+ * The reference stops at equivalence classes; this is the standard abundance model over them (the EM of kallisto / salmon) on the
+ * GPU, in f64. Inputs: the dense table class_counts[pa_counts_len] and, optionally, the serialised overflow words (format below,
+ * pa_overflow_fetch / pa_overflow_merge / pa_overflow_allgather): the reduction unit as it is after the reduce over GPUs.
+ *   eff_t    = max(len_t - mean_read_len + 1, 1) as a double; mean_read_len <= 0: eff_t = len_t
+ *   rows     = the index classes with n_c > 0 + every overflow record (ids sorted, count = its 64-bit pair). The tail slots empty and
+ *              unmapped never take part; the novel slot only through the overflow records: with overflow words their counts must sum
+ *              to class_counts[num_classes] (else PA_ERR_INVALID_ARG), without them the novel reads are left out (stats[6])
+ *   N        = sum of n_c over the rows; N = 0 is legal: every output is 0 and no iteration is run
+ *   start    alpha_t = N / T for the T transcripts of the index; a transcript that occurs in no row has alpha_t = 0 throughout
+ *   one iteration   w_t = alpha_t / eff_t;  d_c = sum_{t in c} w_t;  alpha'_t = w_t * sum_{c with t} n_c / d_c  (a term with d_c = 0 is 0)
+ *   stop     after iteration i >= min_iters when no transcript has both alpha'_t > alpha_change_limit and
+ *            |alpha'_t - alpha_t| / alpha'_t > alpha_change; looked at every check_every iterations and at max_iters; then every
+ *            alpha_t < alpha_limit / 10 becomes 0. The defaults are kallisto's: 50, 10 000, 1e-2, 1e-2, 1e-7; check_every 10
+ *   outputs  est_counts_t = alpha_t; tpm_t = 1e6 (alpha_t / eff_t) / sum_s (alpha_s / eff_s), the sum in transcript order on the host;
+ *            per gene (pa_host_index_genes) the sums of both in transcript order
+ * Counts are converted exactly: a count of 2^53 or more is PA_ERR_UNSUPPORTED. Two runs on one input give bit-identical results.
+ * Every argument is checked before any device call; a call that fails leaves the object as it was. Without a GPU pa_quant_create
+ * returns PA_ERR_NO_DEVICE (checked after h, p and out, before idx: no index handle can exist there). */
+typedef struct pa_quant pa_quant;
+typedef struct pa_quant_params { double mean_read_len, alpha_limit, alpha_change_limit, alpha_change;
+                                 uint32_t min_iters, max_iters, check_every, reserved; } pa_quant_params;
+void pa_quant_default_params(pa_quant_params* p);
+int  pa_quant_create(pa_index* idx, const pa_host_index* h, const pa_quant_params* p, pa_quant** out);   /* NULL p = defaults; h: the host index idx was made from */
+int  pa_quant_set_counts(pa_quant* q, const uint64_t* class_counts, uint64_t counts_len,
+                         const uint32_t* overflow_words, uint64_t n_words);                              /* host arrays; resets alpha to the start */
+int  pa_quant_step(pa_quant* q, uint32_t n_iters);            /* exactly n iterations, no stop rule, no truncation */
+int  pa_quant_run(pa_quant* q, uint32_t* iters, int* converged);  /* stop rule + truncation, from the current alpha */
+int  pa_quant_alpha(const pa_quant* q, double* alpha);        /* current alpha[T] */
+int  pa_quant_fetch(const pa_quant* q, double* est_counts, double* tpm, double* eff_len);   /* [T] each; any may be NULL */
+int  pa_quant_fetch_genes(const pa_quant* q, double* est_counts, double* tpm);              /* [num_genes]; either may be NULL */
+#define PA_QUANT_STATS 8   /* rows, ids (nnz), transcripts with a row, longest row, largest degree, reads used N, novel reads left out, iterations run */
+int  pa_quant_stats(const pa_quant* q, uint64_t stats[PA_QUANT_STATS]);
+int  pa_write_abundance_tsv(const pa_quant* q, const char* path);   /* header + "target_id\tlength\teff_length\test_counts\ttpm", doubles as pa_write_mappability_tsv prints them */
+void pa_quant_destroy(pa_quant* q);
+
 /* ---------------- novel classes + the reduction over GPUs ---------------- */
 /* The dense table counts every result that is no index class in ONE slot (counts[num_classes]). A pa_overflow keeps WHICH
  * id sets those were, keyed by content, on the GPU: attach one to an index and every pa_map_count_batch_device launch files

@@ -110,6 +110,32 @@ int main(int argc, char** argv) {
         EXPECT(pa_count_cells(NULL, h, fastq, fastq, path, 4, 4, dir, 1, cst) == PA_ERR_INVALID_ARG);
     }
 
+    {   /* transcript abundances, host side: the defaults, the struct as this compiler lays it out, and the checks that come before any device call */
+        pa_quant_params qp;
+        pa_quant* qq = NULL;
+        uint64_t qst[PA_QUANT_STATS];
+        uint32_t qit = 1;
+        int qconv = 1;
+        double qd[1];
+        printf("layout pa_quant_params sizeof %zu\n", sizeof(pa_quant_params));
+        LAYOUT_FIELD(pa_quant_params, mean_read_len); LAYOUT_FIELD(pa_quant_params, alpha_limit); LAYOUT_FIELD(pa_quant_params, alpha_change_limit);
+        LAYOUT_FIELD(pa_quant_params, alpha_change); LAYOUT_FIELD(pa_quant_params, min_iters); LAYOUT_FIELD(pa_quant_params, max_iters);
+        LAYOUT_FIELD(pa_quant_params, check_every); LAYOUT_FIELD(pa_quant_params, reserved);
+        pa_quant_default_params(NULL);
+        pa_quant_default_params(&qp);
+        EXPECT(qp.min_iters == 50 && qp.max_iters == 10000 && qp.check_every == 10 && qp.alpha_limit == 1e-7 && qp.alpha_change == 1e-2 && qp.mean_read_len == 0.0);
+        EXPECT(pa_quant_create(NULL, NULL, &qp, &qq) == PA_ERR_INVALID_ARG && qq == NULL);
+        qp.check_every = 0;
+        EXPECT(pa_quant_create(NULL, h, &qp, &qq) == PA_ERR_INVALID_ARG && qq == NULL);
+        EXPECT(pa_quant_create(NULL, h, NULL, &qq) == (ndev < 1 ? PA_ERR_NO_DEVICE : PA_ERR_INVALID_ARG) && qq == NULL);
+        EXPECT(pa_quant_set_counts(NULL, counts, counts_len, NULL, 0) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_quant_step(NULL, 1) == PA_ERR_INVALID_ARG && pa_quant_run(NULL, &qit, &qconv) == PA_ERR_INVALID_ARG && qit == 0 && qconv == 0);
+        EXPECT(pa_quant_alpha(NULL, qd) == PA_ERR_INVALID_ARG && pa_quant_fetch(NULL, qd, NULL, NULL) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_quant_fetch_genes(NULL, qd, NULL) == PA_ERR_INVALID_ARG && pa_quant_stats(NULL, qst) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_write_abundance_tsv(NULL, path) == PA_ERR_INVALID_ARG);
+        pa_quant_destroy(NULL);
+    }
+
     pa_txome *tx = NULL, *tx2 = NULL, *tx3 = NULL;
     EXPECT(pa_txome_synthesize(50, 120, 7, &tx) == PA_OK);
     {   /* the same genes with repeat families and low-complexity tracts in their last exons */
@@ -369,6 +395,30 @@ int main(int argc, char** argv) {
         const uint32_t* words = NULL;
         uint64_t nw = 0;
         EXPECT(pa_overflow_fetch(ovf, NULL, &words, &nw) == PA_OK && nw >= 2 && words[1] == nw);
+        {   /* transcript abundances from that table (the novel reads left out: the table saw three launches, the overflow two) */
+            pa_quant* qq = NULL;
+            pa_quant_params qp;
+            uint64_t qst[PA_QUANT_STATS];
+            uint32_t qit = 0;
+            int qconv = 0;
+            double *qa = (double*)calloc(ntx, 8), *qe = (double*)calloc(ntx, 8), *qt = (double*)calloc(ntx, 8), *ql = (double*)calloc(ntx, 8);
+            double *ge = (double*)calloc(ngenes, 8), *gt = (double*)calloc(ngenes, 8), sum = 0.0, tsum = 0.0;
+            pa_quant_default_params(&qp);
+            qp.mean_read_len = 60.0;
+            EXPECT(pa_quant_create(idx, h, &qp, &qq) == PA_OK && qq);
+            EXPECT(pa_quant_set_counts(qq, h_counts, counts_len - 1, NULL, 0) == PA_ERR_INVALID_ARG);
+            EXPECT(pa_quant_set_counts(qq, h_counts, counts_len, NULL, 0) == PA_OK);
+            EXPECT(pa_quant_step(qq, 2) == PA_OK && pa_quant_alpha(qq, qa) == PA_OK);
+            EXPECT(pa_quant_run(qq, &qit, &qconv) == PA_OK && qit >= 1 && qit <= qp.max_iters);
+            EXPECT(pa_quant_fetch(qq, qe, qt, ql) == PA_OK && pa_quant_fetch_genes(qq, ge, gt) == PA_OK && pa_quant_stats(qq, qst) == PA_OK);
+            for (uint32_t t = 0; t < ntx; ++t) { sum += qe[t]; tsum += qt[t]; }
+            EXPECT(qst[5] > 0 && qst[6] == h_counts[flat.num_classes] && qst[7] == 2 + (uint64_t)qit && ql[0] >= 1.0);
+            EXPECT(sum > 0.999 * (double)qst[5] && sum < 1.001 * (double)qst[5] && tsum > 999999.0 && tsum < 1000001.0);
+            snprintf(path, sizeof path, "%s/abi_check_abundance.tsv", dir);
+            EXPECT(pa_write_abundance_tsv(qq, path) == PA_OK);
+            pa_quant_destroy(qq);
+            free(qa); free(qe); free(qt); free(ql); free(ge); free(gt);
+        }
         uint8_t id[128];
         pa_comm* comm = NULL;
         if (pa_comm_unique_id(id) == PA_OK) {                        /* RCCL present: a world of one */

@@ -194,6 +194,37 @@ pub fn count_cells<P: AsRef<Path>>(index_file: P, r1_fastq: P, r2_fastq: P, whit
     result
 }
 
+/// Transcript abundances (pa_quant_*): the EM over equivalence classes on the GPU, from a class-count table on the host
+/// (`class_counts`: pa_counts_len entries, as the reduce over GPUs leaves it) and, optionally, the serialised overflow words
+/// (pa_overflow_fetch / pa_overflow_allgather; without them the novel reads are left out). Runs to the stop rule and returns
+/// (est_counts, tpm) per transcript; `tsv`, when given, also receives kallisto's abundance.tsv columns.
+pub fn quantify(idx: *mut PaIndex, h: *const PaHostIndex, class_counts: &[u64], overflow_words: Option<&[u32]>, mean_read_len: f64,
+                tsv: Option<&Path>) -> Result<(Vec<f64>, Vec<f64>), Error> {
+    use crate::amd_quant_ffi::*;
+    let mut p: PaQuantParams = unsafe { std::mem::zeroed() };
+    unsafe { pa_quant_default_params(&mut p) };
+    p.mean_read_len = mean_read_len;
+    let mut q = std::ptr::null_mut();
+    check(unsafe { pa_quant_create(idx, h, &p, &mut q) })?;
+    let n = unsafe { pa_host_index_num_transcripts(h) } as usize;
+    let (mut est, mut tpm) = (vec![0f64; n], vec![0f64; n]);
+    let (words, n_words) = match overflow_words { Some(w) => (w.as_ptr(), w.len() as u64), None => (std::ptr::null(), 0) };
+    let mut rc = unsafe { pa_quant_set_counts(q, class_counts.as_ptr(), class_counts.len() as u64, words, n_words) };
+    let (mut iters, mut converged) = (0u32, 0);
+    if rc >= 0 { rc = unsafe { pa_quant_run(q, &mut iters, &mut converged) }; }
+    if rc >= 0 { rc = unsafe { pa_quant_fetch(q, est.as_mut_ptr(), tpm.as_mut_ptr(), std::ptr::null_mut()) }; }
+    if rc >= 0 {
+        if let Some(path) = tsv {
+            let c = CString::new(path.to_string_lossy().into_owned())?;
+            rc = unsafe { pa_write_abundance_tsv(q, c.as_ptr()) };
+        }
+    }
+    let result = check(rc).map(|_| (est, tpm));   // (the message is read before the handle goes)
+    unsafe { pa_quant_destroy(q) };
+    info!("EM: {} iterations, converged: {}", iters, converged != 0);
+    result
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // Drop-in entry points with the reference's EXACT signatures. The GPU copy of an index is made on first use and cached by the
 // CONTENT of the `Pseudoaligner`: k, node / class / transcript counts and a fingerprint of EVERY base of every node, every node's

@@ -23,7 +23,7 @@ from ._ffi import (PA_DEFAULT_ALLOWED_MISMATCHES, PA_ERR_ARENA_FULL, PA_MAPPED_B
 __all__ = ["HostIndex", "Txome", "Pseudoaligner", "build_index", "process_reads", "process_reads_multi", "PaError", "lib", "concat_reads",
            "gather_classes", "unpack_compact", "unpack_tiles", "RESULT_DTYPE", "PA_MAPPED_BIT", "PA_DEFAULT_ALLOWED_MISMATCHES",
            "PA_READ_COVERAGE_THRESHOLD", "PA_CLASS_REF", "Overflow", "Comm", "parse_overflow", "serialise_overflow", "overflow_merge",
-           "CellCounter", "load_whitelist"]
+           "CellCounter", "load_whitelist", "Quantifier"]
 
 PA_CLASS_REF = 0x80000000
 RESULT_DTYPE = np.dtype([("coverage", "<u4"), ("mismatches", "<u4"), ("class_off", "<u4"), ("class_len", "<u4")])
@@ -462,6 +462,18 @@ class Pseudoaligner:
                                    str(out_dir).encode(), num_threads, st.ctypes.data))
         return dict(zip(_ffi.CELL_STAT_NAMES, (int(x) for x in st)))
 
+    def quantify(self, d_counts: int, overflow: Optional["Overflow"] = None, **params) -> "Quantifier":
+        """Transcript abundances from a class-count table on this GPU (d_counts: the device pointer the count launches accumulated into,
+        their streams synchronised) and, optionally, the overflow table that was attached: copies the table back, fetches the overflow,
+        runs the EM to its stop rule and returns the Quantifier (fetch / genes / write_tsv; .iterations, .converged)."""
+        counts = np.zeros(self.counts_len(), np.uint64)
+        check(lib().pa_memcpy_d2h(counts.ctypes.data, d_counts, counts.nbytes, None))
+        check(lib().pa_stream_synchronize(None))
+        q = Quantifier(self, self.host, **params)
+        q.set_counts(counts, overflow.fetch() if overflow is not None else None)
+        q.iterations, q.converged = q.run()
+        return q
+
     def set_overflow(self, overflow: Optional["Overflow"]) -> None:
         """attach the table that remembers WHICH novel classes the fused count launches met (None detaches)"""
         check(lib().pa_index_set_overflow(self._h, overflow._h if overflow else None))
@@ -533,6 +545,80 @@ class CellCounter:
         try:
             if self._h:
                 lib().pa_cell_counter_destroy(self._h)
+                self._h = vp()
+        except Exception:
+            pass
+
+
+class Quantifier:
+    """Transcript abundances by EM over the class-count table on the index's GPU (pa_quant): set_counts(), then step() / run(), then
+    fetch() / genes() / write_tsv(). params: the fields of pa_quant_params (mean_read_len, alpha_limit, alpha_change_limit, alpha_change,
+    min_iters, max_iters, check_every); what is not given keeps the library's default."""
+
+    def __init__(self, aligner: "Pseudoaligner", host_index: HostIndex, **params):
+        self._h = vp()
+        p = _ffi.QuantParams()
+        lib().pa_quant_default_params(C.byref(p))
+        for name, value in params.items():
+            if name not in dict(_ffi.QuantParams._fields_) or name == "reserved":
+                raise TypeError("unknown quantification parameter %r" % name)
+            setattr(p, name, value)
+        self.params = p
+        self._aligner, self._host = aligner, host_index   # the index outlives the quantifier
+        self.num_transcripts = host_index.num_transcripts if host_index is not None else 0
+        check(lib().pa_quant_create(aligner._h if aligner is not None else None, host_index._h if host_index is not None else None, C.byref(p),
+                                    C.byref(self._h)))
+
+    def set_counts(self, class_counts: np.ndarray, overflow: Optional[np.ndarray] = None) -> None:
+        """class_counts: u64[counts_len()] on the host; overflow: the serialised overflow words (Overflow.fetch / allgather) or None"""
+        cc = np.ascontiguousarray(class_counts, np.uint64)
+        if overflow is None:
+            check(lib().pa_quant_set_counts(self._h, cc.ctypes.data, len(cc), None, 0))
+        else:
+            w = np.ascontiguousarray(overflow, np.uint32)
+            check(lib().pa_quant_set_counts(self._h, cc.ctypes.data, len(cc), w.ctypes.data, len(w)))
+
+    def step(self, n_iters: int = 1) -> None:
+        check(lib().pa_quant_step(self._h, n_iters))
+
+    def run(self) -> Tuple[int, bool]:
+        """the stop rule + truncation from the current alpha -> (iterations, converged)"""
+        it, conv = C.c_uint32(), C.c_int()
+        check(lib().pa_quant_run(self._h, C.byref(it), C.byref(conv)))
+        return it.value, bool(conv.value)
+
+    def alpha(self) -> np.ndarray:
+        a = np.zeros(max(self.num_transcripts, 1), np.float64)
+        check(lib().pa_quant_alpha(self._h, a.ctypes.data))
+        return a[: self.num_transcripts]
+
+    def fetch(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(est_counts, tpm, eff_len), each [num_transcripts]"""
+        est, tpm, eff = (np.zeros(max(self.num_transcripts, 1), np.float64) for _ in range(3))
+        check(lib().pa_quant_fetch(self._h, est.ctypes.data, tpm.ctypes.data, eff.ctypes.data))
+        n = self.num_transcripts
+        return est[:n], tpm[:n], eff[:n]
+
+    def genes(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(est_counts, tpm) per gene of HostIndex.genes()"""
+        n = C.c_uint32()
+        check(lib().pa_host_index_genes(self._host._h, None, C.byref(n)))
+        est, tpm = np.zeros(max(n.value, 1), np.float64), np.zeros(max(n.value, 1), np.float64)
+        check(lib().pa_quant_fetch_genes(self._h, est.ctypes.data, tpm.ctypes.data))
+        return est[: n.value], tpm[: n.value]
+
+    def stats(self) -> dict:
+        st = np.zeros(_ffi.PA_QUANT_STATS, np.uint64)
+        check(lib().pa_quant_stats(self._h, st.ctypes.data))
+        return dict(zip(_ffi.QUANT_STAT_NAMES, (int(x) for x in st)))
+
+    def write_tsv(self, path: str) -> None:
+        check(lib().pa_write_abundance_tsv(self._h, str(path).encode()))
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib().pa_quant_destroy(self._h)
                 self._h = vp()
         except Exception:
             pass

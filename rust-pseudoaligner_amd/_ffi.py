@@ -52,6 +52,15 @@ class IndexStats(C.Structure):
                 ("k", C.c_uint32), ("max_class_len", C.c_uint32)]
 
 
+class QuantParams(C.Structure):
+    _fields_ = [("mean_read_len", C.c_double), ("alpha_limit", C.c_double), ("alpha_change_limit", C.c_double), ("alpha_change", C.c_double),
+                ("min_iters", C.c_uint32), ("max_iters", C.c_uint32), ("check_every", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+PA_QUANT_STATS = 8
+QUANT_STAT_NAMES = ("rows", "ids", "transcripts_with_a_row", "longest_row", "largest_degree", "reads_used", "novel_reads_left_out", "iterations")
+
+
 # name -> (restype, argtypes); every symbol declared in include/pseudoaligner_amd.h
 SIGNATURES = {
     "pa_abi_version": (C.c_uint32, []),
@@ -128,6 +137,17 @@ SIGNATURES = {
     "pa_cell_counter_destroy": (None, [vp]),
     "pa_whitelist_load": (C.c_int, [C.c_char_p, C.c_uint32, vp, C.c_uint64, u64p]),
     "pa_count_cells": (C.c_int, [vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, vp]),
+    "pa_quant_default_params": (None, [C.POINTER(QuantParams)]),
+    "pa_quant_create": (C.c_int, [vp, vp, C.POINTER(QuantParams), C.POINTER(vp)]),
+    "pa_quant_set_counts": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64]),
+    "pa_quant_step": (C.c_int, [vp, C.c_uint32]),
+    "pa_quant_run": (C.c_int, [vp, u32p, C.POINTER(C.c_int)]),
+    "pa_quant_alpha": (C.c_int, [vp, vp]),
+    "pa_quant_fetch": (C.c_int, [vp, vp, vp, vp]),
+    "pa_quant_fetch_genes": (C.c_int, [vp, vp, vp]),
+    "pa_quant_stats": (C.c_int, [vp, vp]),
+    "pa_write_abundance_tsv": (C.c_int, [vp, C.c_char_p]),
+    "pa_quant_destroy": (None, [vp]),
     "pa_overflow_create": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.POINTER(vp)]),
     "pa_overflow_destroy": (None, [vp]),
     "pa_overflow_reset": (C.c_int, [vp, vp]),
