@@ -1,16 +1,19 @@
-// Per-barcode (single-cell) class counts — SURVEY.md §8f.3, the use the reference was written for (README.md:3: a
-// pseudo-alignment tool for single-cell RNA-seq): every read carries the index of its cell barcode, and what downstream wants
-// is the SPARSE matrix (barcode, equivalence class) -> reads. On the GPU: one 64-bit key per read (barcode << 32 | column, the
-// columns being those of the dense count table: class id, or novel / empty / unmapped), a radix sort of the keys and a
-// run-length encode — sorted unique keys with their counts, ready for a CSR / triplet matrix on the host.
+// Two single-cell counters, both a radix sort of one 64-bit key per read followed by run-length encodes.
+//
+// 1. Per-barcode class counts (pa::barcode_counts) — SURVEY.md §8f.3, the use the reference was written for (README.md:3: a
+//    pseudo-alignment tool for single-cell RNA-seq): every read carries the index of its cell barcode, and what downstream
+//    wants is the SPARSE matrix (barcode, equivalence class) -> reads. The key is barcode << 32 | column, the columns being
+//    those of the dense count table (class id, or novel / empty / unmapped); the result is the sorted unique keys with their
+//    counts, ready for a CSR / triplet matrix on the host.
+// 2. The UMI count matrix from barcode + UMI reads (pa_cell_counter, second half of the file): (cell, gene) -> molecules.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <memory>
 #include <new>
 #include <vector>
 
+#include "device_prims.hpp"
 #include "hip_buffer.hpp"
 #include "kernel_utils.hpp"
 #include "kernels.hpp"
@@ -50,29 +53,19 @@ int barcode_counts(const DevIndexView& ix, const uint32_t* class_table, uint64_t
     if (n == 0) return PA_OK;
     if (n > 0x7FFFFFFFull) return fail(PA_ERR_UNSUPPORTED, "at most 2^31-1 reads per call");
     DeviceBuffer<unsigned long long> keys_in, keys_sorted;
-    DeviceBuffer<unsigned int> d_runs;
+    DeviceBuffer<uint32_t> d_runs;
     DeviceBuffer<uint8_t> tmp;
-    int e = keys_in.alloc(n);
-    if (e == PA_OK) e = keys_sorted.alloc(n);
-    if (e == PA_OK) e = d_runs.alloc(1);
-    if (e != PA_OK) return e;
-    hipLaunchKernelGGL(pa_barcode_keys_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, d_results, d_arena, d_barcode, n, ix, class_table,
-                       class_table_size, keys_in.get());
+    int e;
+    if ((e = keys_in.alloc(n)) || (e = keys_sorted.alloc(n)) || (e = d_runs.alloc(1))) return e;
+    hipLaunchKernelGGL(pa_barcode_keys_kernel, dim3(grid_for(n)), dim3(256), 0, stream, d_results, d_arena, d_barcode, n, ix, class_table, class_table_size,
+                       keys_in.get());
     PA_HIP_TRY(hipGetLastError());
-    uint32_t col_bits = 1;
-    while (col_bits < 32 && (1ull << col_bits) < (uint64_t)ix.num_classes + 3) ++col_bits;
-    const int end_bit = (int)(32 + (barcode_bits ? (barcode_bits > 32 ? 32 : barcode_bits) : 32));
-    size_t sort_bytes = 0, rle_bytes = 0;
-    // only the bits that can differ are sorted: the column's low bits and the barcode's
-    PA_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, keys_in.get(), keys_sorted.get(), (int)n, 0, end_bit, stream));
-    PA_HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(nullptr, rle_bytes, keys_sorted.get(), (unsigned long long*)d_keys, d_vals, d_runs.get(), (int)n, stream));
-    if ((e = tmp.alloc(sort_bytes > rle_bytes ? sort_bytes : rle_bytes)) != PA_OK) return e;
-    (void)col_bits;
-    PA_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(tmp.get(), sort_bytes, keys_in.get(), keys_sorted.get(), (int)n, 0, end_bit, stream));
-    PA_HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(tmp.get(), rle_bytes, keys_sorted.get(), (unsigned long long*)d_keys, d_vals, d_runs.get(), (int)n, stream));
-    unsigned int runs = 0;
-    PA_HIP_TRY(hipMemcpyAsync(&runs, d_runs.get(), 4, hipMemcpyDeviceToHost, stream));
-    PA_HIP_TRY(hipStreamSynchronize(stream));
+    // the column's 32 bits and the barcode's bits that can differ are sorted (the count as an int: 32-bit indexing, n < 2^31)
+    const uint32_t end_bit = 32 + (barcode_bits ? (barcode_bits > 32 ? 32 : barcode_bits) : 32);
+    uint32_t runs = 0;
+    if ((e = sort_keys(stream, tmp, keys_in.get(), keys_sorted.get(), (int)n, 0, end_bit)) ||
+        (e = run_length_encode(stream, tmp, keys_sorted.get(), n, (unsigned long long*)d_keys, d_vals, d_runs.get())) || (e = fetch_u32(d_runs.get(), stream, runs)))
+        return e;
     *n_entries = runs;
     return PA_OK;
 }
@@ -95,14 +88,6 @@ constexpr uint32_t CELL_BLOCK = 256;                 // 4 waves
 constexpr uint32_t CELL_SMALL_SEGMENT = 64;          // UMIs of a (cell, gene) segment that one wave compares pairwise in registers
 enum : uint32_t { ST_READS = 0, ST_EXACT, ST_CORRECTED, ST_BC_INVALID, ST_UMI_INVALID, ST_UNMAPPED, ST_COUNTED, ST_MOVED, ST_CONFLICT, ST_UMIS };
 
-__host__ __device__ inline uint64_t cell_hash(uint64_t x) {   // murmur3 fmix64, as the dictionary (pa_common.hpp mix64)
-    x ^= x >> 33;
-    x *= 0xff51afd7ed558ccdull;
-    x ^= x >> 33;
-    x *= 0xc4ceb9fe1a85ec53ull;
-    x ^= x >> 33;
-    return x;
-}
 __host__ __device__ inline unsigned long long shl64(unsigned long long x, uint32_t s) { return s >= 64 ? 0ull : x << s; }
 __host__ __device__ inline unsigned long long shr64(unsigned long long x, uint32_t s) { return s >= 64 ? 0ull : x >> s; }
 __host__ __device__ inline unsigned long long low_mask(uint32_t bits) { return bits >= 64 ? ~0ull : (1ull << bits) - 1; }
@@ -110,9 +95,9 @@ __device__ inline uint32_t cell_base(uint8_t c) { return c == 'A' ? 0u : c == 'C
 // two 2-bit codes words at Hamming distance 1: exactly one base differs
 __device__ inline bool hamming1(uint32_t x) { return __popc((x | (x >> 1)) & 0x55555555u) == 1; }
 
-// whitelist table: open addressing, linear probing, slot = barcode << 32 | line, empty = ~0 (a line is < 2^31)
+// whitelist table: open addressing, linear probing from pa_mix64(barcode), slot = barcode << 32 | line, empty = ~0 (a line is < 2^31)
 __device__ inline uint32_t wl_probe(const unsigned long long* __restrict__ slots, uint64_t mask, uint32_t bc) {
-    for (uint64_t j = cell_hash(bc) & mask;; j = (j + 1) & mask) {
+    for (uint64_t j = pa_mix64(bc) & mask;; j = (j + 1) & mask) {
         const unsigned long long s = slots[j];
         if (s == ~0ull) return CELL_NONE;
         if ((uint32_t)(s >> 32) == bc) return (uint32_t)s;
@@ -312,13 +297,6 @@ __global__ __launch_bounds__(CELL_BLOCK) void pa_cell_conflict_kernel(const unsi
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(stats + ST_CONFLICT, (unsigned long long)__popcll(m));
 }
 
-uint32_t bits_for(uint64_t max_value) {   // bits that hold 0..max_value
-    uint32_t b = 0;
-    while (b < 64 && (max_value >> b) != 0) ++b;
-    return b;
-}
-inline uint32_t grid_for(uint64_t n) { return (uint32_t)((n + CELL_BLOCK - 1) / CELL_BLOCK); }
-
 }  // namespace
 
 struct pa_cell_counter {
@@ -340,19 +318,6 @@ struct pa_cell_counter {
 };
 
 namespace {
-
-// hipcub's scratch, sized by a first call with no buffer
-template <class F>
-int cub_call(DeviceBuffer<uint8_t>& tmp, F&& fn) {
-    size_t bytes = 0;
-    PA_HIP_TRY(fn(nullptr, bytes));
-    if (bytes > tmp.size()) {
-        const int e = tmp.alloc(bytes);
-        if (e != PA_OK) return e;
-    }
-    PA_HIP_TRY(fn(tmp.get(), bytes));
-    return PA_OK;
-}
 
 int fetch_stats(pa_cell_counter* c, hipStream_t stream) {
     unsigned long long d[PA_CELL_STATS];
@@ -393,7 +358,7 @@ int pa_cell_counter_create(pa_index* idx, const pa_host_index* h, const uint32_t
             if (b > 3) return fail(PA_ERR_INVALID_ARG, "whitelist barcode %llu: byte %u is not A, C, G or T", (unsigned long long)line, j);
             bc = (bc << 2) | b;
         }
-        uint64_t j = cell_hash(bc) & (cap - 1);
+        uint64_t j = pa_mix64(bc) & (cap - 1);
         while (wl[j] != ~0ull) {
             if ((uint32_t)(wl[j] >> 32) == bc) return fail(PA_ERR_INVALID_ARG, "whitelist barcode %llu repeats barcode %u", (unsigned long long)line, (uint32_t)wl[j]);
             j = (j + 1) & (cap - 1);
@@ -446,12 +411,10 @@ int pa_cell_counter_add_device(pa_cell_counter* c, const pa_read_result* d_resul
     PA_HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     DeviceBuffer<unsigned long long> keys, sorted;
-    DeviceBuffer<unsigned int> d_runs;
+    DeviceBuffer<uint32_t> d_runs;
     DeviceBuffer<uint8_t> tmp;
-    int e = keys.alloc(n_reads);
-    if (e == PA_OK) e = sorted.alloc(n_reads);
-    if (e == PA_OK) e = d_runs.alloc(1);
-    if (e != PA_OK) return e;
+    int e;
+    if ((e = keys.alloc(n_reads)) || (e = sorted.alloc(n_reads)) || (e = d_runs.alloc(1))) return e;
     const uint32_t end_bit = std::max(1u, c->key_bits());
     CellKeyParams p;
     p.results = d_results; p.arena = d_arena; p.r1 = d_r1; p.r1_off = d_r1_offsets; p.n = n_reads;
@@ -461,7 +424,7 @@ int pa_cell_counter_add_device(pa_cell_counter* c, const pa_read_result* d_resul
     p.sentinel = low_mask(end_bit);   // >= every valid key: the dropped reads sort behind the counted ones
     p.keys = keys.get(); p.stats = c->d_stats.get();
     const uint64_t counted_before = c->stats[ST_COUNTED];
-    hipLaunchKernelGGL(pa_cell_keys_kernel, dim3(grid_for(n_reads)), dim3(CELL_BLOCK), 0, s, p);
+    hipLaunchKernelGGL(pa_cell_keys_kernel, dim3(grid_for(n_reads, CELL_BLOCK)), dim3(CELL_BLOCK), 0, s, p);
     PA_HIP_TRY(hipGetLastError());
     if ((e = fetch_stats(c, s)) != PA_OK) return e;
     const uint64_t counted = c->stats[ST_COUNTED] - counted_before;
@@ -479,17 +442,12 @@ int pa_cell_counter_add_device(pa_cell_counter* c, const pa_read_result* d_resul
         c->acc_keys = std::move(nk);
         c->acc_reads = std::move(nr);
     }
-    const int n = (int)n_reads, m = (int)counted;
     // only the key's used bits are sorted; the counted reads are the first `counted` sorted keys
-    e = cub_call(tmp, [&](void* t, size_t& b) { return hipcub::DeviceRadixSort::SortKeys(t, b, keys.get(), sorted.get(), n, 0, (int)end_bit, s); });
-    if (e == PA_OK)
-        e = cub_call(tmp, [&](void* t, size_t& b) {
-            return hipcub::DeviceRunLengthEncode::Encode(t, b, sorted.get(), c->acc_keys.get() + c->acc_n, c->acc_reads.get() + c->acc_n, d_runs.get(), m, s);
-        });
-    if (e != PA_OK) return e;
-    unsigned int runs = 0;
-    PA_HIP_TRY(hipMemcpyAsync(&runs, d_runs.get(), 4, hipMemcpyDeviceToHost, s));
-    PA_HIP_TRY(hipStreamSynchronize(s));
+    uint32_t runs = 0;
+    if ((e = sort_keys(s, tmp, keys.get(), sorted.get(), (int)n_reads, 0, end_bit)) ||
+        (e = run_length_encode(s, tmp, sorted.get(), counted, c->acc_keys.get() + c->acc_n, c->acc_reads.get() + c->acc_n, d_runs.get())) ||
+        (e = fetch_u32(d_runs.get(), s, runs)))
+        return e;
     c->acc_n += runs;
     return PA_OK;
 }
@@ -508,36 +466,25 @@ int pa_cell_counter_finish(pa_cell_counter* c, uint64_t* n_entries) {
     if (M0) {
         DeviceBuffer<unsigned long long> k1, k2, seg, seg_u;
         DeviceBuffer<uint32_t> r1, r2, seg_n, seg_start;
-        DeviceBuffer<unsigned int> d_cnt;
+        DeviceBuffer<uint32_t> d_cnt;
         DeviceBuffer<uint8_t> tmp;
         if ((e = k1.alloc(M0)) || (e = k2.alloc(M0)) || (e = r1.alloc(M0)) || (e = r2.alloc(M0)) || (e = d_cnt.alloc(1))) return e;
-        const int n0 = (int)M0;
-        unsigned int cnt = 0;
-        auto fetch_cnt = [&]() -> int {
-            PA_HIP_TRY(hipMemcpyAsync(&cnt, d_cnt.get(), 4, hipMemcpyDeviceToHost, s));
-            PA_HIP_TRY(hipStreamSynchronize(s));
-            return PA_OK;
-        };
-        // 1. every batch's entries together: sort by key, sum the reads of equal keys -> (k2, r2)[M]
-        e = cub_call(tmp, [&](void* t, size_t& b) { return hipcub::DeviceRadixSort::SortPairs(t, b, c->acc_keys.get(), k1.get(), c->acc_reads.get(), r1.get(), n0, 0, (int)end_bit, s); });
-        if (e == PA_OK) e = cub_call(tmp, [&](void* t, size_t& b) { return hipcub::DeviceReduce::ReduceByKey(t, b, k1.get(), k2.get(), r1.get(), r2.get(), d_cnt.get(), hipcub::Sum(), n0, s); });
-        if (e == PA_OK) e = fetch_cnt();
-        if (e != PA_OK) return e;
+        uint32_t cnt = 0;
+        // 1. every batch's entries together: sort by key, sum the reads of equal keys -> (k2, r2)[M]   (sort counts as int: 32-bit indexing)
+        if ((e = sort_pairs(s, tmp, c->acc_keys.get(), k1.get(), c->acc_reads.get(), r1.get(), (int)M0, 0, end_bit)) ||
+            (e = reduce_by_key_sum(s, tmp, k1.get(), r1.get(), M0, k2.get(), r2.get(), d_cnt.get())) || (e = fetch_u32(d_cnt.get(), s, cnt)))
+            return e;
         const uint64_t M = cnt;
-        const int n1 = (int)M;
         c->acc_keys.release();
         c->acc_reads.release();
         // 2. (cell, gene) segments: their sizes, then their starts seg_start[0 .. segs]
         if ((e = seg.alloc(M)) || (e = seg_u.alloc(M)) || (e = seg_n.alloc(M)) || (e = seg_start.alloc(M + 1))) return e;
-        hipLaunchKernelGGL(pa_cell_segment_kernel, dim3(grid_for(M)), dim3(CELL_BLOCK), 0, s, k2.get(), M, umi_bits, seg.get());
+        hipLaunchKernelGGL(pa_cell_segment_kernel, dim3(grid_for(M, CELL_BLOCK)), dim3(CELL_BLOCK), 0, s, k2.get(), M, umi_bits, seg.get());
         PA_HIP_TRY(hipGetLastError());
-        e = cub_call(tmp, [&](void* t, size_t& b) { return hipcub::DeviceRunLengthEncode::Encode(t, b, seg.get(), seg_u.get(), seg_n.get(), d_cnt.get(), n1, s); });
-        if (e == PA_OK) e = fetch_cnt();
-        if (e != PA_OK) return e;
+        if ((e = run_length_encode(s, tmp, seg.get(), M, seg_u.get(), seg_n.get(), d_cnt.get())) || (e = fetch_u32(d_cnt.get(), s, cnt))) return e;
         const uint32_t segs = cnt;
         PA_HIP_TRY(hipMemsetAsync(seg_start.get(), 0, 4, s));
-        e = cub_call(tmp, [&](void* t, size_t& b) { return hipcub::DeviceScan::InclusiveSum(t, b, seg_n.get(), seg_start.get() + 1, (int)segs, s); });
-        if (e != PA_OK) return e;
+        if ((e = scan_inclusive(s, tmp, seg_n.get(), seg_start.get() + 1, segs))) return e;
         seg.release(); seg_u.release(); seg_n.release();
         // 3. UMI correction -> (cell, corrected UMI, gene) molecules in k1 (reads r2)
         {
@@ -550,25 +497,23 @@ int pa_cell_counter_finish(pa_cell_counter* c, uint64_t* n_entries) {
         }
         seg_start.release();
         // 4. molecules that moved onto one UMI join: sort, sum -> (k1, r1)[M2]
-        e = cub_call(tmp, [&](void* t, size_t& b) { return hipcub::DeviceRadixSort::SortPairs(t, b, k1.get(), k2.get(), r2.get(), r1.get(), n1, 0, (int)end_bit, s); });
-        if (e == PA_OK) e = cub_call(tmp, [&](void* t, size_t& b) { return hipcub::DeviceReduce::ReduceByKey(t, b, k2.get(), k1.get(), r1.get(), r2.get(), d_cnt.get(), hipcub::Sum(), n1, s); });
-        if (e == PA_OK) e = fetch_cnt();
-        if (e != PA_OK) return e;
+        if ((e = sort_pairs(s, tmp, k1.get(), k2.get(), r2.get(), r1.get(), (int)M, 0, end_bit)) ||
+            (e = reduce_by_key_sum(s, tmp, k2.get(), r1.get(), M, k1.get(), r2.get(), d_cnt.get())) || (e = fetch_u32(d_cnt.get(), s, cnt)))
+            return e;
         const uint64_t M2 = cnt;
         // 5. gene conflicts per (cell, UMI): survivors re-keyed cell | gene in k2, the rest get the sentinel
         const unsigned long long sentinel3 = low_mask(end_bit3);
         const uint64_t lost_before = c->stats[ST_CONFLICT];
-        hipLaunchKernelGGL(pa_cell_conflict_kernel, dim3(grid_for(M2)), dim3(CELL_BLOCK), 0, s, k1.get(), r2.get(), M2, c->gene_bits, cell_shift, sentinel3,
+        hipLaunchKernelGGL(pa_cell_conflict_kernel, dim3(grid_for(M2, CELL_BLOCK)), dim3(CELL_BLOCK), 0, s, k1.get(), r2.get(), M2, c->gene_bits, cell_shift, sentinel3,
                            k2.get(), c->d_stats.get());
         PA_HIP_TRY(hipGetLastError());
         if ((e = fetch_stats(c, s)) != PA_OK) return e;
         const uint64_t kept = M2 - (c->stats[ST_CONFLICT] - lost_before);
         // 6. UMIs per (cell, gene): sort the survivors, run-length encode
         if (kept) {
-            e = cub_call(tmp, [&](void* t, size_t& b) { return hipcub::DeviceRadixSort::SortKeys(t, b, k2.get(), k1.get(), (int)M2, 0, (int)end_bit3, s); });
-            if (e == PA_OK) e = cub_call(tmp, [&](void* t, size_t& b) { return hipcub::DeviceRunLengthEncode::Encode(t, b, k1.get(), k2.get(), r1.get(), d_cnt.get(), (int)kept, s); });
-            if (e == PA_OK) e = fetch_cnt();
-            if (e != PA_OK) return e;
+            if ((e = sort_keys(s, tmp, k2.get(), k1.get(), (int)M2, 0, end_bit3)) || (e = run_length_encode(s, tmp, k1.get(), kept, k2.get(), r1.get(), d_cnt.get())) ||
+                (e = fetch_u32(d_cnt.get(), s, cnt)))
+                return e;
             const uint64_t entries = cnt;
             std::vector<unsigned long long> hk(entries);
             c->m_umis.resize(entries);

@@ -8,8 +8,8 @@
 //   pa_compact_write_kernel the 8-byte records and the packed classes (copied out of the launch's arena, whose waves' private slices
 //                           are two thirds padding)
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_scan.hpp>
 
+#include "device_prims.hpp"
 #include "kernels.hpp"
 #include "pa_common.hpp"
 
@@ -56,8 +56,7 @@ __global__ __launch_bounds__(256) void pa_compact_write_kernel(const pa_read_res
 }
 
 size_t scan_bytes(uint64_t n) {
-    size_t bytes = 0;
-    (void)rocprim::exclusive_scan(nullptr, bytes, (const uint32_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), (hipStream_t) nullptr);
+    const size_t bytes = prim_bytes([&](void* t, size_t& b) { return scan_exclusive_on(t, b, (const uint32_t*)nullptr, (uint64_t*)nullptr, (size_t)(n + 1), nullptr); });
     return (bytes + 255) & ~(size_t)255;
 }
 
@@ -83,11 +82,11 @@ extern "C" int pa_results_compact_device(pa_index* idx, const pa_read_result* d_
     uint32_t* d_len = reinterpret_cast<uint32_t*>(base);
     uint64_t* d_off = reinterpret_cast<uint64_t*>(base + (((size_t)(n_reads + 1) * 4 + 255) & ~(size_t)255));
     void* d_tmp = reinterpret_cast<uint8_t*>(d_off) + (((size_t)(n_reads + 1) * 8 + 255) & ~(size_t)255);
-    const size_t tmp_bytes = scan_bytes(n_reads);
+    size_t tmp_bytes = scan_bytes(n_reads);
     const uint32_t blocks = (uint32_t)((n_reads + 1 + 255) / 256);
     hipLaunchKernelGGL(pa_compact_len_kernel, dim3(blocks), dim3(256), 0, s, d_results, n_reads, arena_cap, d_len);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = rocprim::exclusive_scan(d_tmp, const_cast<size_t&>(tmp_bytes), (const uint32_t*)d_len, d_off, (uint64_t)0, (size_t)(n_reads + 1), rocprim::plus<uint64_t>(), s);
+    if (e == hipSuccess) e = scan_exclusive_on(d_tmp, tmp_bytes, (const uint32_t*)d_len, d_off, (size_t)(n_reads + 1), s);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(pa_compact_write_kernel, dim3(blocks), dim3(256), 0, s, d_results, d_arena, n_reads, arena_cap, (const uint64_t*)d_off, d_compact, d_packed, packed_cap,
                            reinterpret_cast<unsigned long long*>(d_packed_words));

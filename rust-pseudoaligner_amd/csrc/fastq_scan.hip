@@ -12,8 +12,8 @@
 // Only whole records count: a window ends behind its last fourth line break, the rest is the next window's head. The encode and
 // render kernels then read sequences and ids where they lie in the window (rec = {id offset, id length, sequence offset, length}).
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_scan.hpp>
 
+#include "device_prims.hpp"
 #include "kernels.hpp"
 #include "pa_common.hpp"
 
@@ -162,9 +162,7 @@ uint32_t fq_chunks(uint64_t begin, uint64_t end) {
 }
 
 size_t fq_scan_tmp_bytes(uint32_t n_chunks) {
-    size_t bytes = 0;
-    (void)rocprim::exclusive_scan(nullptr, bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)n_chunks + 1, rocprim::plus<uint32_t>(), (hipStream_t) nullptr);
-    return bytes;
+    return prim_bytes([&](void* t, size_t& b) { return scan_exclusive_on(t, b, (const uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n_chunks + 1, nullptr); });
 }
 
 // The records of the window text[begin, end): d_info (zeroed here) receives what the host needs to go on. d_chunk / d_first hold n_chunks + 1
@@ -178,7 +176,7 @@ int launch_fq_scan(const uint8_t* d_text, uint64_t begin, uint64_t end, uint32_t
     if (!rescan) {
         hipLaunchKernelGGL(pa_fq_count_kernel, dim3(n_chunks), dim3(256), 0, stream, d_text, base16, begin, end, d_chunk, n_chunks);
         if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-        e = rocprim::exclusive_scan(d_tmp, tmp_bytes, (const uint32_t*)d_chunk, d_first, 0u, (size_t)n_chunks + 1, rocprim::plus<uint32_t>(), stream);
+        e = scan_exclusive_on(d_tmp, tmp_bytes, (const uint32_t*)d_chunk, d_first, (size_t)n_chunks + 1, stream);
         if (e != hipSuccess) return (int)e;
     }
     hipLaunchKernelGGL(pa_fq_fill_kernel, dim3(n_chunks), dim3(256), 0, stream, d_text, base16, begin, end, (const uint32_t*)d_first, d_line_start, cap_lines, d_info);

@@ -22,19 +22,13 @@
 // small and are walked on the host exactly as dbg_build.cpp does.
 #include <hip/hip_runtime.h>
 
-#include <cstring>
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
-
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
 #include <numeric>
 #include <unordered_map>
 
+#include "device_prims.hpp"
 #include "hip_buffer.hpp"
 #include "lane_steps.hpp"
 #include "pa_common.hpp"
@@ -43,11 +37,6 @@ namespace pa {
 namespace {
 
 constexpr uint32_t NONE32 = 0xFFFFFFFFu;
-
-using Bytes = DeviceBuffer<uint8_t>;
-
-// a device temporary of n bytes (16 when n is 0); freed when it goes out of scope
-int dalloc(Bytes& b, size_t n) { return b.alloc(n ? n : 16); }
 
 // ---- k-mers of one or two words on the device ----
 template <class KT> struct DKmer;
@@ -328,8 +317,6 @@ __global__ __launch_bounds__(256) void pa_ib_gather_kernel(const uint32_t* __res
     okmer[i] = dkmer[d]; oexts[i] = dexts[d]; ocol[i] = dcol[d]; osucc[i] = succ[d];
 }
 
-inline dim3 grid_of(uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); }
-
 struct Stage {   // PA_VERBOSE: stage times (device work is synchronised at each mark)
     bool on;
     std::chrono::steady_clock::time_point t;
@@ -342,50 +329,6 @@ struct Stage {   // PA_VERBOSE: stage times (device work is synchronised at each
         t = now;
     }
 };
-
-template <class K, class V>
-int sort_pairs(const K* kin, K* kout, const V* vin, V* vout, uint64_t n, uint32_t begin_bit, uint32_t end_bit) {
-    size_t bytes = 0;
-    PA_HIP_TRY(rocprim::radix_sort_pairs(nullptr, bytes, kin, kout, vin, vout, (size_t)n, begin_bit, end_bit, (hipStream_t) nullptr));
-    Bytes tmp;
-    if (const int e_ = dalloc(tmp, bytes)) return e_;
-    PA_HIP_TRY(rocprim::radix_sort_pairs(tmp.get(), bytes, kin, kout, vin, vout, (size_t)n, begin_bit, end_bit, (hipStream_t) nullptr));
-    PA_HIP_TRY(hipStreamSynchronize(nullptr));   // tmp is freed on return
-    return PA_OK;
-}
-template <class T>
-int scan_incl(const T* in, T* out, uint64_t n) {
-    size_t bytes = 0;
-    PA_HIP_TRY(rocprim::inclusive_scan(nullptr, bytes, in, out, (size_t)n, rocprim::plus<T>(), (hipStream_t) nullptr));
-    Bytes tmp;
-    if (const int e_ = dalloc(tmp, bytes)) return e_;
-    PA_HIP_TRY(rocprim::inclusive_scan(tmp.get(), bytes, in, out, (size_t)n, rocprim::plus<T>(), (hipStream_t) nullptr));
-    PA_HIP_TRY(hipStreamSynchronize(nullptr));
-    return PA_OK;
-}
-template <class T>
-int scan_excl(const T* in, T* out, uint64_t n) {
-    size_t bytes = 0;
-    PA_HIP_TRY(rocprim::exclusive_scan(nullptr, bytes, in, out, T(0), (size_t)n, rocprim::plus<T>(), (hipStream_t) nullptr));
-    Bytes tmp;
-    if (const int e_ = dalloc(tmp, bytes)) return e_;
-    PA_HIP_TRY(rocprim::exclusive_scan(tmp.get(), bytes, in, out, T(0), (size_t)n, rocprim::plus<T>(), (hipStream_t) nullptr));
-    PA_HIP_TRY(hipStreamSynchronize(nullptr));
-    return PA_OK;
-}
-// indices i in [0, n) with flags[i] != 0, ascending
-int select_flagged(const uint32_t* flags, uint64_t n, uint32_t* out, uint32_t* count_host) {
-    Bytes cnt;
-    if (const int e_ = dalloc(cnt, 8)) return e_;
-    size_t bytes = 0;
-    rocprim::counting_iterator<uint32_t> it(0);
-    PA_HIP_TRY(rocprim::select(nullptr, bytes, it, flags, out, cnt.as<uint32_t>(), (size_t)n, (hipStream_t) nullptr));
-    Bytes tmp;
-    if (const int e_ = dalloc(tmp, bytes)) return e_;
-    PA_HIP_TRY(rocprim::select(tmp.get(), bytes, it, flags, out, cnt.as<uint32_t>(), (size_t)n, (hipStream_t) nullptr));
-    PA_HIP_TRY(hipMemcpy(count_host, cnt.get(), 4, hipMemcpyDeviceToHost));
-    return PA_OK;
-}
 
 template <class KT>
 int build_graph_device_t(const uint64_t* packed_in, const uint64_t* tx_start, uint32_t num_tx, uint32_t k, HostIndex& out) {
@@ -407,54 +350,52 @@ int build_graph_device_t(const uint64_t* packed_in, const uint64_t* tx_start, ui
     if (N >= 0xFFFFFFFFull) return fail(PA_ERR_UNSUPPORTED, "the GPU builder handles fewer than 2^32 k-mer occurrences (%llu)", (unsigned long long)N);
     uint32_t logp = 4;   // partitions of dbg_build.cpp: node order = (partition of the first k-mer, k-mer)
     while (logp < 12 && (N >> logp) > (1u << 20)) ++logp;
-    const uint32_t P = 1u << logp;
+    // Everything runs on the null stream, in order; what the host reads comes through a synchronising copy. `tmp` is the scratch
+    // of every sort, scan and selection of the build. A sort's scratch holds a copy of its records, so it is released right after
+    // the sort (HBM is what limits the builder); scans and selections need a few KB.
+    const hipStream_t s = nullptr;
+    DeviceBuffer<uint8_t> tmp;
+    int e;
 
     const uint64_t nwords = (total_bases + 31) / 32;
-    Bytes d_packed, d_txs, d_kcum;
-    if (const int e_ = dalloc(d_packed, (nwords + 3) * 8)) return e_;
+    DeviceBuffer<uint64_t> d_packed, d_txs, d_kcum;
+    if ((e = d_packed.alloc(nwords + 3)) || (e = d_txs.alloc((size_t)num_tx + 1)) || (e = d_kcum.alloc((size_t)num_tx + 1))) return e;
     PA_HIP_TRY(hipMemset(d_packed.get(), 0, (nwords + 3) * 8));
     PA_HIP_TRY(hipMemcpy(d_packed.get(), packed_in, nwords * 8, hipMemcpyHostToDevice));
-    if (const int e_ = dalloc(d_txs, ((size_t)num_tx + 1) * 8)) return e_;
     PA_HIP_TRY(hipMemcpy(d_txs.get(), tx_start, ((size_t)num_tx + 1) * 8, hipMemcpyHostToDevice));
-    if (const int e_ = dalloc(d_kcum, ((size_t)num_tx + 1) * 8)) return e_;
     PA_HIP_TRY(hipMemcpy(d_kcum.get(), kcum.data(), ((size_t)num_tx + 1) * 8, hipMemcpyHostToDevice));
 
     // ---- 1 + 2. records, sorted by k-mer ----
-    Bytes keys, vals;
+    DeviceBuffer<KT> keys;
+    DeviceBuffer<uint32_t> vals;
     {
-        Bytes keys0, vals0;
-        if (const int e_ = dalloc(keys0, N * sizeof(KT))) return e_;
-        if (const int e_ = dalloc(vals0, N * 4)) return e_;
-        if (const int e_ = dalloc(keys, N * sizeof(KT))) return e_;
-        if (const int e_ = dalloc(vals, N * 4)) return e_;
-        hipLaunchKernelGGL(pa_ib_enum_kernel<KT>, grid_of(total_bases), dim3(256), 0, nullptr, d_packed.as<uint64_t>(), d_txs.as<uint64_t>(), d_kcum.as<uint64_t>(),
-                           num_tx, total_bases, k, keys0.as<KT>(), vals0.as<uint32_t>());
+        DeviceBuffer<KT> keys0;
+        DeviceBuffer<uint32_t> vals0;
+        if ((e = keys0.alloc(N)) || (e = vals0.alloc(N)) || (e = keys.alloc(N)) || (e = vals.alloc(N))) return e;
+        hipLaunchKernelGGL(pa_ib_enum_kernel<KT>, dim3(grid_for(total_bases)), dim3(256), 0, s, d_packed.get(), d_txs.get(), d_kcum.get(), num_tx, total_bases, k,
+                           keys0.get(), vals0.get());
         PA_HIP_TRY(hipGetLastError());
         stage.mark("enumerate k-mers");
-        const int rc = sort_pairs(keys0.as<KT>(), keys.as<KT>(), vals0.as<uint32_t>(), vals.as<uint32_t>(), N, 0, 2 * k);
-        if (rc != PA_OK) return rc;
+        if ((e = sort_pairs(s, tmp, keys0.get(), keys.get(), vals0.get(), vals.get(), (size_t)N, 0, 2 * k))) return e;
+        tmp.release();
         stage.mark("radix sort");
     }
     // ---- 3. segments ----
-    Bytes seg;
-    if (const int e_ = dalloc(seg, N * 4)) return e_;
+    DeviceBuffer<uint32_t> seg;
+    if ((e = seg.alloc(N))) return e;
     {
-        Bytes head;
-        if (const int e_ = dalloc(head, N * 4)) return e_;
-        hipLaunchKernelGGL(pa_ib_heads_kernel<KT>, grid_of(N), dim3(256), 0, nullptr, keys.as<KT>(), N, head.as<uint32_t>());
+        DeviceBuffer<uint32_t> head;
+        if ((e = head.alloc(N))) return e;
+        hipLaunchKernelGGL(pa_ib_heads_kernel<KT>, dim3(grid_for(N)), dim3(256), 0, s, keys.get(), N, head.get());
         PA_HIP_TRY(hipGetLastError());
-        const int rc = scan_incl(head.as<uint32_t>(), seg.as<uint32_t>(), N);
-        if (rc != PA_OK) return rc;
+        if ((e = scan_inclusive(s, tmp, head.get(), seg.get(), (size_t)N))) return e;
     }
     uint32_t D = 0;
-    PA_HIP_TRY(hipMemcpy(&D, seg.as<uint32_t>() + (N - 1), 4, hipMemcpyDeviceToHost));
-    Bytes dkmer, dfirst, dexts, dcnt, dhash, coltmp, run_first;
-    if (const int e_ = dalloc(dkmer, (size_t)D * sizeof(KT))) return e_;
-    if (const int e_ = dalloc(dfirst, (size_t)D * 4)) return e_;
-    if (const int e_ = dalloc(dexts, (size_t)D * 4)) return e_;
-    if (const int e_ = dalloc(dcnt, (size_t)D * 4)) return e_;
-    if (const int e_ = dalloc(dhash, (size_t)D * 8)) return e_;
-    if (const int e_ = dalloc(coltmp, (size_t)D * 4)) return e_;
+    if ((e = fetch_u32(seg.get() + (N - 1), s, D))) return e;
+    DeviceBuffer<KT> dkmer;
+    DeviceBuffer<uint32_t> dfirst, dexts, dcnt, coltmp, run_first;
+    DeviceBuffer<unsigned long long> dhash;
+    if ((e = dkmer.alloc(D)) || (e = dfirst.alloc(D)) || (e = dexts.alloc(D)) || (e = dcnt.alloc(D)) || (e = dhash.alloc(D)) || (e = coltmp.alloc(D))) return e;
     PA_HIP_TRY(hipMemset(dexts.get(), 0, (size_t)D * 4));
     PA_HIP_TRY(hipMemset(dcnt.get(), 0, (size_t)D * 4));
     // ---- 4. colours: runs of equal set hash, verified by content ----
@@ -462,34 +403,26 @@ int build_graph_device_t(const uint64_t* packed_in, const uint64_t* tx_start, ui
     uint64_t seed = 0x243f6a8885a308d3ull;
     for (int attempt = 0;; ++attempt) {
         PA_HIP_TRY(hipMemset(dhash.get(), 0, (size_t)D * 8));
-        hipLaunchKernelGGL(pa_ib_segment_kernel<KT>, grid_of(N), dim3(256), 0, nullptr, keys.as<KT>(), vals.as<uint32_t>(), seg.as<uint32_t>(), N, seed,
-                           dkmer.as<KT>(), dfirst.as<uint32_t>(), attempt == 0 ? dexts.as<uint32_t>() : nullptr, attempt == 0 ? dcnt.as<uint32_t>() : nullptr,
-                           dhash.as<unsigned long long>());
+        hipLaunchKernelGGL(pa_ib_segment_kernel<KT>, dim3(grid_for(N)), dim3(256), 0, s, keys.get(), vals.get(), seg.get(), N, seed, dkmer.get(), dfirst.get(),
+                           attempt == 0 ? dexts.get() : nullptr, attempt == 0 ? dcnt.get() : nullptr, dhash.get());
         PA_HIP_TRY(hipGetLastError());
-        Bytes hs, ds0, ds, rid, rh;
-        if (const int e_ = dalloc(hs, (size_t)D * 8)) return e_;
-        if (const int e_ = dalloc(ds0, (size_t)D * 4)) return e_;
-        if (const int e_ = dalloc(ds, (size_t)D * 4)) return e_;
-        if (const int e_ = dalloc(rid, (size_t)D * 4)) return e_;
-        if (const int e_ = dalloc(rh, (size_t)D * 4)) return e_;
-        hipLaunchKernelGGL(pa_ib_iota_kernel, grid_of(D), dim3(256), 0, nullptr, ds0.as<uint32_t>(), (uint64_t)D);
-        { const int rc = sort_pairs(dhash.as<unsigned long long>(), hs.as<unsigned long long>(), ds0.as<uint32_t>(), ds.as<uint32_t>(), D, 0, 64); if (rc != PA_OK) return rc; }
-        hipLaunchKernelGGL(pa_ib_runheads_kernel, grid_of(D), dim3(256), 0, nullptr, hs.as<unsigned long long>(), (uint64_t)D, rh.as<uint32_t>());
+        DeviceBuffer<unsigned long long> hs;
+        DeviceBuffer<uint32_t> ds0, ds, rid, rh, mism;
+        if ((e = hs.alloc(D)) || (e = ds0.alloc(D)) || (e = ds.alloc(D)) || (e = rid.alloc(D)) || (e = rh.alloc(D)) || (e = mism.alloc(1))) return e;
+        hipLaunchKernelGGL(pa_ib_iota_kernel, dim3(grid_for(D)), dim3(256), 0, s, ds0.get(), (uint64_t)D);
+        if ((e = sort_pairs(s, tmp, dhash.get(), hs.get(), ds0.get(), ds.get(), (size_t)D, 0, 64))) return e;
+        tmp.release();
+        hipLaunchKernelGGL(pa_ib_runheads_kernel, dim3(grid_for(D)), dim3(256), 0, s, hs.get(), (uint64_t)D, rh.get());
         PA_HIP_TRY(hipGetLastError());
-        { const int rc = scan_incl(rh.as<uint32_t>(), rid.as<uint32_t>(), D); if (rc != PA_OK) return rc; }
-        PA_HIP_TRY(hipMemcpy(&C, rid.as<uint32_t>() + (D - 1), 4, hipMemcpyDeviceToHost));
-        if (const int e_ = dalloc(run_first, (size_t)C * 4)) return e_;
-        hipLaunchKernelGGL(pa_ib_runs_kernel, grid_of(D), dim3(256), 0, nullptr, ds.as<uint32_t>(), rid.as<uint32_t>(), (uint64_t)D, run_first.as<uint32_t>(),
-                           coltmp.as<uint32_t>());
+        if ((e = scan_inclusive(s, tmp, rh.get(), rid.get(), (size_t)D)) || (e = fetch_u32(rid.get() + (D - 1), s, C)) || (e = run_first.alloc(C))) return e;
+        hipLaunchKernelGGL(pa_ib_runs_kernel, dim3(grid_for(D)), dim3(256), 0, s, ds.get(), rid.get(), (uint64_t)D, run_first.get(), coltmp.get());
         PA_HIP_TRY(hipGetLastError());
-        Bytes mism;
-        if (const int e_ = dalloc(mism, 4)) return e_;
         PA_HIP_TRY(hipMemset(mism.get(), 0, 4));
-        hipLaunchKernelGGL(pa_ib_verify_kernel, grid_of(D), dim3(256), 0, nullptr, vals.as<uint32_t>(), dfirst.as<uint32_t>(), dcnt.as<uint32_t>(), coltmp.as<uint32_t>(),
-                           run_first.as<uint32_t>(), (uint64_t)D, N, mism.as<uint32_t>());
+        hipLaunchKernelGGL(pa_ib_verify_kernel, dim3(grid_for(D)), dim3(256), 0, s, vals.get(), dfirst.get(), dcnt.get(), coltmp.get(), run_first.get(), (uint64_t)D, N,
+                           mism.get());
         PA_HIP_TRY(hipGetLastError());
         uint32_t bad = 0;
-        PA_HIP_TRY(hipMemcpy(&bad, mism.get(), 4, hipMemcpyDeviceToHost));
+        if ((e = fetch_u32(mism.get(), s, bad))) return e;
         if (bad == 0) break;
         if (attempt == 3) return fail(PA_ERR_INTERNAL, "colour interning: set hashes kept colliding (%u k-mers)", bad);
         seed = pa_mix64(seed + attempt + 1);   // two different id lists shared a hash: take another hash
@@ -499,18 +432,18 @@ int build_graph_device_t(const uint64_t* packed_in, const uint64_t* tx_start, ui
     std::vector<unsigned long long> loff((size_t)C + 1, 0);
     std::vector<uint32_t> lids;
     {
-        Bytes llen, d_off, d_ids;
-        if (const int e_ = dalloc(llen, ((size_t)C + 1) * 8)) return e_;
-        if (const int e_ = dalloc(d_off, ((size_t)C + 1) * 8)) return e_;
+        DeviceBuffer<unsigned long long> llen, d_off;
+        DeviceBuffer<uint32_t> d_ids;
+        if ((e = llen.alloc((size_t)C + 1)) || (e = d_off.alloc((size_t)C + 1))) return e;
         PA_HIP_TRY(hipMemset(llen.get(), 0, ((size_t)C + 1) * 8));
-        hipLaunchKernelGGL(pa_ib_listlen_kernel, grid_of(C), dim3(256), 0, nullptr, run_first.as<uint32_t>(), dcnt.as<uint32_t>(), (uint64_t)C, llen.as<unsigned long long>());
+        hipLaunchKernelGGL(pa_ib_listlen_kernel, dim3(grid_for(C)), dim3(256), 0, s, run_first.get(), dcnt.get(), (uint64_t)C, llen.get());
         PA_HIP_TRY(hipGetLastError());
-        { const int rc = scan_excl(llen.as<unsigned long long>(), d_off.as<unsigned long long>(), (uint64_t)C + 1); if (rc != PA_OK) return rc; }
+        if ((e = scan_exclusive(s, tmp, llen.get(), d_off.get(), (size_t)C + 1))) return e;
         PA_HIP_TRY(hipMemcpy(loff.data(), d_off.get(), ((size_t)C + 1) * 8, hipMemcpyDeviceToHost));
         const uint64_t nids = loff[C];
-        if (const int e_ = dalloc(d_ids, nids * 4)) return e_;
-        hipLaunchKernelGGL(pa_ib_listwrite_kernel, grid_of(C), dim3(256), 0, nullptr, vals.as<uint32_t>(), dfirst.as<uint32_t>(), run_first.as<uint32_t>(),
-                           d_off.as<unsigned long long>(), (uint64_t)C, (uint64_t)D, N, d_ids.as<uint32_t>());
+        if ((e = d_ids.alloc(nids))) return e;
+        hipLaunchKernelGGL(pa_ib_listwrite_kernel, dim3(grid_for(C)), dim3(256), 0, s, vals.get(), dfirst.get(), run_first.get(), d_off.get(), (uint64_t)C, (uint64_t)D, N,
+                           d_ids.get());
         PA_HIP_TRY(hipGetLastError());
         lids.resize(nids);
         PA_HIP_TRY(hipMemcpy(lids.data(), d_ids.get(), nids * 4, hipMemcpyDeviceToHost));
@@ -530,54 +463,50 @@ int build_graph_device_t(const uint64_t* packed_in, const uint64_t* tx_start, ui
     }
     // the occurrence records are no longer needed
     keys.release(); vals.release(); seg.release(); dhash.release(); dfirst.release(); run_first.release(); dcnt.release();
-    Bytes dcol;
+    DeviceBuffer<uint32_t> dcol;
     {
-        Bytes d_remap;
-        if (const int e_ = dalloc(d_remap, (size_t)C * 4)) return e_;
+        DeviceBuffer<uint32_t> d_remap;
+        if ((e = d_remap.alloc(C))) return e;
         PA_HIP_TRY(hipMemcpy(d_remap.get(), remap.data(), (size_t)C * 4, hipMemcpyHostToDevice));
-        if (const int e_ = dalloc(dcol, (size_t)D * 4)) return e_;
-        hipLaunchKernelGGL(pa_ib_colour_kernel, grid_of(D), dim3(256), 0, nullptr, coltmp.as<uint32_t>(), d_remap.as<uint32_t>(), (uint64_t)D, dcol.as<uint32_t>());
+        if ((e = dcol.alloc(D))) return e;
+        hipLaunchKernelGGL(pa_ib_colour_kernel, dim3(grid_for(D)), dim3(256), 0, s, coltmp.get(), d_remap.get(), (uint64_t)D, dcol.get());
         PA_HIP_TRY(hipGetLastError());
-        PA_HIP_TRY(hipStreamSynchronize(nullptr));
+        PA_HIP_TRY(hipStreamSynchronize(s));
     }
     coltmp.release();
     stage.mark("class numbering");
 
     // ---- 5 + 6. joins, pointer jumping ----
-    Bytes succ, pd;
-    if (const int e_ = dalloc(succ, (size_t)D * 4)) return e_;
-    if (const int e_ = dalloc(pd, (size_t)D * 8)) return e_;
-    hipLaunchKernelGGL(pa_ib_links_kernel<KT>, grid_of(D), dim3(256), 0, nullptr, dkmer.as<KT>(), dexts.as<uint32_t>(), dcol.as<uint32_t>(), D, k, succ.as<uint32_t>(),
-                       pd.as<unsigned long long>());
+    DeviceBuffer<uint32_t> succ;
+    DeviceBuffer<unsigned long long> pd;
+    if ((e = succ.alloc(D)) || (e = pd.alloc(D))) return e;
+    hipLaunchKernelGGL(pa_ib_links_kernel<KT>, dim3(grid_for(D)), dim3(256), 0, s, dkmer.get(), dexts.get(), dcol.get(), D, k, succ.get(), pd.get());
     PA_HIP_TRY(hipGetLastError());
     stage.mark("joins");
+    DeviceBuffer<uint32_t> cnt;   // one word: the pointers a jump pass moved, then the length of a selection
+    if ((e = cnt.alloc(1))) return e;
     {
-        Bytes cnt;
-        if (const int e_ = dalloc(cnt, 4)) return e_;
         uint32_t prev = NONE32;
         for (int round = 0; round < 40; ++round) {
             PA_HIP_TRY(hipMemset(cnt.get(), 0, 4));
-            const uint32_t jump_blocks = (uint32_t)std::min<uint64_t>(((uint64_t)D + 255) / 256, 8192);
-            hipLaunchKernelGGL(pa_ib_jump_kernel, dim3(jump_blocks), dim3(256), 0, nullptr, pd.as<unsigned long long>(), D, cnt.as<uint32_t>());
+            hipLaunchKernelGGL(pa_ib_jump_kernel, dim3(std::min(grid_for(D), 8192u)), dim3(256), 0, s, pd.get(), D, cnt.get());
             PA_HIP_TRY(hipGetLastError());
             uint32_t now = 0;
-            PA_HIP_TRY(hipMemcpy(&now, cnt.get(), 4, hipMemcpyDeviceToHost));
+            if ((e = fetch_u32(cnt.get(), s, now))) return e;
             if (now == 0 || now == prev) break;   // only the members of pure cycles keep moving
             prev = now;
         }
     }
     stage.mark("pointer jumping");
     // ---- 7. nodes ----
-    Bytes is_start, is_cyclic, starts, cyc;
-    if (const int e_ = dalloc(is_start, (size_t)D * 4)) return e_;
-    if (const int e_ = dalloc(is_cyclic, (size_t)D * 4)) return e_;
-    hipLaunchKernelGGL(pa_ib_classify_kernel, grid_of(D), dim3(256), 0, nullptr, pd.as<unsigned long long>(), D, is_start.as<uint32_t>(), is_cyclic.as<uint32_t>());
+    DeviceBuffer<uint32_t> is_start, is_cyclic, starts, cyc;
+    if ((e = is_start.alloc(D)) || (e = is_cyclic.alloc(D))) return e;
+    hipLaunchKernelGGL(pa_ib_classify_kernel, dim3(grid_for(D)), dim3(256), 0, s, pd.get(), D, is_start.get(), is_cyclic.get());
     PA_HIP_TRY(hipGetLastError());
-    if (const int e_ = dalloc(starts, (size_t)D * 4)) return e_;
     uint32_t ns = 0, ncyc = 0;
-    { const int rc = select_flagged(is_start.as<uint32_t>(), D, starts.as<uint32_t>(), &ns); if (rc != PA_OK) return rc; }
-    if (const int e_ = dalloc(cyc, (size_t)D * 4)) return e_;
-    { const int rc = select_flagged(is_cyclic.as<uint32_t>(), D, cyc.as<uint32_t>(), &ncyc); if (rc != PA_OK) return rc; }
+    if ((e = starts.alloc(D)) || (e = select_flagged_indices(s, tmp, is_start.get(), D, starts.get(), cnt.get())) || (e = fetch_u32(cnt.get(), s, ns)) ||
+        (e = cyc.alloc(D)) || (e = select_flagged_indices(s, tmp, is_cyclic.get(), D, cyc.get(), cnt.get())) || (e = fetch_u32(cnt.get(), s, ncyc)))
+        return e;
     is_start.release();
     if (ns >= NONE32) return fail(PA_ERR_UNSUPPORTED, "too many nodes");
     std::vector<uint32_t> h_len(ns), h_col(ns);
@@ -586,35 +515,30 @@ int build_graph_device_t(const uint64_t* packed_in, const uint64_t* tx_start, ui
     std::vector<uint64_t> h_seq;
     uint64_t nbases = 0;
     if (ns) {
-        Bytes pkey, pkey2, order, node_of, nlen, nlen64, nstart, nexts, ncol, seq;
-        if (const int e_ = dalloc(pkey, (size_t)ns * 4)) return e_;
-        if (const int e_ = dalloc(pkey2, (size_t)ns * 4)) return e_;
-        if (const int e_ = dalloc(order, (size_t)ns * 4)) return e_;
-        hipLaunchKernelGGL(pa_ib_partkey_kernel<KT>, grid_of(ns), dim3(256), 0, nullptr, dkmer.as<KT>(), starts.as<uint32_t>(), ns, logp, pkey.as<uint32_t>());
+        DeviceBuffer<uint32_t> pkey, pkey2, order, node_of, nlen, ncol;
+        DeviceBuffer<unsigned long long> nlen64, nstart, seq;
+        DeviceBuffer<uint8_t> nexts;
+        if ((e = pkey.alloc(ns)) || (e = pkey2.alloc(ns)) || (e = order.alloc(ns))) return e;
+        hipLaunchKernelGGL(pa_ib_partkey_kernel<KT>, dim3(grid_for(ns)), dim3(256), 0, s, dkmer.get(), starts.get(), ns, logp, pkey.get());
         PA_HIP_TRY(hipGetLastError());
         // the first k-mers are in k-mer order; a STABLE sort by partition gives (partition, k-mer) order
-        { const int rc = sort_pairs(pkey.as<uint32_t>(), pkey2.as<uint32_t>(), starts.as<uint32_t>(), order.as<uint32_t>(), ns, 0, logp); if (rc != PA_OK) return rc; }
-        if (const int e_ = dalloc(node_of, (size_t)D * 4)) return e_;
-        hipLaunchKernelGGL(pa_ib_nodeof_kernel, grid_of(ns), dim3(256), 0, nullptr, order.as<uint32_t>(), ns, node_of.as<uint32_t>());
+        if ((e = sort_pairs(s, tmp, pkey.get(), pkey2.get(), starts.get(), order.get(), (size_t)ns, 0, logp))) return e;
+        tmp.release();
+        if ((e = node_of.alloc(D))) return e;
+        hipLaunchKernelGGL(pa_ib_nodeof_kernel, dim3(grid_for(ns)), dim3(256), 0, s, order.get(), ns, node_of.get());
         PA_HIP_TRY(hipGetLastError());
-        if (const int e_ = dalloc(nlen, (size_t)ns * 4)) return e_;
-        if (const int e_ = dalloc(nlen64, ((size_t)ns + 1) * 8)) return e_;
-        if (const int e_ = dalloc(nstart, ((size_t)ns + 1) * 8)) return e_;
-        if (const int e_ = dalloc(nexts, ns)) return e_;
-        if (const int e_ = dalloc(ncol, (size_t)ns * 4)) return e_;
+        if ((e = nlen.alloc(ns)) || (e = nlen64.alloc((size_t)ns + 1)) || (e = nstart.alloc((size_t)ns + 1)) || (e = nexts.alloc(ns)) || (e = ncol.alloc(ns))) return e;
         PA_HIP_TRY(hipMemset(nlen64.get(), 0, ((size_t)ns + 1) * 8));
-        hipLaunchKernelGGL(pa_ib_tails_kernel, grid_of(D), dim3(256), 0, nullptr, pd.as<unsigned long long>(), succ.as<uint32_t>(), is_cyclic.as<uint32_t>(),
-                           node_of.as<uint32_t>(), dexts.as<uint32_t>(), dcol.as<uint32_t>(), D, k, nlen.as<uint32_t>(), nlen64.as<unsigned long long>(),
-                           nexts.as<uint8_t>(), ncol.as<uint32_t>());
+        hipLaunchKernelGGL(pa_ib_tails_kernel, dim3(grid_for(D)), dim3(256), 0, s, pd.get(), succ.get(), is_cyclic.get(), node_of.get(), dexts.get(), dcol.get(), D, k,
+                           nlen.get(), nlen64.get(), nexts.get(), ncol.get());
         PA_HIP_TRY(hipGetLastError());
-        { const int rc = scan_excl(nlen64.as<unsigned long long>(), nstart.as<unsigned long long>(), (uint64_t)ns + 1); if (rc != PA_OK) return rc; }
+        if ((e = scan_exclusive(s, tmp, nlen64.get(), nstart.get(), (size_t)ns + 1))) return e;
         PA_HIP_TRY(hipMemcpy(h_start.data(), nstart.get(), ((size_t)ns + 1) * 8, hipMemcpyDeviceToHost));
         nbases = h_start[ns];
         const uint64_t sw = (nbases + 31) / 32 + 2;
-        if (const int e_ = dalloc(seq, sw * 8)) return e_;
+        if ((e = seq.alloc(sw))) return e;
         PA_HIP_TRY(hipMemset(seq.get(), 0, sw * 8));
-        hipLaunchKernelGGL(pa_ib_seq_kernel<KT>, grid_of(D), dim3(256), 0, nullptr, dkmer.as<KT>(), pd.as<unsigned long long>(), is_cyclic.as<uint32_t>(),
-                           node_of.as<uint32_t>(), nstart.as<unsigned long long>(), D, k, seq.as<unsigned long long>());
+        hipLaunchKernelGGL(pa_ib_seq_kernel<KT>, dim3(grid_for(D)), dim3(256), 0, s, dkmer.get(), pd.get(), is_cyclic.get(), node_of.get(), nstart.get(), D, k, seq.get());
         PA_HIP_TRY(hipGetLastError());
         h_seq.resize(sw);
         PA_HIP_TRY(hipMemcpy(h_seq.data(), seq.get(), sw * 8, hipMemcpyDeviceToHost));
@@ -627,13 +551,11 @@ int build_graph_device_t(const uint64_t* packed_in, const uint64_t* tx_start, ui
     struct CycNode { std::vector<uint32_t> bases; uint32_t colour; uint8_t exts; };
     std::vector<CycNode> cyc_nodes;
     if (ncyc) {
-        Bytes ck, ce, cc, cs;
-        if (const int e_ = dalloc(ck, (size_t)ncyc * sizeof(KT))) return e_;
-        if (const int e_ = dalloc(ce, (size_t)ncyc * 4)) return e_;
-        if (const int e_ = dalloc(cc, (size_t)ncyc * 4)) return e_;
-        if (const int e_ = dalloc(cs, (size_t)ncyc * 4)) return e_;
-        hipLaunchKernelGGL(pa_ib_gather_kernel<KT>, grid_of(ncyc), dim3(256), 0, nullptr, cyc.as<uint32_t>(), ncyc, dkmer.as<KT>(), dexts.as<uint32_t>(),
-                           dcol.as<uint32_t>(), succ.as<uint32_t>(), ck.as<KT>(), ce.as<uint32_t>(), cc.as<uint32_t>(), cs.as<uint32_t>());
+        DeviceBuffer<KT> ck;
+        DeviceBuffer<uint32_t> ce, cc, cs;
+        if ((e = ck.alloc(ncyc)) || (e = ce.alloc(ncyc)) || (e = cc.alloc(ncyc)) || (e = cs.alloc(ncyc))) return e;
+        hipLaunchKernelGGL(pa_ib_gather_kernel<KT>, dim3(grid_for(ncyc)), dim3(256), 0, s, cyc.get(), ncyc, dkmer.get(), dexts.get(), dcol.get(), succ.get(), ck.get(),
+                           ce.get(), cc.get(), cs.get());
         PA_HIP_TRY(hipGetLastError());
         std::vector<uint32_t> which(ncyc), ce_h(ncyc), cc_h(ncyc), cs_h(ncyc);
         std::vector<KT> ck_h(ncyc);
@@ -673,7 +595,6 @@ int build_graph_device_t(const uint64_t* packed_in, const uint64_t* tx_start, ui
             cyc_nodes.push_back(std::move(nd));
         }
     }
-    (void)P;
     // ---- assemble ----
     uint64_t total_bases_out = nbases;
     for (const auto& c : cyc_nodes) total_bases_out += c.bases.size();

@@ -10,10 +10,6 @@
 // wave sums in order), so two runs on one input give the same bits. No floating-point atomics, no block waits on another.
 #include <hip/hip_runtime.h>
 
-#include <cstring>   // (before rocPRIM: its texture iterator calls memset without including it)
-
-#include <rocprim/rocprim.hpp>
-
 #include <algorithm>
 #include <charconv>
 #include <cmath>
@@ -22,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "device_prims.hpp"
 #include "hip_buffer.hpp"
 #include "pa_common.hpp"
 
@@ -244,27 +241,6 @@ __global__ void quant_truncate(uint32_t num_tx, double below, double* alpha, dou
     if (alpha[t] < below) { alpha[t] = 0.0; w[t] = 0.0; }
 }
 
-inline uint32_t grid_for(uint64_t n) { return (uint32_t)((n + 255) / 256); }
-
-// rocPRIM's scratch, sized by a first call without a buffer
-template <class F>
-int prim_call(DeviceBuffer<uint8_t>& tmp, F&& fn) {
-    size_t bytes = 0;
-    PA_HIP_TRY(fn(nullptr, bytes));
-    if (bytes > tmp.size()) {
-        const int e = tmp.alloc(bytes);
-        if (e != PA_OK) return e;
-    }
-    PA_HIP_TRY(fn(tmp.get(), bytes));
-    return PA_OK;
-}
-
-uint32_t bits_for(uint64_t v) {
-    uint32_t b = 1;
-    while (b < 32 && (v >> b)) ++b;
-    return b;
-}
-
 // an f64 as pa_write_mappability_tsv prints it: shortest digits that read back as the same double, fixed notation
 std::string tsv_f64(double v) {
     if (v != v) return "NaN";
@@ -351,10 +327,7 @@ int setup_device(pa_quant* q, const uint64_t* class_counts, const OverflowRows& 
     // rows: the candidates with entries, longest first (a stable sort: equal lengths keep class order, overflow records after the classes)
     hipLaunchKernelGGL(quant_candidates, dim3(grid_for(NC)), dim3(256), 0, s, C, n_ovf, d_counts.get(), q->d_ec_off.get(), d_ovf_len.get(), d_ovf_cnt.get(),
                        key_a.get(), val_a.get());
-    if ((e = prim_call(tmp, [&](void* t, size_t& b) {
-             return rocprim::radix_sort_pairs_desc(t, b, key_a.get(), key_b.get(), val_a.get(), val_b.get(), (size_t)NC, 0u, 32u, s);
-         })))
-        return e;
+    if ((e = sort_pairs_desc(s, tmp, key_a.get(), key_b.get(), val_a.get(), val_b.get(), (size_t)NC, 0, 32))) return e;
     uint32_t bounds[NBIN + 1] = {}, longest = 0, max_degree = 0;
     hipLaunchKernelGGL(quant_bounds, dim3(1), dim3(64), 0, s, key_b.get(), NC, d_bounds.get());
     PA_HIP_TRY(hipMemcpyAsync(bounds, d_bounds.get(), sizeof bounds, hipMemcpyDeviceToHost, s));
@@ -364,10 +337,7 @@ int setup_device(pa_quant* q, const uint64_t* class_counts, const OverflowRows& 
     for (int k = 0; k <= NBIN; ++k) q->rows.begin[k] = bounds[k];
     finish_layout(q->rows);
     // row offsets (key_b holds an entry beyond NC: the scan reads n_rows + 1 lengths and its last output is nnz)
-    if ((e = prim_call(tmp, [&](void* t, size_t& b) {
-             return rocprim::exclusive_scan(t, b, key_b.get(), q->d_row_off.get(), 0u, (size_t)n_rows + 1, rocprim::plus<uint32_t>(), s);
-         })))
-        return e;
+    if ((e = scan_exclusive(s, tmp, key_b.get(), q->d_row_off.get(), (size_t)n_rows + 1))) return e;
     PA_HIP_TRY(hipMemcpyAsync(d_row_cand.get(), val_b.get(), 4ull * n_rows, hipMemcpyDeviceToDevice, s));
     hipLaunchKernelGGL(quant_row_counts, dim3(grid_for(n_rows)), dim3(256), 0, s, n_rows, C, d_row_cand.get(), d_counts.get(), d_ovf_cnt.get(), q->d_row_cnt.get());
     GatherArgs g;
@@ -375,17 +345,11 @@ int setup_device(pa_quant* q, const uint64_t* class_counts, const OverflowRows& 
     g.ec_ids = q->d_ec_ids.get(); g.ovf_src = d_ovf_src.get(); g.words = d_words.get(); g.row_ids = q->d_row_ids.get(); g.pair_key = key_a.get(); g.pair_val = val_a.get();
     hipLaunchKernelGGL(quant_gather, dim3(grid_for(nnz)), dim3(256), 0, s, g);
     // transposed CSR: (transcript, row) pairs sorted by transcript; the sort is stable, so a transcript's rows stay ascending
-    if ((e = prim_call(tmp, [&](void* t, size_t& b) {
-             return rocprim::radix_sort_pairs(t, b, key_a.get(), key_b.get(), val_a.get(), q->d_tx_rows.get(), (size_t)nnz, 0u, bits_for(T - 1), s);
-         })))
-        return e;
+    if ((e = sort_pairs(s, tmp, key_a.get(), key_b.get(), val_a.get(), q->d_tx_rows.get(), (size_t)nnz, 0, std::max(1u, bits_for(T - 1))))) return e;
     hipLaunchKernelGGL(quant_tx_offsets, dim3(grid_for((uint64_t)T + 1)), dim3(256), 0, s, T, key_b.get(), nnz, q->d_tx_off.get());
     // transcripts by degree, largest first
     hipLaunchKernelGGL(quant_degrees, dim3(grid_for(T)), dim3(256), 0, s, T, q->d_tx_off.get(), key_a.get(), val_a.get());
-    if ((e = prim_call(tmp, [&](void* t, size_t& b) {
-             return rocprim::radix_sort_pairs_desc(t, b, key_a.get(), key_b.get(), val_a.get(), q->d_tx_order.get(), (size_t)T, 0u, 32u, s);
-         })))
-        return e;
+    if ((e = sort_pairs_desc(s, tmp, key_a.get(), key_b.get(), val_a.get(), q->d_tx_order.get(), (size_t)T, 0, 32))) return e;
     hipLaunchKernelGGL(quant_bounds, dim3(1), dim3(64), 0, s, key_b.get(), T, d_bounds.get());
     PA_HIP_TRY(hipMemcpyAsync(bounds, d_bounds.get(), sizeof bounds, hipMemcpyDeviceToHost, s));
     PA_HIP_TRY(hipMemcpyAsync(&max_degree, key_b.get(), 4, hipMemcpyDeviceToHost, s));

@@ -13,8 +13,8 @@
 // everything from 0x20 on (but 0x7f) copied — bytes from 0x80 on too: the few non-printable code points beyond ASCII (U+0085, U+00A0 ...),
 // which Rust prints as \u{..}, are copied as they are (documented limitation).
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_scan.hpp>
 
+#include "device_prims.hpp"
 #include "kernels.hpp"
 #include "pa_common.hpp"
 
@@ -155,9 +155,7 @@ __global__ __launch_bounds__(256) void pa_render_write_kernel(const RenderArgs a
 
 // bytes of rocPRIM scratch the scan over n + 1 lengths needs
 size_t render_scan_bytes(uint64_t n) {
-    size_t bytes = 0;
-    (void)rocprim::exclusive_scan(nullptr, bytes, (const uint32_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), (hipStream_t) nullptr);
-    return bytes;
+    return prim_bytes([&](void* t, size_t& b) { return scan_exclusive_on(t, b, (const uint32_t*)nullptr, (uint64_t*)nullptr, (size_t)(n + 1), nullptr); });
 }
 
 // lengths + offsets of the tuples of a finished batch: d_len[n + 1], d_off[n + 1] (d_off[n] = bytes of the whole text), *d_flagged += flagged reads
@@ -168,7 +166,7 @@ int launch_render_len(const pa_read_result* d_results, const uint32_t* d_arena, 
     hipLaunchKernelGGL(pa_render_len_kernel, dim3((uint32_t)((n + 1 + 255) / 256)), dim3(256), 0, stream, a, d_len, d_flagged);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
-    e = rocprim::exclusive_scan(d_tmp, tmp_bytes, (const uint32_t*)d_len, d_off, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), stream);
+    e = scan_exclusive_on(d_tmp, tmp_bytes, (const uint32_t*)d_len, d_off, (size_t)(n + 1), stream);
     return (int)e;
 }
 
