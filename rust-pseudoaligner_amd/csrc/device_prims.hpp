@@ -19,8 +19,12 @@
 
 namespace pa {
 
-// blocks of `block` threads that cover n items
-inline uint32_t grid_for(uint64_t n, uint32_t block = 256) { return (uint32_t)((n + block - 1) / block); }
+// blocks of `block` threads that cover n items; 0 when that count does not fit 32 bits (a launch of no blocks fails, where a count cut
+// to its low 32 bits would run a small grid over the first few items and say nothing)
+inline uint32_t grid_for(uint64_t n, uint32_t block = 256) {
+    const uint64_t blocks = n / block + (n % block != 0);
+    return blocks > 0xFFFFFFFFull ? 0u : (uint32_t)blocks;
+}
 
 // bits that hold 0..max_value: 0 for 0, 64 at most (a radix sort wants at least one: std::max(1u, bits_for(v)))
 inline uint32_t bits_for(uint64_t max_value) {

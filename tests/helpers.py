@@ -1,5 +1,5 @@
 """Test-side plumbing: loads the product package, and wraps the two CHECKERS (oracle/ C restatement, tests/emu lane
-emulator) with ctypes. Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg use this module."""
+emulator) and the probe of csrc/device_prims.hpp (tests/prims) with ctypes. Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg use this module."""
 from __future__ import annotations
 
 import ctypes as C
@@ -28,11 +28,12 @@ def _load_recipe(path, name):
 
 _oracle_build = _load_recipe(ROOT / "oracle" / "build.py", "pa_oracle_build")
 _emu_build = _load_recipe(ROOT / "tests" / "emu" / "build.py", "pa_emu_build")
+_prims_build = _load_recipe(ROOT / "tests" / "prims" / "build.py", "pa_prims_build")
 
 
 def build_all(force: bool = False):
-    """product (hipcc, gfx950) + the two checkers (gcc / g++)"""
-    return _build.build_product(force), _oracle_build.build_oracle(force), _emu_build.build_emu(force)
+    """product (hipcc, gfx950) + the two checkers (gcc / g++) + the device_prims probe (hipcc, gfx950)"""
+    return _build.build_product(force), _oracle_build.build_oracle(force), _emu_build.build_emu(force), _prims_build.build_probe(force)
 
 GOLDEN = ROOT / "tests" / "golden"
 FASTA = GOLDEN / "gencode_small.fa"
@@ -52,6 +53,7 @@ class Counters(C.Structure):
 
 _oracle_lib = None
 _emu_lib = None
+_prims_lib = None
 
 
 def oracle_lib():
@@ -93,6 +95,36 @@ def emu_lib():
         L.emu_free.argtypes = [C.c_void_p]
         _emu_lib = L
     return _emu_lib
+
+
+def prims_lib():
+    """tests/prims/prims_probe.hip: one export per instantiation of csrc/device_prims.hpp the product makes (host arrays in and out)"""
+    global _prims_lib
+    if _prims_lib is None:
+        L = C.CDLL(str(_prims_build.build_probe()))
+        vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
+        L.probe_last_error.restype = C.c_char_p
+        L.probe_bits_for.restype = L.probe_grid_for.restype = L.probe_grid_for_default.restype = u32
+        L.probe_bits_for.argtypes = [u64]
+        L.probe_grid_for.argtypes = [u64, u32]
+        L.probe_grid_for_default.argtypes = [u64]
+        L.probe_tmp_new.restype = vp
+        L.probe_tmp_free.argtypes = [vp]
+        L.probe_tmp_size.restype = u64
+        L.probe_tmp_size.argtypes = [vp]
+        L.probe_sort_keys_ull_int.argtypes = [vp, vp, vp, u64, u32, u32]
+        for name in ("ull_u32_int", "u32_u32_size", "u64_u32_size", "ull_u32_size", "u128_u32_size", "desc_u32_u32_size"):
+            getattr(L, "probe_sort_pairs_" + name).argtypes = [vp, vp, vp, vp, vp, u64, u32, u32]
+        for name in ("inclusive_u32_u32", "exclusive_u32_u32", "exclusive_ull_ull"):
+            getattr(L, "probe_scan_" + name).argtypes = [vp, vp, vp, u64]
+        for name in ("u32_u32", "u32_u64"):
+            getattr(L, "probe_scan_exclusive_on_" + name).argtypes = [vp, vp, u64, vp, u64, u64, vp]
+        L.probe_run_length_encode_ull.argtypes = [vp, vp, u64, vp, vp, u64, vp]
+        L.probe_reduce_by_key_sum_ull_u32.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp]
+        L.probe_select_flagged_indices_u32.argtypes = [vp, vp, u64, vp, u64, vp]
+        L.probe_chain.argtypes = [vp, vp, u64, vp, vp, vp, vp, u64, u32, vp, vp, u64, vp, vp]
+        _prims_lib = L
+    return _prims_lib
 
 
 def pack_read(seq: str) -> np.ndarray:

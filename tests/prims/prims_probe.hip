@@ -1,0 +1,243 @@
+// Test-only probe of csrc/device_prims.hpp (tests/test_gpu_prims.py; never linked into the product): one extern "C" function per
+// wrapper instantiation THE PRODUCT MAKES, with key, value and count types exactly as at the call sites. Every function takes host
+// arrays, uploads them (the outputs too: whatever pattern the caller filled them with is what an element the wrapper does not write
+// still holds afterwards), calls the wrapper on the caller's `tmp` (probe_tmp_new), synchronises, downloads, and returns the wrapper's
+// status. An output of a sort or a scan of n elements has n + PROBE_GUARD elements, so that a write past the end shows
+// (and n = 0 still has something to look at); the outputs of the run and selection entries have `cap` elements.
+//
+// The instantiations, by call site (ull = unsigned long long, u64 = uint64_t = unsigned long: two types to the compiler):
+//   sort_keys<ull, int>                       barcode_counts.hip:66, :447, :514
+//   sort_pairs<ull, u32, int>                 barcode_counts.hip:474, :500
+//   sort_pairs<u32, u32, size_t>              quant.hip:348; index_build.hip:525
+//   sort_pairs<u64, u32, size_t>              index_build.hip:379 (k <= 32)
+//   sort_pairs<u128, u32, size_t>             index_build.hip:379 (k > 32)
+//   sort_pairs<ull, u32, size_t>              index_build.hip:413
+//   sort_pairs_desc<u32, u32, size_t>         quant.hip:330, :352
+//   scan_inclusive<u32, u32>                  barcode_counts.hip:487; index_build.hip:391, :417
+//   scan_exclusive<u32, u32>                  quant.hip:340
+//   scan_exclusive<ull, ull>                  index_build.hip:441, :535
+//   scan_exclusive_on<u32, u32> + prim_bytes  fastq_scan.hip:165, :179
+//   scan_exclusive_on<u32, u64> + prim_bytes  render.hip:158, :169; compact.hip:59, :89
+//   run_length_encode<ull>                    barcode_counts.hip:67, :448, :484, :514
+//   reduce_by_key_sum<ull, u32>               barcode_counts.hip:475, :501
+//   select_flagged_indices<u32>               index_build.hip:507, :508
+//   bits_for                                  barcode_counts.hip:346; quant.hip:348
+//   grid_for                                  every launch of the three; block 256 and (barcode_counts.hip) CELL_BLOCK
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <string>
+
+#include "../../rust-pseudoaligner_amd/csrc/device_prims.hpp"
+
+// the two symbols of the host runtime the header needs (the product has them in host_index.cpp)
+namespace pa {
+std::string& last_error_ref() {
+    static thread_local std::string s;
+    return s;
+}
+int fail(int code, const char* fmt, ...) {
+    char buf[1024];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    last_error_ref() = buf;
+    return code;
+}
+}  // namespace pa
+
+using namespace pa;
+typedef unsigned long long ull;
+typedef DeviceBuffer<uint8_t> Tmp;
+constexpr uint64_t PROBE_GUARD = 4;
+
+namespace {
+
+// n elements of T in HBM holding a copy of h[0 .. n) (at least one element is allocated, so that n == 0 still gives a pointer)
+template <class T>
+struct Dev {
+    DeviceBuffer<T> b;
+    size_t n = 0;
+    int up(const T* h, size_t count) {
+        n = count;
+        const int e = b.alloc(std::max<size_t>(count, 1));
+        if (e != PA_OK) return e;
+        if (count) PA_HIP_TRY(hipMemcpy(b.get(), h, count * sizeof(T), hipMemcpyHostToDevice));
+        return PA_OK;
+    }
+    int down(T* h) const {
+        if (n) PA_HIP_TRY(hipMemcpy(h, b.get(), n * sizeof(T), hipMemcpyDeviceToHost));
+        return PA_OK;
+    }
+    T* get() const { return b.get(); }
+};
+
+int sync() {
+    PA_HIP_TRY(hipStreamSynchronize(nullptr));
+    return PA_OK;
+}
+
+#define TRY(x) do { const int e_ = (x); if (e_ != PA_OK) return e_; } while (0)
+
+template <class K, class N>
+int do_sort_keys(Tmp* tmp, const K* in, K* out, uint64_t n, uint32_t b0, uint32_t b1) {
+    Dev<K> din, dout;
+    TRY(din.up(in, n)); TRY(dout.up(out, n + PROBE_GUARD));
+    TRY(sort_keys(nullptr, *tmp, (const K*)din.get(), dout.get(), (N)n, b0, b1));
+    TRY(sync());
+    return dout.down(out);
+}
+
+template <class K, class V, class N, bool DESC>
+int do_sort_pairs(Tmp* tmp, const K* kin, K* kout, const V* vin, V* vout, uint64_t n, uint32_t b0, uint32_t b1) {
+    Dev<K> dki, dko;
+    Dev<V> dvi, dvo;
+    TRY(dki.up(kin, n)); TRY(dko.up(kout, n + PROBE_GUARD)); TRY(dvi.up(vin, n)); TRY(dvo.up(vout, n + PROBE_GUARD));
+    if (DESC) TRY(sort_pairs_desc(nullptr, *tmp, (const K*)dki.get(), dko.get(), (const V*)dvi.get(), dvo.get(), (N)n, b0, b1));
+    else TRY(sort_pairs(nullptr, *tmp, (const K*)dki.get(), dko.get(), (const V*)dvi.get(), dvo.get(), (N)n, b0, b1));
+    TRY(sync());
+    TRY(dko.down(kout));
+    return dvo.down(vout);
+}
+
+template <class In, class Out, bool INCLUSIVE>
+int do_scan(Tmp* tmp, const In* in, Out* out, uint64_t n) {
+    Dev<In> din;
+    Dev<Out> dout;
+    TRY(din.up(in, n)); TRY(dout.up(out, n + PROBE_GUARD));
+    if (INCLUSIVE) TRY(scan_inclusive(nullptr, *tmp, (const In*)din.get(), dout.get(), (size_t)n));
+    else TRY(scan_exclusive(nullptr, *tmp, (const In*)din.get(), dout.get(), (size_t)n));
+    TRY(sync());
+    return dout.down(out);
+}
+
+// scan_exclusive_on as compact.hip uses it: the scratch is prim_bytes(...) bytes at `offset` of a block the caller owns. block[0 ..
+// block_bytes) goes up and comes back, *need = what prim_bytes said. PA_ERR_INVALID_ARG when the carve does not fit the block.
+template <class In, class Out>
+int do_scan_on(const In* in, Out* out, uint64_t n, uint8_t* block, uint64_t block_bytes, uint64_t offset, uint64_t* need) {
+    const size_t bytes = prim_bytes([&](void* t, size_t& b) { return scan_exclusive_on(t, b, (const In*)nullptr, (Out*)nullptr, (size_t)n, nullptr); });
+    *need = bytes;
+    if (offset + bytes > block_bytes) return fail(PA_ERR_INVALID_ARG, "a carve of %zu bytes at %llu does not fit %llu", bytes, (ull)offset, (ull)block_bytes);
+    Dev<In> din;
+    Dev<Out> dout;
+    Dev<uint8_t> dblock;
+    TRY(din.up(in, n)); TRY(dout.up(out, n + PROBE_GUARD)); TRY(dblock.up(block, block_bytes));
+    size_t given = bytes;
+    PA_HIP_TRY(scan_exclusive_on(dblock.get() + offset, given, (const In*)din.get(), dout.get(), (size_t)n, nullptr));
+    TRY(sync());
+    TRY(dout.down(out));
+    return dblock.down(block);
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* probe_last_error(void) { return last_error_ref().c_str(); }
+int probe_device_count(void) {
+    int n = 0;
+    return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
+}
+
+// ---- host-side helpers of the header ----
+uint32_t probe_bits_for(uint64_t v) { return bits_for(v); }
+uint32_t probe_grid_for(uint64_t n, uint32_t block) { return grid_for(n, block); }
+uint32_t probe_grid_for_default(uint64_t n) { return grid_for(n); }
+uint64_t probe_guard(void) { return PROBE_GUARD; }
+
+// ---- the scratch buffer of a chain of operations ----
+void* probe_tmp_new(void) { return new Tmp(); }
+void probe_tmp_free(void* t) { delete static_cast<Tmp*>(t); }
+uint64_t probe_tmp_size(void* t) { return static_cast<Tmp*>(t)->size(); }
+
+// ---- sorts ----
+int probe_sort_keys_ull_int(void* t, const ull* in, ull* out, uint64_t n, uint32_t b0, uint32_t b1) { return do_sort_keys<ull, int>(static_cast<Tmp*>(t), in, out, n, b0, b1); }
+int probe_sort_pairs_ull_u32_int(void* t, const ull* ki, ull* ko, const uint32_t* vi, uint32_t* vo, uint64_t n, uint32_t b0, uint32_t b1) {
+    return do_sort_pairs<ull, uint32_t, int, false>(static_cast<Tmp*>(t), ki, ko, vi, vo, n, b0, b1);
+}
+int probe_sort_pairs_u32_u32_size(void* t, const uint32_t* ki, uint32_t* ko, const uint32_t* vi, uint32_t* vo, uint64_t n, uint32_t b0, uint32_t b1) {
+    return do_sort_pairs<uint32_t, uint32_t, size_t, false>(static_cast<Tmp*>(t), ki, ko, vi, vo, n, b0, b1);
+}
+int probe_sort_pairs_u64_u32_size(void* t, const uint64_t* ki, uint64_t* ko, const uint32_t* vi, uint32_t* vo, uint64_t n, uint32_t b0, uint32_t b1) {
+    return do_sort_pairs<uint64_t, uint32_t, size_t, false>(static_cast<Tmp*>(t), ki, ko, vi, vo, n, b0, b1);
+}
+int probe_sort_pairs_ull_u32_size(void* t, const ull* ki, ull* ko, const uint32_t* vi, uint32_t* vo, uint64_t n, uint32_t b0, uint32_t b1) {
+    return do_sort_pairs<ull, uint32_t, size_t, false>(static_cast<Tmp*>(t), ki, ko, vi, vo, n, b0, b1);
+}
+// (keys as 16 bytes each, low word first)
+int probe_sort_pairs_u128_u32_size(void* t, const void* ki, void* ko, const uint32_t* vi, uint32_t* vo, uint64_t n, uint32_t b0, uint32_t b1) {
+    return do_sort_pairs<u128, uint32_t, size_t, false>(static_cast<Tmp*>(t), static_cast<const u128*>(ki), static_cast<u128*>(ko), vi, vo, n, b0, b1);
+}
+int probe_sort_pairs_desc_u32_u32_size(void* t, const uint32_t* ki, uint32_t* ko, const uint32_t* vi, uint32_t* vo, uint64_t n, uint32_t b0, uint32_t b1) {
+    return do_sort_pairs<uint32_t, uint32_t, size_t, true>(static_cast<Tmp*>(t), ki, ko, vi, vo, n, b0, b1);
+}
+
+// ---- scans ----
+int probe_scan_inclusive_u32_u32(void* t, const uint32_t* in, uint32_t* out, uint64_t n) { return do_scan<uint32_t, uint32_t, true>(static_cast<Tmp*>(t), in, out, n); }
+int probe_scan_exclusive_u32_u32(void* t, const uint32_t* in, uint32_t* out, uint64_t n) { return do_scan<uint32_t, uint32_t, false>(static_cast<Tmp*>(t), in, out, n); }
+int probe_scan_exclusive_ull_ull(void* t, const ull* in, ull* out, uint64_t n) { return do_scan<ull, ull, false>(static_cast<Tmp*>(t), in, out, n); }
+int probe_scan_exclusive_on_u32_u32(const uint32_t* in, uint32_t* out, uint64_t n, uint8_t* block, uint64_t block_bytes, uint64_t offset, uint64_t* need) {
+    return do_scan_on<uint32_t, uint32_t>(in, out, n, block, block_bytes, offset, need);
+}
+int probe_scan_exclusive_on_u32_u64(const uint32_t* in, uint64_t* out, uint64_t n, uint8_t* block, uint64_t block_bytes, uint64_t offset, uint64_t* need) {
+    return do_scan_on<uint32_t, uint64_t>(in, out, n, block, block_bytes, offset, need);
+}
+
+// ---- runs. unique / counts / sums have `cap` elements (>= the runs the caller expects; what lies behind them must stay as it was);
+// *runs goes up as the caller set it and comes back as the wrapper left it ----
+int probe_run_length_encode_ull(void* t, const ull* in, uint64_t n, ull* unique, uint32_t* counts, uint64_t cap, uint32_t* runs) {
+    Dev<ull> din, du;
+    Dev<uint32_t> dc, dr;
+    TRY(din.up(in, n)); TRY(du.up(unique, cap)); TRY(dc.up(counts, cap)); TRY(dr.up(runs, 1));
+    TRY(run_length_encode(nullptr, *static_cast<Tmp*>(t), (const ull*)din.get(), (size_t)n, du.get(), dc.get(), dr.get()));
+    TRY(sync());
+    TRY(du.down(unique)); TRY(dc.down(counts));
+    return dr.down(runs);
+}
+int probe_reduce_by_key_sum_ull_u32(void* t, const ull* kin, const uint32_t* vin, uint64_t n, ull* unique, uint32_t* sums, uint64_t cap, uint32_t* runs) {
+    Dev<ull> dk, du;
+    Dev<uint32_t> dv, ds, dr;
+    TRY(dk.up(kin, n)); TRY(dv.up(vin, n)); TRY(du.up(unique, cap)); TRY(ds.up(sums, cap)); TRY(dr.up(runs, 1));
+    TRY(reduce_by_key_sum(nullptr, *static_cast<Tmp*>(t), (const ull*)dk.get(), (const uint32_t*)dv.get(), (size_t)n, du.get(), ds.get(), dr.get()));
+    TRY(sync());
+    TRY(du.down(unique)); TRY(ds.down(sums));
+    return dr.down(runs);
+}
+
+// ---- selection: out has `cap` elements ----
+int probe_select_flagged_indices_u32(void* t, const uint32_t* flags, uint64_t n, uint32_t* out, uint64_t cap, uint32_t* count) {
+    Dev<uint32_t> df, dout, dc;
+    TRY(df.up(flags, n)); TRY(dout.up(out, cap)); TRY(dc.up(count, 1));
+    TRY(select_flagged_indices(nullptr, *static_cast<Tmp*>(t), (const uint32_t*)df.get(), (size_t)n, dout.get(), dc.get()));
+    TRY(sync());
+    TRY(dout.down(out));
+    return dc.down(count);
+}
+
+// ---- a chain on one tmp, queued back to back as the product queues them (no synchronisation between the steps: growing tmp while
+// the step before may still run is the header's claim): exclusive scan of small_in -> scan1, sort of keys over [0, end_bit) -> sorted,
+// the same scan -> scan2, run-length encode of `sorted` -> (unique, counts)[cap], *runs. sizes[j] = tmp.size() after step j ----
+int probe_chain(void* t, const uint32_t* small_in, uint64_t small_n, uint32_t* scan1, uint32_t* scan2, const ull* keys, ull* sorted, uint64_t n, uint32_t end_bit,
+                ull* unique, uint32_t* counts, uint64_t cap, uint32_t* runs, uint64_t sizes[4]) {
+    Tmp& tmp = *static_cast<Tmp*>(t);
+    Dev<uint32_t> dsi, ds1, ds2, dc, dr;
+    Dev<ull> dk, dso, du;
+    TRY(dsi.up(small_in, small_n)); TRY(ds1.up(scan1, small_n + PROBE_GUARD)); TRY(ds2.up(scan2, small_n + PROBE_GUARD)); TRY(dk.up(keys, n)); TRY(dso.up(sorted, n + PROBE_GUARD));
+    TRY(du.up(unique, cap)); TRY(dc.up(counts, cap)); TRY(dr.up(runs, 1));
+    TRY(scan_exclusive(nullptr, tmp, (const uint32_t*)dsi.get(), ds1.get(), (size_t)small_n));
+    sizes[0] = tmp.size();
+    TRY(sort_keys(nullptr, tmp, (const ull*)dk.get(), dso.get(), (int)n, 0, end_bit));
+    sizes[1] = tmp.size();
+    TRY(scan_exclusive(nullptr, tmp, (const uint32_t*)dsi.get(), ds2.get(), (size_t)small_n));
+    sizes[2] = tmp.size();
+    TRY(run_length_encode(nullptr, tmp, (const ull*)dso.get(), (size_t)n, du.get(), dc.get(), dr.get()));
+    sizes[3] = tmp.size();
+    TRY(sync());
+    TRY(ds1.down(scan1)); TRY(ds2.down(scan2)); TRY(dso.down(sorted)); TRY(du.down(unique)); TRY(dc.down(counts));
+    return dr.down(runs);
+}
+
+}  // extern "C"
