@@ -496,6 +496,37 @@ int  pa_quant_stats(const pa_quant* q, uint64_t stats[PA_QUANT_STATS]);
 int  pa_write_abundance_tsv(const pa_quant* q, const char* path);   /* header + "target_id\tlength\teff_length\test_counts\ttpm", doubles as pa_write_mappability_tsv prints them */
 void pa_quant_destroy(pa_quant* q);
 
+/* ---------------- bootstrap replicates: resampled EM runs, batched on the GPU ----------------
+ * A replicate resamples the N reads of the last pa_quant_set_counts with replacement and runs the EM above on the resampled counts;
+ * the spread of a transcript's estimates over the replicates is its inferential variance (kallisto -b, salmon --numBootstraps).
+ *   reads    numbered 0 .. N-1 in candidate order: the index classes ascending, then the overflow records in record order; candidate i
+ *            owns reads [cum_i, cum_i + n_i); a candidate without entries or without reads owns none
+ *   draw j of replicate b (b: a global u32 replicate number, j < N): block i = j >> 1 of Philox4x32-10 with the counter
+ *            (lo32(i), hi32(i), b, 0) and the key (lo32(seed), hi32(seed)) gives o0..o3; an even j takes x = o0 | o1 << 32, an odd j
+ *            x = o2 | o3 << 32; the read picked is p = (x * N) >> 64 (the high half of the 128-bit product); n_r^(b) = the number of
+ *            draws whose pick lies in candidate r's interval. All integer: any implementation gives the same counts bit for bit.
+ *            Philox4x32-10 known answers (Random123), counter / key -> output:
+ *              0 0 0 0 / 0 0                                         -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8
+ *              ffffffff x4 / ffffffff x2                             -> 408f276d 41c83b0e a20bc7c6 6d5451fd
+ *              243f6a88 85a308d3 13198a2e 03707344 / a4093822 299f31d0 -> d16cfe09 94fdcceb 5001e420 24126ea1
+ *   limits   N >= 2^32 is PA_ERR_UNSUPPORTED for the bootstrap; N = 0 is legal: all counts 0, no iteration, every output 0
+ *   EM       per replicate the rules above. Rows are the rows of the original table: a row whose resampled count is 0 stays and
+ *            contributes exact zeros. Start alpha_t = N / T for the transcripts that occur in a row of the original table, 0 otherwise.
+ *            Iteration, stop rule and truncation are those of pa_quant_run, per replicate: a replicate stops at the first checked
+ *            iteration at which its own rule holds and is frozen from then on (no longer read-modified, whatever the others still do)
+ *   independence   what replicate b yields (counts, every iterate, its iteration count) depends on (table, params, seed, b) alone: not
+ *            on first, n or the other replicates of its batch; two runs give the same bits
+ * The batch is extra state of the object: made by pa_quant_bootstrap_draw, dropped by pa_quant_set_counts; alpha, pa_quant_step,
+ * pa_quant_run, pa_quant_stats and every other output above never see it. n == 0, n > PA_QUANT_BOOT_MAX_BATCH, first + n beyond 2^32,
+ * k >= n: PA_ERR_INVALID_ARG; counts, step, run or fetch without a drawn batch: PA_ERR_INVALID_ARG ("no bootstrap batch drawn"). */
+#define PA_QUANT_BOOT_MAX_BATCH 64
+int  pa_quant_bootstrap_draw(pa_quant* q, uint64_t seed, uint32_t first, uint32_t n);       /* replicates first .. first+n-1: resample, alpha to the start */
+int  pa_quant_bootstrap_counts(const pa_quant* q, uint32_t k, uint64_t* class_counts, uint64_t counts_len,
+                               uint64_t* overflow_counts, uint64_t n_records);              /* k-th replicate of the batch as a table pa_quant_set_counts accepts: slot num_classes = sum of its overflow counts, the two other tail slots 0; overflow_counts in record order (n_records = the records of the table set), may be NULL when n_records is 0 */
+int  pa_quant_bootstrap_step(pa_quant* q, uint32_t n_iters);                                /* every replicate, exactly n iterations, no stop rule, no freeze */
+int  pa_quant_bootstrap_run(pa_quant* q, uint32_t* iters, int* converged);                  /* [n] each, either may be NULL */
+int  pa_quant_bootstrap_fetch(const pa_quant* q, double* est_counts, double* tpm);          /* [n][T] replicate-major; current alpha; tpm by the rule above per replicate; either may be NULL */
+
 /* ---------------- novel classes + the reduction over GPUs ---------------- */
 /* The dense table counts every result that is no index class in ONE slot (counts[num_classes]). A pa_overflow keeps WHICH
  * id sets those were, keyed by content, on the GPU: attach one to an index and every pa_map_count_batch_device launch files

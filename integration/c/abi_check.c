@@ -133,6 +133,9 @@ int main(int argc, char** argv) {
         EXPECT(pa_quant_alpha(NULL, qd) == PA_ERR_INVALID_ARG && pa_quant_fetch(NULL, qd, NULL, NULL) == PA_ERR_INVALID_ARG);
         EXPECT(pa_quant_fetch_genes(NULL, qd, NULL) == PA_ERR_INVALID_ARG && pa_quant_stats(NULL, qst) == PA_ERR_INVALID_ARG);
         EXPECT(pa_write_abundance_tsv(NULL, path) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_quant_bootstrap_draw(NULL, 1, 0, 1) == PA_ERR_INVALID_ARG && pa_quant_bootstrap_counts(NULL, 0, counts, counts_len, NULL, 0) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_quant_bootstrap_step(NULL, 1) == PA_ERR_INVALID_ARG && pa_quant_bootstrap_run(NULL, &qit, &qconv) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_quant_bootstrap_fetch(NULL, qd, NULL) == PA_ERR_INVALID_ARG && PA_QUANT_BOOT_MAX_BATCH == 64);
         pa_quant_destroy(NULL);
     }
 
@@ -416,6 +419,32 @@ int main(int argc, char** argv) {
             EXPECT(sum > 0.999 * (double)qst[5] && sum < 1.001 * (double)qst[5] && tsum > 999999.0 && tsum < 1000001.0);
             snprintf(path, sizeof path, "%s/abi_check_abundance.tsv", dir);
             EXPECT(pa_write_abundance_tsv(qq, path) == PA_OK);
+            {   /* three bootstrap replicates of that table: each a table of its own with the reads of the original, each run to its own stop */
+                uint64_t* bc = (uint64_t*)calloc(counts_len, 8);
+                double* be = (double*)calloc(3 * (size_t)ntx, 8), *bt = (double*)calloc(3 * (size_t)ntx, 8);
+                uint32_t bit[3] = {0, 0, 0};
+                int bconv[3] = {0, 0, 0};
+                EXPECT(pa_quant_bootstrap_fetch(qq, be, bt) == PA_ERR_INVALID_ARG && pa_quant_bootstrap_step(qq, 1) == PA_ERR_INVALID_ARG);   /* no batch drawn */
+                EXPECT(pa_quant_bootstrap_draw(qq, 7, 0, 0) == PA_ERR_INVALID_ARG && pa_quant_bootstrap_draw(qq, 7, 0, PA_QUANT_BOOT_MAX_BATCH + 1) == PA_ERR_INVALID_ARG);
+                EXPECT(pa_quant_bootstrap_draw(qq, 7, 0xFFFFFFFEu, 3) == PA_ERR_INVALID_ARG);
+                EXPECT(pa_quant_bootstrap_draw(qq, 7, 0, 3) == PA_OK);
+                EXPECT(pa_quant_bootstrap_counts(qq, 3, bc, counts_len, NULL, 0) == PA_ERR_INVALID_ARG);
+                for (uint32_t k = 0; k < 3; ++k) {
+                    uint64_t bsum = 0;
+                    EXPECT(pa_quant_bootstrap_counts(qq, k, bc, counts_len, NULL, 0) == PA_OK);
+                    for (uint64_t i = 0; i < counts_len; ++i) bsum += bc[i];
+                    EXPECT(bsum == qst[5]);
+                }
+                EXPECT(pa_quant_bootstrap_step(qq, 2) == PA_OK && pa_quant_bootstrap_run(qq, bit, bconv) == PA_OK);
+                EXPECT(pa_quant_bootstrap_fetch(qq, be, bt) == PA_OK);
+                for (uint32_t k = 0; k < 3; ++k) {
+                    double bs = 0.0, bts = 0.0;
+                    for (uint32_t t = 0; t < ntx; ++t) { bs += be[(size_t)k * ntx + t]; bts += bt[(size_t)k * ntx + t]; }
+                    EXPECT(bit[k] >= 1 && bit[k] <= qp.max_iters && bs > 0.999 * (double)qst[5] && bs < 1.001 * (double)qst[5] && bts > 999999.0 && bts < 1000001.0);
+                }
+                EXPECT(pa_quant_fetch(qq, qa, NULL, NULL) == PA_OK && memcmp(qa, qe, (size_t)ntx * 8) == 0);   /* the point estimate did not move */
+                free(bc); free(be); free(bt);
+            }
             pa_quant_destroy(qq);
             free(qa); free(qe); free(qt); free(ql); free(ge); free(gt);
         }

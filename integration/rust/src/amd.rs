@@ -225,6 +225,35 @@ pub fn quantify(idx: *mut PaIndex, h: *const PaHostIndex, class_counts: &[u64], 
     result
 }
 
+/// Bootstrap replicates of `quantify` (pa_quant_bootstrap_*): `n` resampled EM runs of the same table, batched on the GPU in groups of
+/// at most `batch` (1 ..= PA_QUANT_BOOT_MAX_BATCH). Replicate b depends on (table, seed, b) alone, so any batch size gives the same bits.
+/// Returns est_counts replicate-major (`n * num_transcripts`) and the iterations of every replicate.
+pub fn quantify_bootstrap(idx: *mut PaIndex, h: *const PaHostIndex, class_counts: &[u64], overflow_words: Option<&[u32]>, mean_read_len: f64,
+                          n: u32, seed: u64, batch: u32) -> Result<(Vec<f64>, Vec<u32>), Error> {
+    use crate::amd_quant_ffi::*;
+    let mut p: PaQuantParams = unsafe { std::mem::zeroed() };
+    unsafe { pa_quant_default_params(&mut p) };
+    p.mean_read_len = mean_read_len;
+    let mut q = std::ptr::null_mut();
+    check(unsafe { pa_quant_create(idx, h, &p, &mut q) })?;
+    let t = unsafe { pa_host_index_num_transcripts(h) } as usize;
+    let (mut est, mut iters) = (vec![0f64; n as usize * t], vec![0u32; n as usize]);
+    let (words, n_words) = match overflow_words { Some(w) => (w.as_ptr(), w.len() as u64), None => (std::ptr::null(), 0) };
+    let mut rc = unsafe { pa_quant_set_counts(q, class_counts.as_ptr(), class_counts.len() as u64, words, n_words) };
+    let batch = batch.clamp(1, PA_QUANT_BOOT_MAX_BATCH);
+    let mut first = 0u32;
+    while rc >= 0 && first < n {
+        let m = batch.min(n - first);
+        rc = unsafe { pa_quant_bootstrap_draw(q, seed, first, m) };
+        if rc >= 0 { rc = unsafe { pa_quant_bootstrap_run(q, iters[first as usize..].as_mut_ptr(), std::ptr::null_mut()) }; }
+        if rc >= 0 { rc = unsafe { pa_quant_bootstrap_fetch(q, est[first as usize * t..].as_mut_ptr(), std::ptr::null_mut()) }; }
+        first += m;
+    }
+    let result = check(rc).map(|_| (est, iters));
+    unsafe { pa_quant_destroy(q) };
+    result
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // Drop-in entry points with the reference's EXACT signatures. The GPU copy of an index is made on first use and cached by the
 // CONTENT of the `Pseudoaligner`: k, node / class / transcript counts and a fingerprint of EVERY base of every node, every node's

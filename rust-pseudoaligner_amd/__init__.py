@@ -566,6 +566,7 @@ class Quantifier:
         self.params = p
         self._aligner, self._host = aligner, host_index   # the index outlives the quantifier
         self.num_transcripts = host_index.num_transcripts if host_index is not None else 0
+        self._counts_len, self._n_records, self._boot_n = 0, 0, 0
         check(lib().pa_quant_create(aligner._h if aligner is not None else None, host_index._h if host_index is not None else None, C.byref(p),
                                     C.byref(self._h)))
 
@@ -577,6 +578,7 @@ class Quantifier:
         else:
             w = np.ascontiguousarray(overflow, np.uint32)
             check(lib().pa_quant_set_counts(self._h, cc.ctypes.data, len(cc), w.ctypes.data, len(w)))
+        self._counts_len, self._n_records, self._boot_n = len(cc), (int(w[0]) if overflow is not None else 0), 0   # what the bootstrap calls size their arrays by
 
     def step(self, n_iters: int = 1) -> None:
         check(lib().pa_quant_step(self._h, n_iters))
@@ -614,6 +616,45 @@ class Quantifier:
 
     def write_tsv(self, path: str) -> None:
         check(lib().pa_write_abundance_tsv(self._h, str(path).encode()))
+
+    # ---- bootstrap replicates (pa_quant_bootstrap_*): a batch of at most PA_QUANT_BOOT_MAX_BATCH resampled EM runs ----
+    def bootstrap_draw(self, seed: int, first: int, n: int) -> None:
+        """resample replicates first .. first + n - 1 of the table last set; their alpha goes to the start"""
+        check(lib().pa_quant_bootstrap_draw(self._h, seed, first, n))
+        self._boot_n = n
+
+    def bootstrap_counts(self, k: int) -> Tuple[np.ndarray, np.ndarray]:
+        """the k-th replicate of the batch -> (class_counts u64[counts_len], overflow counts u64[records] in record order)"""
+        cc = np.zeros(self._counts_len, np.uint64)
+        oc = np.zeros(max(self._n_records, 1), np.uint64)
+        check(lib().pa_quant_bootstrap_counts(self._h, k, cc.ctypes.data, len(cc), oc.ctypes.data if self._n_records else None, self._n_records))
+        return cc, oc[: self._n_records]
+
+    def bootstrap_step(self, n_iters: int = 1) -> None:
+        check(lib().pa_quant_bootstrap_step(self._h, n_iters))
+
+    def bootstrap_run(self) -> Tuple[np.ndarray, np.ndarray]:
+        """the stop rule per replicate -> (iterations u32[n], converged bool[n])"""
+        it, conv = np.zeros(self._boot_n, np.uint32), np.zeros(self._boot_n, np.int32)
+        check(lib().pa_quant_bootstrap_run(self._h, it.ctypes.data, conv.ctypes.data))
+        return it, conv.astype(bool)
+
+    def bootstrap_fetch(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(est_counts, tpm), each [n, num_transcripts]"""
+        est, tpm = (np.zeros((self._boot_n, self.num_transcripts), np.float64) for _ in range(2))
+        check(lib().pa_quant_bootstrap_fetch(self._h, est.ctypes.data, tpm.ctypes.data))
+        return est, tpm
+
+    def bootstrap(self, n: int, seed: int, batch: int = 32, run: bool = True) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """replicates 0 .. n - 1 in batches of `batch` -> (est_counts[n, T], iters[n], converged[n]); run=False: the start, no iteration"""
+        est, iters, conv = np.zeros((n, self.num_transcripts)), np.zeros(n, np.uint32), np.zeros(n, bool)
+        for first in range(0, n, batch):
+            m = min(batch, n - first)
+            self.bootstrap_draw(seed, first, m)
+            if run:
+                iters[first:first + m], conv[first:first + m] = self.bootstrap_run()
+            est[first:first + m] = self.bootstrap_fetch()[0]
+        return est, iters, conv
 
     def __del__(self):
         try:

@@ -58,6 +58,7 @@ class QuantParams(C.Structure):
 
 
 PA_QUANT_STATS = 8
+PA_QUANT_BOOT_MAX_BATCH = 64
 QUANT_STAT_NAMES = ("rows", "ids", "transcripts_with_a_row", "longest_row", "largest_degree", "reads_used", "novel_reads_left_out", "iterations")
 
 
@@ -148,6 +149,11 @@ SIGNATURES = {
     "pa_quant_stats": (C.c_int, [vp, vp]),
     "pa_write_abundance_tsv": (C.c_int, [vp, C.c_char_p]),
     "pa_quant_destroy": (None, [vp]),
+    "pa_quant_bootstrap_draw": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "pa_quant_bootstrap_counts": (C.c_int, [vp, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64]),
+    "pa_quant_bootstrap_step": (C.c_int, [vp, C.c_uint32]),
+    "pa_quant_bootstrap_run": (C.c_int, [vp, vp, vp]),
+    "pa_quant_bootstrap_fetch": (C.c_int, [vp, vp, vp]),
     "pa_overflow_create": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.POINTER(vp)]),
     "pa_overflow_destroy": (None, [vp]),
     "pa_overflow_reset": (C.c_int, [vp, vp]),

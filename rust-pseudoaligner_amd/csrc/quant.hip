@@ -21,21 +21,11 @@
 #include "device_prims.hpp"
 #include "hip_buffer.hpp"
 #include "pa_common.hpp"
+#include "quant_state.hpp"
 
 using namespace pa;
 
 namespace {
-
-constexpr int QB = 256;     // threads of a block
-constexpr int NBIN = 5;
-// bin k holds the rows of at least bin_min_len(k) entries that are in no earlier bin; a row of bin k is summed by bin_group(k) lanes
-__host__ __device__ constexpr uint32_t bin_min_len(int k) { return k == 0 ? 1025u : k == 1 ? 17u : k == 2 ? 9u : k == 3 ? 5u : 1u; }
-constexpr uint32_t bin_group(int k) { return k == 0 ? 256u : k == 1 ? 64u : k == 2 ? 16u : k == 3 ? 8u : 4u; }
-
-struct Layout {
-    uint32_t begin[NBIN + 1];   // rows [begin[k], begin[k + 1]) are bin k; begin[NBIN] = rows with at least one entry
-    uint32_t blk[NBIN + 1];     // blocks [blk[k], blk[k + 1]) serve bin k
-};
 
 void finish_layout(Layout& l) {
     l.blk[0] = 0;
@@ -258,29 +248,6 @@ bool params_ok(const pa_quant_params& p) {
 
 }  // namespace
 
-struct pa_quant {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    pa_quant_params par{};
-    uint32_t num_tx = 0, num_classes = 0, num_genes = 0;
-    std::vector<double> eff;
-    std::vector<uint64_t> len;
-    std::vector<uint32_t> class_len, tx_gene;
-    std::vector<std::string> names;
-    // the index classes and the effective lengths, uploaded once
-    DeviceBuffer<unsigned long long> d_ec_off;
-    DeviceBuffer<uint32_t> d_ec_ids;
-    DeviceBuffer<double> d_eff;
-    // the reduced problem of the last set_counts (ready: there is one, with at least one read)
-    bool ready = false;
-    Layout rows{}, slots{};
-    DeviceBuffer<uint32_t> d_row_off, d_row_ids, d_tx_off, d_tx_rows, d_tx_order;
-    DeviceBuffer<double> d_row_cnt, d_q, d_alpha, d_w;
-    DeviceBuffer<unsigned int> d_flag;
-    PinnedBuffer<unsigned int> h_flag;
-    uint64_t stats[PA_QUANT_STATS] = {};
-};
-
 namespace {
 
 struct OverflowRows {
@@ -306,13 +273,13 @@ int setup_device(pa_quant* q, const uint64_t* class_counts, const OverflowRows& 
     hipStream_t s = q->stream;
     const uint32_t C = q->num_classes, T = q->num_tx, n_ovf = (uint32_t)ovf.cnt.size(), NC = C + n_ovf;
     DeviceBuffer<unsigned long long> d_counts, d_ovf_cnt;
-    DeviceBuffer<uint32_t> d_ovf_src, d_ovf_len, d_words, key_a, key_b, val_a, val_b, d_bounds, d_row_cand;
+    DeviceBuffer<uint32_t> d_ovf_src, d_ovf_len, d_words, key_a, key_b, val_a, val_b, d_bounds;
     DeviceBuffer<uint8_t> tmp;
     const size_t pairs = std::max<size_t>(std::max<size_t>(NC, nnz), T) + 1;
     int e;
     if ((e = d_counts.alloc(C ? C : 1)) || (e = d_ovf_cnt.alloc(n_ovf ? n_ovf : 1)) || (e = d_ovf_src.alloc(n_ovf ? n_ovf : 1)) ||
         (e = d_ovf_len.alloc(n_ovf ? n_ovf : 1)) || (e = d_words.alloc(n_words ? n_words : 1)) || (e = key_a.alloc(pairs)) || (e = key_b.alloc(pairs)) ||
-        (e = val_a.alloc(pairs)) || (e = val_b.alloc(pairs)) || (e = d_bounds.alloc(NBIN + 1)) || (e = d_row_cand.alloc(n_rows)) ||
+        (e = val_a.alloc(pairs)) || (e = val_b.alloc(pairs)) || (e = d_bounds.alloc(NBIN + 1)) || (e = q->d_row_cand.alloc(n_rows)) ||
         (e = q->d_row_off.alloc((size_t)n_rows + 1)) || (e = q->d_row_ids.alloc(nnz)) || (e = q->d_row_cnt.alloc(n_rows)) || (e = q->d_q.alloc(n_rows)) ||
         (e = q->d_tx_off.alloc((size_t)T + 1)) || (e = q->d_tx_rows.alloc(nnz)) || (e = q->d_tx_order.alloc(T)))
         return e;
@@ -338,10 +305,10 @@ int setup_device(pa_quant* q, const uint64_t* class_counts, const OverflowRows& 
     finish_layout(q->rows);
     // row offsets (key_b holds an entry beyond NC: the scan reads n_rows + 1 lengths and its last output is nnz)
     if ((e = scan_exclusive(s, tmp, key_b.get(), q->d_row_off.get(), (size_t)n_rows + 1))) return e;
-    PA_HIP_TRY(hipMemcpyAsync(d_row_cand.get(), val_b.get(), 4ull * n_rows, hipMemcpyDeviceToDevice, s));
-    hipLaunchKernelGGL(quant_row_counts, dim3(grid_for(n_rows)), dim3(256), 0, s, n_rows, C, d_row_cand.get(), d_counts.get(), d_ovf_cnt.get(), q->d_row_cnt.get());
+    PA_HIP_TRY(hipMemcpyAsync(q->d_row_cand.get(), val_b.get(), 4ull * n_rows, hipMemcpyDeviceToDevice, s));
+    hipLaunchKernelGGL(quant_row_counts, dim3(grid_for(n_rows)), dim3(256), 0, s, n_rows, C, q->d_row_cand.get(), d_counts.get(), d_ovf_cnt.get(), q->d_row_cnt.get());
     GatherArgs g;
-    g.nnz = nnz; g.rows = n_rows; g.num_classes = C; g.row_off = q->d_row_off.get(); g.row_cand = d_row_cand.get(); g.ec_off = q->d_ec_off.get();
+    g.nnz = nnz; g.rows = n_rows; g.num_classes = C; g.row_off = q->d_row_off.get(); g.row_cand = q->d_row_cand.get(); g.ec_off = q->d_ec_off.get();
     g.ec_ids = q->d_ec_ids.get(); g.ovf_src = d_ovf_src.get(); g.words = d_words.get(); g.row_ids = q->d_row_ids.get(); g.pair_key = key_a.get(); g.pair_val = val_a.get();
     hipLaunchKernelGGL(quant_gather, dim3(grid_for(nnz)), dim3(256), 0, s, g);
     // transposed CSR: (transcript, row) pairs sorted by transcript; the sort is stable, so a transcript's rows stay ascending
@@ -500,6 +467,8 @@ int pa_quant_set_counts(pa_quant* q, const uint64_t* class_counts, uint64_t coun
     if (reads >> 53) return fail(PA_ERR_UNSUPPORTED, "%llu reads: counts of 2^53 and more are not exact in f64", (unsigned long long)reads);
     // every argument is checked: from here on the state changes
     q->ready = false;
+    q->boot.drop();   // a bootstrap batch belongs to the table it was drawn from
+    q->n_records = (uint32_t)ovf.cnt.size();
     for (uint64_t& x : q->stats) x = 0;
     q->stats[0] = n_rows;
     q->stats[1] = nnz;
