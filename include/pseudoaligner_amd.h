@@ -527,6 +527,70 @@ int  pa_quant_bootstrap_step(pa_quant* q, uint32_t n_iters);                    
 int  pa_quant_bootstrap_run(pa_quant* q, uint32_t* iters, int* converged);                  /* [n] each, either may be NULL */
 int  pa_quant_bootstrap_fetch(const pa_quant* q, double* est_counts, double* tpm);          /* [n][T] replicate-major; current alpha; tpm by the rule above per replicate; either may be NULL */
 
+/* ---------------- paired-end reads: orient the mates, intersect their classes ----------------
+ * The index is stranded: a read maps only as it lies on the transcript strand. A pair is brought into that orientation, its
+ * mates are mapped by two ordinary pa_map_batch_device launches and a stage behind them combines the two results per pair
+ * into ordinary pa_read_result records plus arena ids, which everything downstream (pa_counts_accumulate_device,
+ * pa_results_compact_device, the overflow table, pa_quant_*, the reduce over GPUs) takes as it takes reads.
+ *   orientation   PA_PAIR_FR: mate 1 as given, mate 2 reverse-complemented; PA_PAIR_RF: mate 1 reverse-complemented, mate 2 as
+ *                 given; PA_PAIR_FF: both as given; anything else is PA_ERR_INVALID_ARG
+ *   reverse complement   of the PACKED read: base j of the output is 3 - code of base len - 1 - j of the input. A byte the encoder
+ *                 packed as some code is complemented as that code (an N that became A comes out as T). Bits beyond len in the
+ *                 output words are zero, whatever the input held there; lengths are unchanged
+ *   pair result   each mate mapped as map_read_with_mismatch(allowed_mismatches) maps it (src/pseudoaligner.rs:361-376):
+ *                   both None          unmapped: mismatches bit 31 clear, coverage 0, class_len 0
+ *                   exactly one Some   that mate's class, coverage and mismatches, mapped
+ *                   both Some          ids = the sorted intersection of the two id lists (intersect, src/pseudoaligner.rs:389);
+ *                                      coverage = cov1 + cov2; mismatches = mm1 + mm2; mapped even when the intersection is empty
+ *                                      (class_len 0: counted in the table's "empty" slot)
+ *   representation   class_off carries PA_CLASS_REF only if the id list equals that index class; otherwise the ids lie ascending
+ *                 in the PAIR arena at class_off. Which of the two forms a result that equals an index class takes is not
+ *                 specified. A pair result never points into a mate's arena.
+ * pa_revcomp_tiles_device: tiles (layout above) -> tiles, NOT in place (d_tiles_out sized like d_tiles_in; the reads beyond n_reads
+ * of the last tile come out as zero words); asynchronous on stream; n_reads = 0 is a no-op.
+ * pa_pairs_combine_device: d_res1 / d_arena1 and d_res2 / d_arena2 as two finished pa_map_batch_device launches left them for mate 1
+ * and mate 2 of n_pairs pairs -> d_results[n_pairs], ids in d_arena[arena_cap] (at most PA_MAX_ARENA_ENTRIES are used). d_counts
+ * (may be NULL): u64[pa_counts_len(idx)], every pair counted once by the rule of the class-count table; with an overflow table
+ * attached to idx every result that is no index class and not empty is also filed there, so that sum(overflow record counts) ==
+ * counts[num_classes] holds for pairs as for reads. d_scratch: pa_pairs_scratch_bytes(n_pairs) bytes, 256-byte aligned; it holds the
+ * control block of the launch (nothing is kept on idx) and must stay untouched until pa_pairs_finish. Asynchronous on stream.
+ * pa_pairs_finish: synchronises the stream; PA_OK, or PA_ERR_ARENA_FULL with *arena_needed = a capacity that suffices. On a full
+ * arena no word beyond arena_cap was written and every record whose ids did not fit is recognisable: mapped, class_len > 0,
+ * class_off == PA_MAX_ARENA_ENTRIES; the pairs were all counted, but a lost result may sit in the "novel" slot whatever its content and
+ * is not filed in the overflow table, while the novel results that did fit HAVE been filed: re-run into a count table AND an attached overflow
+ * table both restored to what they held before the failed launch (or find the need with d_counts = NULL first: it does not depend on d_counts). Either output may be NULL.
+ * stats[PA_PAIR_STATS]: [0] pairs, [1] both mates mapped, [2] mate 1 only, [3] mate 2 only, [4] neither, [5] both mapped and the
+ * intersection empty, [6] results by reference, [7] results in the arena; [0] = [1] + [2] + [3] + [4] and [6] + [7] = [0] - [4] -
+ * (mapped results whose class is empty). */
+#define PA_PAIR_FR 0
+#define PA_PAIR_RF 1
+#define PA_PAIR_FF 2
+#define PA_PAIR_STATS 8
+int pa_revcomp_tiles_device(const pa_index* idx, const uint64_t* d_tiles_in, const uint32_t* d_lens, uint64_t n_reads, uint32_t words_per_read,
+                            uint64_t* d_tiles_out, void* stream);
+size_t pa_pairs_scratch_bytes(uint64_t n_pairs);
+int pa_pairs_combine_device(pa_index* idx, const pa_read_result* d_res1, const uint32_t* d_arena1, const pa_read_result* d_res2,
+                            const uint32_t* d_arena2, uint64_t n_pairs, pa_read_result* d_results, uint32_t* d_arena, uint64_t arena_cap,
+                            uint64_t* d_counts, void* d_scratch, size_t scratch_bytes, void* stream);
+int pa_pairs_finish(pa_index* idx, void* d_scratch, void* stream, uint64_t stats[PA_PAIR_STATS], uint64_t* arena_used, uint64_t* arena_needed);
+/* The paired form of pa_map_batch: mates as ASCII (concatenated, offsets[n_pairs + 1] each), encode, reverse complement by `orient`,
+ * two launches, combine, D2H; grows its arenas on PA_ERR_ARENA_FULL. Outputs as pa_map_batch returns them (class ids as a CSR in pair
+ * order, library-owned until the next pa_map_pairs call of this thread). Every argument is checked before any device call. A convenience
+ * path, not one to measure: the call makes and frees its own stream, launch context and buffers, and the two mates and the combine run one
+ * after the other with a host synchronisation between them. */
+int pa_map_pairs(pa_index* idx, const uint8_t* ascii1, const uint64_t* offsets1, const uint8_t* ascii2, const uint64_t* offsets2,
+                 uint64_t n_pairs, int orient, uint32_t allowed_mismatches, pa_read_result* results, uint64_t* class_offsets,
+                 const uint32_t** class_ids);
+
+/* The class-count table of a paired-end run from its two FASTQ files (plain or gzip'ed; the acceptance rules of pa_process_reads; equal
+ * record counts and equal record.id() after a trailing "/1" or "/2" is cut, else PA_ERR_FORMAT with the record number, exactly as
+ * pa_count_cells): batches of about 2 Mi pairs (PA_INGEST_BATCH overrides), the next batch gathered while the GPU maps the two mates of the
+ * one before (on two streams) and combines them. h_counts[pa_counts_len(idx)] is overwritten; an overflow table attached to idx receives the
+ * novel results; *n_pairs and stats[PA_PAIR_STATS] (both may be NULL) are the run's. pa_process_reads_stage_seconds then reports this
+ * call's stages: [0] scan, [1] gather, [2] waiting for the mappings, [3] launch, [4] combine + count, [6] whole, [7] pairs. */
+int pa_count_pairs(pa_index* idx, const char* r1_path, const char* r2_path, int orient, uint32_t allowed_mismatches, int num_threads,
+                   uint64_t* h_counts, uint64_t* n_pairs, uint64_t stats[PA_PAIR_STATS]);
+
 /* ---------------- novel classes + the reduction over GPUs ---------------- */
 /* The dense table counts every result that is no index class in ONE slot (counts[num_classes]). A pa_overflow keeps WHICH
  * id sets those were, keyed by content, on the GPU: attach one to an index and every pa_map_count_batch_device launch files

@@ -139,6 +139,18 @@ int main(int argc, char** argv) {
         pa_quant_destroy(NULL);
     }
 
+    {   /* paired-end reads, host side: the checks that come before any device call */
+        uint64_t pst[PA_PAIR_STATS], pu = 0, pn = 0, poff[2] = {0, 0};
+        pa_read_result pr[1];
+        EXPECT(PA_PAIR_FR == 0 && PA_PAIR_RF == 1 && PA_PAIR_FF == 2 && PA_PAIR_STATS == 8);
+        EXPECT(pa_revcomp_tiles_device(NULL, NULL, NULL, 0, 1, NULL, NULL) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_pairs_scratch_bytes(0) >= 256 && pa_pairs_scratch_bytes(1000) > pa_pairs_scratch_bytes(10));
+        EXPECT(pa_pairs_combine_device(NULL, NULL, NULL, NULL, NULL, 0, NULL, NULL, 0, NULL, NULL, 0, NULL) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_pairs_finish(NULL, NULL, NULL, pst, &pu, &pn) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_map_pairs(NULL, NULL, poff, NULL, poff, 1, PA_PAIR_FR, 2, pr, NULL, NULL) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_count_pairs(NULL, fastq, fastq, PA_PAIR_FR, 2, 1, counts, &pn, pst) == PA_ERR_INVALID_ARG);
+    }
+
     pa_txome *tx = NULL, *tx2 = NULL, *tx3 = NULL;
     EXPECT(pa_txome_synthesize(50, 120, 7, &tx) == PA_OK);
     {   /* the same genes with repeat families and low-complexity tracts in their last exons */
@@ -312,6 +324,54 @@ int main(int argc, char** argv) {
             EXPECT(pw <= arena_cap + 16);
             free(hc); free(hr);
             pa_device_free(d_compact); pa_device_free(d_packed); pa_device_free(d_pw); pa_device_free(d_scr);
+        }
+        {   /* paired-end reads: the batch against its own reverse complement (FR of a pair whose mate 2 is mate 1 reversed: the same read twice) */
+            void *d_rc = NULL, *d_rc2 = NULL, *d_res2 = NULL, *d_arena2 = NULL, *d_pres = NULL, *d_parena = NULL, *d_pscr = NULL;
+            const size_t pscr = pa_pairs_scratch_bytes(nsim);
+            const size_t tile_bytes = pa_tiles_words(nsim, sim_wpr) * 8;
+            uint64_t pst[PA_PAIR_STATS], pu = 0, pn = 0, u2 = 0, n2 = 0;
+            uint64_t *back = (uint64_t*)malloc(tile_bytes), *fwd = (uint64_t*)malloc(tile_bytes);
+            pa_read_result *hp = (pa_read_result*)malloc(nsim * sizeof(pa_read_result)), *h1 = (pa_read_result*)malloc(nsim * sizeof(pa_read_result));
+            EXPECT(pa_device_malloc(0, tile_bytes, &d_rc) == PA_OK && pa_device_malloc(0, tile_bytes, &d_rc2) == PA_OK &&
+                   pa_device_malloc(0, nsim * sizeof(pa_read_result), &d_res2) == PA_OK && pa_device_malloc(0, arena_cap * 4, &d_arena2) == PA_OK &&
+                   pa_device_malloc(0, nsim * sizeof(pa_read_result), &d_pres) == PA_OK && pa_device_malloc(0, arena_cap * 4, &d_parena) == PA_OK &&
+                   pa_device_malloc(0, pscr, &d_pscr) == PA_OK);
+            EXPECT(pa_revcomp_tiles_device(idx, (const uint64_t*)d_tiles, (const uint32_t*)d_lens, nsim, sim_wpr, (uint64_t*)d_tiles, NULL) == PA_ERR_INVALID_ARG);   /* not in place */
+            EXPECT(pa_revcomp_tiles_device(idx, (const uint64_t*)d_tiles, (const uint32_t*)d_lens, nsim, sim_wpr, (uint64_t*)d_rc, NULL) == PA_OK);
+            EXPECT(pa_revcomp_tiles_device(idx, (const uint64_t*)d_rc, (const uint32_t*)d_lens, nsim, sim_wpr, (uint64_t*)d_rc2, NULL) == PA_OK);
+            EXPECT(pa_memcpy_d2h(back, d_rc2, tile_bytes, NULL) == PA_OK && pa_memcpy_d2h(fwd, d_tiles, tile_bytes, NULL) == PA_OK && pa_stream_synchronize(NULL) == PA_OK &&
+                   memcmp(back, fwd, tile_bytes) == 0);
+            EXPECT(pa_map_batch_device(idx, (const uint64_t*)d_rc2, (const uint32_t*)d_lens, nsim, sim_wpr, 2, (pa_read_result*)d_res2, (uint32_t*)d_arena2, arena_cap, NULL,
+                                       NULL) == PA_OK && pa_map_finish(idx, NULL, &u2, &n2) == PA_OK);
+            EXPECT(pa_pairs_combine_device(idx, (const pa_read_result*)d_res, (const uint32_t*)d_arena, (const pa_read_result*)d_res2, (const uint32_t*)d_arena2, nsim,
+                                           (pa_read_result*)d_pres, (uint32_t*)d_parena, arena_cap, NULL, d_pscr, pscr - 1, NULL) == PA_ERR_INVALID_ARG);
+            EXPECT(pa_pairs_combine_device(idx, (const pa_read_result*)d_res, (const uint32_t*)d_arena, (const pa_read_result*)d_res2, (const uint32_t*)d_arena2, nsim,
+                                           (pa_read_result*)d_pres, (uint32_t*)d_parena, arena_cap, NULL, d_pscr, pscr, NULL) == PA_OK);
+            EXPECT(pa_pairs_finish(idx, d_pscr, NULL, pst, &pu, &pn) == PA_OK && pu == pn && pu <= arena_cap);
+            EXPECT(pst[0] == nsim && pst[0] == pst[1] + pst[2] + pst[3] + pst[4] && pst[2] == 0 && pst[3] == 0);
+            EXPECT(pa_memcpy_d2h(hp, d_pres, nsim * sizeof(pa_read_result), NULL) == PA_OK && pa_memcpy_d2h(h1, d_res, nsim * sizeof(pa_read_result), NULL) == PA_OK &&
+                   pa_stream_synchronize(NULL) == PA_OK);
+            for (uint64_t i = 0; i < nsim; ++i)   /* a read paired with itself: its class, twice its coverage */
+                EXPECT(hp[i].class_len == h1[i].class_len && hp[i].coverage == 2 * h1[i].coverage && (hp[i].mismatches & PA_MAPPED_BIT) == (h1[i].mismatches & PA_MAPPED_BIT));
+            {
+                pa_read_result pr[2];
+                uint64_t pco[3] = {9, 9, 9};
+                const uint32_t* pci = NULL;
+                EXPECT(pa_map_pairs(idx, ascii, offsets, ascii, offsets, 2, 3, 2, pr, pco, &pci) == PA_ERR_INVALID_ARG);   /* no such orientation */
+                EXPECT(pa_map_pairs(idx, ascii, offsets, ascii, offsets, 2, PA_PAIR_FF, 2, pr, pco, &pci) == PA_OK && pco[0] == 0 && pco[2] == pco[1] + pr[1].class_len);
+                EXPECT(pr[0].class_len == res[0].class_len && pr[0].coverage == 2 * res[0].coverage);
+            }
+            {   /* the same file as both mates, both as given: every pair is its read twice */
+                uint64_t* pc = (uint64_t*)calloc(counts_len, 8);
+                uint64_t npairs = 0, cst2[PA_PAIR_STATS], tot = 0;
+                EXPECT(pa_count_pairs(idx, fastq, fastq, 7, 2, 2, pc, &npairs, cst2) == PA_ERR_INVALID_ARG);
+                EXPECT(pa_count_pairs(idx, fastq, fastq, PA_PAIR_FF, 2, 2, pc, &npairs, cst2) == PA_OK && npairs == nreads && cst2[0] == nreads && cst2[2] == 0 && cst2[3] == 0);
+                for (uint64_t i = 0; i < counts_len; ++i) tot += pc[i];
+                EXPECT(tot == nreads);
+                free(pc);
+            }
+            free(back); free(fwd); free(hp); free(h1);
+            pa_device_free(d_rc); pa_device_free(d_rc2); pa_device_free(d_res2); pa_device_free(d_arena2); pa_device_free(d_pres); pa_device_free(d_parena); pa_device_free(d_pscr);
         }
         {   /* host to host: the simulated batch from pinned host tiles to compact records + count table, chunks of 64 reads on two streams */
             void *ph_tiles = NULL, *ph_compact = NULL, *ph_packed = NULL, *ph_counts = NULL;

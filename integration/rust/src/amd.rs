@@ -1,4 +1,4 @@
-//! Exporter + drop-in `process_reads` for the reference crate. Add `mod amd_ffi; mod amd;` to src/lib.rs.
+//! Exporter + drop-in `process_reads` for the reference crate. Add `mod amd_ffi; mod amd;` to src/lib.rs (and `mod amd_pairs_ffi;` for `map_pairs`).
 //! The exporter only reads `pub` fields of `Pseudoaligner<K>` (src/pseudoaligner.rs:27-33); `dbg_index` (the boomphf MPHF,
 //! :30) is not exported: every hit is verified against the node sequence (:99-107), which makes it an exact dictionary that
 //! the library rebuilds. Not compiled in the image of this repository (no rustc): kept in step with
@@ -117,6 +117,44 @@ impl AmdIndex {
     }
 }
 impl Drop for AmdIndex { fn drop(&mut self) { unsafe { pa_index_destroy(self.raw) } } }
+
+/// Orientation of a read pair on the (stranded) index: which mate is reverse-complemented before it is mapped.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum PairOrientation { Fr, Rf, Ff }
+
+/// map_read_with_mismatch for read PAIRS (`pa_map_pairs`): every mate oriented and mapped, the two classes intersected
+/// (src/pseudoaligner.rs:389); a pair with one mapped mate takes that mate's result. `None` = neither mate mapped.
+pub fn map_pairs(index: &AmdIndex, mates1: &[&[u8]], mates2: &[&[u8]], orient: PairOrientation, allowed_mismatches: usize)
+                 -> Result<Vec<Option<(Vec<u32>, usize, usize)>>, Error> {
+    use crate::amd_pairs_ffi::*;
+    if mates1.len() != mates2.len() { return Err(anyhow!("{} first mates, {} second mates", mates1.len(), mates2.len())); }
+    let n = mates1.len();
+    let pack = |m: &[&[u8]]| { let mut text = Vec::new(); let mut off = vec![0u64]; for r in m { text.extend_from_slice(r); off.push(text.len() as u64); } (text, off) };
+    let ((t1, o1), (t2, o2)) = (pack(mates1), pack(mates2));
+    let mut res = vec![PaReadResult::default(); n];
+    let mut coff = vec![0u64; n + 1];
+    let mut ids: *const u32 = std::ptr::null();
+    let o = match orient { PairOrientation::Fr => PA_PAIR_FR, PairOrientation::Rf => PA_PAIR_RF, PairOrientation::Ff => PA_PAIR_FF };
+    check(unsafe { pa_map_pairs(index.raw, t1.as_ptr(), o1.as_ptr(), t2.as_ptr(), o2.as_ptr(), n as u64, o, allowed_mismatches as u32, res.as_mut_ptr(), coff.as_mut_ptr(), &mut ids) })?;
+    let all = if coff[n] == 0 { &[][..] } else { unsafe { std::slice::from_raw_parts(ids, coff[n] as usize) } };   // library-owned until this thread's next call
+    Ok((0..n).map(|i| if res[i].mismatches & PA_MAPPED_BIT == 0 { None } else {
+        Some((all[coff[i] as usize..coff[i + 1] as usize].to_vec(), res[i].coverage as usize, (res[i].mismatches & !PA_MAPPED_BIT) as usize))
+    }).collect())
+}
+
+/// The class-count table of a paired-end run from its two FASTQ files (`pa_count_pairs`): (table of `pa_counts_len` entries, pairs, stats).
+/// An overflow table attached to the index receives the novel results; table + overflow are what `quantify` takes.
+pub fn count_pairs<P: AsRef<Path>>(index: &AmdIndex, r1_fastq: P, r2_fastq: P, orient: PairOrientation, allowed_mismatches: usize, threads: usize)
+                                   -> Result<(Vec<u64>, u64, [u64; 8]), Error> {
+    use crate::amd_pairs_ffi::*;
+    let p1 = CString::new(r1_fastq.as_ref().to_string_lossy().as_bytes())?;
+    let p2 = CString::new(r2_fastq.as_ref().to_string_lossy().as_bytes())?;
+    let mut counts = vec![0u64; unsafe { pa_counts_len(index.raw) } as usize];
+    let (mut n, mut stats) = (0u64, [0u64; 8]);
+    let o = match orient { PairOrientation::Fr => PA_PAIR_FR, PairOrientation::Rf => PA_PAIR_RF, PairOrientation::Ff => PA_PAIR_FF };
+    check(unsafe { pa_count_pairs(index.raw, p1.as_ptr(), p2.as_ptr(), o, allowed_mismatches as u32, threads as i32, counts.as_mut_ptr(), &mut n, stats.as_mut_ptr()) })?;
+    Ok((counts, n, stats))
+}
 
 /// One replica of the index per GPU (`pa_index_create_multi`): what `process_reads_path` deals its windows of text to.
 pub struct AmdIndexSet { raw: Vec<*mut PaIndex> }

@@ -486,6 +486,64 @@ class Pseudoaligner:
     def counts_accumulate_device(self, d_results: int, d_arena: int, d_colour: int, n_reads: int, d_counts: int, stream: int = 0) -> None:
         check(lib().pa_counts_accumulate_device(self._h, d_results, d_arena, d_colour or None, n_reads, d_counts, stream or None))
 
+    # ---- paired-end reads (include/pseudoaligner_amd.h, "paired-end reads") -------------------------
+    def revcomp_tiles_device(self, d_tiles_in: int, d_lens: int, n_reads: int, words_per_read: int, d_tiles_out: int, stream: int = 0) -> None:
+        """reverse complement of packed reads in the tile layout, not in place (raw device pointers; asynchronous)"""
+        check(lib().pa_revcomp_tiles_device(self._h, d_tiles_in or None, d_lens or None, n_reads, words_per_read, d_tiles_out or None, stream or None))
+
+    @staticmethod
+    def pairs_scratch_bytes(n_pairs: int) -> int:
+        return lib().pa_pairs_scratch_bytes(n_pairs)
+
+    def pairs_combine_device(self, d_res1: int, d_arena1: int, d_res2: int, d_arena2: int, n_pairs: int, d_results: int, d_arena: int, arena_cap: int,
+                             d_scratch: int, scratch_bytes: int, d_counts: int = 0, stream: int = 0) -> None:
+        """the two mates' records (two finished map_batch_device launches) -> one record per pair + ids in the pair arena; asynchronous"""
+        check(lib().pa_pairs_combine_device(self._h, d_res1 or None, d_arena1 or None, d_res2 or None, d_arena2 or None, n_pairs, d_results or None,
+                                            d_arena or None, arena_cap, d_counts or None, d_scratch or None, scratch_bytes, stream or None))
+
+    def pairs_finish(self, d_scratch: int, stream: int = 0) -> Tuple[dict, int, int]:
+        """waits for pairs_combine_device -> (stats, arena_used, arena_needed); a full arena raises PaError(PA_ERR_ARENA_FULL) whose
+        .arena_needed is the capacity that suffices and .stats the launch's stats"""
+        st = np.zeros(_ffi.PA_PAIR_STATS, np.uint64)
+        used, need = C.c_uint64(), C.c_uint64()
+        rc = lib().pa_pairs_finish(self._h, d_scratch or None, stream or None, st.ctypes.data, C.byref(used), C.byref(need))
+        stats = dict(zip(_ffi.PAIR_STAT_NAMES, (int(x) for x in st)))
+        if rc == PA_ERR_ARENA_FULL:
+            err = PaError(rc, (lib().pa_last_error() or b"").decode("utf-8", "replace"))
+            err.arena_needed, err.stats = need.value, stats
+            raise err
+        check(rc)
+        return stats, used.value, need.value
+
+    def map_pairs(self, reads1: Sequence, reads2: Sequence, orient: str = "fr", allowed_mismatches: int = PA_DEFAULT_ALLOWED_MISMATCHES):
+        """map_batch for read pairs: mates oriented ("fr": mate 2 reverse-complemented, "rf": mate 1, "ff": neither), mapped, their classes
+        intersected -> (results[n] RESULT_DTYPE, class_offsets[n+1], class_ids) in pair order"""
+        if orient not in _ffi.PAIR_ORIENTATIONS:
+            raise ValueError("orient %r: one of %s" % (orient, sorted(_ffi.PAIR_ORIENTATIONS)))
+        d1, o1 = reads1 if isinstance(reads1, tuple) else concat_reads(reads1)
+        d2, o2 = reads2 if isinstance(reads2, tuple) else concat_reads(reads2)
+        if len(o1) != len(o2):
+            raise ValueError("%d first mates, %d second mates" % (len(o1) - 1, len(o2) - 1))
+        n = len(o1) - 1
+        results = np.zeros(n, dtype=RESULT_DTYPE)
+        coff = np.zeros(n + 1, dtype=np.uint64)
+        ids = vp()
+        check(lib().pa_map_pairs(self._h, d1.ctypes.data, o1.ctypes.data, d2.ctypes.data, o2.ctypes.data, n, _ffi.PAIR_ORIENTATIONS[orient], allowed_mismatches,
+                                 results.ctypes.data, coff.ctypes.data, C.byref(ids)))
+        return results, coff, _np_view(ids.value, int(coff[-1]), np.uint32).copy()
+
+    def count_pairs(self, r1: str, r2: str, orient: str = "fr", allowed_mismatches: int = PA_DEFAULT_ALLOWED_MISMATCHES, num_threads: int = 0):
+        """pa_count_pairs: two FASTQ files (plain or gzip'ed) -> (class-count table uint64[counts_len()], stats dict); an attached overflow
+        table receives the novel results, so that Quantifier.set_counts(counts, overflow.fetch()) takes the pair"""
+        if orient not in _ffi.PAIR_ORIENTATIONS:
+            raise ValueError("orient %r: one of %s" % (orient, sorted(_ffi.PAIR_ORIENTATIONS)))
+        counts = np.zeros(self.counts_len(), np.uint64)
+        st = np.zeros(_ffi.PA_PAIR_STATS, np.uint64)
+        n = C.c_uint64()
+        check(lib().pa_count_pairs(self._h, str(r1).encode(), str(r2).encode(), _ffi.PAIR_ORIENTATIONS[orient], allowed_mismatches, num_threads,
+                                   counts.ctypes.data, C.byref(n), st.ctypes.data))
+        return counts, dict(zip(_ffi.PAIR_STAT_NAMES, (int(x) for x in st)))
+
     def encode_reads_device(self, d_ascii: int, d_offsets: int, n_reads: int, words_per_read: int, d_tiles: int, d_lens: int, stream: int = 0):
         check(lib().pa_encode_reads_device(self._h, d_ascii, d_offsets, n_reads, words_per_read, d_tiles, d_lens, stream or None))
 

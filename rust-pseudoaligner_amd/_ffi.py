@@ -58,6 +58,11 @@ class QuantParams(C.Structure):
 
 
 PA_QUANT_STATS = 8
+PA_PAIR_FR, PA_PAIR_RF, PA_PAIR_FF = 0, 1, 2
+PAIR_ORIENTATIONS = {"fr": PA_PAIR_FR, "rf": PA_PAIR_RF, "ff": PA_PAIR_FF}
+PA_PAIR_STATS = 8
+PAIR_STAT_NAMES = ("pairs", "both_mapped", "mate1_only", "mate2_only", "neither", "both_mapped_empty", "by_reference", "in_arena")
+PA_MAX_ARENA_ENTRIES = 0x7FFFFFFF
 PA_QUANT_BOOT_MAX_BATCH = 64
 QUANT_STAT_NAMES = ("rows", "ids", "transcripts_with_a_row", "longest_row", "largest_degree", "reads_used", "novel_reads_left_out", "iterations")
 
@@ -154,6 +159,12 @@ SIGNATURES = {
     "pa_quant_bootstrap_step": (C.c_int, [vp, C.c_uint32]),
     "pa_quant_bootstrap_run": (C.c_int, [vp, vp, vp]),
     "pa_quant_bootstrap_fetch": (C.c_int, [vp, vp, vp]),
+    "pa_revcomp_tiles_device": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp]),
+    "pa_pairs_scratch_bytes": (C.c_size_t, [C.c_uint64]),
+    "pa_pairs_combine_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, C.c_size_t, vp]),
+    "pa_pairs_finish": (C.c_int, [vp, vp, vp, vp, u64p, u64p]),
+    "pa_map_pairs": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_uint32, vp, vp, C.POINTER(vp)]),
+    "pa_count_pairs": (C.c_int, [vp, C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_int, vp, u64p, vp]),
     "pa_overflow_create": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.POINTER(vp)]),
     "pa_overflow_destroy": (None, [vp]),
     "pa_overflow_reset": (C.c_int, [vp, vp]),

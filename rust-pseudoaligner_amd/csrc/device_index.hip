@@ -131,6 +131,10 @@ void index_host_classes(const pa_index* idx, const uint32_t** ec, const uint32_t
     *class_ref = idx->h_class_ref.data();
     *device = idx->device;
 }
+void index_pair_view(pa_index* idx, PairIndexView* out) {
+    std::lock_guard<std::mutex> g(idx->mu);
+    *out = PairIndexView{idx->dv, idx->d_class_table.get(), idx->class_table_size, idx->ovf, idx->device, idx->num_cus};
+}
 void index_host_class_text(pa_index* idx, const uint64_t** off, const char** text) {
     std::call_once(idx->class_text_once, [idx] {
         const uint32_t nc = idx->stats.num_classes;

@@ -1197,7 +1197,7 @@ struct CellBatch {   // one batch of pairs: R2 (all of it) and the R1 prefixes, 
     DeviceBuffer<uint32_t> d_lens, d_arena;
     DeviceBuffer<pa_read_result> d_results;
     uint64_t n = 0, r2_bytes = 0, r1_bytes = 0;
-    uint32_t max_len = 0;
+    uint32_t max_len = 0, max_len1 = 0;   // longest R2 / longest gathered piece of R1
 };
 
 // grow a pinned buffer to `want` elements, keeping the first `keep`
@@ -1213,6 +1213,114 @@ int grow_pinned(PinnedBuffer<T>& b, size_t want, size_t keep) {
 }
 
 double secs_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+
+// The pair scan and gather shared by pa_count_cells and pa_count_pairs: the two files a window of records at a time, record counts and
+// record.id() (after a trailing "/1" or "/2" is cut) compared on the way, whole windows' worth of pairs gathered into a batch — all of
+// R2 and the first `prefix` bytes of every R1 (0xFFFFFFFF: all of it) — each piece copied before its window is given up.
+struct PairReader {
+    const char *r1_path, *r2_path;
+    Pool& pool;
+    const uint32_t prefix;
+    double* st;                    // stage seconds: [0] scan, [1] gather
+    PairCursor f1, f2;
+    uint64_t batch_pairs = DEFAULT_BATCH_READS;
+    int ntask;
+    std::vector<uint64_t> part, part1;
+    std::vector<uint32_t> part_max, part_max1;
+    uint64_t pairs = 0;            // pairs of the batches launched so far (the caller adds a batch when it launches it)
+    bool ended = false;
+    PairReader(const char* r1, const char* r2, Pool& pl, uint32_t prefix_, double* st_)
+        : r1_path(r1), r2_path(r2), pool(pl), prefix(prefix_), st(st_), ntask(pl.size() * 4), part((size_t)ntask + 1), part1((size_t)ntask + 1), part_max((size_t)ntask),
+          part_max1((size_t)ntask) {
+        if (const char* v = getenv("PA_INGEST_BATCH")) { const long long x = atoll(v); if (x >= 1) batch_pairs = (uint64_t)x; }
+    }
+    int open() {
+        int rc;
+        if ((rc = f1.open(r1_path)) != PA_OK || (rc = f2.open(r2_path)) != PA_OK) return rc;
+        return PA_OK;
+    }
+    void release() { f1.text.release(); f2.text.release(); }
+    // gather the next batch into b
+    int gather(CellBatch& b) {
+        b.n = 0; b.r2_bytes = 0; b.r1_bytes = 0; b.max_len = 0; b.max_len1 = 0;
+        int e = PA_OK;
+        if ((e = grow_pinned(b.h_r2off, batch_pairs + 1, 0)) || (e = grow_pinned(b.h_r1off, batch_pairs + 1, 0))) return e;
+        if (prefix != 0xFFFFFFFFu && (e = grow_pinned(b.h_r1, (size_t)batch_pairs * prefix + 64, 0))) return e;
+        while (b.n < batch_pairs) {
+            uint64_t left1 = 0, left2 = 0;
+            auto t0 = std::chrono::steady_clock::now();
+            if ((e = f1.ready(pool, left1)) != PA_OK || (e = f2.ready(pool, left2)) != PA_OK) return e;
+            st[0] += secs_since(t0);
+            if (left1 == 0 || left2 == 0) {
+                if (left1 != left2)
+                    return fail(PA_ERR_FORMAT, "%s has more records than %s: record %llu has no mate", left1 ? r1_path : r2_path, left1 ? r2_path : r1_path,
+                                (unsigned long long)(pairs + b.n));
+                ended = true;
+                break;
+            }
+            t0 = std::chrono::steady_clock::now();
+            const uint64_t m = std::min(std::min(left1, left2), batch_pairs - b.n);
+            const uint64_t a1 = f1.at, a2 = f2.at, base = b.n;
+            std::atomic<uint64_t> bad{~0ull};
+            pool.run(ntask, [&](int t) {   // R2 and R1-prefix bytes per task, ids compared on the way
+                uint64_t sum2 = 0, sum1 = 0;
+                uint32_t mx = 0, mx1 = 0;
+                for (uint64_t i = m * (uint64_t)t / ntask; i < m * (uint64_t)(t + 1) / ntask; ++i) {
+                    uint32_t l1, l2;
+                    const char* id1 = f1.id(a1 + i, l1);
+                    const char* id2 = f2.id(a2 + i, l2);
+                    if (l1 != l2 || memcmp(id1, id2, l1) != 0) {
+                        uint64_t first = bad.load();
+                        while (i < first && !bad.compare_exchange_weak(first, i)) {}
+                    }
+                    const uint32_t len = f2.rec[a2 + i].seq_len, len1 = std::min(f1.rec[a1 + i].seq_len, prefix);
+                    sum2 += len;
+                    sum1 += len1;
+                    mx = std::max(mx, len);
+                    mx1 = std::max(mx1, len1);
+                }
+                part[(size_t)t + 1] = sum2;
+                part1[(size_t)t + 1] = sum1;
+                part_max[(size_t)t] = mx;
+                part_max1[(size_t)t] = mx1;
+            });
+            if (bad.load() != ~0ull)
+                return fail(PA_ERR_FORMAT, "record %llu: the ids of %s and %s differ", (unsigned long long)(pairs + base + bad.load()), r1_path, r2_path);
+            part[0] = b.r2_bytes;
+            part1[0] = b.r1_bytes;
+            for (int t = 0; t < ntask; ++t) {
+                part[(size_t)t + 1] += part[(size_t)t];
+                part1[(size_t)t + 1] += part1[(size_t)t];
+                b.max_len = std::max(b.max_len, part_max[(size_t)t]);
+                b.max_len1 = std::max(b.max_len1, part_max1[(size_t)t]);
+            }
+            if ((e = grow_pinned(b.h_r2, part[(size_t)ntask] + 64, b.r2_bytes)) != PA_OK) return e;
+            if ((e = grow_pinned(b.h_r1, part1[(size_t)ntask] + 64, b.r1_bytes)) != PA_OK) return e;   // (a bounded prefix: sized above, nothing to do)
+            pool.run(ntask, [&](int t) {   // all of R2, the first `prefix` bytes of R1
+                uint64_t o2 = part[(size_t)t], o1 = part1[(size_t)t];
+                for (uint64_t i = m * (uint64_t)t / ntask; i < m * (uint64_t)(t + 1) / ntask; ++i) {
+                    const uint32_t len2 = f2.rec[a2 + i].seq_len;
+                    b.h_r2off.get()[base + i] = o2;
+                    memcpy(b.h_r2.get() + o2, f2.seq(a2 + i), len2);
+                    o2 += len2;
+                    const uint32_t len1 = std::min(f1.rec[a1 + i].seq_len, prefix);
+                    b.h_r1off.get()[base + i] = o1;
+                    memcpy(b.h_r1.get() + o1, f1.seq(a1 + i), len1);
+                    o1 += len1;
+                }
+            });
+            b.r1_bytes = part1[(size_t)ntask];
+            b.r2_bytes = part[(size_t)ntask];
+            b.n += m;
+            f1.at += m;
+            f2.at += m;
+            st[1] += secs_since(t0);
+        }
+        b.h_r2off.get()[b.n] = b.r2_bytes;
+        b.h_r1off.get()[b.n] = b.r1_bytes;
+        return PA_OK;
+    }
+};
 
 // the batch's GPU leg up to the mapping: copies, encode, map (asynchronous on s)
 int cell_batch_map(pa_index* idx, CellBatch& b, hipStream_t s) {
@@ -1285,98 +1393,18 @@ int count_cells_impl(pa_index* idx, const pa_host_index* h, const char* r1_path,
     std::unique_ptr<pa_cell_counter, void (*)(pa_cell_counter*)> own(counter, pa_cell_counter_destroy);
     const uint32_t prefix = bc_len + umi_len;
 
-    PairCursor f1, f2;
-    if ((rc = f1.open(r1_path)) != PA_OK || (rc = f2.open(r2_path)) != PA_OK) return rc;
     Pool pool(num_threads < 1 ? usable_threads() : num_threads);
-    uint64_t batch_pairs = DEFAULT_BATCH_READS;
-    if (const char* v = getenv("PA_INGEST_BATCH")) { const long long x = atoll(v); if (x >= 1) batch_pairs = (uint64_t)x; }
+    PairReader rd(r1_path, r2_path, pool, prefix, st);
+    if ((rc = rd.open()) != PA_OK) return rc;
     hipStream_t s = nullptr;
     PA_HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     struct StreamGuard { pa_index* idx; hipStream_t s; ~StreamGuard() { (void)hipStreamSynchronize(s); (void)pa_index_release_stream(idx, s); (void)hipStreamDestroy(s); } } guard{idx, s};
     CellBatch batches[2];
-    const int ntask = pool.size() * 4;
-    std::vector<uint64_t> part((size_t)ntask + 1), part1((size_t)ntask + 1);
-    std::vector<uint32_t> part_max((size_t)ntask);
-    uint64_t pairs = 0;
-    bool in_flight = false, ended = false;
+    uint64_t& pairs = rd.pairs;
+    bool in_flight = false;
+    bool& ended = rd.ended;
     int cur = 0;
-    // gather the next batch into batches[cur]: whole windows' worth of pairs, each piece copied before its window is given up
-    auto gather = [&](CellBatch& b) -> int {
-        b.n = 0; b.r2_bytes = 0; b.r1_bytes = 0; b.max_len = 0;
-        int e = PA_OK;
-        if ((e = grow_pinned(b.h_r2off, batch_pairs + 1, 0)) || (e = grow_pinned(b.h_r1off, batch_pairs + 1, 0)) ||
-            (e = grow_pinned(b.h_r1, (size_t)batch_pairs * prefix + 64, 0)))
-            return e;
-        while (b.n < batch_pairs) {
-            uint64_t left1 = 0, left2 = 0;
-            auto t0 = std::chrono::steady_clock::now();
-            if ((e = f1.ready(pool, left1)) != PA_OK || (e = f2.ready(pool, left2)) != PA_OK) return e;
-            st[0] += secs_since(t0);
-            if (left1 == 0 || left2 == 0) {
-                if (left1 != left2)
-                    return fail(PA_ERR_FORMAT, "%s has more records than %s: record %llu has no mate", left1 ? r1_path : r2_path, left1 ? r2_path : r1_path,
-                                (unsigned long long)(pairs + b.n));
-                ended = true;
-                break;
-            }
-            t0 = std::chrono::steady_clock::now();
-            const uint64_t m = std::min(std::min(left1, left2), batch_pairs - b.n);
-            const uint64_t a1 = f1.at, a2 = f2.at, base = b.n;
-            std::atomic<uint64_t> bad{~0ull};
-            pool.run(ntask, [&](int t) {   // R2 and R1-prefix bytes per task, ids compared on the way
-                uint64_t sum2 = 0, sum1 = 0;
-                uint32_t mx = 0;
-                for (uint64_t i = m * (uint64_t)t / ntask; i < m * (uint64_t)(t + 1) / ntask; ++i) {
-                    uint32_t l1, l2;
-                    const char* id1 = f1.id(a1 + i, l1);
-                    const char* id2 = f2.id(a2 + i, l2);
-                    if (l1 != l2 || memcmp(id1, id2, l1) != 0) {
-                        uint64_t first = bad.load();
-                        while (i < first && !bad.compare_exchange_weak(first, i)) {}
-                    }
-                    const uint32_t len = f2.rec[a2 + i].seq_len;
-                    sum2 += len;
-                    sum1 += std::min(f1.rec[a1 + i].seq_len, prefix);
-                    mx = std::max(mx, len);
-                }
-                part[(size_t)t + 1] = sum2;
-                part1[(size_t)t + 1] = sum1;
-                part_max[(size_t)t] = mx;
-            });
-            if (bad.load() != ~0ull)
-                return fail(PA_ERR_FORMAT, "record %llu: the ids of %s and %s differ", (unsigned long long)(pairs + base + bad.load()), r1_path, r2_path);
-            part[0] = b.r2_bytes;
-            part1[0] = b.r1_bytes;
-            for (int t = 0; t < ntask; ++t) {
-                part[(size_t)t + 1] += part[(size_t)t];
-                part1[(size_t)t + 1] += part1[(size_t)t];
-                b.max_len = std::max(b.max_len, part_max[(size_t)t]);
-            }
-            if ((e = grow_pinned(b.h_r2, part[(size_t)ntask] + 64, b.r2_bytes)) != PA_OK) return e;
-            pool.run(ntask, [&](int t) {   // all of R2, the first bc_len + umi_len bytes of R1
-                uint64_t o2 = part[(size_t)t], o1 = part1[(size_t)t];
-                for (uint64_t i = m * (uint64_t)t / ntask; i < m * (uint64_t)(t + 1) / ntask; ++i) {
-                    const uint32_t len2 = f2.rec[a2 + i].seq_len;
-                    b.h_r2off.get()[base + i] = o2;
-                    memcpy(b.h_r2.get() + o2, f2.seq(a2 + i), len2);
-                    o2 += len2;
-                    const uint32_t len1 = std::min(f1.rec[a1 + i].seq_len, prefix);
-                    b.h_r1off.get()[base + i] = o1;
-                    memcpy(b.h_r1.get() + o1, f1.seq(a1 + i), len1);
-                    o1 += len1;
-                }
-            });
-            b.r1_bytes = part1[(size_t)ntask];
-            b.r2_bytes = part[(size_t)ntask];
-            b.n += m;
-            f1.at += m;
-            f2.at += m;
-            st[1] += secs_since(t0);
-        }
-        b.h_r2off.get()[b.n] = b.r2_bytes;
-        b.h_r1off.get()[b.n] = b.r1_bytes;
-        return PA_OK;
-    };
+    auto gather = [&](CellBatch& b) -> int { return rd.gather(b); };
     for (;;) {
         CellBatch& b = batches[cur];
         b.n = 0;
@@ -1394,8 +1422,7 @@ int count_cells_impl(pa_index* idx, const pa_host_index* h, const char* r1_path,
         in_flight = true;
         cur ^= 1;
     }
-    f1.text.release();
-    f2.text.release();
+    rd.release();
     if (rc != PA_OK) return rc;
     auto t0 = std::chrono::steady_clock::now();
     uint64_t entries = 0;
@@ -1471,6 +1498,141 @@ int count_cells_impl(pa_index* idx, const pa_host_index* h, const char* r1_path,
     return PA_OK;
 }
 
+
+// ---- pa_count_pairs: two FASTQ files -> the class-count table of the pairs ----
+struct PairBatch : CellBatch {   // + mate 1's tiles and mapping, the reverse-complemented tiles of one mate, the pair stage's outputs
+    DeviceBuffer<uint64_t> d_tiles1, d_rc;
+    DeviceBuffer<uint32_t> d_lens1, d_arena1, d_parena;
+    DeviceBuffer<pa_read_result> d_results1, d_presults;
+    DeviceBuffer<uint8_t> d_scratch;
+};
+
+int pair_map_mate(pa_index* idx, const uint64_t* tiles, const uint32_t* lens, uint64_t n, uint32_t wpr, uint32_t allowed, pa_read_result* res, DeviceBuffer<uint32_t>& arena,
+                  hipStream_t s) {
+    return pa_map_batch_device(idx, tiles, lens, n, wpr, allowed, res, arena.get(), arena.size(), nullptr, s);
+}
+
+// the batch's GPU leg up to the two mappings: mate 1 on s1, mate 2 on s2 (each stream has its own launch context on idx), all asynchronous
+int pair_batch_map(pa_index* idx, PairBatch& b, int orient, uint32_t allowed, hipStream_t s1, hipStream_t s2) {
+    const uint32_t wpr1 = pa_words_per_read(std::max(1u, b.max_len1)), wpr2 = pa_words_per_read(std::max(1u, b.max_len));
+    const size_t tw1 = pa_tiles_words(b.n, wpr1) + 1, tw2 = pa_tiles_words(b.n, wpr2) + 1;
+    const uint64_t hint = pa_map_arena_hint(idx, b.n);
+    int e = PA_OK;
+    if ((e = b.d_r2.reserve(b.r2_bytes + 64, b.h_r2.size())) || (e = b.d_r1.reserve(b.r1_bytes + 64, b.h_r1.size())) ||
+        (e = b.d_r2off.reserve(b.n + 1, b.h_r2off.size())) || (e = b.d_r1off.reserve(b.n + 1, b.h_r1off.size())) ||
+        (e = b.d_tiles.reserve(tw2, tw2)) || (e = b.d_tiles1.reserve(tw1, tw1)) || (e = b.d_rc.reserve(std::max(tw1, tw2), std::max(tw1, tw2))) ||
+        (e = b.d_lens.reserve(b.n + 64, b.h_r1off.size() + 64)) || (e = b.d_lens1.reserve(b.n + 64, b.h_r1off.size() + 64)) ||
+        (e = b.d_results.reserve(b.n + 64, b.h_r1off.size() + 64)) || (e = b.d_results1.reserve(b.n + 64, b.h_r1off.size() + 64)) ||
+        (e = b.d_presults.reserve(b.n + 64, b.h_r1off.size() + 64)) || (e = b.d_arena.reserve(hint, hint)) || (e = b.d_arena1.reserve(hint, hint)))
+        return e;
+    PA_HIP_TRY(hipMemcpyAsync(b.d_r1.get(), b.h_r1.get(), b.r1_bytes, hipMemcpyHostToDevice, s1));
+    PA_HIP_TRY(hipMemcpyAsync(b.d_r1off.get(), b.h_r1off.get(), (b.n + 1) * 8, hipMemcpyHostToDevice, s1));
+    PA_HIP_TRY(hipMemcpyAsync(b.d_r2.get(), b.h_r2.get(), b.r2_bytes, hipMemcpyHostToDevice, s2));
+    PA_HIP_TRY(hipMemcpyAsync(b.d_r2off.get(), b.h_r2off.get(), (b.n + 1) * 8, hipMemcpyHostToDevice, s2));
+    if ((e = pa_encode_reads_device(idx, b.d_r1.get(), b.d_r1off.get(), b.n, wpr1, b.d_tiles1.get(), b.d_lens1.get(), s1)) != PA_OK) return e;
+    if ((e = pa_encode_reads_device(idx, b.d_r2.get(), b.d_r2off.get(), b.n, wpr2, b.d_tiles.get(), b.d_lens.get(), s2)) != PA_OK) return e;
+    const uint64_t *t1 = b.d_tiles1.get(), *t2 = b.d_tiles.get();
+    if (orient == PA_PAIR_RF) {
+        if ((e = pa_revcomp_tiles_device(idx, b.d_tiles1.get(), b.d_lens1.get(), b.n, wpr1, b.d_rc.get(), s1)) != PA_OK) return e;
+        t1 = b.d_rc.get();
+    } else if (orient == PA_PAIR_FR) {
+        if ((e = pa_revcomp_tiles_device(idx, b.d_tiles.get(), b.d_lens.get(), b.n, wpr2, b.d_rc.get(), s2)) != PA_OK) return e;
+        t2 = b.d_rc.get();
+    }
+    if ((e = pair_map_mate(idx, t1, b.d_lens1.get(), b.n, wpr1, allowed, b.d_results1.get(), b.d_arena1, s1)) != PA_OK) return e;
+    return pair_map_mate(idx, t2, b.d_lens.get(), b.n, wpr2, allowed, b.d_results.get(), b.d_arena, s2);
+}
+
+// waits for the two mappings (regrowing an arena as pa_map_finish asks), then combines and counts the batch on s1
+int pair_batch_count(pa_index* idx, PairBatch& b, int orient, uint32_t allowed, uint64_t* d_counts, hipStream_t s1, hipStream_t s2, uint64_t* stats, double* st) {
+    auto t0 = std::chrono::steady_clock::now();
+    const uint32_t wpr1 = pa_words_per_read(std::max(1u, b.max_len1)), wpr2 = pa_words_per_read(std::max(1u, b.max_len));
+    for (int mate = 0; mate < 2; ++mate) {
+        hipStream_t s = mate ? s2 : s1;
+        DeviceBuffer<uint32_t>& arena = mate ? b.d_arena : b.d_arena1;
+        const bool rc = mate ? orient == PA_PAIR_FR : orient == PA_PAIR_RF;
+        const uint64_t* tiles = rc ? b.d_rc.get() : mate ? b.d_tiles.get() : b.d_tiles1.get();
+        uint64_t used = 0, need = 0;
+        int e = pa_map_finish(idx, s, &used, &need);
+        for (int attempt = 0; e == PA_ERR_ARENA_FULL && attempt < 3; ++attempt) {
+            if ((e = arena.alloc(need + need / 8 + 4096)) != PA_OK) return e;
+            e = pair_map_mate(idx, tiles, mate ? b.d_lens.get() : b.d_lens1.get(), b.n, mate ? wpr2 : wpr1, allowed, mate ? b.d_results.get() : b.d_results1.get(), arena, s);
+            if (e == PA_OK) e = pa_map_finish(idx, s, &used, &need);
+        }
+        if (e != PA_OK) return e;
+    }
+    st[2] += secs_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    // the pair arena is sized by a bound on what the batch can need, so that the counted launch cannot run out of it (a re-run would count twice)
+    uint64_t bound = 0;
+    const size_t scratch_bytes = pa_pairs_scratch_bytes(b.n);
+    int e = b.d_scratch.reserve(scratch_bytes, scratch_bytes + scratch_bytes / 4);
+    if (e != PA_OK) return e;
+    if ((e = pairs_arena_bound(idx, b.d_results1.get(), b.d_results.get(), b.n, b.d_scratch.get(), s1, &bound)) != PA_OK) return e;
+    if (bound > PA_MAX_ARENA_ENTRIES) return fail(PA_ERR_UNSUPPORTED, "a batch of %llu pairs may need %llu arena entries: lower PA_INGEST_BATCH", (unsigned long long)b.n, (unsigned long long)bound);
+    if ((e = b.d_parena.reserve(bound + 64, bound + bound / 4 + 4096)) != PA_OK) return e;
+    if ((e = pa_pairs_combine_device(idx, b.d_results1.get(), b.d_arena1.get(), b.d_results.get(), b.d_arena.get(), b.n, b.d_presults.get(), b.d_parena.get(), b.d_parena.size(),
+                                     d_counts, b.d_scratch.get(), scratch_bytes, s1)) != PA_OK)
+        return e;
+    uint64_t bst[PA_PAIR_STATS], used = 0, need = 0;
+    if ((e = pa_pairs_finish(idx, b.d_scratch.get(), s1, bst, &used, &need)) != PA_OK) return e;
+    for (int j = 0; j < PA_PAIR_STATS; ++j) stats[j] += bst[j];
+    st[4] += secs_since(t0);
+    return PA_OK;
+}
+
+int count_pairs_impl(pa_index* idx, const char* r1_path, const char* r2_path, int orient, uint32_t allowed, int num_threads, uint64_t* h_counts, uint64_t* n_pairs,
+                     uint64_t* stats_out) {
+    const auto t_call = std::chrono::steady_clock::now();
+    double* st = last_stage_seconds();
+    for (int j = 0; j < PA_INGEST_STAGES; ++j) st[j] = 0.0;
+    if (!idx || !r1_path || !r2_path || !h_counts) return fail(PA_ERR_INVALID_ARG, "null argument");
+    if (orient != PA_PAIR_FR && orient != PA_PAIR_RF && orient != PA_PAIR_FF) return fail(PA_ERR_INVALID_ARG, "orientation %d (PA_PAIR_FR, PA_PAIR_RF or PA_PAIR_FF)", orient);
+    Pool pool(num_threads < 1 ? usable_threads() : num_threads);
+    PairReader rd(r1_path, r2_path, pool, 0xFFFFFFFFu, st);
+    int rc = rd.open();
+    if (rc != PA_OK) return rc;
+    const uint64_t counts_len = pa_counts_len(idx);
+    DeviceBuffer<uint64_t> d_counts;
+    if ((rc = d_counts.alloc(counts_len)) != PA_OK) return rc;
+    hipStream_t s1 = nullptr, s2 = nullptr;
+    PA_HIP_TRY(hipStreamCreateWithFlags(&s1, hipStreamNonBlocking));
+    struct StreamGuard { pa_index* idx; hipStream_t s; ~StreamGuard() { (void)hipStreamSynchronize(s); (void)pa_index_release_stream(idx, s); (void)hipStreamDestroy(s); } } g1{idx, s1};
+    PA_HIP_TRY(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
+    StreamGuard g2{idx, s2};
+    PA_HIP_TRY(hipMemsetAsync(d_counts.get(), 0, counts_len * 8, s1));
+    PairBatch batches[2];
+    uint64_t stats[PA_PAIR_STATS] = {0};
+    bool in_flight = false;
+    int cur = 0;
+    for (;;) {
+        PairBatch& b = batches[cur];
+        b.n = 0;
+        rc = rd.ended ? PA_OK : rd.gather(b);   // (while the batch before is on the GPU)
+        if (rc != PA_OK) break;
+        if (in_flight) {
+            if ((rc = pair_batch_count(idx, batches[cur ^ 1], orient, allowed, d_counts.get(), s1, s2, stats, st)) != PA_OK) break;
+            in_flight = false;
+        }
+        if (b.n == 0) break;
+        const auto t0 = std::chrono::steady_clock::now();
+        if ((rc = pair_batch_map(idx, b, orient, allowed, s1, s2)) != PA_OK) break;
+        st[3] += secs_since(t0);
+        rd.pairs += b.n;
+        in_flight = true;
+        cur ^= 1;
+    }
+    rd.release();
+    if (rc != PA_OK) return rc;
+    PA_HIP_TRY(hipMemcpyAsync(h_counts, d_counts.get(), counts_len * 8, hipMemcpyDeviceToHost, s1));
+    PA_HIP_TRY(hipStreamSynchronize(s1));
+    if (n_pairs) *n_pairs = rd.pairs;
+    if (stats_out) for (int j = 0; j < PA_PAIR_STATS; ++j) stats_out[j] = stats[j];
+    st[6] = secs_since(t_call);
+    st[7] = (double)rd.pairs;
+    return PA_OK;
+}
+
 }  // namespace
 
 extern "C" int pa_count_cells(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const char* whitelist_path, uint32_t bc_len,
@@ -1481,5 +1643,16 @@ extern "C" int pa_count_cells(pa_index* idx, const pa_host_index* h, const char*
         return fail(PA_ERR_OOM, "out of host memory in pa_count_cells");
     } catch (const std::exception& ex) {
         return fail(PA_ERR_INTERNAL, "pa_count_cells: %s", ex.what());
+    }
+}
+
+extern "C" int pa_count_pairs(pa_index* idx, const char* r1_path, const char* r2_path, int orient, uint32_t allowed_mismatches, int num_threads, uint64_t* h_counts,
+                              uint64_t* n_pairs, uint64_t stats[PA_PAIR_STATS]) {
+    try {
+        return count_pairs_impl(idx, r1_path, r2_path, orient, allowed_mismatches, num_threads, h_counts, n_pairs, stats);
+    } catch (const std::bad_alloc&) {
+        return fail(PA_ERR_OOM, "out of host memory in pa_count_pairs");
+    } catch (const std::exception& ex) {
+        return fail(PA_ERR_INTERNAL, "pa_count_pairs: %s", ex.what());
     }
 }

@@ -132,4 +132,14 @@ int overflow_after_map(pa_overflow* o, const uint32_t* novel_list, const unsigne
                        hipStream_t stream);
 int overflow_device(const pa_overflow* o);
 
+// what the pair stage (pairs.hip) needs of an index handle, beside index_host_classes (device_index.hip)
+struct PairIndexView {
+    DevIndexView dv;
+    const uint32_t* class_table;
+    uint64_t class_table_size;
+    pa_overflow* ovf;      // the attached overflow table, or nullptr
+    int device, num_cus;
+};
+void index_pair_view(pa_index* idx, PairIndexView* out);
+
 }  // namespace pa

@@ -23,6 +23,9 @@ void index_host_classes(const pa_index* idx, const uint32_t** ec, const uint32_t
 void index_host_class_text(pa_index* idx, const uint64_t** off, const char** text);
 // ... and its copy in HBM for the render kernels (render.hip); uploaded on first use. Returns a pa_status
 int index_device_class_text(pa_index* idx, const uint64_t** d_off, const uint8_t** d_text);
+// pairs.hip: an upper bound on the arena entries pa_pairs_combine_device can need for these mate records (the shorter list of every pair with two
+// mapped mates, the list of a mate mapped alone), summed on the device into the first 8 bytes of d_scratch; synchronises `stream`
+int pairs_arena_bound(pa_index* idx, const pa_read_result* d_res1, const pa_read_result* d_res2, uint64_t n_pairs, void* d_scratch, void* stream, uint64_t* bound);
 // One opaque object the FASTQ driver parks on the index between calls (its pinned + device batch buffers: allocating them
 // costs more than packing a batch). take() hands it to the caller and empties the slot, so concurrent calls never share
 // it; put() stores it back (or frees it with `free_fn` when another call already parked one). pa_index_destroy frees it.
