@@ -99,7 +99,7 @@ struct pa_index {
     std::vector<uint32_t> h_arena;
     DeviceBuffer<uint64_t> d_class_text_off;   // device copy of the rendered classes (uploaded on first use, under `mu`)
     DeviceBuffer<uint8_t> d_class_text;
-    // parked by fastq.cpp / record_stream.cpp between calls (guarded by `mu`): the buffer sets of up to four lanes (pa_process_reads_multi with the
+    // parked by fastq_reads.cpp / record_stream.cpp between calls (guarded by `mu`): the buffer sets of up to four lanes (pa_process_reads_multi with the
     // handle listed several times, concurrent callers)
     std::vector<std::pair<void*, void (*)(void*)>> ingest_caches;
     std::vector<std::pair<void*, void (*)(void*)>> host_pipes;   // ... and of pa_map_tiles_host (host_batch.cpp): streams + staging buffers of the chunks in flight
@@ -130,6 +130,27 @@ void index_host_classes(const pa_index* idx, const uint32_t** ec, const uint32_t
     *ec = idx->h_ec.data();
     *class_ref = idx->h_class_ref.data();
     *device = idx->device;
+}
+// (pa_common.hpp) the one expansion behind pa_map_batch and pa_map_pairs
+void classes_to_csr(const pa_index* idx, pa_read_result* results, uint64_t n, const uint32_t* h_arena, std::vector<uint32_t>& ids, uint64_t* class_offsets,
+                    const uint32_t** class_ids) {
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < n; ++i) total += results[i].class_len;
+    ids.resize(total + 1);
+    uint64_t o = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (class_offsets) class_offsets[i] = o;
+        if (results[i].class_len) {
+            const uint32_t* src = (results[i].class_off & PA_CLASS_REF)
+                                      ? idx->h_ec.data() + 4ull * idx->h_class_ref[results[i].class_off & ~PA_CLASS_REF] + 1
+                                      : h_arena + results[i].class_off;
+            memcpy(ids.data() + o, src, results[i].class_len * 4ull);
+        }
+        results[i].class_off = (uint32_t)o;
+        o += results[i].class_len;
+    }
+    if (class_offsets) class_offsets[n] = o;
+    if (class_ids) *class_ids = ids.data();
 }
 void index_pair_view(pa_index* idx, PairIndexView* out) {
     std::lock_guard<std::mutex> g(idx->mu);
@@ -781,25 +802,7 @@ static int map_batch_host(pa_index* idx, const HostReads& in, uint64_t n, uint32
     PA_HIP_TRY(hipMemcpy(results, idx->b_results.get(), n * sizeof(pa_read_result), hipMemcpyDeviceToHost));
     idx->h_arena.resize(used + 1);
     if (used) PA_HIP_TRY(hipMemcpy(idx->h_arena.data(), idx->b_arena.get(), used * 4, hipMemcpyDeviceToHost));
-    if (class_offsets || class_ids) {
-        uint64_t total = 0;
-        for (uint64_t i = 0; i < n; ++i) total += results[i].class_len;
-        idx->h_class_ids.resize(total + 1);
-        uint64_t o = 0;
-        for (uint64_t i = 0; i < n; ++i) {
-            if (class_offsets) class_offsets[i] = o;
-            if (results[i].class_len) {
-                const uint32_t* src = (results[i].class_off & PA_CLASS_REF)
-                                          ? idx->h_ec.data() + 4ull * idx->h_class_ref[results[i].class_off & ~PA_CLASS_REF] + 1
-                                          : idx->h_arena.data() + results[i].class_off;
-                memcpy(idx->h_class_ids.data() + o, src, results[i].class_len * 4ull);
-            }
-            results[i].class_off = (uint32_t)o;
-            o += results[i].class_len;
-        }
-        if (class_offsets) class_offsets[n] = o;
-        if (class_ids) *class_ids = idx->h_class_ids.data();
-    }
+    if (class_offsets || class_ids) classes_to_csr(idx, results, n, idx->h_arena.data(), idx->h_class_ids, class_offsets, class_ids);
     if (nodes_flat) {
         std::vector<uint32_t> hn(n * (size_t)spill_cap), hl(n);
         PA_HIP_TRY(hipMemcpy(hn.data(), d_nodes, hn.size() * 4, hipMemcpyDeviceToHost));

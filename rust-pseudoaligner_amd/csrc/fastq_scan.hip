@@ -6,7 +6,7 @@
 //   rocPRIM exclusive scan every chunk's first line number; the last entry is the window's number of line breaks
 //   pa_fq_fill_kernel      line_start[l + 1] = position behind line break l (the chunk's prefix + a workgroup scan of the lanes' counts)
 //   pa_fq_records_kernel   one lane per record (four lines): '@' / '+' in place (anything else marks the window ODD: the host then
-//                          scans it with the tolerant rules of fastq.cpp), record.id() (bio 1.5: header[1..] trimmed at its end, cut at
+//                          scans it with the tolerant rules of fastq_text.cpp), record.id() (bio 1.5: header[1..] trimmed at its end, cut at
 //                          the first space), record.seq() without a CR, the longest sequence, and the bytes the whole records take
 //
 // Only whole records count: a window ends behind its last fourth line break, the rest is the next window's head. The encode and

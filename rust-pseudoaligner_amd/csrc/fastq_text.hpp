@@ -1,0 +1,57 @@
+// The text of a FASTQ file as the host sees it (fastq_text.cpp): opened (mapped, or inflated when gzip'ed), scanned for its records a window
+// at a time with the tolerant rules of bio's reader. What the file drivers share: pa_process_reads (fastq_reads.cpp) hands the host's scan
+// the text its GPU scan does not take, pa_count_cells / pa_count_pairs (fastq_pairs.cpp) walk their two files with it.
+#pragma once
+#include <sys/mman.h>
+#include <unistd.h>
+
+#include <cstdint>
+#include <vector>
+
+#include "ingest.hpp"
+
+namespace pa {
+namespace ingest {
+
+constexpr uint64_t DEFAULT_BATCH_READS = 2u << 20;   // (4 Mi reads left 1.3 GB of the mapping and 0.23 GB of text to the last, unoverlapped batch: 33 ms of tear-down per 8 M reads against 12)   // PA_INGEST_BATCH overrides (tests exercise the batch seams with small values)
+
+struct FastqText {   // the text of a FASTQ file as the scan sees it: the mapped file, an inflated gzip stream, or the rewritten records
+    const char* data = nullptr;
+    uint64_t fsize = 0;
+    bool mapped = false;
+    std::vector<char> inflated;     // a gzip'ed FASTQ (utils::open_with_gz, src/utils.rs:45-57) is inflated into memory first
+    std::vector<char> normalized;   // the text rewritten into four-line records, if it did not have that shape
+    uint64_t off = 0;               // text before this offset has been handed out as records (windowed scan of pa_process_reads)
+    const char* map_base = nullptr; // the mapping as mmap returned it (data moves on when the rest of a file is rewritten)
+    uint64_t map_size = 0;
+    int fd = -1;                    // of a mapped file (kept open for the call)
+    void release() {
+        if (mapped) munmap((void*)map_base, map_size);   // (the whole mapping: nobody gives parts of it back any more)
+        if (fd >= 0) close(fd);
+        fd = -1;
+        mapped = false;
+        data = nullptr;
+        fsize = 0;
+    }
+};
+
+int open_fastq(const char* fastq_path, FastqText& t);
+
+// The text in WINDOWS: a mapped file is scanned a window at a time (PA_INGEST_WINDOW bytes), so that pa_process_reads has its first batch on
+// the GPU while the rest of the file is still being scanned; a window ends behind its last whole record. A text held in memory (gzip), a
+// window that is not in four-line shape (then: the rest of the file as one text, rewritten) and the last window are scanned as one text.
+struct WindowScan {
+    FastqText& text;
+    uint64_t window = 256ull << 20;
+    bool windowed, done = false;
+    uint64_t nrec = 0;            // records of the current window
+    const char* base = nullptr;   // the window's text: rec_pos counts from here
+    uint64_t size = 0;            // its bytes
+    uint64_t abs = ~0ull;         // its offset in the file's mapping (~0: not part of one)
+    explicit WindowScan(FastqText& t);
+    // the next window with records in it (nrec = 0: the text has ended). records_before: records of the windows before (error messages)
+    int next(const char* fastq_path, uint64_t records_before, Pool& pool, std::vector<RecPos>& rec_pos, std::vector<std::vector<uint32_t>>& brk);
+};
+
+}  // namespace ingest
+}  // namespace pa

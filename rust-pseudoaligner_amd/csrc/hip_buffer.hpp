@@ -1,8 +1,10 @@
-// Owning HIP allocations of the host runtime and its one check of a HIP call's status.
+// Owning HIP allocations of the host runtime, its one check of a HIP call's status, and what every driver that launches on a stream of its own
+// needs around pa_map_batch_device: the owner of that stream and the one rule for a mapping whose arena turned out too small.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <cstdint>
 
 #include "pa_common.hpp"
 
@@ -64,5 +66,42 @@ private:
 
 template <class T> using DeviceBuffer = HipBuffer<T, Mem::device>;
 template <class T> using PinnedBuffer = HipBuffer<T, Mem::pinned>;
+
+// A non-blocking stream that launches on `idx`. The index keeps a launch context per stream (2 GB of list-mode rows): a stream that is
+// destroyed without pa_index_release_stream strands it there. release() and destruction: synchronise, release the context, destroy.
+// Move-only.
+class IndexStream {
+public:
+    IndexStream() = default;
+    IndexStream(IndexStream&& o) noexcept : idx_(o.idx_), s_(o.s_) { o.s_ = nullptr; }
+    IndexStream& operator=(IndexStream&& o) noexcept { if (this != &o) { release(); idx_ = o.idx_; s_ = o.s_; o.s_ = nullptr; } return *this; }
+    ~IndexStream() { release(); }
+    int create(pa_index* idx) { release(); PA_HIP_TRY(hipStreamCreateWithFlags(&s_, hipStreamNonBlocking)); idx_ = idx; return PA_OK; }
+    void release() {
+        if (!s_) return;
+        (void)hipStreamSynchronize(s_); (void)pa_index_release_stream(idx_, s_); (void)hipStreamDestroy(s_);
+        s_ = nullptr;
+    }
+    hipStream_t get() const { return s_; }
+
+private:
+    pa_index* idx_ = nullptr;
+    hipStream_t s_ = nullptr;
+};
+
+// pa_map_finish on `stream`; while it answers PA_ERR_ARENA_FULL — at most three times — the arena is reallocated to need + need / 8 + 4096
+// entries and relaunch() (a pa_status: everything the caller enqueued that wrote into the arena, the mapping first) runs again. Any
+// other status is returned as it is; *used = the arena entries of the mapping that was finished last.
+template <class Relaunch>
+int map_finish_regrow(pa_index* idx, hipStream_t stream, DeviceBuffer<uint32_t>& arena, uint64_t* used, Relaunch&& relaunch) {
+    uint64_t need = 0;
+    int e = pa_map_finish(idx, stream, used, &need);
+    for (int attempt = 0; e == PA_ERR_ARENA_FULL && attempt < 3; ++attempt) {
+        if ((e = arena.alloc(need + need / 8 + 4096)) != PA_OK) return e;
+        e = relaunch();
+        if (e == PA_OK) e = pa_map_finish(idx, stream, used, &need);
+    }
+    return e;
+}
 
 }  // namespace pa

@@ -114,7 +114,7 @@ int read_fasta(const char* path, Txome& out) {
             finish();
             have = true;
             // record.id() / desc() of bio 1.5's FASTA reader: header[1..].trim_end().splitn(2, char::is_whitespace) — the id ends at
-            // the first white-space character of ANY kind (its FASTQ reader splits on ' ' only: fastq.cpp keeps that rule). The id
+            // the first white-space character of ANY kind (its FASTQ reader splits on ' ' only: fastq_text.cpp keeps that rule). The id
             // names the transcript AND seeds from_acgt_bytes_hashn (src/utils.rs:76), so a tab-separated header must cut the same
             // way or the bases substituted for N differ. ASCII white space only (Unicode spaces in a FASTA header: unpinned).
             auto is_ws = [](char c) { return c == ' ' || c == '\t' || c == '\x0b' || c == '\x0c' || c == '\r' || c == '\n'; };

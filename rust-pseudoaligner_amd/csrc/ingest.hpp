@@ -1,4 +1,4 @@
-// The stages of the host ingest pipeline that pa_process_reads (fastq.cpp: records inside a FASTQ file) and the record stream
+// The stages of the host ingest pipeline that pa_process_reads (fastq_reads.cpp: records inside a FASTQ file) and the record stream
 // (record_stream.cpp: records pushed by the caller) share: worker pool, 2-bit packing into pinned tiles, the GPU leg of one
 // batch (H2D -> pa_map_batch_device -> D2H, arena regrown on demand) and the rendering of the reference's Debug tuples
 // (src/pseudoaligner.rs:455-461, :490). Pure host code around the C ABI's device entry points; header-only, internal.
@@ -416,13 +416,8 @@ inline int batch_launch(pa_index* idx, BatchCtx& c, hipStream_t stream) {
 // waits for the batch; an arena that turned out too small is regrown and the batch mapped (and rendered) again. Afterwards the batch's
 // tuples are in c.h_text[0 .. c.text_bytes) — or on their way there (batch_text_wait)
 inline int batch_finish(pa_index* idx, BatchCtx& c, hipStream_t stream) {
-    uint64_t used = 0, need = 0;
-    int e = pa_map_finish(idx, stream, &used, &need);
-    for (int attempt = 0; e == PA_ERR_ARENA_FULL && attempt < 3; ++attempt) {
-        if ((e = c.d_arena.alloc(need + need / 8 + 4096)) != PA_OK) return e;
-        e = batch_launch(idx, c, stream);
-        if (e == PA_OK) e = pa_map_finish(idx, stream, &used, &need);
-    }
+    uint64_t used = 0;
+    int e = map_finish_regrow(idx, stream, c.d_arena, &used, [&] { return batch_launch(idx, c, stream); });
     if (e != PA_OK) return e;
     // (pa_map_finish synchronised the stream: the lengths — and the speculative text, if any — have arrived)
     c.text_bytes = (size_t)c.h_tot.get()[0];

@@ -19,6 +19,10 @@ int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 // host copy of the class records of a device index (device_index.hip): class c = ec[4 * class_ref[c] + 1 ...]; used to
 // resolve results returned by reference (PA_CLASS_REF) without a device round trip
 void index_host_classes(const pa_index* idx, const uint32_t** ec, const uint32_t** class_ref, int* device);
+// records of a launch -> CSR in read order: the class ids (the table above for PA_CLASS_REF, else h_arena, the launch's arena on the host) back to back
+// in `ids`, results[i].class_off rewritten to record i's offset there, class_offsets[n + 1] and *class_ids filled if given
+void classes_to_csr(const pa_index* idx, pa_read_result* results, uint64_t n, const uint32_t* h_arena, std::vector<uint32_t>& ids, uint64_t* class_offsets,
+                    const uint32_t** class_ids);
 // every index class rendered once as the reference prints its ids ("1, 5, 9", no brackets): class c = text[off[c] .. off[c + 1]). Built on first use.
 void index_host_class_text(pa_index* idx, const uint64_t** off, const char** text);
 // ... and its copy in HBM for the render kernels (render.hip); uploaded on first use. Returns a pa_status

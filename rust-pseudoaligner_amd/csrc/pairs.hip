@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "device_prims.hpp"
+#include "hip_buffer.hpp"
 #include "kernel_utils.hpp"
 #include "kernels.hpp"
 #include "pa_common.hpp"
@@ -527,14 +528,11 @@ int map_mate(pa_index* idx, const uint8_t* ascii, const uint64_t* offsets, uint6
         if ((rc = pa_revcomp_tiles_device(idx, b.tiles.get(), b.lens.get(), n, wpr, b.rc_tiles.get(), s)) != PA_OK) return rc;
         tiles = b.rc_tiles.get();
     }
-    uint64_t cap = pa_map_arena_hint(idx, n), used = 0, need = 0;
-    for (int attempt = 0;; ++attempt) {
-        if ((rc = b.arena.alloc(cap)) != PA_OK) return rc;
-        if ((rc = pa_map_batch_device(idx, tiles, b.lens.get(), n, wpr, allowed, b.results.get(), b.arena.get(), cap, nullptr, s)) != PA_OK) return rc;
-        rc = pa_map_finish(idx, s, &used, &need);
-        if (rc == PA_ERR_ARENA_FULL && attempt < 3) { cap = need + need / 8 + 4096; continue; }
-        return rc;
-    }
+    if ((rc = b.arena.alloc(pa_map_arena_hint(idx, n))) != PA_OK) return rc;
+    auto launch = [&] { return pa_map_batch_device(idx, tiles, b.lens.get(), n, wpr, allowed, b.results.get(), b.arena.get(), b.arena.size(), nullptr, s); };
+    if ((rc = launch()) != PA_OK) return rc;
+    uint64_t used = 0;
+    return map_finish_regrow(idx, s, b.arena, &used, launch);
 }
 
 int map_pairs_impl(pa_index* idx, const uint8_t* ascii1, const uint64_t* offsets1, const uint8_t* ascii2, const uint64_t* offsets2, uint64_t n, int orient,
@@ -558,11 +556,11 @@ int map_pairs_impl(pa_index* idx, const uint8_t* ascii1, const uint64_t* offsets
     PairIndexView v;
     index_pair_view(idx, &v);
     PA_HIP_TRY(hipSetDevice(v.device));
-    hipStream_t s = nullptr;   // a stream of this call's own: its launch context on idx is shared with nobody and released at the end
-    PA_HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    struct StreamGuard { pa_index* idx; hipStream_t s; ~StreamGuard() { (void)hipStreamSynchronize(s); (void)pa_index_release_stream(idx, s); (void)hipStreamDestroy(s); } } guard{idx, s};
+    IndexStream stream;   // a stream of this call's own: its launch context on idx is shared with nobody and released at the end
+    int rc = stream.create(idx);
+    if (rc != PA_OK) return rc;
+    const hipStream_t s = stream.get();
     MateBuffers mb[2];
-    int rc;
     if ((rc = map_mate(idx, ascii1, offsets1, n, (uint32_t)maxlen[0], orient == PA_PAIR_RF, allowed, mb[0], s)) != PA_OK) return rc;
     if ((rc = map_mate(idx, ascii2, offsets2, n, (uint32_t)maxlen[1], orient == PA_PAIR_FR, allowed, mb[1], s)) != PA_OK) return rc;
     DeviceBuffer<uint8_t> scratch;
@@ -585,26 +583,7 @@ int map_pairs_impl(pa_index* idx, const uint8_t* ascii1, const uint64_t* offsets
     std::vector<uint32_t> h_arena(used + 1);
     if (used) PA_HIP_TRY(hipMemcpyAsync(h_arena.data(), d_arena.get(), used * 4, hipMemcpyDeviceToHost, s));
     PA_HIP_TRY(hipStreamSynchronize(s));
-    if (class_offsets || class_ids) {
-        int device = 0;
-        const uint32_t *h_ec = nullptr, *h_ref = nullptr;
-        index_host_classes(idx, &h_ec, &h_ref, &device);
-        uint64_t total = 0;
-        for (uint64_t i = 0; i < n; ++i) total += results[i].class_len;
-        t_class_ids.resize(total + 1);
-        uint64_t o = 0;
-        for (uint64_t i = 0; i < n; ++i) {
-            if (class_offsets) class_offsets[i] = o;
-            if (results[i].class_len) {
-                const uint32_t* src = (results[i].class_off & PA_CLASS_REF) ? h_ec + 4ull * h_ref[results[i].class_off & ~PA_CLASS_REF] + 1 : h_arena.data() + results[i].class_off;
-                memcpy(t_class_ids.data() + o, src, results[i].class_len * 4ull);
-            }
-            results[i].class_off = (uint32_t)o;
-            o += results[i].class_len;
-        }
-        if (class_offsets) class_offsets[n] = o;
-        if (class_ids) *class_ids = t_class_ids.data();
-    }
+    if (class_offsets || class_ids) classes_to_csr(idx, results, n, h_arena.data(), t_class_ids, class_offsets, class_ids);
     return PA_OK;
 }
 

@@ -1,7 +1,7 @@
 // process_reads (src/pseudoaligner.rs:420-514) for a caller that HOLDS the reader: the reference's signature consumes an open
 // fastq::Reader (:421), so a drop-in replacement cannot ask for a path. The caller pushes the records it reads — ids as
 // record.id() gives them (:456), sequences as record.seq() (:449) — and pulls the reference's Debug tuples (:490) in push order.
-// Behind the two calls runs the batch pipeline of fastq.cpp with its stages overlapped (ingest.hpp):
+// Behind the two calls runs the batch pipeline of fastq_reads.cpp with its stages overlapped (ingest.hpp):
 //
 //   push     records are copied into the batch being filled; a full batch is 2-bit packed into pinned tiles by the worker
 //            pool and launched (H2D -> pa_map_batch_device -> D2H on the stream's own HIP stream), then the PREVIOUS batch —

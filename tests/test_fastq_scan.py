@@ -1,4 +1,4 @@
-"""The scan stage of pa_process_reads on the CPU tier (pa_fastq_scan_host, csrc/fastq.cpp): record count, header / sequence
+"""The scan stage of pa_process_reads on the CPU tier (pa_fastq_scan_host, csrc/fastq_text.cpp): record count, header / sequence
 extents against a Python reading of the same text — the acceptance rules of bio 1.5's fastq reader as process_reads applies
 them (src/pseudoaligner.rs:430-447): LF / CRLF, no final line break, trailing blank lines, empty sequences (also as the LAST
 record), wrapped records, gzip members, and what is refused."""

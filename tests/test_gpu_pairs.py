@@ -247,3 +247,28 @@ def test_count_pairs_rejects_pairs_that_do_not_match(tmp_path, monkeypatch):
     assert L.pa_count_pairs(al._h, None, p2.encode(), 0, 2, 1, out.ctypes.data, None, None) == E
     assert L.pa_count_pairs(al._h, p1.encode(), p2.encode(), 0, 2, 1, None, None, None) == E
     assert L.pa_count_pairs(None, p1.encode(), p2.encode(), 0, 2, 1, out.ctypes.data, None, None) == E
+
+
+def test_file_drivers_leave_nothing_behind_on_the_index(tmp_path, monkeypatch):
+    """pa_count_pairs, pa_count_cells, pa_count_pairs and pa_map_batch on ONE index in one process: each file driver creates its streams and gives
+    their launch contexts back to the index when it returns, so the second table equals the first word for word and the host-buffer call that
+    follows sees the index as a fresh one does"""
+    name = "gencode_k20_fr"
+    host, r1, r2, orient = pairs_cases.case(name)
+    al = _aligner(name)
+    p1, p2 = _write_pairs(tmp_path, r1, r2, "plain")
+    monkeypatch.setenv("PA_INGEST_BATCH", "700")            # three batches: both batch buffers and a last partial batch
+    counts, stats = al.count_pairs(p1, p2, orient)
+    assert np.array_equal(counts.astype(np.int64), _model(name)[4]) and stats["pairs"] == len(r1)
+    # the same files as a single-cell run: the first 28 bases of mate 1 stand in for barcode + UMI, mate 2 is mapped
+    wl = sorted({s[:16] for s in r1 if len(s) >= 28 and set(s[:16]) <= set("ACGT")})[:64]
+    (tmp_path / "wl.txt").write_text("\n".join(wl) + "\n")
+    out = tmp_path / "cells"
+    out.mkdir()
+    cst = al.count_cells(host, p1, p2, tmp_path / "wl.txt", out, 16, 12, num_threads=4)
+    assert cst["reads"] == len(r1) and (out / "matrix.mtx").read_text().startswith("%%MatrixMarket")
+    counts2, stats2 = al.count_pairs(p1, p2, orient)
+    assert counts2.tobytes() == counts.tobytes() and stats2 == stats
+    res, coff, cids = al.map_batch(r1)
+    o_res, o_coff, o_ids, _ = helpers.Oracle(host).map_reads(r1, 2, 4)
+    helpers.assert_same_as_oracle(res, coff, cids, o_res, o_coff, o_ids, "map_batch after the file drivers")

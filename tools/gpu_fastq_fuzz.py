@@ -1,4 +1,4 @@
-"""Fuzz of pa_process_reads' host stages (csrc/fastq.cpp: line-break scan, record positions, 16-base packing, formatter fast
+"""Fuzz of pa_process_reads' host stages (csrc/fastq_text.cpp, fastq_reads.cpp: line-break scan, record positions, 16-base packing, formatter fast
 paths) against the oracle's tuples: random slices of small.fq rewritten with random ids (quotes, backslashes, control bytes,
 tabs, trailing blanks), random read lengths (0..300: word counts change between batches), lower case / N / IUPAC letters,
 LF or CRLF, with or without a final line break, trailing blank lines, wrapped records, gzip; random batch sizes and thread
