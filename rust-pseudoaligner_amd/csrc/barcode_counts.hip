@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void pa_barcode_keys_kernel(const pa_read_resu
 
 namespace pa {
 
-// device_index.hip hands over the pieces of the index this needs
+// pa_counts_by_barcode_device (device_index.hip) hands over the pieces of the index this needs
 int barcode_counts(const DevIndexView& ix, const uint32_t* class_table, uint64_t class_table_size, const pa_read_result* d_results,
                    const uint32_t* d_arena, const uint32_t* d_barcode, uint64_t n, uint32_t barcode_bits, uint64_t* d_keys, uint32_t* d_vals,
                    uint64_t* n_entries, hipStream_t stream) {

@@ -205,12 +205,12 @@ struct pa_comm {
     DeviceBuffer<unsigned long long> d_scalar;   // two u64 for the size / status exchange of the overflow gather
 };
 
-// hooks for device_index.hip: what the map launch needs to know about an attached overflow table
+// hooks for map_launch_locked (device_index.hip): what the map launch needs to know about an attached overflow table
 namespace pa {
 
 void overflow_launch_params(pa_overflow* o, MapParams& p) { p.novel_status = o->d_ctl.get() + 1; }
 
-// files the novel results a launch listed (per stream: device_index.hip) in the table; same stream, right behind the launch
+// files the novel results a launch listed (per stream: LaunchCtx::novel, device_index.hpp) in the table; same stream, right behind the launch
 int overflow_after_map(pa_overflow* o, const uint32_t* novel_list, const unsigned long long* novel_ctr, uint64_t novel_cap, const uint32_t* d_arena,
                        hipStream_t stream) {
     hipLaunchKernelGGL(pa_overflow_insert_kernel, dim3(1024), dim3(256), 0, stream, novel_list, novel_ctr, novel_cap, d_arena, o->d_keys.get(), o->d_meta.get(),

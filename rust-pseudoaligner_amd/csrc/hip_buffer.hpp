@@ -5,6 +5,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 #include "pa_common.hpp"
 
@@ -56,7 +57,6 @@ public:
     }
 
     T* get() const { return p_; }
-    template <class U> U* as() const { return reinterpret_cast<U*>(p_); }
     size_t size() const { return n_; }
 
 private:
@@ -66,6 +66,21 @@ private:
 
 template <class T> using DeviceBuffer = HipBuffer<T, Mem::device>;
 template <class T> using PinnedBuffer = HipBuffer<T, Mem::pinned>;
+
+// grow-only device scratch of `need` elements: a quarter more than asked for (and 256 bytes' worth) when it has to grow
+template <class T> int grow(DeviceBuffer<T>& b, size_t need) { return b.reserve(need, need + (need + 3) / 4 + 256 / sizeof(T)); }
+
+// n elements to a new device buffer (16 bytes when there are none)
+template <class T> int upload(DeviceBuffer<T>& dst, const T* src, size_t n) {
+    const int e = dst.alloc(n ? n : 16 / sizeof(T));
+    if (e != PA_OK) return e;
+    if (n) PA_HIP_TRY(hipMemcpy(dst.get(), src, n * sizeof(T), hipMemcpyHostToDevice));
+    return PA_OK;
+}
+template <class T> int upload(DeviceBuffer<T>& dst, const std::vector<T>& src) { return upload(dst, src.data(), src.size()); }
+
+// makes `device` current; PA_ERR_NO_DEVICE without a usable GPU, PA_ERR_INVALID_ARG for a device that does not exist (device_plumbing.hip)
+int use_device(int device);
 
 // A non-blocking stream that launches on `idx`. The index keeps a launch context per stream (2 GB of list-mode rows): a stream that is
 // destroyed without pa_index_release_stream strands it there. release() and destruction: synchronise, release the context, destroy.
@@ -89,19 +104,24 @@ private:
     hipStream_t s_ = nullptr;
 };
 
-// pa_map_finish on `stream`; while it answers PA_ERR_ARENA_FULL — at most three times — the arena is reallocated to need + need / 8 + 4096
-// entries and relaunch() (a pa_status: everything the caller enqueued that wrote into the arena, the mapping first) runs again. Any
-// other status is returned as it is; *used = the arena entries of the mapping that was finished last.
-template <class Relaunch>
-int map_finish_regrow(pa_index* idx, hipStream_t stream, DeviceBuffer<uint32_t>& arena, uint64_t* used, Relaunch&& relaunch) {
+// finish(&need) — pa_map_finish of a mapping, or its equal for a caller that holds the launch context's lock; while it answers PA_ERR_ARENA_FULL,
+// at most three times, the arena is reallocated to an eighth more than was needed plus 4096 entries and relaunch() (a pa_status: everything the
+// caller enqueued that wrote into the arena, the mapping first) runs again. Any other status is returned as it is.
+template <class Finish, class Relaunch>
+int map_finish_regrow(DeviceBuffer<uint32_t>& arena, Finish&& finish, Relaunch&& relaunch) {
     uint64_t need = 0;
-    int e = pa_map_finish(idx, stream, used, &need);
+    int e = finish(&need);
     for (int attempt = 0; e == PA_ERR_ARENA_FULL && attempt < 3; ++attempt) {
         if ((e = arena.alloc(need + need / 8 + 4096)) != PA_OK) return e;
         e = relaunch();
-        if (e == PA_OK) e = pa_map_finish(idx, stream, used, &need);
+        if (e == PA_OK) e = finish(&need);
     }
     return e;
+}
+// ... with pa_map_finish on `stream`; *used = the arena entries of the mapping that was finished last
+template <class Relaunch>
+int map_finish_regrow(pa_index* idx, hipStream_t stream, DeviceBuffer<uint32_t>& arena, uint64_t* used, Relaunch&& relaunch) {
+    return map_finish_regrow(arena, [&](uint64_t* need) { return pa_map_finish(idx, stream, used, need); }, relaunch);
 }
 
 }  // namespace pa

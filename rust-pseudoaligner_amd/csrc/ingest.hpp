@@ -348,8 +348,8 @@ inline int window_ensure_scan(BatchCtx& c, uint64_t lines) {
         if ((e = c.d_chunk.alloc(want)) || (e = c.d_first.alloc(want)) || (e = c.d_fq_tmp.alloc(c.fq_tmp_bytes ? c.fq_tmp_bytes : 16))) return e;
         c.chunk_cap = want;
     }
-    const uint64_t need = lines ? lines + 8 : (c.raw_end - c.raw_begin) / 32 + 1024;
-    if ((e = c.d_ls.reserve(need, need + need / 8))) return e;
+    const uint64_t starts = lines ? lines + 8 : (c.raw_end - c.raw_begin) / 32 + 1024;
+    if ((e = c.d_ls.reserve(starts, starts + starts / 8))) return e;
     return window_ensure_recs(c, c.d_ls.size() / 4, false);
 }
 // the window's records found on the GPU, asynchronous on `stream`: c.h_info is valid once c.ev_info has passed

@@ -20,7 +20,7 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
     return v;
 }
 
-// hash of a sorted id list; must equal list_hash_host (device_index.hip)
+// hash of a sorted id list; must equal list_hash_host (device_index.hip: pa_index_create)
 __device__ __forceinline__ uint64_t list_hash_dev(const uint32_t* v, uint32_t n) {
     uint64_t h = 0x243f6a8885a308d3ull ^ n;
     for (uint32_t i = 0; i < n; ++i) h = pa_mix64(h ^ v[i]) + 0x9e3779b97f4a7c15ull;

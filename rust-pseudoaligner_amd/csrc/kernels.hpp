@@ -1,6 +1,8 @@
-// Kernel parameter blocks and launch entry points shared by map_pool.hip, kernels.hip and device_index.hip.
+// Kernel parameter blocks, the map launch's control block and launch entry points shared by map_pool.hip, kernels.hip and device_index.hip.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <cstddef>
 
 #include "device_layout.hpp"
 
@@ -16,6 +18,22 @@ constexpr uint32_t PA_KEY_BIN_SHIFT = 15;       // count_sort.hip: a bin = 32768
 constexpr uint32_t PA_STATUS_ARENA_FULL = 1u;
 constexpr uint32_t PA_STATUS_SPILL_OVERFLOW = 2u;
 constexpr unsigned long long PA_NOVEL_LIST_FULL = 4ull;   // OVF_STATUS_LIST_FULL of collective.hip
+constexpr uint32_t ST_NSTAT = 15;   // scheduler statistics entries (PA_MAP_STATS): one per state of lane_steps.hpp, the dual (forward + probe) iterations, the plain
+                                    // forward step in three parts; map_pool.hip asserts ST_COUNT + 4
+
+// The control block of a map launch: one per launch context (device_index.hip), its first sizeof(MapCtl) bytes cleared before every launch. The kernels
+// reach it through the pointers of MapParams only. The hot atomics (arena_top, tile_ctr, the three stream heads) lie where they were measured.
+struct MapCtl {
+    unsigned long long arena_top;   // arena entries handed out (every wave's partly used chunk included)
+    uint32_t status;                // PA_STATUS_*
+    uint32_t tile_ctr;
+    unsigned long long stats[3 * ST_NSTAT];   // MapParams::dbg
+    unsigned long long pad0[9];
+    unsigned long long novel_ctr, keys_top, defer_top;
+    unsigned long long pad1[5];
+};
+static_assert(offsetof(MapCtl, arena_top) == 0 && offsetof(MapCtl, status) == 8 && offsetof(MapCtl, tile_ctr) == 12 && offsetof(MapCtl, stats) == 16, "MapCtl head");
+static_assert(offsetof(MapCtl, novel_ctr) == 448 && offsetof(MapCtl, keys_top) == 456 && offsetof(MapCtl, defer_top) == 464 && sizeof(MapCtl) == 512, "MapCtl stream heads");
 
 struct MapParams {
     DevIndexView ix;
@@ -55,7 +73,7 @@ struct MapParams {
     unsigned long long* novel_ctr;     // results listed so far (may run past novel_cap: then novel_status gets PA_NOVEL_LIST_FULL)
     unsigned long long* novel_status;
     uint64_t novel_cap;                // pairs
-    // optional scheduler statistics (PA_MAP_STATS): [ST_COUNT] iterations, [ST_COUNT] slots served, [ST_COUNT] clock ticks per state
+    // optional scheduler statistics (PA_MAP_STATS): [ST_NSTAT] iterations, [ST_NSTAT] slots served, [ST_NSTAT] clock ticks per state
     unsigned long long* dbg;
     uint32_t ablate;           // A/B knob (PA_MAP_ABLATE; 0 in production): 1 = window-mode results are not stored, 2 = no class counts,
                                // 4 = no dual (forward + probe) iterations, 8 = output steps do not refill the slots they free
@@ -132,7 +150,7 @@ int overflow_after_map(pa_overflow* o, const uint32_t* novel_list, const unsigne
                        hipStream_t stream);
 int overflow_device(const pa_overflow* o);
 
-// what the pair stage (pairs.hip) needs of an index handle, beside index_host_classes (device_index.hip)
+// what the pair stage (pairs.hip) needs of an index handle (device_index.hip), beside index_host_classes
 struct PairIndexView {
     DevIndexView dv;
     const uint32_t* class_table;

@@ -75,7 +75,7 @@ __device__ __forceinline__ DevIndexView view_of(karg_ptr p) {   // member-wise: 
     return v;
 }
 
-constexpr uint32_t ST_NSTAT = ST_COUNT + 4;   // statistics entries: one per state, the dual (forward + probe) iterations, and the plain forward step
+static_assert(ST_NSTAT == ST_COUNT + 4, "kernels.hpp");   // statistics entries: one per state, the dual (forward + probe) iterations, and the plain forward step
                                                // split into issue / wait / compute (PA_MAP_STATS only)
 constexpr uint32_t ST_DUAL = ST_COUNT;
 constexpr uint32_t POOL_FIXED = 960;   // per wave: arena chunk {cur, end} (16 B), statistics, key chunk {cur, end} (8 B at +256), state bytes (128 B), pop list (64 B)

@@ -19,7 +19,7 @@ int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 // host copy of the class records of a device index (device_index.hip): class c = ec[4 * class_ref[c] + 1 ...]; used to
 // resolve results returned by reference (PA_CLASS_REF) without a device round trip
 void index_host_classes(const pa_index* idx, const uint32_t** ec, const uint32_t** class_ref, int* device);
-// records of a launch -> CSR in read order: the class ids (the table above for PA_CLASS_REF, else h_arena, the launch's arena on the host) back to back
+// map_batch.hip: records of a launch -> CSR in read order: the class ids (the table above for PA_CLASS_REF, else h_arena, the launch's arena on the host) back to back
 // in `ids`, results[i].class_off rewritten to record i's offset there, class_offsets[n + 1] and *class_ids filled if given
 void classes_to_csr(const pa_index* idx, pa_read_result* results, uint64_t n, const uint32_t* h_arena, std::vector<uint32_t>& ids, uint64_t* class_offsets,
                     const uint32_t** class_ids);
@@ -30,12 +30,12 @@ int index_device_class_text(pa_index* idx, const uint64_t** d_off, const uint8_t
 // pairs.hip: an upper bound on the arena entries pa_pairs_combine_device can need for these mate records (the shorter list of every pair with two
 // mapped mates, the list of a mate mapped alone), summed on the device into the first 8 bytes of d_scratch; synchronises `stream`
 int pairs_arena_bound(pa_index* idx, const pa_read_result* d_res1, const pa_read_result* d_res2, uint64_t n_pairs, void* d_scratch, void* stream, uint64_t* bound);
-// One opaque object the FASTQ driver parks on the index between calls (its pinned + device batch buffers: allocating them
-// costs more than packing a batch). take() hands it to the caller and empties the slot, so concurrent calls never share
-// it; put() stores it back (or frees it with `free_fn` when another call already parked one). pa_index_destroy frees it.
+// Opaque objects the FASTQ drivers park on the index between calls (their pinned + device batch buffers: allocating them
+// costs more than packing a batch; up to four, `Parked` of device_index.hpp). take() hands one to the caller alone, so concurrent
+// calls never share it; put() stores it back (or frees it with `free_fn` when four are parked). pa_index_destroy frees them.
 void* index_take_ingest_cache(pa_index* idx);
 void index_put_ingest_cache(pa_index* idx, void* cache, void (*free_fn)(void*));
-// the same for the streams and staging buffers of pa_map_tiles_host (host_batch.cpp)
+// the same for the streams and staging buffers of pa_map_tiles_host (host_batch.cpp): up to two
 void* index_take_host_pipe(pa_index* idx);
 void index_put_host_pipe(pa_index* idx, void* pipe, void (*free_fn)(void*));
 
