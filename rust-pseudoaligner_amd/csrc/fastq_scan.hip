@@ -111,9 +111,9 @@ __global__ __launch_bounds__(256) void pa_fq_records_kernel(const uint8_t* __res
         const uint32_t p0 = line_start[4 * r], p1 = line_start[4 * r + 1], p2 = line_start[4 * r + 2];
         const uint32_t e0 = p1 - 1, e1 = p2 - 1;            // the line breaks that end the header and the sequence line
         odd = t[p0] != '@' || t[p2] != '+';
-        // record.id() (:456): header[1..] without trailing white space, up to its first space (a tab stays part of the id)
+        // record.id() (:456): header[1..] without trailing white space (str::trim_end: 0x09-0x0D and the blank), up to its first space (a tab stays part of the id)
         uint32_t hend = e0, ide = p0 + 1;
-        while (hend > p0 + 1 && (t[hend - 1] == '\r' || t[hend - 1] == ' ' || t[hend - 1] == '\t' || t[hend - 1] == '\n')) --hend;
+        while (hend > p0 + 1 && (t[hend - 1] == ' ' || (uint8_t)(t[hend - 1] - 0x09) <= 0x0D - 0x09)) --hend;
         while (ide < hend && t[ide] != ' ') ++ide;
         const uint32_t id_len = e0 > p0 ? ide - (p0 + 1) : 0u;
         const uint32_t len = e1 - p1;

@@ -254,9 +254,10 @@ int scan_fastq(const char* fastq_path, FastqText& t, uint64_t avail, bool last, 
                             rp[rec].hdr = (uint32_t)std::min<uint64_t>(e - p, 0xFFFFFFFFull);
                             if (data[p] != '@') odd(rec);
                             // record.id() (:456) = header[1..].trim_end().splitn(2, ' ').next() in bio 1.5: cut at the first SPACE only (a tab stays
-                            // part of the id), after trailing white space was trimmed. Found here, while the header's bytes are in the cache
+                            // part of the id), after trailing white space was trimmed (str::trim_end: White_Space, in ASCII 0x09-0x0D — VT and FF too — and
+                            // the blank). Found here, while the header's bytes are in the cache
                             uint64_t hend = e, ide = p + 1;
-                            while (hend > p + 1 && (data[hend - 1] == '\r' || data[hend - 1] == ' ' || data[hend - 1] == '\t' || data[hend - 1] == '\n')) --hend;
+                            while (hend > p + 1 && (data[hend - 1] == ' ' || (uint8_t)(data[hend - 1] - 0x09) <= 0x0D - 0x09)) --hend;
                             while (ide < hend && data[ide] != ' ') ++ide;
                             rp[rec].id_len = e > p ? (uint32_t)std::min<uint64_t>(ide - (p + 1), 0xFFFFFFFFull) : 0u;
                             break;

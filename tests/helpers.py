@@ -1,5 +1,5 @@
 """Test-side plumbing: loads the product package, and wraps the two CHECKERS (oracle/ C restatement, tests/emu lane
-emulator) and the probe of csrc/device_prims.hpp (tests/prims) with ctypes. Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg use this module."""
+emulator) and the probes of csrc/device_prims.hpp (tests/prims) and of the text kernels (tests/text) with ctypes. Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg use this module."""
 from __future__ import annotations
 
 import ctypes as C
@@ -29,11 +29,13 @@ def _load_recipe(path, name):
 _oracle_build = _load_recipe(ROOT / "oracle" / "build.py", "pa_oracle_build")
 _emu_build = _load_recipe(ROOT / "tests" / "emu" / "build.py", "pa_emu_build")
 _prims_build = _load_recipe(ROOT / "tests" / "prims" / "build.py", "pa_prims_build")
+_text_build = _load_recipe(ROOT / "tests" / "text" / "build.py", "pa_text_build")
 
 
 def build_all(force: bool = False):
-    """product (hipcc, gfx950) + the two checkers (gcc / g++) + the device_prims probe (hipcc, gfx950)"""
-    return _build.build_product(force), _oracle_build.build_oracle(force), _emu_build.build_emu(force), _prims_build.build_probe(force)
+    """product (hipcc, gfx950) + the two checkers (gcc / g++) + the device_prims probe and the text probe (hipcc, gfx950)"""
+    return (_build.build_product(force), _oracle_build.build_oracle(force), _emu_build.build_emu(force), _prims_build.build_probe(force),
+            _text_build.build_probe(force))
 
 GOLDEN = ROOT / "tests" / "golden"
 FASTA = GOLDEN / "gencode_small.fa"
@@ -54,6 +56,7 @@ class Counters(C.Structure):
 _oracle_lib = None
 _emu_lib = None
 _prims_lib = None
+_text_lib = None
 
 
 def oracle_lib():
@@ -125,6 +128,26 @@ def prims_lib():
         L.probe_chain.argtypes = [vp, vp, u64, vp, vp, vp, vp, u64, u32, vp, vp, u64, vp, vp]
         _prims_lib = L
     return _prims_lib
+
+
+def text_lib():
+    """tests/text/text_probe.hip: the launch functions of csrc/fastq_scan.hip and csrc/render.hip, and the host's scan, on host arrays.
+    PA_TEXT_PROBE_SO: another build of the probe to load (a mutated one, when the tests themselves are tested)."""
+    global _text_lib
+    if _text_lib is None:
+        import os
+        L = C.CDLL(os.environ.get("PA_TEXT_PROBE_SO") or str(_text_build.build_probe()))
+        vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
+        L.tp_last_error.restype = C.c_char_p
+        L.tp_guard.restype = L.tp_text_slack.restype = L.tp_info_bytes.restype = u64
+        L.tp_flag_buckets.restype = L.tp_chunks.restype = u32
+        L.tp_chunks.argtypes = [u64, u64]
+        L.tp_scan.argtypes = [vp, u64, u64, u64, vp, u64, vp, u64, vp, vp, u64, vp, u64, vp, vp, vp]
+        L.tp_encode_rec.argtypes = [vp, u64, vp, u64, u32, vp, vp]
+        L.tp_render.argtypes = [vp, u64, vp, u64, vp, u64, vp, vp, vp, u64, vp, u64, u64, C.c_uint8, vp, vp, vp, u64, u64, vp, u64, u64, vp]
+        L.tp_host_scan.argtypes = [C.c_char_p, C.c_int, vp, vp, vp, vp, vp, u64]
+        _text_lib = L
+    return _text_lib
 
 
 def pack_read(seq: str) -> np.ndarray:
