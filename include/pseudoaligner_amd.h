@@ -66,7 +66,8 @@ typedef enum pa_status {
     PA_ERR_ARENA_FULL = -7,    /* caller-provided class arena too small; required size reported */
     PA_ERR_UNSUPPORTED = -8,
     PA_ERR_INTERNAL = -9,
-    PA_ERR_BUFFER_TOO_SMALL = -10   /* pa_records_pull: the caller's buffer cannot hold even the next tuple; *n_bytes = the bytes it needs */
+    PA_ERR_BUFFER_TOO_SMALL = -10,  /* pa_records_pull: the caller's buffer cannot hold even the next tuple; *n_bytes = the bytes it needs */
+    PA_ERR_NOT_BGZF = -11           /* pa_bgzf_scan: the bytes are not BGZF from first to last (ordinary gzip, a truncated member, ...) */
 } pa_status;
 
 /* ------------------------------------------------------------------------------------------
@@ -325,7 +326,7 @@ int pa_map_batch_nodes(pa_index* idx, const uint8_t* ascii, const uint64_t* offs
  * ("-" = stdout) in INPUT order (the reference's order is completion order, :490). num_threads sizes the
  * host parse/format pool. n_reads_out/n_flagged_out may be NULL.
  * Input: plain or gzip'ed (multi-member) FASTQ (a gzip'ed file is inflated into host memory first — one zlib stream, some 0.4 GB/s, and the whole
- * text resident: the reference's CLI takes plain files only, src/bin/pseudoaligner.rs:139; inflate large files upstream) in the four-line form every sequencer writes — "@id ...", sequence, "+...",
+ * text resident: the reference's CLI takes plain files only, src/bin/pseudoaligner.rs:139; inflate large files upstream — or recompress them once with `bgzip`: a file that is BGZF from first byte to last (pa_bgzf_scan accepts it) is NOT inflated by the host. Its members' compressed bytes go to HBM as they lie in the file, window by window, and are inflated there (pa_bgzf_inflate_device's kernel, on the copy stream ahead of the scan); the host inflates, member by member, only the unfinished record in front of a window, the last piece of the text and the rest of a text that is not in four-line shape. A corrupt member ends the call with PA_ERR_FORMAT, "corrupt gzip stream", naming the member's file offset and the reason; unlike the one-stream path, which finds corruption before the output file is created, the output may then already hold the tuples of the windows before. PA_INGEST_BGZF=0 forces the one-stream path) in the four-line form every sequencer writes — "@id ...", sequence, "+...",
  * qualities; LF or CRLF; trailing blank lines tolerated (a last record with an empty sequence is still that record). A file whose records are not four lines each (sequence or qualities
  * wrapped over several lines, which bio's reader accepts) is first rewritten into that form by a sequential pass (as many
  * quality lines as sequence lines, as bio 1.5 reads them), then scanned in parallel like any other. PA_ERR_FORMAT with
@@ -383,6 +384,12 @@ void pa_record_stream_destroy(pa_record_stream* s);
  * out[4] waiting for the rendered tuples, out[5] waiting for the writer (0 for a record stream), out[6] the whole call (streams: the
  * sum of the others), out[7] reads. */
 #define PA_INGEST_STAGES 8
+/* What the last pa_process_reads[_multi] call of this thread read: out[0] text_kind (0 a plain mapped file, 1 gzip inflated by the host, 2 BGZF inflated on
+ * the GPU), out[1] members of the file (0 unless BGZF), out[2] members inflated on the GPU (launches: a member of a window that was read twice counts twice),
+ * out[3] members inflated by the host, out[4] bytes copied host to device as input (text, compressed bytes, member rows, record tables), out[5] bytes of text
+ * that first existed in HBM. */
+#define PA_INGEST_INPUT_STATS 6
+int pa_process_reads_input_stats(uint64_t out[PA_INGEST_INPUT_STATS]);
 int pa_process_reads_stage_seconds(double out[PA_INGEST_STAGES]);
 int pa_record_stream_stage_seconds(const pa_record_stream* s, double out[PA_INGEST_STAGES]);
 
@@ -394,6 +401,54 @@ int pa_record_stream_stage_seconds(const pa_record_stream* s, double out[PA_INGE
  * window that is not in shape: offsets of the records from there on refer to the rewritten rest). Every output pointer but n_records may be NULL. */
 int pa_fastq_scan_host(const char* fastq_path, int num_threads, uint64_t* n_records, uint64_t* starts, uint32_t* header_len,
                        uint32_t* seq_len, uint64_t capacity, int* text_kind);
+
+/* ---------------- BGZF: blocked gzip (bgzip / htslib), inflated on the GPU ----------------
+ * A BGZF file is a multi-member gzip whose members hold at most 64 KiB of text each and carry their own size in a "BC" extra subfield,
+ * so that the members are found without inflating and are independent of each other. One row of the member table per member: */
+typedef struct pa_bgzf_member {
+    uint64_t in_off;     /* first byte of the member's DEFLATE payload in the compressed bytes */
+    uint64_t out_off;    /* sum of the ISIZE of the members before it */
+    uint64_t file_off;   /* where the member (its gzip header) starts in the compressed bytes: for error messages */
+    uint32_t in_len;     /* payload bytes */
+    uint32_t out_len;    /* ISIZE, 0 .. 65536 */
+    uint32_t crc32;      /* CRC-32 of the text, from the trailer */
+    uint32_t reserved;   /* 0 */
+} pa_bgzf_member;
+#define PA_BGZF_MAX_ISIZE 65536u
+/* Host only. Walks data[0, size) from gzip header to gzip header, hopping by BSIZE, and returns PA_OK only if the bytes are BGZF from first
+ * to last: every member has the magic 1f 8b 08 with FEXTRA set and no reserved flag, a "BC" subfield of length 2 anywhere among its
+ * subfields (which fill XLEN exactly), FNAME / FCOMMENT / FHCRC skipped where present, a block that lies inside the bytes and holds
+ * header and trailer, and ISIZE <= 65536. Anything else (ordinary gzip, a truncated last member, a BSIZE that points past the end, no bytes
+ * at all) is PA_ERR_NOT_BGZF with *n = 0 and *text_bytes = 0. A file without the 28-byte EOF block is accepted, and so are empty members
+ * anywhere. *n = the members, *text_bytes = the sum of ISIZE. members == NULL only counts; otherwise the first min(*n, cap) rows are
+ * written and PA_ERR_BUFFER_TOO_SMALL is returned when cap < *n. */
+int pa_bgzf_scan(const uint8_t* data, uint64_t size, pa_bgzf_member* members, uint64_t cap, uint64_t* n, uint64_t* text_bytes);
+/* d_status[i] of pa_bgzf_inflate_device: 0, or why member i is refused. The verdict is zlib's: a member is accepted exactly when zlib
+ * inflates its payload as one raw DEFLATE stream that ends inside the payload's last byte, gives out_len bytes and has the trailer's CRC-32. */
+#define PA_INFLATE_OK 0u
+#define PA_INFLATE_BAD_MEMBER 1u          /* the table row itself: payload beyond comp_bytes, out_len > 65536, text beyond text_cap */
+#define PA_INFLATE_BAD_BLOCK_TYPE 2u      /* reserved block type 3 */
+#define PA_INFLATE_STORED_LEN 3u          /* stored block: NLEN is not the complement of LEN */
+#define PA_INFLATE_TOO_MANY_SYMBOLS 4u    /* dynamic block: more than 286 literal/length or 30 distance codes */
+#define PA_INFLATE_BAD_CODE_LENGTHS 5u    /* over-subscribed code, or an incomplete one that is not a single code of one bit */
+#define PA_INFLATE_BAD_REPEAT 6u          /* code 16 with nothing to repeat, or a repeat that runs past HLIT + HDIST */
+#define PA_INFLATE_NO_END_OF_BLOCK 7u     /* dynamic block without a code for symbol 256 */
+#define PA_INFLATE_BAD_SYMBOL 8u          /* unused code, literal/length symbol 286 / 287, distance symbol 30 / 31 */
+#define PA_INFLATE_DISTANCE_TOO_FAR 9u    /* a match reaches in front of the member's first byte */
+#define PA_INFLATE_INPUT_EXHAUSTED 10u    /* the payload ends inside the stream */
+#define PA_INFLATE_TRAILING_INPUT 11u     /* the stream ends before the payload's last byte */
+#define PA_INFLATE_OUTPUT_TOO_LONG 12u    /* more text than ISIZE */
+#define PA_INFLATE_OUTPUT_TOO_SHORT 13u   /* less */
+#define PA_INFLATE_CRC_MISMATCH 14u
+/* Inflates the members d_members[0, n_members) (a device copy of rows of the table above, in_off relative to d_comp) on HIP device `device`,
+ * asynchronously on `stream`: member i's text goes to d_text[out_off_i - out_off_0 ...), so a run of consecutive rows can be passed as it
+ * stands in the table. One wave per member; a member whose status is not 0 may have written any part of ITS out_len bytes, and nothing is
+ * ever written outside a member's own bytes or read outside its own payload. d_status[n_members]. PA_ERR_INVALID_ARG for null pointers;
+ * corrupt payloads are not an error of the call: they are the statuses. */
+int pa_bgzf_inflate_device(int device, const uint8_t* d_comp, uint64_t comp_bytes, const pa_bgzf_member* d_members, uint64_t n_members,
+                           uint8_t* d_text, uint64_t text_cap, uint32_t* d_status, void* stream);
+/* the name of a status above ("crc mismatch"), for messages; "unknown" beyond them */
+const char* pa_inflate_status_name(uint32_t status);
 
 /* ---------------- equivalence-class count table (multi-GPU reduction unit) ---------------- */
 /* counts[c] += number of reads whose class equals index class c; reads with a novel (non-index)

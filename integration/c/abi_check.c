@@ -179,6 +179,23 @@ int main(int argc, char** argv) {
     uint64_t merged_words = 0;
     EXPECT(pa_overflow_merge(bufs, nwords, 2, merged, 16, &merged_words) == PA_OK && merged_words == 7 && merged[3] == 4);
 
+    /* BGZF: the member table of a two-member file (28 bytes of text, then the EOF block), found on the host */
+    static const uint8_t bgzf_file[] = {0x1f, 0x8b, 0x08, 0x04, 0x00, 0x00, 0x00, 0x00, 0x00, 0xff, 0x06, 0x00, 0x42, 0x43, 0x02, 0x00, 0x2b, 0x00, 0x73, 0x28, 0x32, 0xe4, 0x72, 0x74, 0x76, 0x0f, 0x81, 0x60, 0x2e, 0x6d, 0x2e, 0x4f, 0x38, 0xe0, 0x02, 0x00, 0x9d, 0x3b, 0x6e, 0x4c, 0x1c, 0x00, 0x00, 0x00, 0x1f, 0x8b, 0x08, 0x04, 0x00, 0x00, 0x00, 0x00, 0x00, 0xff, 0x06, 0x00, 0x42, 0x43, 0x02, 0x00, 0x1b, 0x00, 0x03, 0x00, 0x00, 0x00, 0x00, 0x00, 0x00, 0x00, 0x00, 0x00};
+    static const char bgzf_text[] = "@r1\nACGTACGTAC\n+\nIIIIIIIIII\n";
+    pa_bgzf_member bgzf_rows[2];
+    uint64_t bgzf_n = 0, bgzf_text_bytes = 0;
+    EXPECT(pa_bgzf_scan(bgzf_file, sizeof bgzf_file, bgzf_rows, 2, &bgzf_n, &bgzf_text_bytes) == PA_OK && bgzf_n == 2 && bgzf_text_bytes == 28 &&
+           bgzf_rows[0].in_off == 18 && bgzf_rows[0].out_len == 28 && bgzf_rows[1].out_off == 28 && bgzf_rows[1].out_len == 0 && bgzf_rows[1].in_len == 2);
+    EXPECT(pa_bgzf_scan(bgzf_file, sizeof bgzf_file - 1, NULL, 0, &bgzf_n, NULL) == PA_ERR_NOT_BGZF && bgzf_n == 0);
+    EXPECT(strcmp(pa_inflate_status_name(PA_INFLATE_CRC_MISMATCH), "crc mismatch") == 0);
+    {
+        uint64_t ist[PA_INGEST_INPUT_STATS];
+        EXPECT(pa_process_reads_input_stats(ist) == PA_OK && pa_process_reads_input_stats(NULL) == PA_ERR_INVALID_ARG);
+    }
+    printf("layout pa_bgzf_member sizeof %zu\n", sizeof(pa_bgzf_member));
+    LAYOUT_FIELD(pa_bgzf_member, in_off); LAYOUT_FIELD(pa_bgzf_member, out_off); LAYOUT_FIELD(pa_bgzf_member, file_off); LAYOUT_FIELD(pa_bgzf_member, in_len);
+    LAYOUT_FIELD(pa_bgzf_member, out_len); LAYOUT_FIELD(pa_bgzf_member, crc32); LAYOUT_FIELD(pa_bgzf_member, reserved);
+
     /* ---- device half: with a GPU it runs, without one every entry point refuses (there is no CPU fallback) ---- */
     pa_index* idx = NULL;
     int rc = pa_index_create(&flat, 0, &idx);
@@ -188,6 +205,11 @@ int main(int argc, char** argv) {
         pa_txome_device* td = NULL;
         EXPECT(rc == PA_ERR_NO_DEVICE && idx == NULL);
         EXPECT(pa_device_malloc(0, 64, &p) == PA_ERR_NO_DEVICE);
+        {
+            uint32_t bst[2];
+            uint8_t btext[32];
+            EXPECT(pa_bgzf_inflate_device(0, bgzf_file, sizeof bgzf_file, bgzf_rows, 2, btext, sizeof btext, bst, NULL) == PA_ERR_NO_DEVICE);
+        }
         EXPECT(pa_overflow_create(0, 16, 64, &o) == PA_ERR_NO_DEVICE);
         EXPECT(pa_txome_upload(tx2, 60, 0, &td) == PA_ERR_NO_DEVICE);
         EXPECT(pa_event_create(&ev) < 0);
@@ -220,6 +242,18 @@ int main(int argc, char** argv) {
         pa_index_stats st;
         EXPECT(pa_index_get_stats(idx, &st) == PA_OK && st.k == 20 && st.num_nodes == flat.num_nodes);
         EXPECT(pa_counts_len(idx) == counts_len);
+        {   /* the two members inflated on the GPU */
+            void *d_bcomp = NULL, *d_brows = NULL, *d_btext = NULL, *d_bst = NULL;
+            uint32_t bst[2] = {99, 99};
+            char btext[28];
+            EXPECT(pa_device_malloc(0, sizeof bgzf_file, &d_bcomp) == PA_OK && pa_device_malloc(0, sizeof bgzf_rows, &d_brows) == PA_OK &&
+                   pa_device_malloc(0, 64, &d_btext) == PA_OK && pa_device_malloc(0, 8, &d_bst) == PA_OK);
+            EXPECT(pa_memcpy_h2d(d_bcomp, bgzf_file, sizeof bgzf_file, NULL) == PA_OK && pa_memcpy_h2d(d_brows, bgzf_rows, sizeof bgzf_rows, NULL) == PA_OK);
+            EXPECT(pa_bgzf_inflate_device(0, (const uint8_t*)d_bcomp, sizeof bgzf_file, (const pa_bgzf_member*)d_brows, 2, (uint8_t*)d_btext, 28, (uint32_t*)d_bst, NULL) == PA_OK);
+            EXPECT(pa_memcpy_d2h(btext, d_btext, 28, NULL) == PA_OK && pa_memcpy_d2h(bst, d_bst, 8, NULL) == PA_OK && pa_stream_synchronize(NULL) == PA_OK);
+            EXPECT(bst[0] == PA_INFLATE_OK && bst[1] == PA_INFLATE_OK && memcmp(btext, bgzf_text, 28) == 0);
+            pa_device_free(d_bcomp); pa_device_free(d_brows); pa_device_free(d_btext); pa_device_free(d_bst);
+        }
         /* single reads and host batches */
         const char* ex1 = "GGCTGTCAACCAGTCCATAGGCAGGGCCATCAGGCACCAAAGGGATTCTGCCAGCATAGT";
         uint32_t cls[64], ncls = 0, cov = 0, mm = 0, nodes[256], nn = 0;

@@ -1,4 +1,4 @@
-//! Exporter + drop-in `process_reads` for the reference crate. Add `mod amd_ffi; mod amd;` to src/lib.rs (and `mod amd_pairs_ffi;` for `map_pairs`).
+//! Exporter + drop-in `process_reads` for the reference crate. Add `mod amd_ffi; mod amd;` to src/lib.rs (and `mod amd_pairs_ffi;` for `map_pairs`, `mod amd_bgzf_ffi;` for `bgzf_members`).
 //! The exporter only reads `pub` fields of `Pseudoaligner<K>` (src/pseudoaligner.rs:27-33); `dbg_index` (the boomphf MPHF,
 //! :30) is not exported: every hit is verified against the node sequence (:99-107), which makes it an exact dictionary that
 //! the library rebuilds. Not compiled in the image of this repository (no rustc): kept in step with
@@ -154,6 +154,26 @@ pub fn count_pairs<P: AsRef<Path>>(index: &AmdIndex, r1_fastq: P, r2_fastq: P, o
     let o = match orient { PairOrientation::Fr => PA_PAIR_FR, PairOrientation::Rf => PA_PAIR_RF, PairOrientation::Ff => PA_PAIR_FF };
     check(unsafe { pa_count_pairs(index.raw, p1.as_ptr(), p2.as_ptr(), o, allowed_mismatches as u32, threads as i32, counts.as_mut_ptr(), &mut n, stats.as_mut_ptr()) })?;
     Ok((counts, n, stats))
+}
+
+/// The member table of a BGZF file (`pa_bgzf_scan`): one row per member and the bytes of text the file holds; `None` when the bytes are
+/// not BGZF from first to last (ordinary gzip, a truncated member). The rows are what `pa_bgzf_inflate_device` takes, copied to the GPU.
+pub fn bgzf_members(data: &[u8]) -> Result<Option<(Vec<crate::amd_bgzf_ffi::PaBgzfMember>, u64)>, Error> {
+    use crate::amd_bgzf_ffi::*;
+    let (mut n, mut text) = (0u64, 0u64);
+    let rc = unsafe { pa_bgzf_scan(data.as_ptr(), data.len() as u64, std::ptr::null_mut(), 0, &mut n, &mut text) };
+    if rc == PA_ERR_NOT_BGZF { return Ok(None); }
+    check(rc)?;
+    let mut rows = vec![PaBgzfMember::default(); n as usize];
+    check(unsafe { pa_bgzf_scan(data.as_ptr(), data.len() as u64, rows.as_mut_ptr(), n, &mut n, &mut text) })?;
+    Ok(Some((rows, text)))
+}
+
+/// What this thread's last `process_reads_path` read (`pa_process_reads_input_stats`): [text_kind, members_total, members_gpu, members_host, bytes_h2d, text_bytes_gpu]
+pub fn process_reads_input_stats() -> Result<[u64; 6], Error> {
+    let mut st = [0u64; 6];
+    check(unsafe { crate::amd_bgzf_ffi::pa_process_reads_input_stats(st.as_mut_ptr()) })?;
+    Ok(st)
 }
 
 /// One replica of the index per GPU (`pa_index_create_multi`): what `process_reads_path` deals its windows of text to.

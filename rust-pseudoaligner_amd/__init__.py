@@ -901,6 +901,16 @@ def process_reads_stage_seconds() -> dict:
     return dict(zip(INGEST_STAGES, st))
 
 
+INPUT_STATS = ("text_kind", "members_total", "members_gpu", "members_host", "bytes_h2d", "text_bytes_gpu")
+
+
+def process_reads_input_stats() -> dict:
+    """what this thread's last process_reads call read (pa_process_reads_input_stats): text_kind 0 plain, 1 gzip inflated by the host, 2 BGZF inflated on the GPU"""
+    st = (C.c_uint64 * 6)()
+    check(lib().pa_process_reads_input_stats(st))
+    return dict(zip(INPUT_STATS, [int(x) for x in st]))
+
+
 def process_reads(fastq_path: str, index: Pseudoaligner, out_path: str = "-", num_threads: int = 2) -> Tuple[int, int]:
     """process_reads (src/pseudoaligner.rs:420-425): one `(flag, "id", [ids], coverage)` line per read, input order.
     Returns (reads, reads flagged true by the rule at :455)."""
@@ -927,6 +937,68 @@ def fastq_scan(fastq_path: str, num_threads: int = 2) -> Tuple[np.ndarray, np.nd
         check(lib().pa_fastq_scan_host(str(fastq_path).encode(), num_threads, C.byref(n), starts.ctypes.data_as(_ffi.u64p),
                                        hdr.ctypes.data_as(_ffi.u32p), seq.ctypes.data_as(_ffi.u32p), len(starts), C.byref(kind)))
     return starts, hdr, seq, kind.value
+
+
+BGZF_MEMBER_DTYPE = np.dtype([("in_off", "<u8"), ("out_off", "<u8"), ("file_off", "<u8"), ("in_len", "<u4"), ("out_len", "<u4"), ("crc32", "<u4"), ("reserved", "<u4")])
+
+
+def bgzf_scan(path_or_bytes) -> Optional[Tuple[np.ndarray, int]]:
+    """pa_bgzf_scan: the member table of a BGZF file (BGZF_MEMBER_DTYPE, one row per member) and the bytes of text it holds, found from
+    header to header without inflating; None when the bytes are not BGZF from first to last (ordinary gzip, a truncated member, ...)"""
+    data = path_or_bytes if isinstance(path_or_bytes, (bytes, bytearray, memoryview)) else open(path_or_bytes, "rb").read()
+    buf = np.frombuffer(bytes(data), np.uint8)
+    n, text = C.c_uint64(), C.c_uint64()
+    rc = lib().pa_bgzf_scan(buf.ctypes.data, len(buf), None, 0, C.byref(n), C.byref(text))
+    if rc == _ffi.PA_ERR_NOT_BGZF:
+        return None
+    check(rc)
+    members = np.zeros(n.value, BGZF_MEMBER_DTYPE)
+    check(lib().pa_bgzf_scan(buf.ctypes.data, len(buf), members.ctypes.data_as(C.POINTER(_ffi.BgzfMember)), len(members), C.byref(n), C.byref(text)))
+    return members, text.value
+
+
+def bgzf_inflate_device(device: int, d_comp: int, comp_bytes: int, d_members: int, n_members: int, d_text: int, text_cap: int, d_status: int, stream: int = 0) -> None:
+    """pa_bgzf_inflate_device on device pointers (ints): members d_members[0, n_members) of the compressed bytes at d_comp inflated to
+    d_text[out_off - out_off of the first ...), one status word per member; asynchronous on `stream`"""
+    check(lib().pa_bgzf_inflate_device(device, d_comp, comp_bytes, d_members, n_members, d_text, text_cap, d_status, stream or None))
+
+
+def inflate_status_name(status: int) -> str:
+    return lib().pa_inflate_status_name(status).decode()
+
+
+def bgzf_inflate(data: bytes, device: int = 0) -> Tuple[bytes, np.ndarray]:
+    """A whole BGZF file inflated on the GPU -> (text, statuses). The text of a member whose status is not 0 is unspecified. PaError when
+    the bytes are not BGZF (there is no host fallback here: use gzip for anything else)."""
+    scanned = bgzf_scan(data)
+    if scanned is None:
+        raise PaError(_ffi.PA_ERR_NOT_BGZF, "not BGZF")
+    members, text_bytes = scanned
+    L = lib()
+    status = np.zeros(len(members), np.uint32)
+    text = np.zeros(text_bytes, np.uint8)
+    ptrs = []
+
+    def dev(nbytes):
+        p = vp()
+        check(L.pa_device_malloc(device, max(nbytes, 16), C.byref(p)))
+        ptrs.append(p)
+        return p
+    try:
+        comp = np.frombuffer(bytes(data), np.uint8)
+        d_comp, d_mem, d_text, d_status = dev(comp.nbytes), dev(members.nbytes), dev(text.nbytes), dev(status.nbytes)
+        check(L.pa_memcpy_h2d(d_comp, comp.ctypes.data, comp.nbytes, None))
+        check(L.pa_memcpy_h2d(d_mem, members.ctypes.data, members.nbytes, None))
+        check(L.pa_memset_device(d_text, 0, max(text.nbytes, 16), None))
+        check(L.pa_bgzf_inflate_device(device, d_comp, comp.nbytes, d_mem, len(members), d_text, text.nbytes, d_status, None))
+        if text.nbytes:
+            check(L.pa_memcpy_d2h(text.ctypes.data, d_text, text.nbytes, None))
+        check(L.pa_memcpy_d2h(status.ctypes.data, d_status, status.nbytes, None))
+        check(L.pa_stream_synchronize(None))
+    finally:
+        for p in ptrs:
+            L.pa_device_free(p)
+    return text.tobytes(), status
 
 
 PA_COMPACT_MAPPED, PA_COMPACT_BY_REF, PA_COMPACT_PACKED = 0x10000000, 0x20000000, 0x40000000

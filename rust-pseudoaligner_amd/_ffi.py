@@ -16,6 +16,7 @@ PA_ERR_NO_DEVICE = -4
 PA_ERR_ARENA_FULL = -7
 PA_ERR_UNSUPPORTED = -8
 PA_ERR_BUFFER_TOO_SMALL = -10
+PA_ERR_NOT_BGZF = -11
 PA_CELL_STATS = 10
 CELL_STAT_NAMES = ("reads", "barcode_exact", "barcode_corrected", "barcode_invalid", "umi_invalid", "not_confidently_mapped", "reads_counted",
                    "umis_corrected", "molecules_lost_to_conflicts", "umis_in_matrix")
@@ -57,6 +58,13 @@ class QuantParams(C.Structure):
                 ("min_iters", C.c_uint32), ("max_iters", C.c_uint32), ("check_every", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class BgzfMember(C.Structure):
+    _fields_ = [("in_off", C.c_uint64), ("out_off", C.c_uint64), ("file_off", C.c_uint64), ("in_len", C.c_uint32), ("out_len", C.c_uint32),
+                ("crc32", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+INFLATE_STATUS_NAMES = ("OK", "BAD_MEMBER", "BAD_BLOCK_TYPE", "STORED_LEN", "TOO_MANY_SYMBOLS", "BAD_CODE_LENGTHS", "BAD_REPEAT", "NO_END_OF_BLOCK", "BAD_SYMBOL",
+                        "DISTANCE_TOO_FAR", "INPUT_EXHAUSTED", "TRAILING_INPUT", "OUTPUT_TOO_LONG", "OUTPUT_TOO_SHORT", "CRC_MISMATCH")   # PA_INFLATE_*: the index is the code
 PA_QUANT_STATS = 8
 PA_PAIR_FR, PA_PAIR_RF, PA_PAIR_FF = 0, 1, 2
 PAIR_ORIENTATIONS = {"fr": PA_PAIR_FR, "rf": PA_PAIR_RF, "ff": PA_PAIR_FF}
@@ -118,6 +126,7 @@ SIGNATURES = {
     "pa_map_stage_ms": (C.c_int, [vp, vp, C.POINTER(C.c_float)]),
     "pa_process_reads_stage_seconds": (C.c_int, [C.POINTER(C.c_double)]),
     "pa_record_stream_stage_seconds": (C.c_int, [vp, C.POINTER(C.c_double)]),
+    "pa_process_reads_input_stats": (C.c_int, [u64p]),
     "pa_map_arena_hint": (C.c_uint64, [vp, C.c_uint64]),
     "pa_map_tiles_host": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, C.c_uint64, u64p, vp, C.c_uint64, C.c_int]),
     "pa_host_alloc_pinned": (C.c_int, [C.c_size_t, C.POINTER(vp)]),
@@ -132,6 +141,9 @@ SIGNATURES = {
     "pa_process_reads": (C.c_int, [vp, C.c_char_p, C.c_char_p, C.c_int, u64p, u64p]),
     "pa_process_reads_multi": (C.c_int, [C.POINTER(vp), C.c_int, C.c_char_p, C.c_char_p, C.c_int, u64p, u64p]),
     "pa_fastq_scan_host": (C.c_int, [C.c_char_p, C.c_int, u64p, u64p, u32p, u32p, C.c_uint64, C.POINTER(C.c_int)]),
+    "pa_bgzf_scan": (C.c_int, [vp, C.c_uint64, C.POINTER(BgzfMember), C.c_uint64, u64p, u64p]),
+    "pa_bgzf_inflate_device": (C.c_int, [C.c_int, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, vp]),
+    "pa_inflate_status_name": (C.c_char_p, [C.c_uint32]),
     "pa_counts_len": (C.c_uint64, [vp]),
     "pa_counts_accumulate_device": (C.c_int, [vp, vp, vp, vp, C.c_uint64, vp, vp]),
     "pa_counts_by_barcode_device": (C.c_int, [vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, u64p, vp]),

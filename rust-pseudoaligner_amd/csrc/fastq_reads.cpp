@@ -226,11 +226,27 @@ struct TextPipe {
         if (read_async) { pool.end(); read_async = false; }
         return read_bad.exchange(0) ? fail(PA_ERR_IO, "%s: read failed: %s", fastq_path, strerror(errno)) : PA_OK;
     }
+    // a BGZF window: bytes [off, off + len) of the COMPRESSED file into dst (pinned), by the pool, with streaming stores
+    void read_comp_begin(uint64_t off, uint64_t len, uint8_t* dst) {
+        read_async = false;
+        if (len == 0) return;
+        const uint64_t PIECE = 2ull << 20;
+        const int ntask = (int)std::min<uint64_t>((len + PIECE - 1) / PIECE, 1u << 20);
+        const uint8_t* src = (const uint8_t*)text.map_base;
+        auto piece = [src, off, len, dst, ntask](int t) {
+            const uint64_t a = len * (uint64_t)t / (uint64_t)ntask, b = len * (uint64_t)(t + 1) / (uint64_t)ntask;
+            copy_streaming(dst + a, src + off + a, (size_t)(b - a));
+        };
+        if (ntask == 1) { piece(0); return; }
+        read_async = true;
+        pool.begin(ntask, piece);
+    }
     int read_text(uint64_t off, uint64_t len, uint8_t* dst) {
         read_begin(off, len, dst);
         return read_end();
     }
     int read_small(uint64_t off, uint64_t len, uint8_t* dst) {   // by the caller itself, whatever the pool is doing (a window's head: <= 1 MiB)
+        if (text.bgzf) return len ? bgzf_read_host(text, fastq_path, off, len, dst) : PA_OK;   // (the members that hold the unfinished record: inflated by this thread)
         if (len) read_piece(off, len, dst, 0, 1);
         return read_bad.load() ? fail(PA_ERR_IO, "%s: read failed: %s", fastq_path, strerror(errno)) : PA_OK;
     }
@@ -329,6 +345,11 @@ struct TextPipe {
 
 constexpr int WIN_OK = 0, WIN_ODD = 1, WIN_EMPTY = 2;
 
+uint64_t* last_input_stats() {   // pa_process_reads_input_stats: of this thread's last call
+    static thread_local uint64_t st[PA_INGEST_INPUT_STATS] = {0};
+    return st;
+}
+
 int process_reads_impl(pa_index* const* idxs, int nidx, const char* fastq_path, const char* out_path, int num_threads, uint64_t* n_reads_out, uint64_t* n_flagged_out) {
     if (!idxs || nidx < 1 || !fastq_path || !out_path) return fail(PA_ERR_INVALID_ARG, "null argument");
     for (int i = 0; i < nidx; ++i)
@@ -349,7 +370,9 @@ int process_reads_impl(pa_index* const* idxs, int nidx, const char* fastq_path, 
 
     FastqText text;
     {
-        const int orc = open_fastq(fastq_path, text);
+        const char* v = getenv("PA_INGEST_BGZF");   // (diagnosis and A/B: PA_INGEST_BGZF=0 inflates a BGZF file on the host like any other .gz)
+        if (!(v && *v && atoi(v) == 0)) open_bgzf(fastq_path, text);
+        const int orc = text.bgzf ? PA_OK : open_fastq(fastq_path, text);
         if (orc != PA_OK) return orc;
     }
     FILE* out = strcmp(out_path, "-") == 0 ? stdout : fopen(out_path, "wb");
@@ -364,6 +387,11 @@ int process_reads_impl(pa_index* const* idxs, int nidx, const char* fastq_path, 
     uint64_t W = 64ull << 20;   // bytes of a window the GPU scans (64 MiB: 128 MiB leaves more of the first read and the last kernels unoverlapped, 16 MiB costs launches) (PA_INGEST_WINDOW; never more than 256 bytes per read of a batch: the tests' small batches give small windows)
     if (const char* v = getenv("PA_INGEST_WINDOW")) { const long long x = atoll(v); if (x >= 1) W = (uint64_t)x; }
     W = std::min<uint64_t>(std::min<uint64_t>(W, BATCH_READS * 256), 1ull << 31);
+    if (text.bgzf) W = std::max<uint64_t>(W, PA_BGZF_MAX_ISIZE);   // a window's own text is a run of whole members
+    const bool was_bgzf = text.bgzf;
+    const uint64_t members_total = text.members.size();
+    uint64_t members_gpu = 0, bytes_h2d = 0, text_bytes_gpu = 0;
+    const int text_kind0 = text.bgzf ? 2 : !text.inflated.empty() ? 1 : 0;
     const bool verbose = getenv("PA_VERBOSE") != nullptr;
     const bool lane_serial = knob_int("PA_LANE_SERIAL", 1) != 0;   // (knobs builds: A/B of the one-window-at-a-time rule for lanes that share a GPU)
     const bool host_only = getenv("PA_INGEST_HOST_SCAN") != nullptr;   // (diagnosis: every window through the host's scan)
@@ -424,6 +452,10 @@ int process_reads_impl(pa_index* const* idxs, int nidx, const char* fastq_path, 
             if ((e = window_ensure_scan(c, c.h_info.get()->lines)) != PA_OK) return e;
             if ((e = window_scan_enqueue(c, true, l.scan)) != PA_OK) return e;
         }
+        for (uint64_t i = 0; i < c.n_members; ++i)   // (they came back on the copy stream ahead of ev_h2d, which the scan waited for)
+            if (c.h_mstat.get()[i] != PA_INFLATE_OK)
+                return fail(PA_ERR_FORMAT, "%s: corrupt gzip stream: member at byte %llu: %s", fastq_path, (unsigned long long)c.h_mrows.get()[i].file_off,
+                            pa_inflate_status_name(c.h_mstat.get()[i]));
         if (c.h_info.get()->odd) return WIN_ODD;
         if (c.h_info.get()->n == 0) return WIN_EMPTY;
         if (c.h_info.get()->max_seq > PA_MAX_READ_LEN) return fail(PA_ERR_UNSUPPORTED, "read longer than %u bases", PA_MAX_READ_LEN);
@@ -439,10 +471,39 @@ int process_reads_impl(pa_index* const* idxs, int nidx, const char* fastq_path, 
     // ---- windows the GPU scans ----
     // The text of window w + 1 is read (by the pool's workers, asynchronously) while this thread waits for window w - 1's scan, launches its kernels and
     // enqueues window w's scan: the reads follow each other without a gap, and so do the copies to the GPU behind them.
-    struct Pre { bool active = false; uint64_t id = 0, main_from = 0, main_len = 0; BatchCtx* c = nullptr; Lane* l = nullptr; };
+    struct Pre { bool active = false; uint64_t id = 0, main_from = 0, main_len = 0, comp_len = 0, n_members = 0; BatchCtx* c = nullptr; Lane* l = nullptr; };
     auto start_read = [&](Pre& p, uint64_t id) -> int {
         p.active = false;
         if (!gpu_mode || read_to + KEEP >= text.fsize) return PA_OK;
+        p.comp_len = p.n_members = 0;
+        if (text.bgzf) {
+            // the window's own text is a run of whole members: from the member that holds read_to (read_to is a member's first byte except behind a discarded
+            // window: the scan then starts inside the member) to the last member boundary at or below W and at or below fsize - KEEP
+            const uint64_t m0 = bgzf_member_at(text, read_to), from = text.members[m0].out_off, limit = std::min<uint64_t>(from + W, text.fsize - KEEP);
+            uint64_t m1 = m0;
+            while (m1 < text.members.size() && text.members[m1].out_off + text.members[m1].out_len <= limit) ++m1;
+            if (m1 == m0 || text.members[m1 - 1].out_off + text.members[m1 - 1].out_len <= read_to) return PA_OK;   // no whole member left in front of the host's part
+            const uint64_t comp_from = text.members[m0].file_off, comp_to = m1 < text.members.size() ? text.members[m1].file_off : text.map_size;
+            p.main_from = from;
+            p.main_len = text.members[m1 - 1].out_off + text.members[m1 - 1].out_len - from;
+            p.comp_len = comp_to - comp_from;
+            p.n_members = m1 - m0;
+            p.id = id;
+            int e = tp.acquire(id, &p.c);
+            if (e != PA_OK) return e;
+            p.l = &tp.lane_of(id);
+            if ((e = window_ensure_raw(*p.c, WINDOW_HEAD_ROOM + p.main_len)) != PA_OK) return e;
+            if ((e = window_ensure_comp(*p.c, p.comp_len, p.n_members)) != PA_OK) return e;
+            for (uint64_t i = 0; i < p.n_members; ++i) {
+                pa_bgzf_member r = text.members[m0 + i];
+                r.in_off -= comp_from;
+                p.c->h_mrows.get()[i] = r;
+            }
+            tp.read_comp_begin(comp_from, p.comp_len, p.c->h_comp.get());
+            read_to = from + p.main_len;
+            p.active = true;
+            return PA_OK;
+        }
         p.main_len = std::min<uint64_t>(W, text.fsize - KEEP - read_to);
         p.main_from = read_to;
         p.id = id;
@@ -469,15 +530,26 @@ int process_reads_impl(pa_index* const* idxs, int nidx, const char* fastq_path, 
             if (!vt0[id % 8]) { (void)hipEventCreate(&vt0[id % 8]); (void)hipEventCreate(&vt1[id % 8]); }
             else { float ms = 0; if (hipEventElapsedTime(&ms, vt0[id % 8], vt1[id % 8]) == hipSuccess) { v_h2d_ms += ms; v_h2d_bytes += vbytes[id % 8]; } }
             (void)hipEventRecord(vt0[id % 8], l.copy);
-            vbytes[id % 8] = main_len;
+            vbytes[id % 8] = cur.n_members ? cur.comp_len : main_len;
         }
         // lanes that share a GPU (a handle listed twice) send their windows one at a time: with two copies of one direction queued at once the runtime
         // runs one of them as a blit kernel, at a fraction of the DMA engine's rate (host_batch.cpp has the measurement)
         for (size_t o = 0; o < lanes.size() && lane_serial; ++o)
             if (&lanes[o] != &l && lanes[o].device == l.device && lanes[o].last_h2d && hipStreamWaitEvent(l.copy, lanes[o].last_h2d, 0) != hipSuccess) { rc = fail(PA_ERR_HIP, "hipStreamWaitEvent failed"); break; }
         if (rc != PA_OK) break;
-        if (hipMemcpyAsync(c.d_raw.get() + WINDOW_HEAD_ROOM, c.h_raw.get() + WINDOW_HEAD_ROOM, main_len, hipMemcpyHostToDevice, l.copy) != hipSuccess ||
+        c.n_members = cur.n_members;
+        if (cur.n_members) {   // BGZF: the compressed members cross the link, the text first exists in HBM; statuses back ahead of ev_h2d
+            if (hipMemcpyAsync(c.d_comp.get(), c.h_comp.get(), cur.comp_len, hipMemcpyHostToDevice, l.copy) != hipSuccess ||
+                hipMemcpyAsync(c.d_mrows.get(), c.h_mrows.get(), cur.n_members * sizeof(pa_bgzf_member), hipMemcpyHostToDevice, l.copy) != hipSuccess) { rc = fail(PA_ERR_HIP, "copy of a compressed window to the GPU failed"); break; }
+            if ((rc = bgzf_inflate_launch(c.d_comp.get(), cur.comp_len, c.d_mrows.get(), cur.n_members, c.d_raw.get() + WINDOW_HEAD_ROOM, main_len, c.d_mstat.get(), l.copy)) != PA_OK) break;
+            if (hipMemcpyAsync(c.h_mstat.get(), c.d_mstat.get(), cur.n_members * sizeof(uint32_t), hipMemcpyDeviceToHost, l.copy) != hipSuccess ||
+                hipEventRecord(c.ev_h2d, l.copy) != hipSuccess) { rc = fail(PA_ERR_HIP, "copy of a compressed window to the GPU failed"); break; }
+            members_gpu += cur.n_members;
+            bytes_h2d += cur.comp_len + cur.n_members * sizeof(pa_bgzf_member);
+            text_bytes_gpu += main_len;
+        } else if (hipMemcpyAsync(c.d_raw.get() + WINDOW_HEAD_ROOM, c.h_raw.get() + WINDOW_HEAD_ROOM, main_len, hipMemcpyHostToDevice, l.copy) != hipSuccess ||
             hipEventRecord(c.ev_h2d, l.copy) != hipSuccess) { rc = fail(PA_ERR_HIP, "copy of a text window to the GPU failed"); break; }
+        else bytes_h2d += main_len;
         l.last_h2d = c.ev_h2d;
         if (verbose) (void)hipEventRecord(vt1[id % 8], l.copy);
         if ((rc = start_read(nxt, id + 1)) != PA_OK) break;             // the next window's text starts to arrive
@@ -489,7 +561,8 @@ int process_reads_impl(pa_index* const* idxs, int nidx, const char* fastq_path, 
             else if (r != PA_OK) { rc = r; break; }
         }
         if ((rc = tp.use(l)) != PA_OK) break;
-        const uint64_t head = main_from - rec_start;   // the unfinished record of the window before
+        const uint64_t head = main_from > rec_start ? main_from - rec_start : 0;   // the unfinished record of the window before
+        const uint64_t skip = rec_start > main_from ? rec_start - main_from : 0;   // (BGZF behind a discarded window: the first record starts inside the first member)
         if (!discard && head > WINDOW_HEAD_ROOM) { W = std::max<uint64_t>(W, 2 * head); discard = true; }
         if (discard) {   // this window's text (and what was being read behind it) is read again, from the first record not yet taken
             if (nxt.active) { (void)tp.read_end(); nxt.active = false; }
@@ -503,9 +576,10 @@ int process_reads_impl(pa_index* const* idxs, int nidx, const char* fastq_path, 
         if (head) {
             if ((rc = tp.read_small(rec_start, head, c.h_raw.get() + WINDOW_HEAD_ROOM - head)) != PA_OK) break;
             if (hipMemcpyAsync(c.d_raw.get() + WINDOW_HEAD_ROOM - head, c.h_raw.get() + WINDOW_HEAD_ROOM - head, head, hipMemcpyHostToDevice, l.scan) != hipSuccess) { rc = fail(PA_ERR_HIP, "copy of a window's head failed"); break; }
+            bytes_h2d += head;
         }
         tp.t_read += TextPipe::now() - t0; t0 = TextPipe::now();
-        c.raw_begin = WINDOW_HEAD_ROOM - head;
+        c.raw_begin = WINDOW_HEAD_ROOM - head + skip;
         c.raw_end = WINDOW_HEAD_ROOM + main_len;
         if ((rc = window_ensure_scan(c, 0)) != PA_OK) break;
         if (hipStreamWaitEvent(l.scan, c.ev_h2d, 0) != hipSuccess) { rc = fail(PA_ERR_HIP, "hipStreamWaitEvent failed"); break; }
@@ -531,6 +605,7 @@ int process_reads_impl(pa_index* const* idxs, int nidx, const char* fastq_path, 
     }
 
     // ---- the rest of the text (its end; all of it when it is not in four-line shape): the host's scan, the same kernels ----
+    if (rc == PA_OK && text.bgzf) rc = bgzf_materialise(text, fastq_path, pool, &rec_start);   // what is left (the last KEEP bytes; everything from here on when the text is not in four-line shape): inflated by the host's pool
     if (rc == PA_OK) {
         IngestCache* const hc = lanes[0].cache;   // (the scan's lists are parked with lane 0's buffers)
         text.off = rec_start;
@@ -588,6 +663,8 @@ int process_reads_impl(pa_index* const* idxs, int nidx, const char* fastq_path, 
                 // (the copies ride on the lane's kernel stream: this path is bound by the host's scan, not by the link)
                 if (hipMemcpyAsync(c.d_raw.get() + WINDOW_HEAD_ROOM, c.h_raw.get() + WINDOW_HEAD_ROOM, bytes, hipMemcpyHostToDevice, l.stream) != hipSuccess ||
                     hipMemcpyAsync(c.d_rec.get(), c.h_rec.get(), n * sizeof(uint4), hipMemcpyHostToDevice, l.stream) != hipSuccess) { rc = fail(PA_ERR_HIP, "copy of a text window to the GPU failed"); break; }
+                bytes_h2d += bytes + n * sizeof(uint4);
+                c.n_members = 0;
                 c.raw_begin = WINDOW_HEAD_ROOM;
                 c.raw_end = WINDOW_HEAD_ROOM + bytes;
                 c.n = n;
@@ -615,6 +692,10 @@ int process_reads_impl(pa_index* const* idxs, int nidx, const char* fastq_path, 
     {
         double* st = pa::ingest::last_stage_seconds();
         st[0] = tp.t_scan; st[1] = tp.t_read; st[2] = tp.t_wait; st[3] = tp.t_launch; st[4] = tp.t_text; st[5] = tp.t_push; st[6] = TextPipe::now() - t_begin; st[7] = (double)tp.reported;
+    }
+    {
+        uint64_t* is = last_input_stats();
+        is[0] = (uint64_t)text_kind0; is[1] = members_total; is[2] = members_gpu; is[3] = was_bgzf ? text.members_host : 0; is[4] = bytes_h2d; is[5] = text_bytes_gpu;
     }
     if (verbose)
         fprintf(stderr, "\n[pa ingest] %llu reads, %d threads, %d lane(s): %llu windows scanned on the GPU (%llu scanned twice), %llu batches by the host; host scan %.3f s, read %.3f s, wait GPU %.3f s, launch %.3f s, wait text %.3f s, wait writer %.3f s, total %.3f s (before the first window %.3f s)\n",
@@ -674,6 +755,12 @@ extern "C" int pa_process_reads_multi(pa_index* const* idx, int n_idx, const cha
     } catch (const std::exception& ex) {
         return fail(PA_ERR_INTERNAL, "pa_process_reads_multi: %s", ex.what());
     }
+}
+
+extern "C" int pa_process_reads_input_stats(uint64_t out[PA_INGEST_INPUT_STATS]) {
+    if (!out) return fail(PA_ERR_INVALID_ARG, "null argument");
+    memcpy(out, last_input_stats(), sizeof(uint64_t) * PA_INGEST_INPUT_STATS);
+    return PA_OK;
 }
 
 extern "C" int pa_process_reads_stage_seconds(double out[PA_INGEST_STAGES]) {

@@ -101,6 +101,87 @@ bool normalize_fastq(const char* d, uint64_t n, std::vector<char>& out, uint64_t
 
 }  // namespace
 
+namespace {
+// one member inflated into out[0, out_len): nullptr, or what is wrong with it
+const char* inflate_member_host(const uint8_t* comp, const pa_bgzf_member& m, uint8_t* out) {
+    z_stream z;
+    memset(&z, 0, sizeof z);
+    if (inflateInit2(&z, -15) != Z_OK) return "zlib failed to start";
+    uint8_t spare[8];
+    z.next_in = const_cast<Bytef*>(comp + m.in_off);
+    z.avail_in = m.in_len;
+    z.next_out = m.out_len ? out : spare;
+    z.avail_out = m.out_len ? m.out_len : 0;
+    int r = inflate(&z, Z_FINISH);
+    if (r != Z_STREAM_END && z.avail_out == 0) {   // the text is complete but the end-of-block bits are still to be read, or there is more text than ISIZE: spare room tells
+        z.next_out = spare;
+        z.avail_out = sizeof spare;
+        r = inflate(&z, Z_FINISH);
+    }
+    const char* why = nullptr;
+    if (r != Z_STREAM_END) why = z.msg ? "invalid deflate stream" : z.total_out > m.out_len ? "more text than ISIZE" : "input exhausted";
+    else if (z.avail_in) why = "bytes behind the end of the stream";
+    else if (z.total_out != m.out_len) why = z.total_out > m.out_len ? "more text than ISIZE" : "less text than ISIZE";
+    else if ((uint32_t)crc32(crc32(0L, Z_NULL, 0), out, m.out_len) != m.crc32) why = "crc mismatch";
+    inflateEnd(&z);
+    return why;
+}
+}  // namespace
+
+uint64_t pa::ingest::bgzf_member_at(const FastqText& t, uint64_t off) {
+    uint64_t lo = 0, hi = t.members.size();   // the last member with out_off <= off
+    while (hi - lo > 1) {
+        const uint64_t mid = (lo + hi) / 2;
+        if (t.members[mid].out_off <= off) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+int pa::ingest::bgzf_read_host(FastqText& t, const char* fastq_path, uint64_t off, uint64_t len, uint8_t* dst) {
+    std::vector<uint8_t> tmp(PA_BGZF_MAX_ISIZE);
+    const uint8_t* comp = (const uint8_t*)t.map_base;
+    for (uint64_t i = bgzf_member_at(t, off); i < t.members.size() && t.members[i].out_off < off + len; ++i) {
+        const pa_bgzf_member& m = t.members[i];
+        if (m.out_len == 0) continue;
+        if (const char* why = inflate_member_host(comp, m, tmp.data()))
+            return fail(PA_ERR_FORMAT, "%s: corrupt gzip stream: member at byte %llu: %s", fastq_path, (unsigned long long)m.file_off, why);
+        ++t.members_host;
+        const uint64_t a = std::max<uint64_t>(off, m.out_off), b = std::min<uint64_t>(off + len, m.out_off + m.out_len);
+        if (b > a) memcpy(dst + (a - off), tmp.data() + (a - m.out_off), (size_t)(b - a));
+    }
+    return PA_OK;
+}
+
+int pa::ingest::bgzf_materialise(FastqText& t, const char* fastq_path, Pool& pool, uint64_t* from) {
+    const uint64_t first = t.fsize ? bgzf_member_at(t, std::min(*from, t.fsize - 1)) : 0, n = t.members.size() - first;
+    const uint64_t base = t.members.empty() ? 0 : t.members[first].out_off;
+    t.inflated.resize((size_t)(t.fsize - base));
+    const uint8_t* comp = (const uint8_t*)t.map_base;
+    std::atomic<uint64_t> bad{~0ull};
+    const int ntask = (int)std::max<uint64_t>(1, std::min<uint64_t>(n, (uint64_t)pool.size() * 4));
+    pool.run(ntask, [&](int k) {
+        uint8_t spare[8];
+        for (uint64_t i = first + n * (uint64_t)k / (uint64_t)ntask; i < first + n * (uint64_t)(k + 1) / (uint64_t)ntask; ++i) {
+            const pa_bgzf_member& m = t.members[i];
+            if (inflate_member_host(comp, m, m.out_len ? (uint8_t*)t.inflated.data() + (m.out_off - base) : spare)) {
+                uint64_t cur = bad.load();
+                while (i < cur && !bad.compare_exchange_weak(cur, i)) {}
+            }
+        }
+    });
+    if (bad.load() != ~0ull) {   // (said again by one thread, for the message)
+        const pa_bgzf_member& m = t.members[bad.load()];
+        std::vector<uint8_t> tmp(PA_BGZF_MAX_ISIZE + 8);
+        const char* why = inflate_member_host(comp, m, tmp.data());
+        return fail(PA_ERR_FORMAT, "%s: corrupt gzip stream: member at byte %llu: %s", fastq_path, (unsigned long long)m.file_off, why ? why : "corrupt");
+    }
+    t.members_host += n;
+    *from -= base;
+    t.data = t.inflated.data();
+    t.fsize -= base;
+    return PA_OK;
+}
+
 int pa::ingest::open_fastq(const char* fastq_path, FastqText& t) {
     const char*& data = t.data;
     uint64_t& fsize = t.fsize;

@@ -25,17 +25,35 @@ struct FastqText {   // the text of a FASTQ file as the scan sees it: the mapped
     const char* map_base = nullptr; // the mapping as mmap returned it (data moves on when the rest of a file is rewritten)
     uint64_t map_size = 0;
     int fd = -1;                    // of a mapped file (kept open for the call)
+    // A BGZF file (pa_bgzf_scan accepts it; pa_process_reads only): the mapping is the COMPRESSED file (map_base / map_size, `mapped` stays false: nothing
+    // may read text out of it), fsize = the bytes of text (sum of ISIZE), offsets everywhere are text offsets, `members` finds the bytes behind them.
+    // data stays null until materialise() has inflated the text's tail on the host (the part the GPU windows do not take).
+    bool bgzf = false;
+    std::vector<pa_bgzf_member> members;
+    uint64_t members_host = 0;      // members inflated by the host so far (pa_process_reads_input_stats)
     void release() {
-        if (mapped) munmap((void*)map_base, map_size);   // (the whole mapping: nobody gives parts of it back any more)
+        if (mapped || bgzf) munmap((void*)map_base, map_size);   // (the whole mapping: nobody gives parts of it back any more)
         if (fd >= 0) close(fd);
         fd = -1;
         mapped = false;
+        bgzf = false;
         data = nullptr;
         fsize = 0;
     }
 };
 
 int open_fastq(const char* fastq_path, FastqText& t);
+// bgzf.cpp (pa_process_reads only): a file that is BGZF from first byte to last is opened as the BGZF kind above (t.bgzf set); anything else, an unreadable
+// file included, leaves t untouched for open_fastq, with its results and its errors
+void open_bgzf(const char* fastq_path, FastqText& t);
+// BGZF kind: the index of the member that holds text offset `off` (the last member that starts at or before it: empty members in front are skipped)
+uint64_t bgzf_member_at(const FastqText& t, uint64_t off);
+// BGZF kind: text bytes [off, off + len) into dst, the members that hold them inflated by the calling thread with zlib, each checked (stream end, ISIZE, CRC-32).
+// PA_ERR_FORMAT "corrupt gzip stream" naming the member's file offset otherwise
+int bgzf_read_host(FastqText& t, const char* fastq_path, uint64_t off, uint64_t len, uint8_t* dst);
+// BGZF kind: the text from the member that holds `from` to the end inflated into t.inflated by the pool; t.data / t.fsize then describe that tail as a text in
+// memory and *from is rewritten to the same byte's offset in it
+int bgzf_materialise(FastqText& t, const char* fastq_path, Pool& pool, uint64_t* from);
 
 // The text in WINDOWS: a mapped file is scanned a window at a time (PA_INGEST_WINDOW bytes), so that pa_process_reads has its first batch on
 // the GPU while the rest of the file is still being scanned; a window ends behind its last whole record. A text held in memory (gzip), a

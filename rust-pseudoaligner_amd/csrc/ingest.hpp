@@ -171,6 +171,15 @@ struct BatchCtx {   // pinned host buffers + device buffers of one batch in flig
     PinnedBuffer<uint4> h_rec;
     PinnedBuffer<FqInfo> h_info;
     hipEvent_t ev_h2d = nullptr, ev_info = nullptr;
+    // (c) a window of a BGZF file: its members' compressed bytes as they lie in the file (pinned copy, copy in HBM), their rows of the member table (in_off
+    // counted from the window's first compressed byte) and their statuses; pa::bgzf_inflate_launch writes the text to d_raw + WINDOW_HEAD_ROOM on the copy stream
+    PinnedBuffer<uint8_t> h_comp;
+    DeviceBuffer<uint8_t> d_comp;
+    PinnedBuffer<pa_bgzf_member> h_mrows;
+    DeviceBuffer<pa_bgzf_member> d_mrows;
+    PinnedBuffer<uint32_t> h_mstat;
+    DeviceBuffer<uint32_t> d_mstat;
+    uint64_t n_members = 0;   // of the window in the slot (0: not a BGZF window)
     // the tuples' way back on a stream of its own (the lane's; not owned here): the next window's kernels do not queue behind 14 MB of text going to the host
     hipStream_t back = nullptr;
     hipEvent_t ev_render = nullptr;
@@ -313,6 +322,21 @@ inline int window_ensure_raw(BatchCtx& c, uint64_t bytes) {
     c.d_raw.release();
     int e = c.h_raw.alloc(want);
     return e != PA_OK ? e : c.d_raw.alloc(want);
+}
+// buffers of a BGZF window of `bytes` compressed bytes in `members` members (grow-only; h_* then d_*: the device buffer is empty unless both are there)
+inline int window_ensure_comp(BatchCtx& c, uint64_t bytes, uint64_t members) {
+    int e = PA_OK;
+    if (bytes + 64 > c.d_comp.size()) {
+        const size_t want = (size_t)(bytes + bytes / 8 + 4096);
+        c.d_comp.release();
+        if ((e = c.h_comp.alloc(want)) || (e = c.d_comp.alloc(want))) return e;
+    }
+    if (members > c.d_mstat.size()) {
+        const size_t want = (size_t)(members + members / 4 + 64);
+        c.d_mstat.release();
+        if ((e = c.h_mrows.alloc(want)) || (e = c.d_mrows.alloc(want)) || (e = c.h_mstat.alloc(want)) || (e = c.d_mstat.alloc(want))) return e;
+    }
+    return PA_OK;
 }
 inline int window_ensure_events(BatchCtx& c) {
     if (!c.ev_h2d) PA_HIP_TRY(hipEventCreateWithFlags(&c.ev_h2d, hipEventDisableTiming));
