@@ -536,22 +536,10 @@ int count_pairs_impl(pa_index* idx, const char* r1_path, const char* r2_path, in
 
 extern "C" int pa_count_cells(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const char* whitelist_path, uint32_t bc_len,
                               uint32_t umi_len, const char* out_dir, int num_threads, uint64_t stats[PA_CELL_STATS]) {
-    try {
-        return count_cells_impl(idx, h, r1_path, r2_path, whitelist_path, bc_len, umi_len, out_dir, num_threads, stats);
-    } catch (const std::bad_alloc&) {
-        return fail(PA_ERR_OOM, "out of host memory in pa_count_cells");
-    } catch (const std::exception& ex) {
-        return fail(PA_ERR_INTERNAL, "pa_count_cells: %s", ex.what());
-    }
+    return no_throw("pa_count_cells", [&] { return count_cells_impl(idx, h, r1_path, r2_path, whitelist_path, bc_len, umi_len, out_dir, num_threads, stats); });
 }
 
 extern "C" int pa_count_pairs(pa_index* idx, const char* r1_path, const char* r2_path, int orient, uint32_t allowed_mismatches, int num_threads, uint64_t* h_counts,
                               uint64_t* n_pairs, uint64_t stats[PA_PAIR_STATS]) {
-    try {
-        return count_pairs_impl(idx, r1_path, r2_path, orient, allowed_mismatches, num_threads, h_counts, n_pairs, stats);
-    } catch (const std::bad_alloc&) {
-        return fail(PA_ERR_OOM, "out of host memory in pa_count_pairs");
-    } catch (const std::exception& ex) {
-        return fail(PA_ERR_INTERNAL, "pa_count_pairs: %s", ex.what());
-    }
+    return no_throw("pa_count_pairs", [&] { return count_pairs_impl(idx, r1_path, r2_path, orient, allowed_mismatches, num_threads, h_counts, n_pairs, stats); });
 }

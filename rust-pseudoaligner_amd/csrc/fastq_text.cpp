@@ -137,6 +137,30 @@ uint64_t pa::ingest::bgzf_member_at(const FastqText& t, uint64_t off) {
     return lo;
 }
 
+WindowPlan pa::ingest::plan_window(const FastqText& t, uint64_t read_to, uint64_t W, uint64_t KEEP) {
+    WindowPlan p;
+    if (read_to + KEEP >= t.fsize) return p;
+    if (!t.bgzf) {
+        p.text_from = read_to;
+        p.text_len = std::min<uint64_t>(W, t.fsize - KEEP - read_to);
+        p.active = true;
+        return p;
+    }
+    auto end_of = [&t](uint64_t m) { return t.members[m].out_off + t.members[m].out_len; };
+    const uint64_t m0 = bgzf_member_at(t, read_to), from = t.members[m0].out_off, limit = std::min<uint64_t>(from + W, t.fsize - KEEP);
+    uint64_t m1 = m0;
+    while (m1 < t.members.size() && end_of(m1) <= limit) ++m1;
+    if (m1 == m0 || end_of(m1 - 1) <= read_to) return p;   // no whole member left in front of the host's part
+    p.text_from = from;
+    p.text_len = end_of(m1 - 1) - from;
+    p.first_member = m0;
+    p.n_members = m1 - m0;
+    p.comp_from = t.members[m0].file_off;
+    p.comp_len = (m1 < t.members.size() ? t.members[m1].file_off : t.map_size) - p.comp_from;
+    p.active = true;
+    return p;
+}
+
 int pa::ingest::bgzf_read_host(FastqText& t, const char* fastq_path, uint64_t off, uint64_t len, uint8_t* dst) {
     std::vector<uint8_t> tmp(PA_BGZF_MAX_ISIZE);
     const uint8_t* comp = (const uint8_t*)t.map_base;

@@ -6,6 +6,7 @@
 #include <unistd.h>
 
 #include <cstdint>
+#include <new>
 #include <vector>
 
 #include "ingest.hpp"
@@ -48,6 +49,17 @@ int open_fastq(const char* fastq_path, FastqText& t);
 void open_bgzf(const char* fastq_path, FastqText& t);
 // BGZF kind: the index of the member that holds text offset `off` (the last member that starts at or before it: empty members in front are skipped)
 uint64_t bgzf_member_at(const FastqText& t, uint64_t off);
+// The next window of pa_process_reads: the text [text_from, text_from + text_len) behind read_to that the GPU scans, at most W bytes of it and none of the text's
+// last KEEP bytes (the end of the text is the host's). Plain text: starts at read_to. BGZF kind: a run of whole members, from the member that holds read_to
+// (read_to is a member's first byte except behind a discarded window: the scan then starts inside the member) to the last member boundary at or below
+// text_from + W and fsize - KEEP; comp_from / comp_len are those members' bytes in the file. !active: nothing (no whole member) is left in front of the host's part.
+// Arithmetic only: no buffer, no pool, no GPU (tests/plan drives it over made-up texts)
+struct WindowPlan {
+    bool active = false;
+    uint64_t text_from = 0, text_len = 0;
+    uint64_t first_member = 0, n_members = 0, comp_from = 0, comp_len = 0;   // (BGZF kind only)
+};
+WindowPlan plan_window(const FastqText& t, uint64_t read_to, uint64_t W, uint64_t KEEP);
 // BGZF kind: text bytes [off, off + len) into dst, the members that hold them inflated by the calling thread with zlib, each checked (stream end, ISIZE, CRC-32).
 // PA_ERR_FORMAT "corrupt gzip stream" naming the member's file offset otherwise
 int bgzf_read_host(FastqText& t, const char* fastq_path, uint64_t off, uint64_t len, uint8_t* dst);
@@ -70,6 +82,18 @@ struct WindowScan {
     // the next window with records in it (nrec = 0: the text has ended). records_before: records of the windows before (error messages)
     int next(const char* fastq_path, uint64_t records_before, Pool& pool, std::vector<RecPos>& rec_pos, std::vector<std::vector<uint32_t>>& brk);
 };
+
+// The C ABI's edge of a file driver: nothing thrown crosses it (std::bad_alloc out of the growable buffers, std::system_error out of thread creation)
+template <class F>
+int no_throw(const char* entry, F&& body) {
+    try {
+        return body();
+    } catch (const std::bad_alloc&) {
+        return fail(PA_ERR_OOM, "out of host memory in %s", entry);
+    } catch (const std::exception& ex) {
+        return fail(PA_ERR_INTERNAL, "%s: %s", entry, ex.what());
+    }
+}
 
 }  // namespace ingest
 }  // namespace pa

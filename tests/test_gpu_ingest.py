@@ -277,3 +277,40 @@ def test_record_stream_over_several_lanes(aligner):
         rs.flush()
         assert rs.drain() == b""
         rs.close()
+
+
+def test_unfinished_record_longer_than_the_head_room(aligner, tmp_path, monkeypatch):
+    """a record that starts in one window and ends more than the head room (1 MiB) into the next: the second window is dropped and read
+    again from the record's first byte with a window that holds it. One lane, two lanes, the host's scan and the BGZF copy of the file give
+    the same bytes, and they are the oracle's tuples"""
+    import bgzf_cases as bc
+    window = 2097152
+    ids, seqs = make_reads(9001, 31)
+    ids[3000] = "L" * (3 << 19)
+    want = expected_lines(aligner, ids, seqs)
+    fq = tmp_path / "h.fq"
+    write_fastq(fq, ids, seqs)
+    text = fq.read_bytes()
+    s = text.index(b"@" + b"L" * 64)
+    e = text.index(b"\n@", s + (3 << 19)) + 1
+    assert s + (1 << 20) < window < e, (s, e)
+    gz = tmp_path / "h.fq.gz"
+    gz.write_bytes(bc.bgzf(text))
+    monkeypatch.setenv("PA_INGEST_WINDOW", str(window))
+    monkeypatch.delenv("PA_INGEST_BATCH", raising=False)
+    outs = []
+    for path, lanes, host in ((fq, 0, False), (fq, 2, False), (fq, 0, True), (gz, 0, False)):
+        if host:
+            monkeypatch.setenv("PA_INGEST_HOST_SCAN", "1")
+        else:
+            monkeypatch.delenv("PA_INGEST_HOST_SCAN", raising=False)
+        out = tmp_path / ("o%d.txt" % len(outs))
+        if lanes == 0:
+            n, _ = pa.process_reads(str(path), aligner, str(out), 4)
+        else:
+            n, _ = pa.process_reads_multi(str(path), [aligner] * lanes, str(out), 4)
+        assert n == len(ids), (path.name, lanes, host)
+        outs.append(out.read_bytes())
+    monkeypatch.delenv("PA_INGEST_HOST_SCAN", raising=False)
+    assert outs[0].decode().splitlines() == want
+    assert all(o == outs[0] for o in outs[1:])
