@@ -515,6 +515,61 @@ int pa_whitelist_load(const char* path, uint32_t bc_len, char* out, uint64_t cap
 int pa_count_cells(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const char* whitelist_path,
                    uint32_t bc_len, uint32_t umi_len, const char* out_dir, int num_threads, uint64_t stats[PA_CELL_STATS]);
 
+/* ---------------- BUS output: sorted (barcode, UMI, equivalence class) records ----------------
+ * The interchange format of the kallisto | bustools family (Melsted, Ntranos, Pachter 2019): where the cell counter above gives one
+ * answer (cells x genes) and drops a read whose class spans two genes, this keeps the class of every (barcode, UMI). No whitelist,
+ * no correction, no gene table. Per read, in this order; the first rule that applies decides:
+ *   1 r1_short    R1 has fewer than bc_len + umi_len bytes: dropped
+ *   2 barcode_n   a barcode byte is not A, C, G or T (lower case is no base): dropped (kallisto substitutes a base; this drops and counts)
+ *   3 umi_n       the same for a UMI byte: dropped
+ *   4 unmapped    R2 unmapped, or mapped with class_len == 0 (or a reference to an index class without ids): dropped
+ *   5 bad_class   a class reference >= num_classes, an arena range not inside [0, arena_len), an id >= T, or an arena list that is
+ *                 not strictly ascending: dropped. Nothing outside the given buffers is ever read
+ *   6 recorded    kept as (barcode, UMI, ec); barcode and UMI packed 2 bits per base, A=0 C=1 G=2 T=3, first base most significant
+ * stats[PA_BUS_STATS]: [0] reads, [1] r1_short, [2] barcode_n, [3] umi_n, [4] unmapped, [5] bad_class, [6] recorded, [7] records
+ * (after finish); [0] = [1] + .. + [6].
+ * bc_len >= 1, umi_len >= 1, bc_len + umi_len <= 32 (both in one 64-bit word), else PA_ERR_UNSUPPORTED before any device call.
+ * ec numbering, a pure function of (index, set of recorded classes); T transcripts, M index classes with at least two ids:
+ *   t < T        the set {t} (an index class of one id, an arena list of one id)
+ *   T + j        the j-th index class with at least two ids, in class-id order (also an arena list whose content equals it)
+ *   T + M + r    the r-th novel class: a recorded list of at least two ids that equals no index class, in lexicographic order of the
+ *                ascending id lists ({1,5} < {1,5,7} < {2,3})
+ * More than 2^31 - 1 ecs: PA_ERR_UNSUPPORTED. Records: distinct (barcode, UMI, ec), count = its reads (summed as u32, clamped at
+ * 2^32 - 1), ascending by barcode, then UMI, then ec; flags = pad = 0. The records, the ec table and so the three files do not
+ * depend on how the reads were split into batches nor on where in an arena a list lay. Two different lists under one 64-bit content
+ * hash are PA_ERR_INTERNAL naming the hash (never expected). */
+#define PA_BUS_STATS 8
+typedef struct pa_bus_record {   /* = the 32-byte record of a BUS v1 file, little-endian */
+    uint64_t barcode, umi;
+    int32_t ec;
+    uint32_t count, flags, pad;
+} pa_bus_record;
+typedef struct pa_bus pa_bus;
+/* The writer of one run on idx's GPU. h: the host index idx was created from (its classes number the ecs, its names go to
+ * transcripts.txt); it must outlive the writer. Every argument is checked before any device call. */
+int pa_bus_create(pa_index* idx, const pa_host_index* h, uint32_t bc_len, uint32_t umi_len, pa_bus** out);
+/* One batch: d_results / d_arena[arena_len] as pa_map_batch_device or pa_pairs_combine_device left them, d_r1 the R1s (ASCII, back to
+ * back, d_r1_offsets[n+1]; only the first bc_len + umi_len bytes of each are read). Any number of calls. Synchronous on `stream`.
+ * PA_ERR_INVALID_ARG after finish. */
+int pa_bus_add_device(pa_bus* b, const pa_read_result* d_results, const uint32_t* d_arena, uint64_t arena_len, const uint8_t* d_r1,
+                      const uint64_t* d_r1_offsets, uint64_t n_reads, void* stream);
+/* Collapse over the run, number the ecs (synchronous). A second call only reports the same numbers. */
+int pa_bus_finish(pa_bus* b, uint64_t* n_records, uint32_t* n_ecs);
+/* after finish: the records in file order (cap < n_records: PA_ERR_BUFFER_TOO_SMALL) */
+int pa_bus_records(const pa_bus* b, pa_bus_record* out, uint64_t cap);
+/* after finish: ec e = ids[offsets[e] .. offsets[e + 1]), ascending; offsets[n_ecs + 1]. ids NULL: only *n_ids (offsets may be NULL
+ * then); ids_cap < *n_ids: PA_ERR_BUFFER_TOO_SMALL */
+int pa_bus_ecs(const pa_bus* b, uint64_t* offsets, uint32_t* ids, uint64_t ids_cap, uint64_t* n_ids);
+int pa_bus_stats(const pa_bus* b, uint64_t stats[PA_BUS_STATS]);
+/* after finish: out_dir/output.bus (header "BUS\0", u32 version 1, bclen, umilen, tlen = 0, then the records), out_dir/matrix.ec
+ * ("ec\tid,id,..." for every ec 0 .. n_ecs - 1, 0-based transcript ids) and out_dir/transcripts.txt (the index's names, one per line) */
+int pa_bus_write(const pa_bus* b, const char* out_dir);
+void pa_bus_destroy(pa_bus* b);
+/* The whole chain from files, as pa_count_cells reads them (same acceptance rules, batches and stage seconds; [4] = add_device +
+ * finish, [5] = writing) -> the three files of pa_bus_write in out_dir. stats may be NULL. */
+int pa_write_bus(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, uint32_t bc_len, uint32_t umi_len,
+                 const char* out_dir, int num_threads, uint64_t stats[PA_BUS_STATS]);
+
 /* ---------------- transcript abundances: EM over the class-count table (bulk RNA-seq) ----------------
  * The reference stops at equivalence classes; this is the standard abundance model over them (the EM of kallisto / salmon) on the
  * GPU, in f64. Inputs: the dense table class_counts[pa_counts_len] and, optionally, the serialised overflow words (format below,

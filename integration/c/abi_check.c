@@ -38,6 +38,10 @@ int main(int argc, char** argv) {
     LAYOUT_FIELD(pa_index_stats, num_kmers); LAYOUT_FIELD(pa_index_stats, table_slots); LAYOUT_FIELD(pa_index_stats, bytes_table); LAYOUT_FIELD(pa_index_stats, bytes_graph);
     LAYOUT_FIELD(pa_index_stats, bytes_classes); LAYOUT_FIELD(pa_index_stats, bytes_total); LAYOUT_FIELD(pa_index_stats, num_nodes); LAYOUT_FIELD(pa_index_stats, num_classes);
     LAYOUT_FIELD(pa_index_stats, k); LAYOUT_FIELD(pa_index_stats, max_class_len);
+    LAYOUT_STRUCT(pa_bus_record);   /* = the 32-byte record of a BUS file */
+    LAYOUT_FIELD(pa_bus_record, barcode); LAYOUT_FIELD(pa_bus_record, umi); LAYOUT_FIELD(pa_bus_record, ec); LAYOUT_FIELD(pa_bus_record, count);
+    LAYOUT_FIELD(pa_bus_record, flags); LAYOUT_FIELD(pa_bus_record, pad);
+    EXPECT(sizeof(pa_bus_record) == 32 && offsetof(pa_bus_record, ec) == 16 && offsetof(pa_bus_record, pad) == 28);
 
     /* ---- host half ---- */
     EXPECT(pa_abi_version() == PA_ABI_VERSION);
@@ -108,6 +112,19 @@ int main(int argc, char** argv) {
         EXPECT(pa_cell_counter_stats(NULL, cst) == PA_ERR_INVALID_ARG);
         pa_cell_counter_destroy(NULL);
         EXPECT(pa_count_cells(NULL, h, fastq, fastq, path, 4, 4, dir, 1, cst) == PA_ERR_INVALID_ARG);
+        /* BUS output: every entry point refuses a null handle before any device call */
+        pa_bus* bus = NULL;
+        uint64_t bst[PA_BUS_STATS], nrec = 0, nids = 0;
+        uint32_t necs = 0;
+        EXPECT(pa_bus_create(NULL, h, 16, 12, &bus) == PA_ERR_INVALID_ARG && bus == NULL);
+        EXPECT(pa_bus_add_device(NULL, NULL, NULL, 0, NULL, NULL, 0, NULL) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_bus_finish(NULL, &nrec, &necs) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_bus_records(NULL, NULL, 0) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_bus_ecs(NULL, NULL, NULL, 0, &nids) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_bus_stats(NULL, bst) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_bus_write(NULL, dir) == PA_ERR_INVALID_ARG);
+        pa_bus_destroy(NULL);
+        EXPECT(pa_write_bus(NULL, h, fastq, fastq, 4, 4, dir, 1, bst) == PA_ERR_INVALID_ARG);
     }
 
     {   /* transcript abundances, host side: the defaults, the struct as this compiler lays it out, and the checks that come before any device call */
@@ -479,6 +496,28 @@ int main(int argc, char** argv) {
             EXPECT(pa_cell_counter_stats(cc, cst) == PA_OK && cst[0] == nsim && cst[0] == cst[3] + cst[4] + cst[5] + cst[6] && cst[1] == nsim);
             EXPECT(pa_cell_counter_add_device(cc, (const pa_read_result*)d_res, (const uint32_t*)d_arena, (const uint8_t*)d_r1, (const uint64_t*)d_r1o, nsim, NULL) == PA_ERR_INVALID_ARG);
             pa_cell_counter_destroy(cc);
+            {   /* BUS records of the same batch (barcode 4 + UMI 4), then the file-level entry on the FASTQ as both R1 and R2 */
+                pa_bus* bus = NULL;
+                uint64_t nrec = 0, nids = 0, bst[PA_BUS_STATS];
+                uint32_t necs = 0;
+                EXPECT(pa_bus_create(idx, h, 17, 16, &bus) == PA_ERR_UNSUPPORTED && bus == NULL);
+                EXPECT(pa_bus_create(idx, h, 4, 4, &bus) == PA_OK && bus);
+                EXPECT(pa_bus_add_device(bus, (const pa_read_result*)d_res, (const uint32_t*)d_arena, arena_cap, (const uint8_t*)d_r1, (const uint64_t*)d_r1o, nsim, NULL) == PA_OK);
+                EXPECT(pa_bus_finish(bus, &nrec, &necs) == PA_OK && nrec >= 1 && necs >= ntx);
+                pa_bus_record* rec = (pa_bus_record*)calloc(nrec + 1, sizeof(pa_bus_record));
+                EXPECT(pa_bus_records(bus, rec, nrec - 1) == PA_ERR_BUFFER_TOO_SMALL);
+                EXPECT(pa_bus_records(bus, rec, nrec) == PA_OK && rec[0].count >= 1 && rec[0].flags == 0 && rec[0].ec >= 0 && (uint32_t)rec[0].ec < necs);
+                EXPECT(pa_bus_ecs(bus, NULL, NULL, 0, &nids) == PA_OK && nids >= necs);
+                uint64_t* eoff = (uint64_t*)calloc((size_t)necs + 1, 8);
+                uint32_t* eids = (uint32_t*)calloc(nids + 1, 4);
+                EXPECT(pa_bus_ecs(bus, eoff, eids, nids, &nids) == PA_OK && eoff[0] == 0 && eoff[necs] == nids && eids[0] == 0);
+                EXPECT(pa_bus_stats(bus, bst) == PA_OK && bst[0] == nsim && bst[0] == bst[1] + bst[2] + bst[3] + bst[4] + bst[5] + bst[6] && bst[7] == nrec);
+                EXPECT(pa_bus_write(bus, dir) == PA_OK);
+                EXPECT(pa_bus_add_device(bus, (const pa_read_result*)d_res, (const uint32_t*)d_arena, arena_cap, (const uint8_t*)d_r1, (const uint64_t*)d_r1o, nsim, NULL) == PA_ERR_INVALID_ARG);
+                pa_bus_destroy(bus);
+                free(rec); free(eoff); free(eids);
+                EXPECT(pa_write_bus(idx, h, fastq, fastq, 4, 4, dir, 2, bst) == PA_OK && bst[0] == nreads && bst[0] == bst[1] + bst[2] + bst[3] + bst[4] + bst[5] + bst[6]);
+            }
             free(mc); free(mg); free(mu); free(r1); free(r1o);
             EXPECT(pa_device_free(d_r1) == PA_OK && pa_device_free(d_r1o) == PA_OK);
             snprintf(path, sizeof path, "%s/abi_check_whitelist.txt", dir);

@@ -23,7 +23,7 @@ from ._ffi import (PA_DEFAULT_ALLOWED_MISMATCHES, PA_ERR_ARENA_FULL, PA_MAPPED_B
 __all__ = ["HostIndex", "Txome", "Pseudoaligner", "build_index", "process_reads", "process_reads_multi", "PaError", "lib", "concat_reads",
            "gather_classes", "unpack_compact", "unpack_tiles", "RESULT_DTYPE", "PA_MAPPED_BIT", "PA_DEFAULT_ALLOWED_MISMATCHES",
            "PA_READ_COVERAGE_THRESHOLD", "PA_CLASS_REF", "Overflow", "Comm", "parse_overflow", "serialise_overflow", "overflow_merge",
-           "CellCounter", "load_whitelist", "Quantifier"]
+           "CellCounter", "load_whitelist", "Quantifier", "BusWriter", "BUS_RECORD_DTYPE"]
 
 PA_CLASS_REF = 0x80000000
 RESULT_DTYPE = np.dtype([("coverage", "<u4"), ("mismatches", "<u4"), ("class_off", "<u4"), ("class_len", "<u4")])
@@ -462,6 +462,14 @@ class Pseudoaligner:
                                    str(out_dir).encode(), num_threads, st.ctypes.data))
         return dict(zip(_ffi.CELL_STAT_NAMES, (int(x) for x in st)))
 
+    def write_bus(self, host_index: HostIndex, r1: str, r2: str, out_dir: str, bc_len: int = 16, umi_len: int = 12, num_threads: int = 0) -> dict:
+        """Paired R1 (barcode + UMI) / R2 (cDNA) FASTQ -> out_dir/output.bus (sorted, collapsed BUS v1 records), matrix.ec and
+        transcripts.txt (pa_write_bus): the input of the kallisto | bustools family. Returns the stats (BusWriter.stats)."""
+        st = np.zeros(_ffi.PA_BUS_STATS, np.uint64)
+        check(lib().pa_write_bus(self._h, host_index._h, str(r1).encode(), str(r2).encode(), bc_len, umi_len, str(out_dir).encode(), num_threads,
+                                 st.ctypes.data))
+        return dict(zip(_ffi.BUS_STAT_NAMES, (int(x) for x in st)))
+
     def quantify(self, d_counts: int, overflow: Optional["Overflow"] = None, **params) -> "Quantifier":
         """Transcript abundances from a class-count table on this GPU (d_counts: the device pointer the count launches accumulated into,
         their streams synchronised) and, optionally, the overflow table that was attached: copies the table back, fetches the overflow,
@@ -603,6 +611,63 @@ class CellCounter:
         try:
             if self._h:
                 lib().pa_cell_counter_destroy(self._h)
+                self._h = vp()
+        except Exception:
+            pass
+
+
+BUS_RECORD_DTYPE = np.dtype([("barcode", "<u8"), ("umi", "<u8"), ("ec", "<i4"), ("count", "<u4"), ("flags", "<u4"), ("pad", "<u4")])   # pa_bus_record
+
+
+class BusWriter:
+    """Sorted (barcode, UMI, equivalence class) records on the index's GPU (pa_bus): feed it device-resident batches (the mapping's
+    records of the R2s + the R1s), then finish() and read records() / ecs(), or write() the three files of a BUS run."""
+
+    def __init__(self, aligner: "Pseudoaligner", host_index: HostIndex, bc_len: int = 16, umi_len: int = 12):
+        self._h = vp()
+        self._aligner, self._host = aligner, host_index   # the index and the host index outlive the writer
+        check(lib().pa_bus_create(aligner._h if aligner is not None else None, host_index._h if host_index is not None else None, bc_len, umi_len,
+                                  C.byref(self._h)))
+
+    def add_device(self, d_results: int, d_arena: int, arena_len: int, d_r1: int, d_r1_offsets: int, n_reads: int, stream: int = 0) -> None:
+        check(lib().pa_bus_add_device(self._h, d_results, d_arena, arena_len, d_r1, d_r1_offsets, n_reads, stream or None))
+
+    def finish(self) -> Tuple[int, int]:
+        """(records, ecs)"""
+        n, e = C.c_uint64(), C.c_uint32()
+        check(lib().pa_bus_finish(self._h, C.byref(n), C.byref(e)))
+        return n.value, e.value
+
+    def records(self) -> np.ndarray:
+        """the records after finish (BUS_RECORD_DTYPE), ascending by barcode, UMI, ec"""
+        n, _ = self.finish()
+        out = np.zeros(max(n, 1), BUS_RECORD_DTYPE)
+        check(lib().pa_bus_records(self._h, out.ctypes.data, n))
+        return out[:n]
+
+    def ecs(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(offsets[n_ecs + 1], ids): ec e = ids[offsets[e]:offsets[e + 1]]"""
+        _, n_ecs = self.finish()
+        n_ids = C.c_uint64()
+        check(lib().pa_bus_ecs(self._h, None, None, 0, C.byref(n_ids)))
+        off, ids = np.zeros(n_ecs + 1, np.uint64), np.zeros(max(n_ids.value, 1), np.uint32)
+        check(lib().pa_bus_ecs(self._h, off.ctypes.data, ids.ctypes.data, n_ids.value, C.byref(n_ids)))
+        return off, ids[:n_ids.value]
+
+    def stats(self) -> dict:
+        st = np.zeros(_ffi.PA_BUS_STATS, np.uint64)
+        check(lib().pa_bus_stats(self._h, st.ctypes.data))
+        return dict(zip(_ffi.BUS_STAT_NAMES, (int(x) for x in st)))
+
+    def write(self, out_dir: str) -> None:
+        """out_dir/output.bus, matrix.ec, transcripts.txt"""
+        self.finish()
+        check(lib().pa_bus_write(self._h, str(out_dir).encode()))
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib().pa_bus_destroy(self._h)
                 self._h = vp()
         except Exception:
             pass

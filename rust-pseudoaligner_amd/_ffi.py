@@ -20,6 +20,8 @@ PA_ERR_NOT_BGZF = -11
 PA_CELL_STATS = 10
 CELL_STAT_NAMES = ("reads", "barcode_exact", "barcode_corrected", "barcode_invalid", "umi_invalid", "not_confidently_mapped", "reads_counted",
                    "umis_corrected", "molecules_lost_to_conflicts", "umis_in_matrix")
+PA_BUS_STATS = 8
+BUS_STAT_NAMES = ("reads", "r1_short", "barcode_n", "umi_n", "unmapped", "bad_class", "recorded", "records")
 PA_MAPPED_BIT = 0x80000000
 PA_DEFAULT_ALLOWED_MISMATCHES = 2
 PA_READ_COVERAGE_THRESHOLD = 32
@@ -51,6 +53,10 @@ class IndexStats(C.Structure):
     _fields_ = [("num_kmers", C.c_uint64), ("table_slots", C.c_uint64), ("bytes_table", C.c_uint64), ("bytes_graph", C.c_uint64),
                 ("bytes_classes", C.c_uint64), ("bytes_total", C.c_uint64), ("num_nodes", C.c_uint32), ("num_classes", C.c_uint32),
                 ("k", C.c_uint32), ("max_class_len", C.c_uint32)]
+
+
+class BusRecord(C.Structure):
+    _fields_ = [("barcode", C.c_uint64), ("umi", C.c_uint64), ("ec", C.c_int32), ("count", C.c_uint32), ("flags", C.c_uint32), ("pad", C.c_uint32)]
 
 
 class QuantParams(C.Structure):
@@ -155,6 +161,15 @@ SIGNATURES = {
     "pa_cell_counter_destroy": (None, [vp]),
     "pa_whitelist_load": (C.c_int, [C.c_char_p, C.c_uint32, vp, C.c_uint64, u64p]),
     "pa_count_cells": (C.c_int, [vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, vp]),
+    "pa_bus_create": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
+    "pa_bus_add_device": (C.c_int, [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp]),
+    "pa_bus_finish": (C.c_int, [vp, u64p, u32p]),
+    "pa_bus_records": (C.c_int, [vp, vp, C.c_uint64]),
+    "pa_bus_ecs": (C.c_int, [vp, vp, vp, C.c_uint64, u64p]),
+    "pa_bus_stats": (C.c_int, [vp, vp]),
+    "pa_bus_write": (C.c_int, [vp, C.c_char_p]),
+    "pa_bus_destroy": (None, [vp]),
+    "pa_write_bus": (C.c_int, [vp, vp, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, vp]),
     "pa_quant_default_params": (None, [C.POINTER(QuantParams)]),
     "pa_quant_create": (C.c_int, [vp, vp, C.POINTER(QuantParams), C.POINTER(vp)]),
     "pa_quant_set_counts": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64]),

@@ -437,6 +437,57 @@ int count_cells_impl(pa_index* idx, const pa_host_index* h, const char* r1_path,
     return PA_OK;
 }
 
+// ---- pa_write_bus: the same two files -> sorted (barcode, UMI, ec) records, output.bus + matrix.ec + transcripts.txt ----
+
+// waits for the mapping (regrowing the arena as pa_map_finish asks), then adds the batch's records
+int bus_batch_add(pa_index* idx, pa_bus* bus, CellBatch& b, hipStream_t s, double* st) {
+    auto t0 = std::chrono::steady_clock::now();
+    Mate &r1 = b.mate[0], &r2 = b.mate[1];
+    uint64_t used = 0;
+    int e = map_finish_regrow(idx, s, r2.d_arena, &used, [&] { return r2.map(idx, r2.d_tiles.get(), b.n, PA_DEFAULT_ALLOWED_MISMATCHES, s); });
+    st[2] += secs_since(t0);
+    if (e != PA_OK) return e;
+    t0 = std::chrono::steady_clock::now();
+    e = pa_bus_add_device(bus, r2.d_results.get(), r2.d_arena.get(), r2.d_arena.size(), r1.d_bytes.get(), r1.d_off.get(), b.n, s);
+    st[4] += secs_since(t0);
+    return e;
+}
+
+int write_bus_impl(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, uint32_t bc_len, uint32_t umi_len, const char* out_dir,
+                   int num_threads, uint64_t* stats) {
+    const auto t_call = std::chrono::steady_clock::now();
+    double* st = last_stage_seconds();
+    for (int j = 0; j < PA_INGEST_STAGES; ++j) st[j] = 0.0;
+    if (!idx || !h || !r1_path || !r2_path || !out_dir) return fail(PA_ERR_INVALID_ARG, "null argument");
+    struct stat sd;
+    if (stat(out_dir, &sd) != 0 || !S_ISDIR(sd.st_mode)) return fail(PA_ERR_IO, "%s is no directory", out_dir);
+    pa_bus* bus = nullptr;
+    int rc = pa_bus_create(idx, h, bc_len, umi_len, &bus);
+    if (rc != PA_OK) return rc;
+    std::unique_ptr<pa_bus, void (*)(pa_bus*)> own(bus, pa_bus_destroy);
+
+    Pool pool(num_threads < 1 ? usable_threads() : num_threads);
+    PairReader rd(r1_path, r2_path, pool, bc_len + umi_len, st);
+    if ((rc = rd.open()) != PA_OK) return rc;
+    IndexStream stream;
+    if ((rc = stream.create(idx)) != PA_OK) return rc;
+    hipStream_t s = stream.get();
+    CellBatch batches[2];
+    rc = run_batches(rd, batches, [&](CellBatch& b) { return cell_batch_map(idx, b, s); }, [&](CellBatch& b) { return bus_batch_add(idx, bus, b, s, st); });
+    if (rc != PA_OK) return rc;
+    auto t0 = std::chrono::steady_clock::now();
+    uint64_t n_records = 0;
+    uint32_t n_ecs = 0;
+    if ((rc = pa_bus_finish(bus, &n_records, &n_ecs)) != PA_OK) return rc;
+    st[4] += secs_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    if ((rc = pa_bus_write(bus, out_dir)) != PA_OK) return rc;
+    st[5] = secs_since(t0);
+    if (stats) (void)pa_bus_stats(bus, stats);
+    st[6] = secs_since(t_call);
+    st[7] = (double)rd.pairs;
+    return PA_OK;
+}
 
 // ---- pa_count_pairs: two FASTQ files -> the class-count table of the pairs ----
 struct PairBatch : CellBatch {   // + the reverse-complemented tiles of one mate, the pair stage's outputs
@@ -542,4 +593,9 @@ extern "C" int pa_count_cells(pa_index* idx, const pa_host_index* h, const char*
 extern "C" int pa_count_pairs(pa_index* idx, const char* r1_path, const char* r2_path, int orient, uint32_t allowed_mismatches, int num_threads, uint64_t* h_counts,
                               uint64_t* n_pairs, uint64_t stats[PA_PAIR_STATS]) {
     return no_throw("pa_count_pairs", [&] { return count_pairs_impl(idx, r1_path, r2_path, orient, allowed_mismatches, num_threads, h_counts, n_pairs, stats); });
+}
+
+extern "C" int pa_write_bus(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, uint32_t bc_len, uint32_t umi_len, const char* out_dir,
+                            int num_threads, uint64_t stats[PA_BUS_STATS]) {
+    return no_throw("pa_write_bus", [&] { return write_bus_impl(idx, h, r1_path, r2_path, bc_len, umi_len, out_dir, num_threads, stats); });
 }
