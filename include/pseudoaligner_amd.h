@@ -382,7 +382,8 @@ void pa_record_stream_destroy(pa_record_stream* s);
  * text that is not in four-line shape; 0 for a record stream), out[1] pack (pa_process_reads: reading the windows' text into pinned
  * memory; a record stream: gathering ids and sequences), out[2] waiting for the GPU (a window's scan, its kernels), out[3] launch,
  * out[4] waiting for the rendered tuples, out[5] waiting for the writer (0 for a record stream), out[6] the whole call (streams: the
- * sum of the others), out[7] reads. */
+ * sum of the others), out[7] reads. The paired drivers (pa_count_cells, pa_write_bus, pa_count_pairs) report through the same getter, with
+ * the meanings their own comments give. */
 #define PA_INGEST_STAGES 8
 /* What the last pa_process_reads[_multi] call of this thread read: out[0] text_kind (0 a plain mapped file, 1 gzip inflated by the host, 2 BGZF inflated on
  * the GPU), out[1] members of the file (0 unless BGZF), out[2] members inflated on the GPU (launches: a member of a window that was read twice counts twice),
@@ -511,7 +512,15 @@ int pa_whitelist_load(const char* path, uint32_t bc_len, char* out, uint64_t cap
  * sorted by cell then gene), out_dir/barcodes.tsv (the whitelist barcodes with at least one UMI, in whitelist order = the columns),
  * out_dir/features.tsv ("name\tname\tGene Expression" for every gene). stats may be NULL. Batches of about 2 M pairs; the next batch
  * is read while the GPU maps and counts the one before. pa_process_reads_stage_seconds then reports this call's stages:
- * [0] scan, [1] gather, [2] waiting for the mapping, [3] launch, [4] counting (add_device + finish), [5] writing, [6] whole, [7] pairs. */
+ * [0] scan, [1] gather, [2] waiting for the mapping, [3] launch, [4] counting (add_device + finish), [5] writing, [6] whole, [7] pairs.
+ * Which input takes which path (pa_count_cells, pa_write_bus and pa_count_pairs alike). DEVICE path: the host does not look at the text — windows of
+ * the files (a BGZF file's compressed members) go to HBM, the GPU inflates, finds the records, compares the ids and gathers R2 and the R1 prefix
+ * (pa_pairs_gather_device's kernels); only the end of each file, and text that is not in four-line shape, is scanned by the host. It is taken when BOTH
+ * files are BGZF; with PA_PAIRS_DEVICE_PLAIN=1 in the environment also when the files are plain text or BGZF in any mix (plain text is on request only
+ * until its rate has been measured against the host path's). HOST path (scan, id compare and gather on the worker pool; gzip and BGZF inflated whole by
+ * zlib): everything else — a plain file without that request, an ordinary-gzip file on either side, or PA_PAIRS_HOST_SCAN=1. Results and error messages
+ * are the same on both. On the device path the stages mean: [0] the host's scan (the tails), [1] reading windows into pinned memory, [2] waiting for
+ * the GPU (a window's scan, a batch's gather, the mapping), [3] launch. pa_pairs_input_path says which path the last call took. */
 int pa_count_cells(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const char* whitelist_path,
                    uint32_t bc_len, uint32_t umi_len, const char* out_dir, int num_threads, uint64_t stats[PA_CELL_STATS]);
 
@@ -700,6 +709,38 @@ int pa_map_pairs(pa_index* idx, const uint8_t* ascii1, const uint64_t* offsets1,
  * call's stages: [0] scan, [1] gather, [2] waiting for the mappings, [3] launch, [4] combine + count, [6] whole, [7] pairs. */
 int pa_count_pairs(pa_index* idx, const char* r1_path, const char* r2_path, int orient, uint32_t allowed_mismatches, int num_threads,
                    uint64_t* h_counts, uint64_t* n_pairs, uint64_t stats[PA_PAIR_STATS]);
+
+/* ---------------- the pair scan on the device: ids compared, R2 and the R1 prefix gathered ---------------- */
+#define PA_PAIRS_CTL_WORDS 8            /* u64 words of the control block d_ctl */
+#define PA_PAIRS_WHOLE_READ 0xFFFFFFFFu /* prefix: all of R1 */
+/* What the paired drivers do per batch on the host today (record.id() of record i of both files compared after a trailing "/1" or "/2"
+ * is cut, every R2 sequence and the first `prefix` bytes of every R1 sequence copied back to back), for texts and record tables that lie in
+ * HBM. One call handles a SEGMENT: m pairs, record i of d_rec1 with record i of d_rec2, that land at positions [base, base + m) of a batch.
+ *   d_text1 / d_text2   the two texts (text1_bytes / text2_bytes of them are readable), any alignment
+ *   d_rec1 / d_rec2     m rows of four u32 each, 16-byte aligned: {id offset, id length, sequence offset, sequence length}, offsets into
+ *                       the row's own text (the layout the GPU's FASTQ scan writes). A row that points outside its text is not read: the
+ *                       pair gets two empty pieces and its batch position is folded into d_ctl[5]
+ *   prefix              bytes of every R1 sequence that are kept; PA_PAIRS_WHOLE_READ: all of it
+ *   d_bytes1 / d_off1   R1's pieces back to back and their offsets (u64[base + m + 1] at least; d_off1[base + m] = the bytes so far), so that
+ *   d_bytes2 / d_off2   piece i of the batch is d_bytes[d_off[i] .. d_off[i + 1]); the same for R2's whole sequences. A piece that
+ *                       would end beyond cap1 / cap2 is not written (no byte beyond the capacity ever is); d_ctl[3] / d_ctl[4] still count
+ *                       it, so bytes > capacity says that the batch did not fit
+ *   d_ctl               u64[PA_PAIRS_CTL_WORDS], on the device: [0] the smallest batch position whose two ids differ (~0: none), [1] the longest
+ *                       R1 piece, [2] the longest R2 piece, [3] R1 bytes, [4] R2 bytes, [5] the smallest batch position with a row outside its
+ *                       text (~0: none). A call with base == 0 opens a batch and resets the block; later segments of the batch continue it (the
+ *                       running byte counts are the bases of their offsets), in call order on one stream
+ *   d_scratch           pa_pairs_gather_scratch_bytes(m) bytes (0: m is beyond the 2^30 pairs of one segment), 256-byte aligned, free again
+ *                       when the call's work on the stream is done
+ * Asynchronous on stream; m = 0 is valid (an empty segment still opens the batch at base == 0 and writes d_off[base]). */
+size_t pa_pairs_gather_scratch_bytes(uint64_t m);
+int pa_pairs_gather_device(int device, const uint8_t* d_text1, uint64_t text1_bytes, const uint32_t* d_rec1, const uint8_t* d_text2,
+                           uint64_t text2_bytes, const uint32_t* d_rec2, uint64_t m, uint32_t prefix, uint64_t base, uint8_t* d_bytes1,
+                           uint64_t cap1, uint64_t* d_off1, uint8_t* d_bytes2, uint64_t cap2, uint64_t* d_off2, uint64_t* d_ctl, void* d_scratch,
+                           size_t scratch_bytes, void* stream);
+/* What this thread's last pa_count_cells / pa_write_bus / pa_count_pairs call read: R1's six entries, then R2's, in pa_process_reads_input_stats' meaning
+ * (on the host path only text_kind is filled in). pa_pairs_input_path: 1 when that call took the device path, 0 for the host path. */
+int pa_pairs_input_stats(uint64_t out[2 * PA_INGEST_INPUT_STATS]);
+int pa_pairs_input_path(void);
 
 /* ---------------- novel classes + the reduction over GPUs ---------------- */
 /* The dense table counts every result that is no index class in ONE slot (counts[num_classes]). A pa_overflow keeps WHICH

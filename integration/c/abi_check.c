@@ -166,6 +166,14 @@ int main(int argc, char** argv) {
         EXPECT(pa_pairs_finish(NULL, NULL, NULL, pst, &pu, &pn) == PA_ERR_INVALID_ARG);
         EXPECT(pa_map_pairs(NULL, NULL, poff, NULL, poff, 1, PA_PAIR_FR, 2, pr, NULL, NULL) == PA_ERR_INVALID_ARG);
         EXPECT(pa_count_pairs(NULL, fastq, fastq, PA_PAIR_FR, 2, 1, counts, &pn, pst) == PA_ERR_INVALID_ARG);
+        /* the pair scan on the device: its scratch is sized on the host, null outputs are refused before any device call */
+        EXPECT(PA_PAIRS_CTL_WORDS == 8 && PA_PAIRS_WHOLE_READ == 0xFFFFFFFFu);
+        {
+            uint64_t pis[2 * PA_INGEST_INPUT_STATS];
+            EXPECT(pa_pairs_input_stats(pis) == PA_OK && pa_pairs_input_stats(NULL) == PA_ERR_INVALID_ARG && (pa_pairs_input_path() == 0 || pa_pairs_input_path() == 1));
+        }
+        EXPECT(pa_pairs_gather_scratch_bytes(0) >= 256 && pa_pairs_gather_scratch_bytes(1000) > pa_pairs_gather_scratch_bytes(10) && pa_pairs_gather_scratch_bytes(1ull << 31) == 0);
+        EXPECT(pa_pairs_gather_device(0, NULL, 0, NULL, NULL, 0, NULL, 0, 0, 0, NULL, 0, NULL, NULL, 0, NULL, NULL, NULL, 0, NULL) == PA_ERR_INVALID_ARG);
     }
 
     pa_txome *tx = NULL, *tx2 = NULL, *tx3 = NULL;
@@ -227,6 +235,11 @@ int main(int argc, char** argv) {
             uint8_t btext[32];
             EXPECT(pa_bgzf_inflate_device(0, bgzf_file, sizeof bgzf_file, bgzf_rows, 2, btext, sizeof btext, bst, NULL) == PA_ERR_NO_DEVICE);
         }
+        {
+            uint64_t goff[4], gctl[PA_PAIRS_CTL_WORDS];
+            void* gscr = (void*)(uintptr_t)256;   /* (never touched: the call refuses before it looks at device memory) */
+            EXPECT(pa_pairs_gather_device(0, NULL, 0, NULL, NULL, 0, NULL, 0, 2, 0, NULL, 0, goff, NULL, 0, goff + 2, gctl, gscr, 4096, NULL) == PA_ERR_NO_DEVICE);
+        }
         EXPECT(pa_overflow_create(0, 16, 64, &o) == PA_ERR_NO_DEVICE);
         EXPECT(pa_txome_upload(tx2, 60, 0, &td) == PA_ERR_NO_DEVICE);
         EXPECT(pa_event_create(&ev) < 0);
@@ -270,6 +283,29 @@ int main(int argc, char** argv) {
             EXPECT(pa_memcpy_d2h(btext, d_btext, 28, NULL) == PA_OK && pa_memcpy_d2h(bst, d_bst, 8, NULL) == PA_OK && pa_stream_synchronize(NULL) == PA_OK);
             EXPECT(bst[0] == PA_INFLATE_OK && bst[1] == PA_INFLATE_OK && memcmp(btext, bgzf_text, 28) == 0);
             pa_device_free(d_bcomp); pa_device_free(d_brows); pa_device_free(d_btext); pa_device_free(d_bst);
+        }
+        {   /* two pairs matched and gathered on the GPU: "a/1" with "a/2", "b" with "c" (position 1 differs); R1 cut to two bytes */
+            static const char gt1[] = "a/1ACGTbGGG", gt2[] = "a/2TTTTTcCA";
+            const uint32_t grec1[8] = {0, 3, 3, 4, 7, 1, 8, 3}, grec2[8] = {0, 3, 3, 5, 8, 1, 9, 2};
+            const size_t gsb = pa_pairs_gather_scratch_bytes(2);
+            void *d_gt1 = NULL, *d_gt2 = NULL, *d_gr1 = NULL, *d_gr2 = NULL, *d_gb1 = NULL, *d_gb2 = NULL, *d_go1 = NULL, *d_go2 = NULL, *d_gctl = NULL, *d_gscr = NULL;
+            uint64_t gctl[PA_PAIRS_CTL_WORDS], go1[3], go2[3];
+            char gb1[4], gb2[7];
+            EXPECT(pa_device_malloc(0, 16, &d_gt1) == PA_OK && pa_device_malloc(0, 16, &d_gt2) == PA_OK && pa_device_malloc(0, 32, &d_gr1) == PA_OK &&
+                   pa_device_malloc(0, 32, &d_gr2) == PA_OK && pa_device_malloc(0, 64, &d_gb1) == PA_OK && pa_device_malloc(0, 64, &d_gb2) == PA_OK &&
+                   pa_device_malloc(0, 24, &d_go1) == PA_OK && pa_device_malloc(0, 24, &d_go2) == PA_OK && pa_device_malloc(0, sizeof gctl, &d_gctl) == PA_OK &&
+                   pa_device_malloc(0, gsb, &d_gscr) == PA_OK);
+            EXPECT(pa_memcpy_h2d(d_gt1, gt1, 11, NULL) == PA_OK && pa_memcpy_h2d(d_gt2, gt2, 11, NULL) == PA_OK && pa_memcpy_h2d(d_gr1, grec1, 32, NULL) == PA_OK &&
+                   pa_memcpy_h2d(d_gr2, grec2, 32, NULL) == PA_OK && pa_stream_synchronize(NULL) == PA_OK);
+            EXPECT(pa_pairs_gather_device(0, (const uint8_t*)d_gt1, 11, (const uint32_t*)d_gr1, (const uint8_t*)d_gt2, 11, (const uint32_t*)d_gr2, 2, 2, 0, (uint8_t*)d_gb1, 64,
+                                          (uint64_t*)d_go1, (uint8_t*)d_gb2, 64, (uint64_t*)d_go2, (uint64_t*)d_gctl, d_gscr, gsb, NULL) == PA_OK);
+            EXPECT(pa_memcpy_d2h(gctl, d_gctl, sizeof gctl, NULL) == PA_OK && pa_memcpy_d2h(go1, d_go1, 24, NULL) == PA_OK && pa_memcpy_d2h(go2, d_go2, 24, NULL) == PA_OK &&
+                   pa_memcpy_d2h(gb1, d_gb1, 4, NULL) == PA_OK && pa_memcpy_d2h(gb2, d_gb2, 7, NULL) == PA_OK && pa_stream_synchronize(NULL) == PA_OK);
+            EXPECT(gctl[0] == 1 && gctl[1] == 2 && gctl[2] == 5 && gctl[3] == 4 && gctl[4] == 7 && gctl[5] == ~0ull);
+            EXPECT(go1[0] == 0 && go1[1] == 2 && go1[2] == 4 && go2[0] == 0 && go2[1] == 5 && go2[2] == 7);
+            EXPECT(memcmp(gb1, "ACGG", 4) == 0 && memcmp(gb2, "TTTTTCA", 7) == 0);
+            pa_device_free(d_gt1); pa_device_free(d_gt2); pa_device_free(d_gr1); pa_device_free(d_gr2); pa_device_free(d_gb1); pa_device_free(d_gb2);
+            pa_device_free(d_go1); pa_device_free(d_go2); pa_device_free(d_gctl); pa_device_free(d_gscr);
         }
         /* single reads and host batches */
         const char* ex1 = "GGCTGTCAACCAGTCCATAGGCAGGGCCATCAGGCACCAAAGGGATTCTGCCAGCATAGT";

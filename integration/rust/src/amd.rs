@@ -176,6 +176,36 @@ pub fn process_reads_input_stats() -> Result<[u64; 6], Error> {
     Ok(st)
 }
 
+/// What this thread's last paired call (`count_pairs_path` and the cells / BUS drivers) read: ([R1's input stats], [R2's], device path taken),
+/// the stats in `process_reads_input_stats`' meaning (`pa_pairs_input_stats`, `pa_pairs_input_path`).
+pub fn pairs_input_stats() -> Result<([u64; 6], [u64; 6], bool), Error> {
+    let mut st = [0u64; 12];
+    check(unsafe { crate::amd_pairscan_ffi::pa_pairs_input_stats(st.as_mut_ptr()) })?;
+    let (mut r1, mut r2) = ([0u64; 6], [0u64; 6]);
+    r1.copy_from_slice(&st[..6]);
+    r2.copy_from_slice(&st[6..]);
+    Ok((r1, r2, unsafe { crate::amd_pairscan_ffi::pa_pairs_input_path() } == 1))
+}
+
+/// Device buffers of one segment of a batch of pairs for `pairs_gather_segment` (`pa_pairs_gather_device`): raw device pointers and sizes, as the header names them.
+pub struct PairSegment {
+    pub d_text1: *const u8, pub text1_bytes: u64, pub d_rec1: *const u32,
+    pub d_text2: *const u8, pub text2_bytes: u64, pub d_rec2: *const u32,
+    pub m: u64, pub prefix: u32, pub base: u64,
+    pub d_bytes1: *mut u8, pub cap1: u64, pub d_off1: *mut u64,
+    pub d_bytes2: *mut u8, pub cap2: u64, pub d_off2: *mut u64,
+    pub d_ctl: *mut u64, pub d_scratch: *mut std::ffi::c_void, pub scratch_bytes: usize,
+}
+
+/// The ids of `m` pairs compared and their R1 prefixes and R2 sequences gathered on GPU `device`, asynchronous on `stream`; `base == 0` opens a batch.
+/// # Safety
+/// Every pointer of `seg` is a device pointer that is valid for the sizes the header gives.
+pub unsafe fn pairs_gather_segment(device: i32, seg: &PairSegment, stream: *mut std::ffi::c_void) -> Result<(), Error> {
+    use crate::amd_pairscan_ffi::pa_pairs_gather_device;
+    check(pa_pairs_gather_device(device, seg.d_text1, seg.text1_bytes, seg.d_rec1, seg.d_text2, seg.text2_bytes, seg.d_rec2, seg.m, seg.prefix, seg.base,
+                                 seg.d_bytes1, seg.cap1, seg.d_off1, seg.d_bytes2, seg.cap2, seg.d_off2, seg.d_ctl, seg.d_scratch, seg.scratch_bytes, stream))
+}
+
 /// One replica of the index per GPU (`pa_index_create_multi`): what `process_reads_path` deals its windows of text to.
 pub struct AmdIndexSet { raw: Vec<*mut PaIndex> }
 unsafe impl Send for AmdIndexSet {}

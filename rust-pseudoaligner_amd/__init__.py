@@ -1066,6 +1066,49 @@ def bgzf_inflate(data: bytes, device: int = 0) -> Tuple[bytes, np.ndarray]:
     return text.tobytes(), status
 
 
+def pairs_input_stats() -> dict:
+    """what this thread's last count_cells / write_bus / count_pairs call read (pa_pairs_input_stats, pa_pairs_input_path):
+    {"device_path": whether the GPU scanned, compared and gathered, "r1": {...}, "r2": {...}} with the entries of process_reads_input_stats per file"""
+    st = (C.c_uint64 * 12)()
+    check(lib().pa_pairs_input_stats(st))
+    v = [int(x) for x in st]
+    return {"device_path": lib().pa_pairs_input_path() == 1, "r1": dict(zip(INPUT_STATS, v[:6])), "r2": dict(zip(INPUT_STATS, v[6:]))}
+
+
+def pairs_gather_scratch_bytes(m: int) -> int:
+    """pa_pairs_gather_scratch_bytes: the scratch one segment of m pairs needs (0: more pairs than a segment takes)"""
+    return lib().pa_pairs_gather_scratch_bytes(m)
+
+
+def pairs_gather_device(text1, rec1, text2, rec2, prefix: int, base: int, bytes1, off1, bytes2, off2, ctl, m: Optional[int] = None, scratch=None) -> None:
+    """pa_pairs_gather_device on torch tensors of one GPU, asynchronous on torch's current stream: one SEGMENT of a batch of pairs.
+      text1, text2   uint8: the two texts
+      rec1, rec2     int32 [m, 4], contiguous: {id offset, id length, sequence offset, sequence length} per record (the bits of u32)
+      prefix         bytes of every R1 sequence that are kept (_ffi.PA_PAIRS_WHOLE_READ: all)
+      base           the batch position of the segment's first pair; 0 opens a batch (ctl is reset)
+      bytes1, bytes2 uint8: the gathered pieces (nothing is written beyond their sizes)
+      off1, off2     int64, at least base + m + 1 entries
+      ctl            int64 [8]: _ffi.PAIRS_CTL_NAMES, then two unused words
+      scratch        uint8, pairs_gather_scratch_bytes(m) bytes (allocated here when None)"""
+    import torch
+    m = int(rec1.shape[0]) if m is None else int(m)
+    dev = ctl.device
+    for name, t, dt in (("text1", text1, torch.uint8), ("rec1", rec1, torch.int32), ("text2", text2, torch.uint8), ("rec2", rec2, torch.int32), ("bytes1", bytes1, torch.uint8),
+                        ("off1", off1, torch.int64), ("bytes2", bytes2, torch.uint8), ("off2", off2, torch.int64), ("ctl", ctl, torch.int64)):
+        if t.dtype != dt or not t.is_contiguous() or t.device != dev or dev.type != "cuda":
+            raise ValueError("%s: a contiguous %s tensor on %s is expected" % (name, dt, dev))
+    if rec1.numel() < 4 * m or rec2.numel() < 4 * m or off1.numel() < base + m + 1 or off2.numel() < base + m + 1 or ctl.numel() < _ffi.PA_PAIRS_CTL_WORDS:
+        raise ValueError("record tables of m rows, offsets of base + m + 1 entries and a control block of %d words are expected" % _ffi.PA_PAIRS_CTL_WORDS)
+    need = pairs_gather_scratch_bytes(m)
+    if scratch is None:
+        scratch = torch.empty(need + 256, dtype=torch.uint8, device=dev)
+    pad = (-scratch.data_ptr()) % 256
+    check(lib().pa_pairs_gather_device(dev.index or 0, text1.data_ptr() or None, text1.numel(), rec1.data_ptr() or None, text2.data_ptr() or None, text2.numel(),
+                                       rec2.data_ptr() or None, m, prefix, base, bytes1.data_ptr() or None, bytes1.numel(), off1.data_ptr(), bytes2.data_ptr() or None,
+                                       bytes2.numel(), off2.data_ptr(), ctl.data_ptr(), scratch.data_ptr() + pad, scratch.numel() - pad,
+                                       torch.cuda.current_stream(dev).cuda_stream or None))
+
+
 PA_COMPACT_MAPPED, PA_COMPACT_BY_REF, PA_COMPACT_PACKED = 0x10000000, 0x20000000, 0x40000000
 
 

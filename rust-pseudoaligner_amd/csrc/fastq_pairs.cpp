@@ -3,6 +3,12 @@
 // one PairReader, keep two batches of pairs — each two Mates — and run them through one loop (run_batches): batch b is gathered while batch
 // b - 1 is on the GPU. The streams they launch on are IndexStreams, a mapping that ran out of arena goes through map_finish_regrow
 // (hip_buffer.hpp).
+// PairReader has two forms. In the DEVICE form the host does not look at the text: each file is a WindowFeed (window_feed.hpp: raw or compressed
+// windows to HBM, records found by fastq_scan.hip), and the ids are compared and R2 / the R1 prefix gathered on the GPU (pair_scan.hip), straight into
+// the buffers that encode, counter and BUS stage read. It is the default when BOTH files are BGZF (the host form inflates them whole through one zlib
+// stream each). With a plain text file on either side it is taken only on request, PA_PAIRS_DEVICE_PLAIN=1: its rate on plain text has not been
+// measured against the host form's yet. An ordinary-gzip file on either side, or PA_PAIRS_HOST_SCAN=1, keeps the HOST form for the
+// whole call in any case: the host's WindowScan, ids compared and bytes gathered into pinned memory by the pool.
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
 #include <zlib.h>
@@ -18,6 +24,7 @@
 #include <unordered_set>
 
 #include "fastq_text.hpp"
+#include "window_feed.hpp"
 
 using namespace pa;
 using namespace pa::ingest;
@@ -83,11 +90,11 @@ struct PairCursor {
     std::vector<RecPos> rec;
     std::vector<std::vector<uint32_t>> brk;
     uint64_t at = 0, before = 0;   // next record of the window, records of the windows before it
-    int open(const char* p) {
+    void adopt(const char* p, FastqText&& opened) {   // a text that open_fastq has opened
         path = p;
-        const int rc = open_fastq(p, text);
-        if (rc == PA_OK) ws.reset(new WindowScan(text));
-        return rc;
+        text = std::move(opened);
+        opened = FastqText();
+        ws.reset(new WindowScan(text));
     }
     // records left in the window (0: the file has ended); the window before is given up
     int ready(Pool& pool, uint64_t& left) {
@@ -135,10 +142,12 @@ struct Mate {
     DeviceBuffer<pa_read_result> d_results;
     uint64_t bytes = 0;
     uint32_t max_len = 0;   // longest gathered piece
+    bool on_device = false; // the gather ran on the GPU: d_bytes and d_off hold the batch already
     uint32_t wpr() const { return pa_words_per_read(std::max(1u, max_len)); }
     // bytes and offsets of the batch's n pairs to the device, asynchronous on s
     int to_device(uint64_t n, hipStream_t s) {
         int e = PA_OK;
+        if (on_device) return PA_OK;
         if ((e = d_bytes.reserve(bytes + 64, h_bytes.size())) || (e = d_off.reserve(n + 1, h_off.size()))) return e;
         PA_HIP_TRY(hipMemcpyAsync(d_bytes.get(), h_bytes.get(), bytes, hipMemcpyHostToDevice, s));
         PA_HIP_TRY(hipMemcpyAsync(d_off.get(), h_off.get(), (n + 1) * 8, hipMemcpyHostToDevice, s));
@@ -147,7 +156,7 @@ struct Mate {
     // ... and packed into tiles there, with room for the mapping's outputs (spare: reads beyond the pinned offsets' size that the per-read
     // buffers are grown to — each driver's own amount)
     int encode(pa_index* idx, uint64_t n, size_t spare, hipStream_t s) {
-        const size_t tw = pa_tiles_words(n, wpr()) + 1, reads = h_off.size() + spare;
+        const size_t tw = pa_tiles_words(n, wpr()) + 1, reads = (on_device ? d_off.size() : h_off.size()) + spare;
         const uint64_t hint = pa_map_arena_hint(idx, n);
         int e = to_device(n, s);
         if (e || (e = d_tiles.reserve(tw, tw)) || (e = d_lens.reserve(n + 64, reads)) || (e = d_results.reserve(n + 64, reads)) || (e = d_arena.reserve(hint, hint)))
@@ -160,10 +169,39 @@ struct Mate {
     }
 };
 
+struct GpuEvent {   // an event that is created on first use and may be pending
+    hipEvent_t e = nullptr;
+    bool pending = false;
+    GpuEvent() = default;
+    GpuEvent(const GpuEvent&) = delete;
+    GpuEvent& operator=(const GpuEvent&) = delete;
+    ~GpuEvent() { if (e) (void)hipEventDestroy(e); }
+};
+
 struct CellBatch {   // one batch of pairs: R1 (pa_count_cells: its barcode + UMI prefix, which is never encoded or mapped) and R2
     Mate mate[2];
     uint64_t n = 0;
+    GpuEvent consumed[2];   // device form: behind the last work of the batch's consumers on their streams (the next gather into these buffers waits for it)
 };
+
+uint64_t* last_pairs_input() {   // pa_pairs_input_stats / pa_pairs_input_path: of this thread's last paired call — R1's six entries, R2's, the path
+    static thread_local uint64_t st[2 * PA_INGEST_INPUT_STATS + 1] = {0};
+    return st;
+}
+
+// `want` bytes in b, the first `keep` of them kept (copied on s, which is waited for)
+int grow_device_keep(DeviceBuffer<uint8_t>& b, size_t want, size_t keep, hipStream_t s) {
+    if (want <= b.size()) return PA_OK;
+    DeviceBuffer<uint8_t> nb;
+    const int e = nb.alloc(std::max(want, b.size() + b.size() / 2));
+    if (e != PA_OK) return e;
+    if (keep) {
+        PA_HIP_TRY(hipMemcpyAsync(nb.get(), b.get(), keep, hipMemcpyDeviceToDevice, s));
+        PA_HIP_TRY(hipStreamSynchronize(s));
+    }
+    b = std::move(nb);
+    return PA_OK;
+}
 
 // The pair scan and gather shared by pa_count_cells and pa_count_pairs: the two files a window of records at a time, record counts and
 // record.id() (after a trailing "/1" or "/2" is cut) compared on the way, whole windows' worth of pairs gathered into a batch — all of
@@ -180,19 +218,164 @@ struct PairReader {
     std::vector<uint32_t> part_max, part_max1;
     uint64_t pairs = 0;            // pairs of the batches launched so far (run_batches adds a batch when it launches it)
     bool ended = false;
+    // the device form: the two files as window feeds, one stream for match + gather, the batch's control block
+    bool device = false;
+    FastqText text[2];
+    std::unique_ptr<WindowFeed> feed[2];
+    FeedWindow win[2];
+    uint64_t at[2] = {0, 0};       // next record of each file's window
+    hipStream_t gs = nullptr;
+    std::vector<hipStream_t> consumers;   // the streams the batches are consumed on (set by the driver before the first batch)
+    DeviceBuffer<uint64_t> d_ctl;
+    PinnedBuffer<uint64_t> h_ctl;
+    DeviceBuffer<uint8_t> d_scratch;
     PairReader(const char* r1, const char* r2, Pool& pl, uint32_t prefix_, double* st_)
         : r1_path(r1), r2_path(r2), pool(pl), prefix(prefix_), st(st_), ntask(pl.size() * 4), part((size_t)ntask + 1), part1((size_t)ntask + 1), part_max((size_t)ntask),
           part_max1((size_t)ntask) {
         if (const char* v = getenv("PA_INGEST_BATCH")) { const long long x = atoll(v); if (x >= 1) batch_pairs = (uint64_t)x; }
     }
+    ~PairReader() { release(); }
+    // Both files are opened; the device form is taken when both are BGZF — or, with PA_PAIRS_DEVICE_PLAIN=1, plain mapped text or BGZF in any mix — and
+    // PA_PAIRS_HOST_SCAN is not set
     int open() {
-        int rc;
-        if ((rc = f1.open(r1_path)) != PA_OK || (rc = f2.open(r2_path)) != PA_OK) return rc;
+        const char* v = getenv("PA_PAIRS_HOST_SCAN");
+        const bool host_only = v && *v && atoi(v) != 0;
+        v = getenv("PA_INGEST_BGZF");
+        const bool bgzf = !host_only && !(v && *v && atoi(v) == 0);
+        v = getenv("PA_PAIRS_DEVICE_PLAIN");
+        const bool plain_too = v && *v && atoi(v) != 0;
+        const char* const paths[2] = {r1_path, r2_path};
+        int rc = PA_OK;
+        bool takes = !host_only;
+        for (int i = 0; i < 2; ++i) {
+            if (bgzf) open_bgzf(paths[i], text[i]);
+            if (!text[i].bgzf && (rc = open_fastq(paths[i], text[i])) != PA_OK) return rc;
+            takes = takes && WindowFeed::takes(text[i]) && (text[i].bgzf || plain_too);
+        }
+        uint64_t* const is = last_pairs_input();
+        memset(is, 0, sizeof(uint64_t) * (2 * PA_INGEST_INPUT_STATS + 1));
+        if (!takes) {   // today's host form for the whole call (a BGZF file is then inflated like any other .gz)
+            for (int i = 0; i < 2; ++i)
+                if (text[i].bgzf) { text[i].release(); text[i] = FastqText(); if ((rc = open_fastq(paths[i], text[i])) != PA_OK) return rc; }
+            for (int i = 0; i < 2; ++i) is[i * PA_INGEST_INPUT_STATS] = text[i].inflated.empty() ? 0u : 1u;
+            f1.adopt(r1_path, std::move(text[0]));
+            f2.adopt(r2_path, std::move(text[1]));
+            return PA_OK;
+        }
+        device = true;
+        uint64_t window = 64ull << 20;
+        if ((v = getenv("PA_INGEST_WINDOW"))) { const long long x = atoll(v); if (x >= 1) window = (uint64_t)x; }
+        window = std::min<uint64_t>(std::min<uint64_t>(window, batch_pairs * 256), 1ull << 31);
+        PA_HIP_TRY(hipStreamCreateWithFlags(&gs, hipStreamNonBlocking));
+        if ((rc = d_ctl.alloc(PA_PAIRS_CTL_WORDS)) != PA_OK || (rc = h_ctl.alloc(PA_PAIRS_CTL_WORDS)) != PA_OK) return rc;
+        for (int i = 0; i < 2; ++i) {
+            feed[i].reset(new WindowFeed(paths[i], text[i], pool, st, window, batch_pairs));
+            if ((rc = feed[i]->start()) != PA_OK) return rc;
+        }
         return PA_OK;
     }
-    void release() { f1.text.release(); f2.text.release(); }
+    void release() {
+        if (device) {
+            if (gs) (void)hipStreamSynchronize(gs);
+            uint64_t* const is = last_pairs_input();
+            for (int i = 0; i < 2; ++i) {
+                if (!feed[i]) continue;
+                const FeedStats fs = feed[i]->stats();
+                memcpy(is + i * PA_INGEST_INPUT_STATS, &fs, sizeof fs);
+                feed[i].reset();
+            }
+            is[2 * PA_INGEST_INPUT_STATS] = 1;
+            if (gs) { (void)hipStreamDestroy(gs); gs = nullptr; }
+            device = false;
+        }
+        for (int i = 0; i < 2; ++i) { text[i].release(); text[i] = FastqText(); }
+        f1.text.release(); f2.text.release();
+    }
+    // the batch's consumers have been given their last work: the next gather into the batch's buffers waits for it (device form)
+    int consumed(CellBatch& b) {
+        if (!device) return PA_OK;
+        for (size_t i = 0; i < consumers.size() && i < 2; ++i) {
+            GpuEvent& ev = b.consumed[i];
+            if (!ev.e) PA_HIP_TRY(hipEventCreateWithFlags(&ev.e, hipEventDisableTiming));
+            PA_HIP_TRY(hipEventRecord(ev.e, consumers[i]));
+            ev.pending = true;
+        }
+        return PA_OK;
+    }
+    // the batch's control block, once, behind its gathers: the first bad id, the longest pieces, the bytes
+    int close_device_batch(CellBatch& b) {
+        Mate &m1 = b.mate[0], &m2 = b.mate[1];
+        if (b.n == 0) return PA_OK;
+        const auto t0 = std::chrono::steady_clock::now();
+        PA_HIP_TRY(hipMemcpyAsync(h_ctl.get(), d_ctl.get(), PA_PAIRS_CTL_WORDS * 8, hipMemcpyDeviceToHost, gs));
+        PA_HIP_TRY(hipStreamSynchronize(gs));
+        st[2] += secs_since(t0);
+        const uint64_t* const c = h_ctl.get();
+        if (c[5] != ~0ull) return fail(PA_ERR_INTERNAL, "pair scan: the record of pair %llu lies outside its window", (unsigned long long)(pairs + c[5]));
+        if (c[0] != ~0ull) return fail(PA_ERR_FORMAT, "record %llu: the ids of %s and %s differ", (unsigned long long)(pairs + c[0]), r1_path, r2_path);
+        if (c[3] > m1.d_bytes.size() || c[4] > m2.d_bytes.size()) return fail(PA_ERR_INTERNAL, "pair scan: a batch of %llu + %llu bytes did not fit its buffers", (unsigned long long)c[3], (unsigned long long)c[4]);
+        m1.max_len = (uint32_t)c[1];
+        m2.max_len = (uint32_t)c[2];
+        m1.bytes = c[3];
+        m2.bytes = c[4];
+        return PA_OK;
+    }
+    // the device form of gather(): segments of m = min(records left in R1's window, in R2's window, room in the batch) pairs, matched and gathered on gs
+    int gather_device(CellBatch& b) {
+        Mate &m1 = b.mate[0], &m2 = b.mate[1];
+        b.n = 0; m2.bytes = 0; m1.bytes = 0; m2.max_len = 0; m1.max_len = 0;
+        m1.on_device = m2.on_device = true;
+        int e = PA_OK;
+        const size_t offs = (size_t)batch_pairs + 128;   // (the per-read buffers of the mapping are sized from it: a full batch + 64 fits)
+        if ((e = m1.d_off.reserve(offs, offs)) || (e = m2.d_off.reserve(offs, offs))) return e;
+        for (GpuEvent& ev : b.consumed)
+            if (ev.pending) { PA_HIP_TRY(hipStreamWaitEvent(gs, ev.e, 0)); ev.pending = false; }
+        uint64_t ub1 = 0, ub2 = 0;   // bounds of the bytes gathered so far: pairs x the longest sequence of their windows
+        while (b.n < batch_pairs) {
+            for (int i = 0; i < 2; ++i) {
+                if (at[i] < win[i].n) continue;
+                if (win[i].slot >= 0 && (e = feed[i]->release(win[i].slot, gs)) != PA_OK) return e;
+                if ((e = feed[i]->next(win[i])) != PA_OK) {   // (an id that differs in the pairs gathered so far is the earlier error, as on the host path)
+                    const std::string why = last_error_ref();
+                    const int earlier = close_device_batch(b);
+                    if (earlier != PA_OK) return earlier;
+                    last_error_ref() = why;
+                    return e;
+                }
+                at[i] = 0;
+            }
+            const uint64_t left1 = win[0].n - at[0], left2 = win[1].n - at[1];
+            if (left1 == 0 || left2 == 0) {
+                if ((e = close_device_batch(b)) != PA_OK) return e;   // (an id that differs in front of the missing mate is the earlier error)
+                if (left1 != left2)
+                    return fail(PA_ERR_FORMAT, "%s has more records than %s: record %llu has no mate", left1 ? r1_path : r2_path, left1 ? r2_path : r1_path,
+                                (unsigned long long)(pairs + b.n));
+                ended = true;
+                return PA_OK;
+            }
+            const auto t0 = std::chrono::steady_clock::now();
+            const uint64_t m = segment_pairs(left1, left2, batch_pairs, b.n);
+            const uint64_t nb1 = ub1 + m * std::min<uint64_t>(win[0].max_seq, prefix), nb2 = ub2 + m * (uint64_t)win[1].max_seq;
+            if ((e = grow_device_keep(m1.d_bytes, nb1 + 64, ub1, gs)) != PA_OK || (e = grow_device_keep(m2.d_bytes, nb2 + 64, ub2, gs)) != PA_OK) return e;
+            const size_t sb = pa_pairs_gather_scratch_bytes(m);
+            if ((e = d_scratch.reserve(sb, sb + sb / 4)) != PA_OK) return e;
+            PA_HIP_TRY(hipStreamWaitEvent(gs, win[0].ready, 0));
+            PA_HIP_TRY(hipStreamWaitEvent(gs, win[1].ready, 0));
+            if ((e = pairs_gather_launch(win[0].d_raw, win[0].raw_bytes, reinterpret_cast<const uint32_t*>(win[0].d_rec + at[0]), win[1].d_raw, win[1].raw_bytes,
+                                         reinterpret_cast<const uint32_t*>(win[1].d_rec + at[1]), m, prefix, b.n, m1.d_bytes.get(), m1.d_bytes.size(), m1.d_off.get(),
+                                         m2.d_bytes.get(), m2.d_bytes.size(), m2.d_off.get(), d_ctl.get(), d_scratch.get(), d_scratch.size(), gs)) != PA_OK)
+                return e;
+            ub1 = nb1; ub2 = nb2;
+            b.n += m;
+            at[0] += m;
+            at[1] += m;
+            st[3] += secs_since(t0);
+        }
+        return close_device_batch(b);
+    }
     // gather the next batch into b: R1 (its prefix) into mate[0], R2 into mate[1]
     int gather(CellBatch& b) {
+        if (device) return gather_device(b);
         Mate &m1 = b.mate[0], &m2 = b.mate[1];
         b.n = 0; m2.bytes = 0; m1.bytes = 0; m2.max_len = 0; m1.max_len = 0;
         int e = PA_OK;
@@ -286,7 +469,7 @@ int run_batches(PairReader& rd, Batch (&batches)[2], Launch&& launch, Finish&& f
         rc = rd.ended ? PA_OK : rd.gather(b);   // (while the batch before is on the GPU)
         if (rc != PA_OK) break;
         if (in_flight) {
-            if ((rc = finish(batches[cur ^ 1])) != PA_OK) break;
+            if ((rc = finish(batches[cur ^ 1])) != PA_OK || (rc = rd.consumed(batches[cur ^ 1])) != PA_OK) break;
             in_flight = false;
         }
         if (b.n == 0) break;
@@ -360,6 +543,7 @@ int count_cells_impl(pa_index* idx, const pa_host_index* h, const char* r1_path,
     IndexStream stream;
     if ((rc = stream.create(idx)) != PA_OK) return rc;
     hipStream_t s = stream.get();
+    rd.consumers = {s};
     CellBatch batches[2];
     rc = run_batches(rd, batches, [&](CellBatch& b) { return cell_batch_map(idx, b, s); }, [&](CellBatch& b) { return cell_batch_count(idx, counter, b, s, st); });
     if (rc != PA_OK) return rc;
@@ -472,6 +656,7 @@ int write_bus_impl(pa_index* idx, const pa_host_index* h, const char* r1_path, c
     IndexStream stream;
     if ((rc = stream.create(idx)) != PA_OK) return rc;
     hipStream_t s = stream.get();
+    rd.consumers = {s};
     CellBatch batches[2];
     rc = run_batches(rd, batches, [&](CellBatch& b) { return cell_batch_map(idx, b, s); }, [&](CellBatch& b) { return bus_batch_add(idx, bus, b, s, st); });
     if (rc != PA_OK) return rc;
@@ -505,7 +690,7 @@ int pair_batch_map(pa_index* idx, PairBatch& b, int orient, uint32_t allowed, co
     int e = PA_OK;
     for (int m = 0; m < 2; ++m)
         if ((e = b.mate[m].encode(idx, b.n, 64, s[m])) != PA_OK) return e;
-    if ((e = b.d_presults.reserve(b.n + 64, b.mate[0].h_off.size() + 64)) != PA_OK) return e;
+    if ((e = b.d_presults.reserve(b.n + 64, std::max(b.mate[0].h_off.size(), b.mate[0].d_off.size()) + 64)) != PA_OK) return e;
     for (int m = 0; m < 2; ++m) {
         Mate& x = b.mate[m];
         const uint64_t* tiles = x.d_tiles.get();
@@ -569,6 +754,7 @@ int count_pairs_impl(pa_index* idx, const char* r1_path, const char* r2_path, in
     if ((rc = streams[0].create(idx)) != PA_OK || (rc = streams[1].create(idx)) != PA_OK) return rc;
     const hipStream_t s[2] = {streams[0].get(), streams[1].get()};
     PA_HIP_TRY(hipMemsetAsync(d_counts.get(), 0, counts_len * 8, s[0]));
+    rd.consumers = {s[0], s[1]};
     PairBatch batches[2];
     uint64_t stats[PA_PAIR_STATS] = {0};
     rc = run_batches(rd, batches, [&](PairBatch& b) { return pair_batch_map(idx, b, orient, allowed, s); },
@@ -599,3 +785,11 @@ extern "C" int pa_write_bus(pa_index* idx, const pa_host_index* h, const char* r
                             int num_threads, uint64_t stats[PA_BUS_STATS]) {
     return no_throw("pa_write_bus", [&] { return write_bus_impl(idx, h, r1_path, r2_path, bc_len, umi_len, out_dir, num_threads, stats); });
 }
+
+extern "C" int pa_pairs_input_stats(uint64_t out[2 * PA_INGEST_INPUT_STATS]) {
+    if (!out) return fail(PA_ERR_INVALID_ARG, "null argument");
+    memcpy(out, last_pairs_input(), sizeof(uint64_t) * 2 * PA_INGEST_INPUT_STATS);
+    return PA_OK;
+}
+
+extern "C" int pa_pairs_input_path(void) { return (int)last_pairs_input()[2 * PA_INGEST_INPUT_STATS]; }

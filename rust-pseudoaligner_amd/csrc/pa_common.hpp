@@ -33,6 +33,10 @@ int pairs_arena_bound(pa_index* idx, const pa_read_result* d_res1, const pa_read
 // inflate.hip: the launch of pa_bgzf_inflate_device by itself, on the current device (no device query, no hipSetDevice): what pa_process_reads enqueues per window
 int bgzf_inflate_launch(const uint8_t* d_comp, uint64_t comp_bytes, const pa_bgzf_member* d_members, uint64_t n_members, uint8_t* d_text, uint64_t text_cap,
                         uint32_t* d_status, void* stream);
+// pair_scan.hip: one segment of pa_pairs_gather_device by itself, on the current device (no device query, no hipSetDevice, no check of the pointers)
+int pairs_gather_launch(const uint8_t* d_text1, uint64_t text1_bytes, const uint32_t* d_rec1, const uint8_t* d_text2, uint64_t text2_bytes, const uint32_t* d_rec2, uint64_t m,
+                        uint32_t prefix, uint64_t base, uint8_t* d_bytes1, uint64_t cap1, uint64_t* d_off1, uint8_t* d_bytes2, uint64_t cap2, uint64_t* d_off2, uint64_t* d_ctl,
+                        void* d_scratch, size_t scratch_bytes, void* stream);
 // Opaque objects the FASTQ drivers park on the index between calls (their pinned + device batch buffers: allocating them
 // costs more than packing a batch; up to four, `Parked` of device_index.hpp). take() hands one to the caller alone, so concurrent
 // calls never share it; put() stores it back (or frees it with `free_fn` when four are parked). pa_index_destroy frees them.

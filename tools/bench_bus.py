@@ -4,7 +4,9 @@
 each as the median of `--rounds` rounds with its min and max; within a round the two take turns chunk by chunk (who goes first alternates),
 so that both see the same clocks. Then
   file_pairs_per_s, file_stages_s         pa_write_bus on the plain R1 / R2 FASTQ tools/bench_cells.py makes (files in the page cache)
-Usage: python tools/bench_bus.py [--pairs N] [--rounds R] [--threads T] [--dir DIR] [--no-files]"""
+  --input plain|bgzf, --host-scan, --calls N   the file-level leg on BGZF files / on the host path / timed N times (tools/pairs_input.py);
+  --files-only skips the device-resident leg
+Usage: python tools/bench_bus.py [--pairs N] [--rounds R] [--threads T] [--dir DIR] [--no-files] [--input plain|bgzf] [--host-scan] [--calls N] [--files-only]"""
 import argparse
 import json
 import statistics
@@ -19,6 +21,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tools"))
 
+import pairs_input
 from bench_cells import BASES, fastq_chunk, make_pairs   # the same pairs and the same files
 
 
@@ -35,7 +38,10 @@ def main():
     ap.add_argument("--whitelist", type=int, default=100_000)
     ap.add_argument("--dir", default=None)
     ap.add_argument("--no-files", action="store_true")
+    ap.add_argument("--files-only", action="store_true")
+    pairs_input.add_args(ap)
     a = ap.parse_args()
+    pairs_input.apply(a)
     import torch
     import importlib
     pa = importlib.import_module("rust-pseudoaligner_amd")
@@ -68,7 +74,7 @@ def main():
     dev = torch.device("cuda")
     chunk = 1_000_000
     chunks = []
-    for first in range(0, a.pairs, chunk):
+    for first in range(0, 0 if a.files_only else a.pairs, chunk):
         m = min(chunk, a.pairs - first)
         r1, r2 = make_pairs(rng, txome_bytes, starts, lens, cells, m, read_len, umi_len)
         d_r2 = torch.from_numpy(r2.reshape(-1)).to(dev)
@@ -99,7 +105,7 @@ def main():
     times = {"bus_add": [], "bus_finish": [], "cells_add": [], "cells_finish": []}
     bus_stats = cells_stats = None
     n_records = n_ecs = entries = 0
-    for rnd in range(a.rounds + 1):   # (round 0 warms the allocators and the code objects up and is left out)
+    for rnd in range(0 if a.files_only else a.rounds + 1):   # (round 0 warms the allocators and the code objects up and is left out)
         bus = pa.BusWriter(al, host, bc_len, umi_len)
         counter = pa.CellCounter(al, host, tx_gene, len(names), wl_text, bc_len, umi_len)
         t_bus = t_cells = 0.0
@@ -128,17 +134,20 @@ def main():
         times["cells_finish"].append(f_cells)
     del chunks
     torch.cuda.empty_cache()
-    result = {"pairs": a.pairs, "rounds": a.rounds, "threads": a.threads, "cells": a.cells, "read_len": read_len,
+    result = {"pairs": a.pairs, "rounds": a.rounds, "threads": a.threads, "cells": a.cells, "read_len": read_len}
+    if not a.files_only:
+        result.update({
               "bus_add_ms_per_10M": spread(times["bus_add"]), "bus_finish_ms": spread(times["bus_finish"]),
               "cells_add_ms_per_10M": spread(times["cells_add"]), "cells_finish_ms": spread(times["cells_finish"]),
               "add_ratio_bus_over_cells": round(statistics.median(times["bus_add"]) / statistics.median(times["cells_add"]), 3),
               "finish_ratio_bus_over_cells": round(statistics.median(times["bus_finish"]) / statistics.median(times["cells_finish"]), 3),
-              "bus_records": n_records, "bus_ecs": n_ecs, "matrix_entries": entries, "bus_stats": bus_stats, "cells_stats": cells_stats}
+              "bus_records": n_records, "bus_ecs": n_ecs, "matrix_entries": entries, "bus_stats": bus_stats, "cells_stats": cells_stats})
 
     # ---- file-level leg: the same number of pairs as plain FASTQ ----
     if not a.no_files:
         t1 = time.perf_counter()
-        with open(d / "r1.fq", "wb") as f1, open(d / "r2.fq", "wb") as f2:
+        p1, p2 = d / ("r1.fq" + pairs_input.suffix(a)), d / ("r2.fq" + pairs_input.suffix(a))
+        with pairs_input.Writer(p1, a.input) as f1, pairs_input.Writer(p2, a.input) as f2:
             for first in range(0, a.pairs, chunk):
                 m = min(chunk, a.pairs - first)
                 r1, r2 = make_pairs(rng, txome_bytes, starts, lens, cells, m, read_len, umi_len)
@@ -147,16 +156,15 @@ def main():
         print("[bench_bus] files written in %.1f s" % (time.perf_counter() - t1), file=sys.stderr)
         out = d / "out"
         out.mkdir()
-        al.write_bus(host, d / "r1.fq", d / "r2.fq", out, bc_len, umi_len, num_threads=a.threads)   # warm-up: page cache, buffers
-        t1 = time.perf_counter()
-        file_stats = al.write_bus(host, d / "r1.fq", d / "r2.fq", out, bc_len, umi_len, num_threads=a.threads)
-        file_s = time.perf_counter() - t1
+        al.write_bus(host, p1, p2, out, bc_len, umi_len, num_threads=a.threads)   # warm-up: page cache, buffers
+        secs, file_stats = pairs_input.timed_calls(lambda: al.write_bus(host, p1, p2, out, bc_len, umi_len, num_threads=a.threads), a.calls)
+        file_s = secs[-1]
         st = (pa._ffi.C.c_double * 8)()
         pa.lib().pa_process_reads_stage_seconds(st)
         stages = dict(zip(("scan", "gather", "map_wait", "launch", "bus", "write", "whole", "pairs"), [round(x, 4) for x in st]))
         result.update({"file_seconds": round(file_s, 3), "file_pairs_per_s": round(a.pairs / file_s), "file_stages_s": stages,
                        "bus_share_of_file_call": round(stages["bus"] / stages["whole"], 4) if stages["whole"] else None,
-                       "output_bus_bytes": (out / "output.bus").stat().st_size, "file_stats": file_stats})
+                       "output_bus_bytes": (out / "output.bus").stat().st_size, "file_stats": file_stats, **pairs_input.report(pa, a, a.pairs, secs)})
     print(json.dumps(result))
     tmp.cleanup()
 

@@ -3,7 +3,9 @@
   finish_ms               pa_cell_counter_finish of that run (UMI correction, gene conflicts, count)
   file_pairs_per_s        pa_count_cells on generated plain R1 / R2 FASTQ of the same size (files in the page cache)
   file_stages_s           that call's stage split (pa_process_reads_stage_seconds)
-Usage: python tools/bench_cells.py [--pairs N] [--threads T] [--dir DIR]"""
+  --input plain|bgzf, --host-scan, --calls N   the file-level leg on BGZF files / on the host path / timed N times (tools/pairs_input.py);
+  --files-only skips the device-resident leg
+Usage: python tools/bench_cells.py [--pairs N] [--threads T] [--dir DIR] [--input plain|bgzf] [--host-scan] [--calls N] [--files-only]"""
 import argparse
 import json
 import sys
@@ -15,6 +17,9 @@ import numpy as np
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tools"))
+
+import pairs_input
 
 BASES = np.frombuffer(b"ACGT", np.uint8)
 
@@ -58,7 +63,10 @@ def main():
     ap.add_argument("--cells", type=int, default=10_000)
     ap.add_argument("--whitelist", type=int, default=100_000)
     ap.add_argument("--dir", default=None)
+    ap.add_argument("--files-only", action="store_true")
+    pairs_input.add_args(ap)
     a = ap.parse_args()
+    pairs_input.apply(a)
     import torch
     import importlib
     pa = importlib.import_module("rust-pseudoaligner_amd")
@@ -89,10 +97,11 @@ def main():
 
     # ---- device-resident leg: chunks of 1 M pairs mapped on the GPU, then counted ----
     dev = torch.device("cuda")
-    counter = pa.CellCounter(al, host, tx_gene, len(names), [bytes(r).decode() for r in whitelist], bc_len, umi_len)
-    add_s = 0.0
+    add_s = finish_s = 0.0
+    entries, dev_stats = 0, None
     chunk = 1_000_000
-    for first in range(0, a.pairs, chunk):
+    counter = None if a.files_only else pa.CellCounter(al, host, tx_gene, len(names), [bytes(r).decode() for r in whitelist], bc_len, umi_len)
+    for first in range(0, 0 if a.files_only else a.pairs, chunk):
         m = min(chunk, a.pairs - first)
         r1, r2 = make_pairs(rng, txome_bytes, starts, lens, cells, m, read_len, umi_len)
         d_r2 = torch.from_numpy(r2.reshape(-1)).to(dev)
@@ -114,16 +123,18 @@ def main():
         counter.add_device(d_res.data_ptr(), d_arena.data_ptr(), d_r1.data_ptr(), d_r1off.data_ptr(), m)
         add_s += time.perf_counter() - t1
         del d_r2, d_r1, d_tiles, d_res, d_arena
-    t1 = time.perf_counter()
-    entries = counter.finish()
-    finish_s = time.perf_counter() - t1
-    dev_stats = counter.stats()
-    del counter
+    if counter is not None:
+        t1 = time.perf_counter()
+        entries = counter.finish()
+        finish_s = time.perf_counter() - t1
+        dev_stats = counter.stats()
+        del counter
     torch.cuda.empty_cache()
 
     # ---- file-level leg: the same number of pairs as plain FASTQ ----
     t1 = time.perf_counter()
-    with open(d / "r1.fq", "wb") as f1, open(d / "r2.fq", "wb") as f2:
+    p1, p2 = d / ("r1.fq" + pairs_input.suffix(a)), d / ("r2.fq" + pairs_input.suffix(a))
+    with pairs_input.Writer(p1, a.input) as f1, pairs_input.Writer(p2, a.input) as f2:
         for first in range(0, a.pairs, chunk):
             m = min(chunk, a.pairs - first)
             r1, r2 = make_pairs(rng, txome_bytes, starts, lens, cells, m, read_len, umi_len)
@@ -133,10 +144,9 @@ def main():
     print("[bench_cells] files written in %.1f s" % (time.perf_counter() - t1), file=sys.stderr)
     out = d / "out"
     out.mkdir()
-    al.count_cells(host, d / "r1.fq", d / "r2.fq", d / "wl.txt", out, bc_len, umi_len, num_threads=a.threads)   # warm-up: page cache, buffers
-    t1 = time.perf_counter()
-    file_stats = al.count_cells(host, d / "r1.fq", d / "r2.fq", d / "wl.txt", out, bc_len, umi_len, num_threads=a.threads)
-    file_s = time.perf_counter() - t1
+    al.count_cells(host, p1, p2, d / "wl.txt", out, bc_len, umi_len, num_threads=a.threads)   # warm-up: page cache, buffers
+    secs, file_stats = pairs_input.timed_calls(lambda: al.count_cells(host, p1, p2, d / "wl.txt", out, bc_len, umi_len, num_threads=a.threads), a.calls)
+    file_s = secs[-1]
     st = (pa._ffi.C.c_double * 8)()
     pa.lib().pa_process_reads_stage_seconds(st)
     stages = dict(zip(("scan", "gather", "map_wait", "launch", "count", "write", "whole", "pairs"), [round(x, 4) for x in st]))
@@ -145,7 +155,7 @@ def main():
                       "matrix_entries": entries, "device_stats": dev_stats,
                       "file_seconds": round(file_s, 3), "file_pairs_per_s": round(a.pairs / file_s), "file_stages_s": stages,
                       "count_share_of_file_call": round(stages["count"] / stages["whole"], 4) if stages["whole"] else None,
-                      "file_stats": file_stats}))
+                      "file_stats": file_stats, **pairs_input.report(pa, a, a.pairs, secs)}))
     tmp.cleanup()
 
 

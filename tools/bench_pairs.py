@@ -23,6 +23,8 @@ import torch  # noqa: F401  (before the product library touches HIP: one runtime
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tools"))
+import pairs_input  # noqa: E402
 pa = importlib.import_module("rust-pseudoaligner_amd")
 L = pa.lib()
 FRAG, MATE = 300, 100
@@ -87,7 +89,9 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--file-pairs", type=int, default=2_000_000, help="pairs written to FASTQ for the count_pairs leg")
     ap.add_argument("--out", default=str(ROOT / "profiles" / "r10_pairs_bench.json"))
+    pairs_input.add_args(ap)   # the count_pairs leg on BGZF files / on the host path / timed several times
     a = ap.parse_args()
+    pairs_input.apply(a)
     n = a.pairs
     tx = pa.Txome.synthesize(20000, 200000, 7) if a.index == "config3" else pa.Txome.synthesize(5000, 17000, 7)
     host = pa.HostIndex.from_txome(tx, 24, a.threads)
@@ -149,17 +153,16 @@ def main():
     with tempfile.TemporaryDirectory(dir=os.environ.get("TMPDIR")) as d:
         paths = []
         for k, mate in enumerate((m1, m2)):
-            p = os.path.join(d, "R%d.fq" % (k + 1))
-            with open(p, "wb") as f:
+            p = os.path.join(d, "R%d.fq%s" % (k + 1, pairs_input.suffix(a)))
+            with pairs_input.Writer(p, a.input) as f:
                 for lo in range(0, fn, 1 << 18):
                     rows = lut[mate[lo:min(fn, lo + (1 << 18))]]
                     f.write(b"".join(b"@p%d/%d\n%s\n+\n%s\n" % (lo + i, k + 1, r.tobytes(), b"I" * MATE) for i, r in enumerate(rows)))
             paths.append(p)
         al.count_pairs(paths[0], paths[1], "fr", num_threads=a.threads)          # warm: page cache, buffers
-        t0 = time.perf_counter()
-        _, st = al.count_pairs(paths[0], paths[1], "fr", num_threads=a.threads)
-        dt = time.perf_counter() - t0
-        out["count_pairs"] = {"pairs": fn, "pairs_per_s": fn / dt, "stage_seconds": pa.process_reads_stage_seconds(), "stats": st}
+        secs, (_, st) = pairs_input.timed_calls(lambda: al.count_pairs(paths[0], paths[1], "fr", num_threads=a.threads), a.calls)
+        dt = secs[-1]
+        out["count_pairs"] = {"pairs": fn, "pairs_per_s": fn / dt, "stage_seconds": pa.process_reads_stage_seconds(), "stats": st, **pairs_input.report(pa, a, fn, secs)}
     Path(a.out).parent.mkdir(parents=True, exist_ok=True)
     Path(a.out).write_text(json.dumps(out, indent=1) + "\n")
     print(json.dumps(out))
