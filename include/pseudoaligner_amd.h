@@ -710,6 +710,61 @@ int pa_map_pairs(pa_index* idx, const uint8_t* ascii1, const uint64_t* offsets1,
 int pa_count_pairs(pa_index* idx, const char* r1_path, const char* r2_path, int orient, uint32_t allowed_mismatches, int num_threads,
                    uint64_t* h_counts, uint64_t* n_pairs, uint64_t stats[PA_PAIR_STATS]);
 
+/* ---------------- unstranded libraries: both strands mapped, the two answers merged ----------------
+ * In an unstranded library every fragment is read from either strand at random, while the index is stranded. An ITEM (a single read, or
+ * a pair) therefore gets two candidate results in the format of pa_read_result plus arena ids, and a stage behind them merges the two
+ * per item into ordinary records plus arena ids, which everything downstream takes as it takes reads.
+ *   candidates    S (sense):      a read as given;                 a pair by the pair rule on (mate 1, revcomp mate 2) = PA_PAIR_FR
+ *                 R (antisense):  the read's reverse complement;   a pair by the pair rule on (revcomp mate 1, mate 2) = PA_PAIR_RF
+ *   item result   neither mapped      unmapped: mismatches bit 31 clear, coverage 0, class_len 0, class_off 0
+ *                 exactly one mapped  that candidate's ids, coverage and mismatches
+ *                 both mapped         the keys (class non-empty, coverage, -mismatches) are compared lexicographically; the larger key
+ *                                     wins and the result is that candidate. Equal keys are a TIE: ids = the sorted union of the two
+ *                                     lists without duplicates, coverage and mismatches the common values, mapped even when the union
+ *                                     is empty
+ *                 (two equally good explanations of a fragment that is as likely from either strand are both compatible: the union;
+ *                 a weaker hit on the other strand must not dilute a strong one; an empty intersection of mates is worse evidence than
+ *                 any non-empty one)
+ *   representation   class_off carries PA_CLASS_REF only if the id list equals that index class; otherwise the ids lie ascending in the
+ *                 OUTPUT arena at class_off. Which of the two forms a result that equals an index class takes is not specified. A
+ *                 result never points into a candidate's arena. Records with class_len == 0 have class_off == 0.
+ * pa_strands_merge_device / pa_strands_finish: the contract of pa_pairs_combine_device / pa_pairs_finish with S in the place of mate 1
+ * and R in the place of mate 2 — asynchronous on stream; d_scratch of pa_strands_scratch_bytes(n) bytes (0: n is beyond one launch, the
+ * pair stage's limit), 256-byte aligned, holding the launch's control block until the finish; d_counts may be NULL, otherwise every item
+ * is counted once by the rule of the class-count table and, with an overflow table attached to idx, every result that is no index class
+ * and not empty is filed there; n = 0 is valid; PA_ERR_ARENA_FULL comes with an exact *arena_needed (it does not depend on d_counts or
+ * on the order the items were handled in), no word beyond arena_cap was written and every lost record is mapped with class_len > 0 and
+ * class_off == PA_MAX_ARENA_ENTRIES; what pa_pairs_finish says about re-running a counted launch holds here too.
+ * stats[PA_STRAND_STATS]: [0] items, [1] both candidates mapped, [2] S only, [3] R only, [4] neither, [5] ties, [6] results by
+ * reference, [7] results in the arena; [0] = [1] + [2] + [3] + [4] and [6] + [7] = [0] - [4] - (mapped results whose class is empty).
+ * A STRANDED library shows in them as [2] >> [3] (or the reverse, for the opposite protocol): the cheap check of the library type. */
+#define PA_STRAND_FWD 0
+#define PA_STRAND_REV 1
+#define PA_STRAND_BOTH 2
+#define PA_STRAND_STATS 8
+size_t pa_strands_scratch_bytes(uint64_t n);
+int pa_strands_merge_device(pa_index* idx, const pa_read_result* d_resS, const uint32_t* d_arenaS, const pa_read_result* d_resR,
+                            const uint32_t* d_arenaR, uint64_t n, pa_read_result* d_results, uint32_t* d_arena, uint64_t arena_cap,
+                            uint64_t* d_counts, void* d_scratch, size_t scratch_bytes, void* stream);
+int pa_strands_finish(pa_index* idx, void* d_scratch, void* stream, uint64_t stats[PA_STRAND_STATS], uint64_t* arena_used, uint64_t* arena_needed);
+/* pa_map_batch with a strand: PA_STRAND_FWD maps the reads as given (what pa_map_batch returns), PA_STRAND_REV their reverse complements,
+ * PA_STRAND_BOTH both and merges the two by the rule above; anything else is PA_ERR_INVALID_ARG. pa_map_pairs_unstranded: pa_map_pairs
+ * for an unstranded library — four mappings, the two candidates by two uncounted combines, the merge. Arguments, checks (all before any
+ * device call) and output ownership as pa_map_pairs (the class ids are library-owned until this thread's next call of pa_map_pairs or
+ * of one of these two). Convenience paths, not ones to measure: each call makes and frees its own stream, launch context and buffers
+ * and runs its mappings one after the other with host synchronisations between them. */
+int pa_map_batch_strand(pa_index* idx, const uint8_t* ascii, const uint64_t* offsets, uint64_t n_reads, int strand, uint32_t allowed_mismatches,
+                        pa_read_result* results, uint64_t* class_offsets, const uint32_t** class_ids);
+int pa_map_pairs_unstranded(pa_index* idx, const uint8_t* ascii1, const uint64_t* offsets1, const uint8_t* ascii2, const uint64_t* offsets2,
+                            uint64_t n_pairs, uint32_t allowed_mismatches, pa_read_result* results, uint64_t* class_offsets,
+                            const uint32_t** class_ids);
+/* pa_count_pairs for an unstranded library: the same files, paths (host scan / device path, chosen by the same conditions), batches, error
+ * messages and stage-second slots ([2] waiting for the four mappings, [4] the two combines + the merge + count). Per batch both mates and
+ * their reverse complements are mapped (four streams), the two candidates combined uncounted, and ONE counted merge goes into the table
+ * and an attached overflow table. stats[PA_STRAND_STATS] (may be NULL) are the run's. */
+int pa_count_pairs_unstranded(pa_index* idx, const char* r1_path, const char* r2_path, uint32_t allowed_mismatches, int num_threads,
+                              uint64_t* h_counts, uint64_t* n_pairs, uint64_t stats[PA_STRAND_STATS]);
+
 /* ---------------- the pair scan on the device: ids compared, R2 and the R1 prefix gathered ---------------- */
 #define PA_PAIRS_CTL_WORDS 8            /* u64 words of the control block d_ctl */
 #define PA_PAIRS_WHOLE_READ 0xFFFFFFFFu /* prefix: all of R1 */
@@ -737,7 +792,7 @@ int pa_pairs_gather_device(int device, const uint8_t* d_text1, uint64_t text1_by
                            uint64_t text2_bytes, const uint32_t* d_rec2, uint64_t m, uint32_t prefix, uint64_t base, uint8_t* d_bytes1,
                            uint64_t cap1, uint64_t* d_off1, uint8_t* d_bytes2, uint64_t cap2, uint64_t* d_off2, uint64_t* d_ctl, void* d_scratch,
                            size_t scratch_bytes, void* stream);
-/* What this thread's last pa_count_cells / pa_write_bus / pa_count_pairs call read: R1's six entries, then R2's, in pa_process_reads_input_stats' meaning
+/* What this thread's last pa_count_cells / pa_write_bus / pa_count_pairs / pa_count_pairs_unstranded call read: R1's six entries, then R2's, in pa_process_reads_input_stats' meaning
  * (on the host path only text_kind is filled in). pa_pairs_input_path: 1 when that call took the device path, 0 for the host path. */
 int pa_pairs_input_stats(uint64_t out[2 * PA_INGEST_INPUT_STATS]);
 int pa_pairs_input_path(void);

@@ -166,6 +166,14 @@ int main(int argc, char** argv) {
         EXPECT(pa_pairs_finish(NULL, NULL, NULL, pst, &pu, &pn) == PA_ERR_INVALID_ARG);
         EXPECT(pa_map_pairs(NULL, NULL, poff, NULL, poff, 1, PA_PAIR_FR, 2, pr, NULL, NULL) == PA_ERR_INVALID_ARG);
         EXPECT(pa_count_pairs(NULL, fastq, fastq, PA_PAIR_FR, 2, 1, counts, &pn, pst) == PA_ERR_INVALID_ARG);
+        /* unstranded libraries: the same checks */
+        EXPECT(PA_STRAND_FWD == 0 && PA_STRAND_REV == 1 && PA_STRAND_BOTH == 2 && PA_STRAND_STATS == 8);
+        EXPECT(pa_strands_scratch_bytes(0) >= 256 && pa_strands_scratch_bytes(1000) > pa_strands_scratch_bytes(10) && pa_strands_scratch_bytes(1ull << 31) == 0);
+        EXPECT(pa_strands_merge_device(NULL, NULL, NULL, NULL, NULL, 0, NULL, NULL, 0, NULL, NULL, 0, NULL) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_strands_finish(NULL, NULL, NULL, pst, &pu, &pn) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_map_batch_strand(NULL, NULL, poff, 1, PA_STRAND_BOTH, 2, pr, NULL, NULL) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_map_pairs_unstranded(NULL, NULL, poff, NULL, poff, 1, 2, pr, NULL, NULL) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_count_pairs_unstranded(NULL, fastq, fastq, 2, 1, counts, &pn, pst) == PA_ERR_INVALID_ARG);
         /* the pair scan on the device: its scratch is sized on the host, null outputs are refused before any device call */
         EXPECT(PA_PAIRS_CTL_WORDS == 8 && PA_PAIRS_WHOLE_READ == 0xFFFFFFFFu);
         {
@@ -440,6 +448,36 @@ int main(int argc, char** argv) {
                    pa_stream_synchronize(NULL) == PA_OK);
             for (uint64_t i = 0; i < nsim; ++i)   /* a read paired with itself: its class, twice its coverage */
                 EXPECT(hp[i].class_len == h1[i].class_len && hp[i].coverage == 2 * h1[i].coverage && (hp[i].mismatches & PA_MAPPED_BIT) == (h1[i].mismatches & PA_MAPPED_BIT));
+            {   /* unstranded: the same records as both candidates — every mapped item is a tie of a list with itself: the read's own result */
+                uint64_t sst[PA_STRAND_STATS], su = 0, sn = 0;
+                EXPECT(pa_strands_scratch_bytes(nsim) <= pscr);
+                EXPECT(pa_strands_merge_device(idx, (const pa_read_result*)d_res, (const uint32_t*)d_arena, (const pa_read_result*)d_res2, (const uint32_t*)d_arena2, nsim,
+                                               (pa_read_result*)d_pres, (uint32_t*)d_parena, arena_cap, NULL, d_pscr, pscr, NULL) == PA_OK);
+                EXPECT(pa_strands_finish(idx, d_pscr, NULL, sst, &su, &sn) == PA_OK && su == sn && su <= arena_cap);
+                EXPECT(sst[0] == nsim && sst[0] == sst[1] + sst[2] + sst[3] + sst[4] && sst[2] == 0 && sst[3] == 0 && sst[5] == sst[1]);
+                EXPECT(pa_memcpy_d2h(hp, d_pres, nsim * sizeof(pa_read_result), NULL) == PA_OK && pa_stream_synchronize(NULL) == PA_OK);
+                for (uint64_t i = 0; i < nsim; ++i)
+                    EXPECT(hp[i].class_len == h1[i].class_len && hp[i].coverage == h1[i].coverage && hp[i].mismatches == h1[i].mismatches);
+            }
+            {   /* ... and through the host-buffer paths: a bad strand is refused, both strands of two reads, an unstranded pair of a read with itself */
+                pa_read_result sr[2];
+                uint64_t sco[3] = {9, 9, 9};
+                const uint32_t* sci = NULL;
+                EXPECT(pa_map_batch_strand(idx, ascii, offsets, 2, 3, 2, sr, sco, &sci) == PA_ERR_INVALID_ARG);
+                EXPECT(pa_map_batch_strand(idx, ascii, offsets, 2, PA_STRAND_FWD, 2, sr, sco, &sci) == PA_OK && sco[0] == 0 && sr[0].class_len == res[0].class_len &&
+                       sr[0].coverage == res[0].coverage);
+                EXPECT(pa_map_batch_strand(idx, ascii, offsets, 2, PA_STRAND_BOTH, 2, sr, sco, &sci) == PA_OK && sco[0] == 0 && sco[2] == sco[1] + sr[1].class_len);
+                EXPECT(pa_map_pairs_unstranded(idx, ascii, offsets, ascii, offsets, 2, 2, sr, sco, &sci) == PA_OK && sco[0] == 0 && sco[2] == sco[1] + sr[1].class_len);
+            }
+            {   /* ... and from files: every pair counted once */
+                uint64_t* pc = (uint64_t*)calloc(counts_len, 8);
+                uint64_t npairs = 0, sst[PA_STRAND_STATS], tot = 0;
+                EXPECT(pa_count_pairs_unstranded(idx, fastq, fastq, 2, 2, pc, &npairs, sst) == PA_OK && npairs == nreads && sst[0] == nreads &&
+                       sst[0] == sst[1] + sst[2] + sst[3] + sst[4]);
+                for (uint64_t i = 0; i < counts_len; ++i) tot += pc[i];
+                EXPECT(tot == nreads);
+                free(pc);
+            }
             {
                 pa_read_result pr[2];
                 uint64_t pco[3] = {9, 9, 9};

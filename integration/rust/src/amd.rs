@@ -1,4 +1,4 @@
-//! Exporter + drop-in `process_reads` for the reference crate. Add `mod amd_ffi; mod amd;` to src/lib.rs (and `mod amd_pairs_ffi;` for `map_pairs`, `mod amd_bgzf_ffi;` for `bgzf_members`, `mod amd_bus_ffi;` for `write_bus`).
+//! Exporter + drop-in `process_reads` for the reference crate. Add `mod amd_ffi; mod amd;` to src/lib.rs (and `mod amd_pairs_ffi;` for `map_pairs`, `mod amd_strands_ffi;` for `map_pairs_unstranded`, `mod amd_bgzf_ffi;` for `bgzf_members`, `mod amd_bus_ffi;` for `write_bus`).
 //! The exporter only reads `pub` fields of `Pseudoaligner<K>` (src/pseudoaligner.rs:27-33); `dbg_index` (the boomphf MPHF,
 //! :30) is not exported: every hit is verified against the node sequence (:99-107), which makes it an exact dictionary that
 //! the library rebuilds. Not compiled in the image of this repository (no rustc): kept in step with
@@ -153,6 +153,62 @@ pub fn count_pairs<P: AsRef<Path>>(index: &AmdIndex, r1_fastq: P, r2_fastq: P, o
     let (mut n, mut stats) = (0u64, [0u64; 8]);
     let o = match orient { PairOrientation::Fr => PA_PAIR_FR, PairOrientation::Rf => PA_PAIR_RF, PairOrientation::Ff => PA_PAIR_FF };
     check(unsafe { pa_count_pairs(index.raw, p1.as_ptr(), p2.as_ptr(), o, allowed_mismatches as u32, threads as i32, counts.as_mut_ptr(), &mut n, stats.as_mut_ptr()) })?;
+    Ok((counts, n, stats))
+}
+
+/// Which strand of a single read is mapped on the (stranded) index; `Both`: an unstranded library, the two answers merged.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum Strand { Fwd, Rev, Both }
+
+fn results_to_options(res: &[PaReadResult], coff: &[u64], ids: *const u32) -> Vec<Option<(Vec<u32>, usize, usize)>> {
+    let n = res.len();
+    let all = if coff[n] == 0 { &[][..] } else { unsafe { std::slice::from_raw_parts(ids, coff[n] as usize) } };   // library-owned until this thread's next call
+    (0..n).map(|i| if res[i].mismatches & PA_MAPPED_BIT == 0 { None } else {
+        Some((all[coff[i] as usize..coff[i + 1] as usize].to_vec(), res[i].coverage as usize, (res[i].mismatches & !PA_MAPPED_BIT) as usize))
+    }).collect()
+}
+
+/// map_read_with_mismatch for a batch of reads on a chosen strand (`pa_map_batch_strand`). `Strand::Both` maps the read and its reverse
+/// complement and merges the two answers by the rule of unstranded libraries (include/pseudoaligner_amd.h): the better one, or on a tie
+/// the union of the two classes.
+pub fn map_reads_strand(index: &AmdIndex, reads: &[&[u8]], strand: Strand, allowed_mismatches: usize) -> Result<Vec<Option<(Vec<u32>, usize, usize)>>, Error> {
+    use crate::amd_strands_ffi::*;
+    let n = reads.len();
+    let (mut text, mut off) = (Vec::new(), vec![0u64]);
+    for r in reads { text.extend_from_slice(r); off.push(text.len() as u64); }
+    let mut res = vec![PaReadResult::default(); n];
+    let mut coff = vec![0u64; n + 1];
+    let mut ids: *const u32 = std::ptr::null();
+    let s = match strand { Strand::Fwd => PA_STRAND_FWD, Strand::Rev => PA_STRAND_REV, Strand::Both => PA_STRAND_BOTH };
+    check(unsafe { pa_map_batch_strand(index.raw, text.as_ptr(), off.as_ptr(), n as u64, s, allowed_mismatches as u32, res.as_mut_ptr(), coff.as_mut_ptr(), &mut ids) })?;
+    Ok(results_to_options(&res, &coff, ids))
+}
+
+/// `map_pairs` for an UNSTRANDED library (`pa_map_pairs_unstranded`): every pair is mapped as `Fr` and as `Rf` and the two answers are merged.
+pub fn map_pairs_unstranded(index: &AmdIndex, mates1: &[&[u8]], mates2: &[&[u8]], allowed_mismatches: usize) -> Result<Vec<Option<(Vec<u32>, usize, usize)>>, Error> {
+    use crate::amd_strands_ffi::*;
+    if mates1.len() != mates2.len() { return Err(anyhow!("{} first mates, {} second mates", mates1.len(), mates2.len())); }
+    let n = mates1.len();
+    let pack = |m: &[&[u8]]| { let mut text = Vec::new(); let mut off = vec![0u64]; for r in m { text.extend_from_slice(r); off.push(text.len() as u64); } (text, off) };
+    let ((t1, o1), (t2, o2)) = (pack(mates1), pack(mates2));
+    let mut res = vec![PaReadResult::default(); n];
+    let mut coff = vec![0u64; n + 1];
+    let mut ids: *const u32 = std::ptr::null();
+    check(unsafe { pa_map_pairs_unstranded(index.raw, t1.as_ptr(), o1.as_ptr(), t2.as_ptr(), o2.as_ptr(), n as u64, allowed_mismatches as u32, res.as_mut_ptr(), coff.as_mut_ptr(), &mut ids) })?;
+    Ok(results_to_options(&res, &coff, ids))
+}
+
+/// `count_pairs` for an UNSTRANDED library (`pa_count_pairs_unstranded`): (table, pairs, stats). stats: [0] pairs, [1] both candidates mapped,
+/// [2] sense only, [3] antisense only, [4] neither, [5] ties, [6] by reference, [7] in the arena; [2] far above [3] (or the reverse) says
+/// that the library is stranded after all.
+pub fn count_pairs_unstranded<P: AsRef<Path>>(index: &AmdIndex, r1_fastq: P, r2_fastq: P, allowed_mismatches: usize, threads: usize)
+                                              -> Result<(Vec<u64>, u64, [u64; 8]), Error> {
+    use crate::amd_strands_ffi::*;
+    let p1 = CString::new(r1_fastq.as_ref().to_string_lossy().as_bytes())?;
+    let p2 = CString::new(r2_fastq.as_ref().to_string_lossy().as_bytes())?;
+    let mut counts = vec![0u64; unsafe { pa_counts_len(index.raw) } as usize];
+    let (mut n, mut stats) = (0u64, [0u64; 8]);
+    check(unsafe { pa_count_pairs_unstranded(index.raw, p1.as_ptr(), p2.as_ptr(), allowed_mismatches as u32, threads as i32, counts.as_mut_ptr(), &mut n, stats.as_mut_ptr()) })?;
     Ok((counts, n, stats))
 }
 

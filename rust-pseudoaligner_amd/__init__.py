@@ -341,13 +341,21 @@ class Pseudoaligner:
         return list(buf[: n.value]), cov.value
 
     # ---- batches ------------------------------------------------------------------------------------
-    def map_batch(self, reads: Sequence, allowed_mismatches: int = PA_DEFAULT_ALLOWED_MISMATCHES):
-        """-> (results[n] RESULT_DTYPE, class_offsets[n+1], class_ids) in input order; `mismatches` has bit 31 = mapped."""
+    def map_batch(self, reads: Sequence, allowed_mismatches: int = PA_DEFAULT_ALLOWED_MISMATCHES, strand: str = "fwd"):
+        """-> (results[n] RESULT_DTYPE, class_offsets[n+1], class_ids) in input order; `mismatches` has bit 31 = mapped.
+        strand: "fwd" the reads as given (pa_map_batch), "rev" their reverse complements, "both" both strands mapped and the two answers
+        merged by the rule of unstranded libraries (pa_map_batch_strand)"""
+        if strand not in _ffi.STRANDS:
+            raise ValueError("strand %r: one of %s" % (strand, sorted(_ffi.STRANDS)))
         data, offsets = reads if isinstance(reads, tuple) else concat_reads(reads)
         n = len(offsets) - 1
         results = np.zeros(n, dtype=RESULT_DTYPE)
         coff = np.zeros(n + 1, dtype=np.uint64)
         ids = vp()
+        if strand != "fwd":
+            check(lib().pa_map_batch_strand(self._h, data.ctypes.data, offsets.ctypes.data, n, _ffi.STRANDS[strand], allowed_mismatches, results.ctypes.data,
+                                            coff.ctypes.data, C.byref(ids)))
+            return results, coff, _np_view(ids.value, int(coff[-1]), np.uint32).copy()
         check(lib().pa_map_batch(self._h, data.ctypes.data, offsets.ctypes.data, n, allowed_mismatches, results.ctypes.data,
                                  coff.ctypes.data, C.byref(ids)))
         class_ids = _np_view(ids.value, int(coff[-1]), np.uint32).copy()
@@ -523,11 +531,36 @@ class Pseudoaligner:
         check(rc)
         return stats, used.value, need.value
 
+    # ---- unstranded libraries (include/pseudoaligner_amd.h, "unstranded libraries") ------------------
+    @staticmethod
+    def strands_scratch_bytes(n: int) -> int:
+        return lib().pa_strands_scratch_bytes(n)
+
+    def strands_merge_device(self, d_res_s: int, d_arena_s: int, d_res_r: int, d_arena_r: int, n: int, d_results: int, d_arena: int, arena_cap: int,
+                             d_scratch: int, scratch_bytes: int, d_counts: int = 0, stream: int = 0) -> None:
+        """the sense and the antisense candidate of every item (records + arenas) -> one record per item + ids in the output arena; asynchronous"""
+        check(lib().pa_strands_merge_device(self._h, d_res_s or None, d_arena_s or None, d_res_r or None, d_arena_r or None, n, d_results or None,
+                                            d_arena or None, arena_cap, d_counts or None, d_scratch or None, scratch_bytes, stream or None))
+
+    def strands_finish(self, d_scratch: int, stream: int = 0) -> Tuple[dict, int, int]:
+        """waits for strands_merge_device -> (stats, arena_used, arena_needed); a full arena raises PaError(PA_ERR_ARENA_FULL) whose
+        .arena_needed is the capacity that suffices and .stats the launch's stats"""
+        st = np.zeros(_ffi.PA_STRAND_STATS, np.uint64)
+        used, need = C.c_uint64(), C.c_uint64()
+        rc = lib().pa_strands_finish(self._h, d_scratch or None, stream or None, st.ctypes.data, C.byref(used), C.byref(need))
+        stats = dict(zip(_ffi.STRAND_STAT_NAMES, (int(x) for x in st)))
+        if rc == PA_ERR_ARENA_FULL:
+            err = PaError(rc, (lib().pa_last_error() or b"").decode("utf-8", "replace"))
+            err.arena_needed, err.stats = need.value, stats
+            raise err
+        check(rc)
+        return stats, used.value, need.value
+
     def map_pairs(self, reads1: Sequence, reads2: Sequence, orient: str = "fr", allowed_mismatches: int = PA_DEFAULT_ALLOWED_MISMATCHES):
         """map_batch for read pairs: mates oriented ("fr": mate 2 reverse-complemented, "rf": mate 1, "ff": neither), mapped, their classes
-        intersected -> (results[n] RESULT_DTYPE, class_offsets[n+1], class_ids) in pair order"""
-        if orient not in _ffi.PAIR_ORIENTATIONS:
-            raise ValueError("orient %r: one of %s" % (orient, sorted(_ffi.PAIR_ORIENTATIONS)))
+        intersected; "un": an unstranded library, "fr" and "rf" both and the two answers merged -> (results[n] RESULT_DTYPE, class_offsets[n+1], class_ids) in pair order"""
+        if orient != "un" and orient not in _ffi.PAIR_ORIENTATIONS:
+            raise ValueError("orient %r: one of %s" % (orient, sorted(_ffi.PAIR_ORIENTATIONS) + ["un"]))
         d1, o1 = reads1 if isinstance(reads1, tuple) else concat_reads(reads1)
         d2, o2 = reads2 if isinstance(reads2, tuple) else concat_reads(reads2)
         if len(o1) != len(o2):
@@ -536,6 +569,10 @@ class Pseudoaligner:
         results = np.zeros(n, dtype=RESULT_DTYPE)
         coff = np.zeros(n + 1, dtype=np.uint64)
         ids = vp()
+        if orient == "un":   # an unstranded library: both orientations mapped, the two answers merged
+            check(lib().pa_map_pairs_unstranded(self._h, d1.ctypes.data, o1.ctypes.data, d2.ctypes.data, o2.ctypes.data, n, allowed_mismatches,
+                                                results.ctypes.data, coff.ctypes.data, C.byref(ids)))
+            return results, coff, _np_view(ids.value, int(coff[-1]), np.uint32).copy()
         check(lib().pa_map_pairs(self._h, d1.ctypes.data, o1.ctypes.data, d2.ctypes.data, o2.ctypes.data, n, _ffi.PAIR_ORIENTATIONS[orient], allowed_mismatches,
                                  results.ctypes.data, coff.ctypes.data, C.byref(ids)))
         return results, coff, _np_view(ids.value, int(coff[-1]), np.uint32).copy()
@@ -543,11 +580,15 @@ class Pseudoaligner:
     def count_pairs(self, r1: str, r2: str, orient: str = "fr", allowed_mismatches: int = PA_DEFAULT_ALLOWED_MISMATCHES, num_threads: int = 0):
         """pa_count_pairs: two FASTQ files (plain or gzip'ed) -> (class-count table uint64[counts_len()], stats dict); an attached overflow
         table receives the novel results, so that Quantifier.set_counts(counts, overflow.fetch()) takes the pair"""
-        if orient not in _ffi.PAIR_ORIENTATIONS:
-            raise ValueError("orient %r: one of %s" % (orient, sorted(_ffi.PAIR_ORIENTATIONS)))
+        if orient != "un" and orient not in _ffi.PAIR_ORIENTATIONS:
+            raise ValueError("orient %r: one of %s" % (orient, sorted(_ffi.PAIR_ORIENTATIONS) + ["un"]))
         counts = np.zeros(self.counts_len(), np.uint64)
         st = np.zeros(_ffi.PA_PAIR_STATS, np.uint64)
         n = C.c_uint64()
+        if orient == "un":   # pa_count_pairs_unstranded: the stats are the merge's (STRAND_STAT_NAMES)
+            check(lib().pa_count_pairs_unstranded(self._h, str(r1).encode(), str(r2).encode(), allowed_mismatches, num_threads, counts.ctypes.data, C.byref(n),
+                                                  st.ctypes.data))
+            return counts, dict(zip(_ffi.STRAND_STAT_NAMES, (int(x) for x in st)))
         check(lib().pa_count_pairs(self._h, str(r1).encode(), str(r2).encode(), _ffi.PAIR_ORIENTATIONS[orient], allowed_mismatches, num_threads,
                                    counts.ctypes.data, C.byref(n), st.ctypes.data))
         return counts, dict(zip(_ffi.PAIR_STAT_NAMES, (int(x) for x in st)))

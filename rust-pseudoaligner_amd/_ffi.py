@@ -76,6 +76,10 @@ PA_PAIR_FR, PA_PAIR_RF, PA_PAIR_FF = 0, 1, 2
 PAIR_ORIENTATIONS = {"fr": PA_PAIR_FR, "rf": PA_PAIR_RF, "ff": PA_PAIR_FF}
 PA_PAIR_STATS = 8
 PAIR_STAT_NAMES = ("pairs", "both_mapped", "mate1_only", "mate2_only", "neither", "both_mapped_empty", "by_reference", "in_arena")
+PA_STRAND_FWD, PA_STRAND_REV, PA_STRAND_BOTH = 0, 1, 2
+STRANDS = {"fwd": PA_STRAND_FWD, "rev": PA_STRAND_REV, "both": PA_STRAND_BOTH}
+PA_STRAND_STATS = 8
+STRAND_STAT_NAMES = ("items", "both_mapped", "sense_only", "antisense_only", "neither", "ties", "by_reference", "in_arena")
 PA_PAIRS_CTL_WORDS = 8
 PAIRS_CTL_NAMES = ("first_bad", "max_len1", "max_len2", "bytes1", "bytes2", "first_outside")
 PA_PAIRS_WHOLE_READ = 0xFFFFFFFF
@@ -195,6 +199,12 @@ SIGNATURES = {
     "pa_pairs_finish": (C.c_int, [vp, vp, vp, vp, u64p, u64p]),
     "pa_map_pairs": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint64, C.c_int, C.c_uint32, vp, vp, C.POINTER(vp)]),
     "pa_count_pairs": (C.c_int, [vp, C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_int, vp, u64p, vp]),
+    "pa_strands_scratch_bytes": (C.c_size_t, [C.c_uint64]),
+    "pa_strands_merge_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, C.c_size_t, vp]),
+    "pa_strands_finish": (C.c_int, [vp, vp, vp, vp, u64p, u64p]),
+    "pa_map_batch_strand": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_int, C.c_uint32, vp, vp, C.POINTER(vp)]),
+    "pa_map_pairs_unstranded": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.POINTER(vp)]),
+    "pa_count_pairs_unstranded": (C.c_int, [vp, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int, vp, u64p, vp]),
     "pa_pairs_input_stats": (C.c_int, [u64p]),
     "pa_pairs_input_path": (C.c_int, []),
     "pa_pairs_gather_scratch_bytes": (C.c_size_t, [C.c_uint64]),

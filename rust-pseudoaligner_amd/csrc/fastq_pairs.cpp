@@ -1,5 +1,6 @@
 // The drivers that read PAIRED FASTQ files: pa_count_cells (R1 = barcode + UMI, R2 mapped -> the cells x genes UMI matrix) and pa_count_pairs
-// (both mates mapped, their classes intersected -> the class-count table), with the barcode whitelist's reader. Both walk the two files with
+// (both mates mapped, their classes intersected -> the class-count table; pa_count_pairs_unstranded: both orientations, merged), with the
+// barcode whitelist's reader. All walk the two files with
 // one PairReader, keep two batches of pairs — each two Mates — and run them through one loop (run_batches): batch b is gathered while batch
 // b - 1 is on the GPU. The streams they launch on are IndexStreams, a mapping that ran out of arena goes through map_finish_regrow
 // (hip_buffer.hpp).
@@ -769,7 +770,134 @@ int count_pairs_impl(pa_index* idx, const char* r1_path, const char* r2_path, in
     return PA_OK;
 }
 
+// ---- pa_count_pairs_unstranded: the same two files -> the class-count table of the merged candidates ----
+// Streams: s[m] maps mate m as given, s[2 + m] its reverse complement: four launch contexts on idx, so that all four mappings of a batch are in
+// flight while the next batch is gathered. The tiles and lengths s[2 + m] reads are made on s[m]: it waits for `encoded[m]`.
+struct StrandBatch : CellBatch {
+    DeviceBuffer<uint64_t> d_rc[2];                   // per mate: the reverse-complemented tiles and what their mapping leaves
+    DeviceBuffer<uint32_t> d_rc_arena[2];
+    DeviceBuffer<pa_read_result> d_rc_results[2];
+    GpuEvent encoded[2];
+    DeviceBuffer<uint32_t> d_carena[2], d_marena;     // the candidates' (S, R) and the merge's outputs
+    DeviceBuffer<pa_read_result> d_cresults[2], d_mresults;
+    DeviceBuffer<uint8_t> d_cscratch[2], d_mscratch;
+};
+
+int strand_map_rc(pa_index* idx, StrandBatch& b, int m, uint32_t allowed, hipStream_t s) {
+    Mate& x = b.mate[m];
+    return pa_map_batch_device(idx, b.d_rc[m].get(), x.d_lens.get(), b.n, x.wpr(), allowed, b.d_rc_results[m].get(), b.d_rc_arena[m].get(), b.d_rc_arena[m].size(), nullptr, s);
+}
+
+// the batch's GPU leg up to the four mappings, all asynchronous
+int strand_batch_map(pa_index* idx, StrandBatch& b, uint32_t allowed, const hipStream_t s[4]) {
+    int e = PA_OK;
+    const size_t reads = std::max(b.mate[0].h_off.size(), b.mate[0].d_off.size()) + 64;
+    const uint64_t hint = pa_map_arena_hint(idx, b.n);
+    for (int m = 0; m < 2; ++m) {
+        Mate& x = b.mate[m];
+        if ((e = x.encode(idx, b.n, 64, s[m])) != PA_OK) return e;
+        const size_t tw = pa_tiles_words(b.n, x.wpr()) + 1;
+        if ((e = b.d_rc[m].reserve(tw, tw)) || (e = b.d_rc_results[m].reserve(b.n + 64, reads)) || (e = b.d_rc_arena[m].reserve(hint, hint)) ||
+            (e = b.d_cresults[m].reserve(b.n + 64, reads)))
+            return e;
+        GpuEvent& ev = b.encoded[m];
+        if (!ev.e) PA_HIP_TRY(hipEventCreateWithFlags(&ev.e, hipEventDisableTiming));
+        PA_HIP_TRY(hipEventRecord(ev.e, s[m]));
+        PA_HIP_TRY(hipStreamWaitEvent(s[2 + m], ev.e, 0));
+        if ((e = pa_revcomp_tiles_device(idx, x.d_tiles.get(), x.d_lens.get(), b.n, x.wpr(), b.d_rc[m].get(), s[2 + m])) != PA_OK) return e;
+        if ((e = x.map(idx, x.d_tiles.get(), b.n, allowed, s[m])) != PA_OK || (e = strand_map_rc(idx, b, m, allowed, s[2 + m])) != PA_OK) return e;
+    }
+    return b.d_mresults.reserve(b.n + 64, reads);
+}
+
+// waits for the four mappings (regrowing an arena as pa_map_finish asks), combines S on s[0] and R on s[1], both uncounted, then merges and counts on s[0]
+int strand_batch_count(pa_index* idx, StrandBatch& b, uint32_t allowed, uint64_t* d_counts, const hipStream_t s[4], uint64_t* stats, double* st) {
+    auto t0 = std::chrono::steady_clock::now();
+    int e = PA_OK;
+    for (int m = 0; m < 2; ++m) {
+        Mate& x = b.mate[m];
+        uint64_t used = 0;
+        if ((e = map_finish_regrow(idx, s[m], x.d_arena, &used, [&] { return x.map(idx, x.d_tiles.get(), b.n, allowed, s[m]); })) != PA_OK) return e;
+        if ((e = map_finish_regrow(idx, s[2 + m], b.d_rc_arena[m], &used, [&] { return strand_map_rc(idx, b, m, allowed, s[2 + m]); })) != PA_OK) return e;
+    }
+    st[2] += secs_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    // every arena is sized by a bound on what its launch can need: the combines are not re-run, and the counted merge cannot be (it would count twice)
+    Mate &m1 = b.mate[0], &m2 = b.mate[1];
+    const pa_read_result* res1[2] = {m1.d_results.get(), b.d_rc_results[0].get()};   // candidate c: mate 1's records, its arena, mate 2's
+    const uint32_t* ar1[2] = {m1.d_arena.get(), b.d_rc_arena[0].get()};
+    const pa_read_result* res2[2] = {b.d_rc_results[1].get(), m2.d_results.get()};
+    const uint32_t* ar2[2] = {b.d_rc_arena[1].get(), m2.d_arena.get()};
+    const size_t cbytes = pa_pairs_scratch_bytes(b.n), mbytes = pa_strands_scratch_bytes(b.n);
+    const char* const full = "a batch of %llu pairs may need %llu arena entries: lower PA_INGEST_BATCH";
+    for (int c = 0; c < 2; ++c) {
+        uint64_t bound = 0;
+        if ((e = b.d_cscratch[c].reserve(cbytes, cbytes + cbytes / 4)) != PA_OK) return e;
+        if ((e = pairs_arena_bound(idx, res1[c], res2[c], b.n, b.d_cscratch[c].get(), s[c], &bound)) != PA_OK) return e;
+        if (bound > PA_MAX_ARENA_ENTRIES) return fail(PA_ERR_UNSUPPORTED, full, (unsigned long long)b.n, (unsigned long long)bound);
+        if ((e = b.d_carena[c].reserve(bound + 64, bound + bound / 4 + 4096)) != PA_OK) return e;
+        if ((e = pa_pairs_combine_device(idx, res1[c], ar1[c], res2[c], ar2[c], b.n, b.d_cresults[c].get(), b.d_carena[c].get(), b.d_carena[c].size(), nullptr,
+                                         b.d_cscratch[c].get(), cbytes, s[c])) != PA_OK)
+            return e;
+    }
+    for (int c = 0; c < 2; ++c)
+        if ((e = pa_pairs_finish(idx, b.d_cscratch[c].get(), s[c], nullptr, nullptr, nullptr)) != PA_OK) return e;
+    uint64_t bound = 0;
+    if ((e = b.d_mscratch.reserve(mbytes, mbytes + mbytes / 4)) != PA_OK) return e;
+    if ((e = strands_arena_bound(idx, b.d_cresults[0].get(), b.d_cresults[1].get(), b.n, b.d_mscratch.get(), s[0], &bound)) != PA_OK) return e;
+    if (bound > PA_MAX_ARENA_ENTRIES) return fail(PA_ERR_UNSUPPORTED, full, (unsigned long long)b.n, (unsigned long long)bound);
+    if ((e = b.d_marena.reserve(bound + 64, bound + bound / 4 + 4096)) != PA_OK) return e;
+    if ((e = pa_strands_merge_device(idx, b.d_cresults[0].get(), b.d_carena[0].get(), b.d_cresults[1].get(), b.d_carena[1].get(), b.n, b.d_mresults.get(), b.d_marena.get(),
+                                     b.d_marena.size(), d_counts, b.d_mscratch.get(), mbytes, s[0])) != PA_OK)
+        return e;
+    uint64_t bst[PA_STRAND_STATS], used = 0, need = 0;
+    if ((e = pa_strands_finish(idx, b.d_mscratch.get(), s[0], bst, &used, &need)) != PA_OK) return e;
+    for (int j = 0; j < PA_STRAND_STATS; ++j) stats[j] += bst[j];
+    st[4] += secs_since(t0);
+    return PA_OK;
+}
+
+int count_pairs_unstranded_impl(pa_index* idx, const char* r1_path, const char* r2_path, uint32_t allowed, int num_threads, uint64_t* h_counts, uint64_t* n_pairs,
+                                uint64_t* stats_out) {
+    const auto t_call = std::chrono::steady_clock::now();
+    double* st = last_stage_seconds();
+    for (int j = 0; j < PA_INGEST_STAGES; ++j) st[j] = 0.0;
+    if (!idx || !r1_path || !r2_path || !h_counts) return fail(PA_ERR_INVALID_ARG, "null argument");
+    Pool pool(num_threads < 1 ? usable_threads() : num_threads);
+    PairReader rd(r1_path, r2_path, pool, 0xFFFFFFFFu, st);
+    int rc = rd.open();
+    if (rc != PA_OK) return rc;
+    const uint64_t counts_len = pa_counts_len(idx);
+    DeviceBuffer<uint64_t> d_counts;
+    if ((rc = d_counts.alloc(counts_len)) != PA_OK) return rc;
+    IndexStream streams[4];
+    hipStream_t s[4];
+    for (int j = 0; j < 4; ++j) {
+        if ((rc = streams[j].create(idx)) != PA_OK) return rc;
+        s[j] = streams[j].get();
+    }
+    PA_HIP_TRY(hipMemsetAsync(d_counts.get(), 0, counts_len * 8, s[0]));
+    rd.consumers = {s[0], s[1]};   // (the gathered bytes and offsets are read by the encodes on s[0] and s[1] alone)
+    StrandBatch batches[2];
+    uint64_t stats[PA_STRAND_STATS] = {0};
+    rc = run_batches(rd, batches, [&](StrandBatch& b) { return strand_batch_map(idx, b, allowed, s); },
+                     [&](StrandBatch& b) { return strand_batch_count(idx, b, allowed, d_counts.get(), s, stats, st); });
+    if (rc != PA_OK) return rc;
+    PA_HIP_TRY(hipMemcpyAsync(h_counts, d_counts.get(), counts_len * 8, hipMemcpyDeviceToHost, s[0]));
+    PA_HIP_TRY(hipStreamSynchronize(s[0]));
+    if (n_pairs) *n_pairs = rd.pairs;
+    if (stats_out) for (int j = 0; j < PA_STRAND_STATS; ++j) stats_out[j] = stats[j];
+    st[6] = secs_since(t_call);
+    st[7] = (double)rd.pairs;
+    return PA_OK;
+}
+
 }  // namespace
+
+extern "C" int pa_count_pairs_unstranded(pa_index* idx, const char* r1_path, const char* r2_path, uint32_t allowed_mismatches, int num_threads, uint64_t* h_counts,
+                                         uint64_t* n_pairs, uint64_t stats[PA_STRAND_STATS]) {
+    return no_throw("pa_count_pairs_unstranded", [&] { return count_pairs_unstranded_impl(idx, r1_path, r2_path, allowed_mismatches, num_threads, h_counts, n_pairs, stats); });
+}
 
 extern "C" int pa_count_cells(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const char* whitelist_path, uint32_t bc_len,
                               uint32_t umi_len, const char* out_dir, int num_threads, uint64_t stats[PA_CELL_STATS]) {

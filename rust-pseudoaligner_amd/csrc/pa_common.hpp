@@ -30,6 +30,8 @@ int index_device_class_text(pa_index* idx, const uint64_t** d_off, const uint8_t
 // pairs.hip: an upper bound on the arena entries pa_pairs_combine_device can need for these mate records (the shorter list of every pair with two
 // mapped mates, the list of a mate mapped alone), summed on the device into the first 8 bytes of d_scratch; synchronises `stream`
 int pairs_arena_bound(pa_index* idx, const pa_read_result* d_res1, const pa_read_result* d_res2, uint64_t n_pairs, void* d_scratch, void* stream, uint64_t* bound);
+// strands.hip: the same for pa_strands_merge_device and two candidates' records (the sum of both lengths where both are mapped, else the mapped one's)
+int strands_arena_bound(pa_index* idx, const pa_read_result* d_resS, const pa_read_result* d_resR, uint64_t n, void* d_scratch, void* stream, uint64_t* bound);
 // inflate.hip: the launch of pa_bgzf_inflate_device by itself, on the current device (no device query, no hipSetDevice): what pa_process_reads enqueues per window
 int bgzf_inflate_launch(const uint8_t* d_comp, uint64_t comp_bytes, const pa_bgzf_member* d_members, uint64_t n_members, uint8_t* d_text, uint64_t text_cap,
                         uint32_t* d_status, void* stream);

@@ -22,7 +22,9 @@
 //                             takes exactly that much arena with one atomic, the second pass writes (a block of 64 ids: one burst) and
 //                             lane 0 looks the list up by content where it lies
 // A mate mapped alone whose ids lie in its mate arena is the pair "list with itself": the same two kernels copy it into the pair arena.
-// The control block (arena top, status, stats, novel counter) lives at the start of the caller's scratch.
+// The control block (arena top, status, stats, novel counter) lives at the start of the caller's scratch. What this stage shares with the
+// unstranded stage (strands.hip) — control block, scratch layout, parameter block, the helpers on id lists — is pair_stage.hpp. The
+// host-buffer paths at the end (pa_map_pairs, pa_map_pairs_unstranded, pa_map_batch_strand) share map_mate and the stage runners.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -34,81 +36,13 @@
 #include "kernel_utils.hpp"
 #include "kernels.hpp"
 #include "pa_common.hpp"
+#include "pair_stage.hpp"
 
 namespace pa {
 namespace {
 
 constexpr uint32_t PAIR_LANE_MAX = 16;                                // the shorter list has at most this many ids: a lane; more: a wave
-constexpr uint32_t PAIR_UNFIT = (uint32_t)PA_MAX_ARENA_ENTRIES;       // class_off of a record whose ids did not fit the arena
-constexpr uint32_t NO_CLASS = 0xFFFFFFFFu;
-constexpr uint32_t PAIR_CTL_BYTES = 256;
 constexpr uint32_t ST_PAIRS = 0, ST_BOTH = 1, ST_ONLY1 = 2, ST_ONLY2 = 3, ST_NEITHER = 4, ST_EMPTY = 5, ST_REF = 6, ST_ARENA = 7;
-
-struct PairCtl {   // the first PAIR_CTL_BYTES of the scratch, zeroed by every launch
-    unsigned long long arena_top;                // ids asked for so far (exact: no chunks, no padding)
-    unsigned long long stats[PA_PAIR_STATS];
-    unsigned long long novel_ctr;                // results on the novel list
-    unsigned long long arena_cap;                // of the launch (what pa_pairs_finish clamps arena_used to)
-    uint32_t status, pad;
-};
-static_assert(sizeof(PairCtl) <= PAIR_CTL_BYTES, "the control block fits its slot");
-
-struct PairParams {
-    DevIndexView ix;
-    const uint32_t* class_table;
-    uint64_t class_table_size;
-    const pa_read_result *res1, *res2;
-    const uint32_t *arena1, *arena2;
-    uint32_t n;                  // pairs (below 2^31)
-    pa_read_result* results;
-    uint32_t* arena;
-    uint64_t arena_cap;
-    unsigned long long* counts;  // or nullptr
-    PairCtl* ctl;
-    uint32_t* flags;             // [2n + 1]: lane bin [0, n), wave bin [n, 2n), one zero
-    uint32_t* off;               // [2n + 1]: their exclusive scan; off[n] = lane items, off[2n] = all items
-    uint32_t* items;             // [n]: pair of every item, lane items first
-    uint32_t* novel;             // [2n] {arena offset, length} of the results for the overflow table, or nullptr
-};
-
-__device__ __forceinline__ const uint32_t* ids_of(const pa_read_result& r, const uint32_t* arena, const DevIndexView& ix) {
-    return (r.class_off & PA_CLASS_REF) ? class_ids(ix, ix.class_ref[r.class_off & ~PA_CLASS_REF]) : arena + r.class_off;
-}
-
-// first position in v[lo, hi) whose id is not below a
-__device__ __forceinline__ uint32_t lower_bound_ids(const uint32_t* __restrict__ v, uint32_t lo, uint32_t hi, uint32_t a) {
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (v[mid] < a) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// class_of_list (kernel_utils.hpp) for the list {v[t] : bit t of keep}, n = its length: the same hash, the same table
-__device__ __forceinline__ uint32_t class_of_masked(const uint32_t* __restrict__ v, uint32_t keep, uint32_t n, const DevIndexView& ix, const uint32_t* class_table,
-                                                    uint64_t class_table_size) {
-    uint64_t h = 0x243f6a8885a308d3ull ^ n;
-    for (uint32_t k = keep; k != 0; k &= k - 1) h = pa_mix64(h ^ v[__ffs((int)k) - 1]) + 0x9e3779b97f4a7c15ull;
-    uint64_t j = h % class_table_size;
-    for (;;) {
-        const uint32_t cand = class_table[j];
-        if (cand == NO_CLASS) return cand;
-        if (ix.class_len[cand] == n) {
-            const uint32_t* ids = class_ids(ix, ix.class_ref[cand]);
-            bool eq = true;
-            uint32_t o = 0;
-            for (uint32_t k = keep; k != 0 && eq; k &= k - 1) eq = ids[o++] == v[__ffs((int)k) - 1];
-            if (eq) return cand;
-        }
-        if (++j == class_table_size) j = 0;
-    }
-}
-
-// adds the number of lanes whose flag is set to *ctr, one atomic per wave (every lane of the wave calls it)
-__device__ __forceinline__ void wave_count(bool flag, unsigned long long* ctr) {
-    const unsigned long long m = __ballot(flag);
-    if (m != 0 && lane_id() == (uint32_t)__ffsll((long long)m) - 1) atomicAdd(ctr, (unsigned long long)__popcll(m));
-}
 
 // the two lists of a pair that has work to do: a = the shorter one (mate 1 on a tie); a mate mapped alone is paired with itself
 struct PairLists {
@@ -228,13 +162,6 @@ __global__ __launch_bounds__(256) void pa_pairs_scatter_kernel(const PairParams 
     if (i >= p.n) return;
     if (p.flags[i]) p.items[p.off[i]] = (uint32_t)i;
     if (p.flags[(uint64_t)p.n + i]) p.items[p.off[(uint64_t)p.n + i]] = (uint32_t)i;
-}
-
-// the class fields of a pair's record (coverage and mismatches are the classify kernel's)
-__device__ __forceinline__ void put_class(const PairParams& p, uint32_t pair, uint32_t off, uint32_t len) {
-    uint32_t* rec = reinterpret_cast<uint32_t*>(p.results + pair);
-    rec[2] = off;
-    rec[3] = len;
 }
 
 // ---------------------------------------------------------------------------------------------- a lane per short pair
@@ -371,27 +298,6 @@ __global__ __launch_bounds__(256) void pa_pairs_wave_kernel(const PairParams p) 
     }
 }
 
-// ---------------------------------------------------------------------------------------------- scratch
-size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-struct PairScratch {
-    size_t flags, off, items, novel, tmp, tmp_bytes, total;
-};
-PairScratch scratch_layout(uint64_t n) {
-    PairScratch s{};
-    size_t at = PAIR_CTL_BYTES;
-    s.flags = at; at += round256((2 * n + 1) * 4);
-    s.off = at;   at += round256((2 * n + 1) * 4);
-    s.items = at; at += round256((n + 1) * 4);
-    s.novel = at; at += round256((n + 1) * 8);
-    s.tmp = at;
-    s.tmp_bytes = round256(prim_bytes([&](void* t, size_t& b) { return scan_exclusive_on(t, b, (const uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)(2 * n + 1), nullptr); }));
-    s.total = at + s.tmp_bytes;
-    return s;
-}
-
-constexpr uint64_t PAIR_MAX_PAIRS = 0x7FFFFFF0ull;   // pair and item indices, and 2 n + 1 flags, are 32-bit
-
 }  // namespace
 }  // namespace pa
 
@@ -428,21 +334,8 @@ extern "C" int pa_pairs_combine_device(pa_index* idx, const pa_read_result* d_re
     PA_HIP_TRY(hipSetDevice(v.device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     uint8_t* base = static_cast<uint8_t*>(d_scratch);
-    PairParams p{};
-    p.ix = v.dv;
-    p.class_table = v.class_table;
-    p.class_table_size = v.class_table_size;
+    PairParams p = stage_params(v, n_pairs, d_results, d_arena, arena_cap, d_counts, d_scratch, lay);
     p.res1 = d_res1; p.res2 = d_res2; p.arena1 = d_arena1; p.arena2 = d_arena2;
-    p.n = (uint32_t)n_pairs;
-    p.results = d_results;
-    p.arena = d_arena;
-    p.arena_cap = arena_cap > PA_MAX_ARENA_ENTRIES ? PA_MAX_ARENA_ENTRIES : arena_cap;   // offsets leave bit 31 of class_off free
-    p.counts = reinterpret_cast<unsigned long long*>(d_counts);
-    p.ctl = reinterpret_cast<PairCtl*>(base);
-    p.flags = reinterpret_cast<uint32_t*>(base + lay.flags);
-    p.off = reinterpret_cast<uint32_t*>(base + lay.off);
-    p.items = reinterpret_cast<uint32_t*>(base + lay.items);
-    p.novel = (d_counts && v.ovf) ? reinterpret_cast<uint32_t*>(base + lay.novel) : nullptr;
     PA_HIP_TRY(hipMemsetAsync(base, 0, PAIR_CTL_BYTES, s));
     if (n_pairs == 0) return PA_OK;
     const uint32_t blocks = grid_for(n_pairs);
@@ -483,19 +376,7 @@ int pa::pairs_arena_bound(pa_index* idx, const pa_read_result* d_res1, const pa_
 }
 
 extern "C" int pa_pairs_finish(pa_index* idx, void* d_scratch, void* stream, uint64_t stats[PA_PAIR_STATS], uint64_t* arena_used, uint64_t* arena_needed) {
-    if (!idx || !d_scratch) return fail(PA_ERR_INVALID_ARG, "null argument");
-    PairIndexView v;
-    index_pair_view(idx, &v);
-    PA_HIP_TRY(hipSetDevice(v.device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    PairCtl h{};
-    PA_HIP_TRY(hipMemcpyAsync(&h, d_scratch, sizeof h, hipMemcpyDeviceToHost, s));
-    PA_HIP_TRY(hipStreamSynchronize(s));
-    if (stats) for (int j = 0; j < PA_PAIR_STATS; ++j) stats[j] = h.stats[j];
-    if (arena_used) *arena_used = h.arena_top < h.arena_cap ? h.arena_top : h.arena_cap;
-    if (arena_needed) *arena_needed = h.arena_top;
-    if (h.status & PA_STATUS_ARENA_FULL) return fail(PA_ERR_ARENA_FULL, "pair arena too small: %llu entries needed", h.arena_top);
-    return PA_OK;
+    return stage_finish(idx, d_scratch, stream, stats, arena_used, arena_needed, "pair");
 }
 
 // ---- host-buffer convenience: encode, orient, two launches, combine, D2H, CSR in pair order ----
@@ -509,7 +390,8 @@ struct MateBuffers {
 };
 
 // one mate of every pair: H2D, encode, reverse complement if asked, map (the arena regrown as pa_map_finish asks)
-int map_mate(pa_index* idx, const uint8_t* ascii, const uint64_t* offsets, uint64_t n, uint32_t maxlen, bool revcomp, uint32_t allowed, MateBuffers& b, hipStream_t s) {
+int map_mate(pa_index* idx, const uint8_t* ascii, const uint64_t* offsets, uint64_t n, uint32_t maxlen, bool revcomp, uint32_t allowed, MateBuffers& b, hipStream_t s,
+             uint64_t* arena_used = nullptr) {
     const uint32_t wpr = pa_words_per_read(std::max(1u, maxlen));
     const uint64_t total = offsets[n] - offsets[0];
     int rc;
@@ -532,68 +414,166 @@ int map_mate(pa_index* idx, const uint8_t* ascii, const uint64_t* offsets, uint6
     auto launch = [&] { return pa_map_batch_device(idx, tiles, b.lens.get(), n, wpr, allowed, b.results.get(), b.arena.get(), b.arena.size(), nullptr, s); };
     if ((rc = launch()) != PA_OK) return rc;
     uint64_t used = 0;
-    return map_finish_regrow(idx, s, b.arena, &used, launch);
+    rc = map_finish_regrow(idx, s, b.arena, &used, launch);
+    if (arena_used) *arena_used = used;
+    return rc;
 }
 
-int map_pairs_impl(pa_index* idx, const uint8_t* ascii1, const uint64_t* offsets1, const uint8_t* ascii2, const uint64_t* offsets2, uint64_t n, int orient,
+// the argument checks of the host-buffer paths for one read set ("mate 1", "mate 2", "read"); *maxlen = its longest read (at least 1)
+int check_reads(const char* what, const uint8_t* ascii, const uint64_t* offsets, uint64_t n, uint64_t* maxlen) {
+    *maxlen = 1;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (offsets[i + 1] < offsets[i]) return fail(PA_ERR_INVALID_ARG, "%s: offsets not monotone at %llu", what, (unsigned long long)i);
+        *maxlen = std::max(*maxlen, offsets[i + 1] - offsets[i]);
+    }
+    if (n && offsets[n] != offsets[0] && !ascii) return fail(PA_ERR_INVALID_ARG, "null argument");
+    if (*maxlen > PA_MAX_READ_LEN) return fail(PA_ERR_UNSUPPORTED, "read longer than %u bases", PA_MAX_READ_LEN);
+    return PA_OK;
+}
+
+std::vector<uint32_t>& csr_ids() {   // the CSR's ids of the host-buffer paths below: library-owned until this thread's next call of one of them
+    static thread_local std::vector<uint32_t> ids;
+    return ids;
+}
+
+// records and the used part of their arena to the host, the classes as a CSR in item order
+int results_to_host(pa_index* idx, const pa_read_result* d_results, const uint32_t* d_arena, uint64_t used, uint64_t n, pa_read_result* results, uint64_t* class_offsets,
+                    const uint32_t** class_ids, hipStream_t s) {
+    PA_HIP_TRY(hipMemcpyAsync(results, d_results, n * sizeof(pa_read_result), hipMemcpyDeviceToHost, s));
+    std::vector<uint32_t> h_arena(used + 1);
+    if (used) PA_HIP_TRY(hipMemcpyAsync(h_arena.data(), d_arena, used * 4, hipMemcpyDeviceToHost, s));
+    PA_HIP_TRY(hipStreamSynchronize(s));
+    if (class_offsets || class_ids) classes_to_csr(idx, results, n, h_arena.data(), csr_ids(), class_offsets, class_ids);
+    return PA_OK;
+}
+
+// One stage (pair combine or strand merge) over two finished record sets, uncounted, its arena grown until the ids fit
+struct StageOut {
+    DeviceBuffer<uint8_t> scratch;
+    DeviceBuffer<pa_read_result> results;
+    DeviceBuffer<uint32_t> arena;
+    uint64_t used = 0;
+};
+template <class Launch, class Finish>
+int run_stage(uint64_t n, size_t scratch_bytes, StageOut& o, Launch&& launch, Finish&& finish) {
+    int rc;
+    if ((rc = o.scratch.alloc(scratch_bytes)) || (rc = o.results.alloc(n + 1))) return rc;
+    uint64_t cap = 4 * n + 4096, need = 0;
+    for (int attempt = 0;; ++attempt) {
+        if ((rc = o.arena.alloc(cap)) != PA_OK) return rc;
+        if ((rc = launch(o, cap, scratch_bytes)) != PA_OK) return rc;
+        rc = finish(o, &need);
+        if (rc == PA_ERR_ARENA_FULL && attempt < 2) { cap = need + 64; continue; }
+        return rc;
+    }
+}
+int combine_mates(pa_index* idx, const MateBuffers& m1, const MateBuffers& m2, uint64_t n, StageOut& o, hipStream_t s) {
+    return run_stage(n, pa_pairs_scratch_bytes(n), o,
+                     [&](StageOut& x, uint64_t cap, size_t sb) {
+                         return pa_pairs_combine_device(idx, m1.results.get(), m1.arena.get(), m2.results.get(), m2.arena.get(), n, x.results.get(), x.arena.get(), cap, nullptr,
+                                                        x.scratch.get(), sb, s);
+                     },
+                     [&](StageOut& x, uint64_t* need) { return pa_pairs_finish(idx, x.scratch.get(), s, nullptr, &x.used, need); });
+}
+int merge_strands(pa_index* idx, const pa_read_result* resS, const uint32_t* arenaS, const pa_read_result* resR, const uint32_t* arenaR, uint64_t n, StageOut& o, hipStream_t s) {
+    return run_stage(n, pa_strands_scratch_bytes(n), o,
+                     [&](StageOut& x, uint64_t cap, size_t sb) {
+                         return pa_strands_merge_device(idx, resS, arenaS, resR, arenaR, n, x.results.get(), x.arena.get(), cap, nullptr, x.scratch.get(), sb, s);
+                     },
+                     [&](StageOut& x, uint64_t* need) { return pa_strands_finish(idx, x.scratch.get(), s, nullptr, &x.used, need); });
+}
+
+
+// pa_map_pairs (orient) and pa_map_pairs_unstranded (unstranded: orient is not looked at)
+int map_pairs_impl(pa_index* idx, const uint8_t* ascii1, const uint64_t* offsets1, const uint8_t* ascii2, const uint64_t* offsets2, uint64_t n, int orient, bool unstranded,
                    uint32_t allowed, pa_read_result* results, uint64_t* class_offsets, const uint32_t** class_ids) {
     if (!idx || !offsets1 || !offsets2 || (n && !results)) return fail(PA_ERR_INVALID_ARG, "null argument");
-    if (orient != PA_PAIR_FR && orient != PA_PAIR_RF && orient != PA_PAIR_FF) return fail(PA_ERR_INVALID_ARG, "orientation %d (PA_PAIR_FR, PA_PAIR_RF or PA_PAIR_FF)", orient);
+    if (!unstranded && orient != PA_PAIR_FR && orient != PA_PAIR_RF && orient != PA_PAIR_FF)
+        return fail(PA_ERR_INVALID_ARG, "orientation %d (PA_PAIR_FR, PA_PAIR_RF or PA_PAIR_FF)", orient);
     if (n > PAIR_MAX_PAIRS) return fail(PA_ERR_UNSUPPORTED, "at most %llu pairs in one call", (unsigned long long)PAIR_MAX_PAIRS);
     uint64_t maxlen[2] = {1, 1};
-    const uint64_t* offs[2] = {offsets1, offsets2};
-    const uint8_t* asc[2] = {ascii1, ascii2};
-    for (int mt = 0; mt < 2; ++mt) {
-        for (uint64_t i = 0; i < n; ++i) {
-            if (offs[mt][i + 1] < offs[mt][i]) return fail(PA_ERR_INVALID_ARG, "mate %d: offsets not monotone at pair %llu", mt + 1, (unsigned long long)i);
-            maxlen[mt] = std::max(maxlen[mt], offs[mt][i + 1] - offs[mt][i]);
-        }
-        if (n && offs[mt][n] != offs[mt][0] && !asc[mt]) return fail(PA_ERR_INVALID_ARG, "null argument");
-        if (maxlen[mt] > PA_MAX_READ_LEN) return fail(PA_ERR_UNSUPPORTED, "read longer than %u bases", PA_MAX_READ_LEN);
-    }
-    static thread_local std::vector<uint32_t> t_class_ids;   // the CSR's ids: library-owned until this thread's next call
+    int rc;
+    if ((rc = check_reads("mate 1", ascii1, offsets1, n, &maxlen[0])) != PA_OK || (rc = check_reads("mate 2", ascii2, offsets2, n, &maxlen[1])) != PA_OK) return rc;
     if (n == 0) { if (class_offsets) class_offsets[0] = 0; if (class_ids) *class_ids = nullptr; return PA_OK; }
     PairIndexView v;
     index_pair_view(idx, &v);
     PA_HIP_TRY(hipSetDevice(v.device));
     IndexStream stream;   // a stream of this call's own: its launch context on idx is shared with nobody and released at the end
-    int rc = stream.create(idx);
-    if (rc != PA_OK) return rc;
+    if ((rc = stream.create(idx)) != PA_OK) return rc;
     const hipStream_t s = stream.get();
-    MateBuffers mb[2];
-    if ((rc = map_mate(idx, ascii1, offsets1, n, (uint32_t)maxlen[0], orient == PA_PAIR_RF, allowed, mb[0], s)) != PA_OK) return rc;
-    if ((rc = map_mate(idx, ascii2, offsets2, n, (uint32_t)maxlen[1], orient == PA_PAIR_FR, allowed, mb[1], s)) != PA_OK) return rc;
-    DeviceBuffer<uint8_t> scratch;
-    DeviceBuffer<pa_read_result> d_results;
-    DeviceBuffer<uint32_t> d_arena;
-    const size_t scratch_bytes = pa_pairs_scratch_bytes(n);
-    if ((rc = scratch.alloc(scratch_bytes)) || (rc = d_results.alloc(n + 1))) return rc;
-    uint64_t cap = 4 * n + 4096, used = 0, need = 0;
-    for (int attempt = 0;; ++attempt) {
-        if ((rc = d_arena.alloc(cap)) != PA_OK) return rc;
-        if ((rc = pa_pairs_combine_device(idx, mb[0].results.get(), mb[0].arena.get(), mb[1].results.get(), mb[1].arena.get(), n, d_results.get(), d_arena.get(), cap,
-                                          nullptr, scratch.get(), scratch_bytes, s)) != PA_OK)
-            return rc;
-        rc = pa_pairs_finish(idx, scratch.get(), s, nullptr, &used, &need);
-        if (rc == PA_ERR_ARENA_FULL && attempt < 2) { cap = need + 64; continue; }
-        if (rc != PA_OK) return rc;
-        break;
+    if (!unstranded) {
+        MateBuffers mb[2];
+        StageOut pair;
+        if ((rc = map_mate(idx, ascii1, offsets1, n, (uint32_t)maxlen[0], orient == PA_PAIR_RF, allowed, mb[0], s)) != PA_OK) return rc;
+        if ((rc = map_mate(idx, ascii2, offsets2, n, (uint32_t)maxlen[1], orient == PA_PAIR_FR, allowed, mb[1], s)) != PA_OK) return rc;
+        if ((rc = combine_mates(idx, mb[0], mb[1], n, pair, s)) != PA_OK) return rc;
+        return results_to_host(idx, pair.results.get(), pair.arena.get(), pair.used, n, results, class_offsets, class_ids, s);
     }
-    PA_HIP_TRY(hipMemcpyAsync(results, d_results.get(), n * sizeof(pa_read_result), hipMemcpyDeviceToHost, s));
-    std::vector<uint32_t> h_arena(used + 1);
-    if (used) PA_HIP_TRY(hipMemcpyAsync(h_arena.data(), d_arena.get(), used * 4, hipMemcpyDeviceToHost, s));
-    PA_HIP_TRY(hipStreamSynchronize(s));
-    if (class_offsets || class_ids) classes_to_csr(idx, results, n, h_arena.data(), t_class_ids, class_offsets, class_ids);
-    return PA_OK;
+    // four mappings one after the other on the one stream (map_mate finishes each before the next is launched), the two candidates, the merge
+    MateBuffers fw[2], rv[2];
+    StageOut cand[2], item;
+    if ((rc = map_mate(idx, ascii1, offsets1, n, (uint32_t)maxlen[0], false, allowed, fw[0], s)) != PA_OK) return rc;
+    if ((rc = map_mate(idx, ascii2, offsets2, n, (uint32_t)maxlen[1], false, allowed, fw[1], s)) != PA_OK) return rc;
+    if ((rc = map_mate(idx, ascii1, offsets1, n, (uint32_t)maxlen[0], true, allowed, rv[0], s)) != PA_OK) return rc;
+    if ((rc = map_mate(idx, ascii2, offsets2, n, (uint32_t)maxlen[1], true, allowed, rv[1], s)) != PA_OK) return rc;
+    if ((rc = combine_mates(idx, fw[0], rv[1], n, cand[0], s)) != PA_OK) return rc;   // S: PA_PAIR_FR
+    if ((rc = combine_mates(idx, rv[0], fw[1], n, cand[1], s)) != PA_OK) return rc;   // R: PA_PAIR_RF
+    if ((rc = merge_strands(idx, cand[0].results.get(), cand[0].arena.get(), cand[1].results.get(), cand[1].arena.get(), n, item, s)) != PA_OK) return rc;
+    return results_to_host(idx, item.results.get(), item.arena.get(), item.used, n, results, class_offsets, class_ids, s);
+}
+
+int map_batch_strand_impl(pa_index* idx, const uint8_t* ascii, const uint64_t* offsets, uint64_t n, int strand, uint32_t allowed, pa_read_result* results,
+                          uint64_t* class_offsets, const uint32_t** class_ids) {
+    if (!idx || !offsets || (n && !results)) return fail(PA_ERR_INVALID_ARG, "null argument");
+    if (strand != PA_STRAND_FWD && strand != PA_STRAND_REV && strand != PA_STRAND_BOTH)
+        return fail(PA_ERR_INVALID_ARG, "strand %d (PA_STRAND_FWD, PA_STRAND_REV or PA_STRAND_BOTH)", strand);
+    if (n > PAIR_MAX_PAIRS) return fail(PA_ERR_UNSUPPORTED, "at most %llu reads in one call", (unsigned long long)PAIR_MAX_PAIRS);
+    uint64_t maxlen = 1;
+    int rc = check_reads("read", ascii, offsets, n, &maxlen);
+    if (rc != PA_OK) return rc;
+    if (n == 0) { if (class_offsets) class_offsets[0] = 0; if (class_ids) *class_ids = nullptr; return PA_OK; }
+    PairIndexView v;
+    index_pair_view(idx, &v);
+    PA_HIP_TRY(hipSetDevice(v.device));
+    IndexStream stream;
+    if ((rc = stream.create(idx)) != PA_OK) return rc;
+    const hipStream_t s = stream.get();
+    MateBuffers fw, rv;
+    uint64_t used = 0;
+    if (strand != PA_STRAND_BOTH) {
+        MateBuffers& b = strand == PA_STRAND_REV ? rv : fw;
+        if ((rc = map_mate(idx, ascii, offsets, n, (uint32_t)maxlen, strand == PA_STRAND_REV, allowed, b, s, &used)) != PA_OK) return rc;
+        return results_to_host(idx, b.results.get(), b.arena.get(), used, n, results, class_offsets, class_ids, s);
+    }
+    StageOut item;
+    if ((rc = map_mate(idx, ascii, offsets, n, (uint32_t)maxlen, false, allowed, fw, s)) != PA_OK) return rc;
+    if ((rc = map_mate(idx, ascii, offsets, n, (uint32_t)maxlen, true, allowed, rv, s)) != PA_OK) return rc;
+    if ((rc = merge_strands(idx, fw.results.get(), fw.arena.get(), rv.results.get(), rv.arena.get(), n, item, s)) != PA_OK) return rc;
+    return results_to_host(idx, item.results.get(), item.arena.get(), item.used, n, results, class_offsets, class_ids, s);
+}
+
+template <class F>
+int no_bad_alloc(const char* what, F&& f) {
+    try {
+        return f();
+    } catch (const std::bad_alloc&) {
+        return fail(PA_ERR_OOM, "out of host memory in %s", what);
+    }
 }
 
 }  // namespace
 
 extern "C" int pa_map_pairs(pa_index* idx, const uint8_t* ascii1, const uint64_t* offsets1, const uint8_t* ascii2, const uint64_t* offsets2, uint64_t n_pairs,
                             int orient, uint32_t allowed_mismatches, pa_read_result* results, uint64_t* class_offsets, const uint32_t** class_ids) {
-    try {
-        return map_pairs_impl(idx, ascii1, offsets1, ascii2, offsets2, n_pairs, orient, allowed_mismatches, results, class_offsets, class_ids);
-    } catch (const std::bad_alloc&) {
-        return fail(PA_ERR_OOM, "out of host memory in pa_map_pairs");
-    }
+    return no_bad_alloc("pa_map_pairs", [&] { return map_pairs_impl(idx, ascii1, offsets1, ascii2, offsets2, n_pairs, orient, false, allowed_mismatches, results, class_offsets, class_ids); });
+}
+
+extern "C" int pa_map_pairs_unstranded(pa_index* idx, const uint8_t* ascii1, const uint64_t* offsets1, const uint8_t* ascii2, const uint64_t* offsets2, uint64_t n_pairs,
+                                       uint32_t allowed_mismatches, pa_read_result* results, uint64_t* class_offsets, const uint32_t** class_ids) {
+    return no_bad_alloc("pa_map_pairs_unstranded", [&] { return map_pairs_impl(idx, ascii1, offsets1, ascii2, offsets2, n_pairs, 0, true, allowed_mismatches, results, class_offsets, class_ids); });
+}
+
+extern "C" int pa_map_batch_strand(pa_index* idx, const uint8_t* ascii, const uint64_t* offsets, uint64_t n_reads, int strand, uint32_t allowed_mismatches,
+                                   pa_read_result* results, uint64_t* class_offsets, const uint32_t** class_ids) {
+    return no_bad_alloc("pa_map_batch_strand", [&] { return map_batch_strand_impl(idx, ascii, offsets, n_reads, strand, allowed_mismatches, results, class_offsets, class_ids); });
 }

@@ -1,13 +1,18 @@
 #!/usr/bin/env python
 """Timing of the paired-end stage (csrc/pairs.hip) on device-resident pairs, and of pa_count_pairs from files in the page cache.
 
-  python tools/bench_pairs.py [--pairs 10000000] [--index config3|17k] [--out profiles/r10_pairs_bench.json]
+  python tools/bench_pairs.py [--pairs 10000000] [--index config3|17k] [--orient fr|un] [--out profiles/r10_pairs_bench.json]
 
 Pairs of 2 x 100 bases: fragments of 300 bases from Txome.simulate_host (1 % substitutions), cut in numpy — mate 1 = the first 100 bases,
 mate 2 = the reverse complement of the last 100 ("fr"). Reported, each the median of 5 runs timed with HIP events on the launch stream:
 the reverse complement of mate 2, the two map launches, combine without the table, combine with the table and an overflow table attached;
 the stats vector; the ratio combine / map and the bytes the combine stage must move (32 bytes of records in and 16 out per pair plus the ids
-of the non-trivial pairs, counted on the host from the mates' records); and count_pairs pairs/s with its stage seconds. None is a gate."""
+of the non-trivial pairs, counted on the host from the mates' records); and count_pairs pairs/s with its stage seconds. None is a gate.
+
+--orient un: the same pairs as an UNSTRANDED library (the mates of every odd pair swapped) through the unstranded stage (csrc/strands.hip): the four
+map launches, the two uncounted combines, the merge without the table and with the table and an overflow table attached, the merge against the
+two combines and against the four maps it follows, the merge's stats vector, and count_pairs pairs/s for "un" beside "fr" on the same files
+(default --out profiles/r13_strands_bench.json)."""
 import argparse
 import importlib
 import json
@@ -82,15 +87,103 @@ def timed(fn, reps=5):
     return statistics.median(ms), ms
 
 
+def count_pairs_leg(a, al, m1, m2, orients):
+    """count_pairs from files in the page cache, once per orientation on the same two files -> {orient: report}"""
+    fn = min(a.file_pairs, len(m1))
+    lut = np.frombuffer(b"ACGT", np.uint8)
+    rep = {}
+    with tempfile.TemporaryDirectory(dir=os.environ.get("TMPDIR")) as d:
+        paths = []
+        for k, mate in enumerate((m1, m2)):
+            p = os.path.join(d, "R%d.fq%s" % (k + 1, pairs_input.suffix(a)))
+            with pairs_input.Writer(p, a.input) as f:
+                for lo in range(0, fn, 1 << 18):
+                    rows = lut[mate[lo:min(fn, lo + (1 << 18))]]
+                    f.write(b"".join(b"@p%d/%d\n%s\n+\n%s\n" % (lo + i, k + 1, r.tobytes(), b"I" * MATE) for i, r in enumerate(rows)))
+            paths.append(p)
+        for orient in orients:
+            al.count_pairs(paths[0], paths[1], orient, num_threads=a.threads)          # warm: page cache, buffers
+            secs, (_, st) = pairs_input.timed_calls(lambda: al.count_pairs(paths[0], paths[1], orient, num_threads=a.threads), a.calls)
+            dt = secs[-1]
+            rep[orient] = {"pairs": fn, "pairs_per_s": fn / dt, "stage_seconds": pa.process_reads_stage_seconds(), "stats": st, **pairs_input.report(pa, a, fn, secs)}
+    return rep
+
+
+def unstranded(a, al, tx, m1, m2):
+    """--orient un: the device-resident legs of the unstranded stage, then count_pairs "un" beside "fr" on the same files"""
+    n = a.pairs
+    m1, m2 = m1.copy(), m2.copy()
+    odd = np.arange(1, n, 2)
+    m1[odd], m2[odd] = m2[odd].copy(), m1[odd].copy()
+    out = {"pairs": n, "index": a.index, "transcripts": tx.num_transcripts, "mate_len": MATE, "fragment": FRAG, "orient": "un"}
+    cap = al.arena_hint(n)
+    mate = []
+    for m in (m1, m2):
+        t, l, wpr = to_tiles(m)
+        d_t, d_l = up(t), up(l)
+        d_rc = torch.zeros(len(t), dtype=torch.int64, device="cuda")
+        res = [torch.zeros(4 * n, dtype=torch.int32, device="cuda") for _ in range(2)]
+        arena = [torch.zeros(cap, dtype=torch.int32, device="cuda") for _ in range(2)]
+        torch.cuda.synchronize()
+        al.revcomp_tiles_device(d_t.data_ptr(), d_l.data_ptr(), n, wpr, d_rc.data_ptr())
+        mate.append((d_t, d_rc, d_l, res, arena, wpr))
+
+    def four_maps():
+        for d_t, d_rc, d_l, res, arena, wpr in mate:
+            for k, tiles in enumerate((d_t, d_rc)):
+                al.map_batch_device(tiles.data_ptr(), d_l.data_ptr(), n, wpr, res[k].data_ptr(), arena[k].data_ptr(), cap)
+                al.map_finish()
+    out["four_maps_ms"], _ = timed(four_maps)
+
+    pcap = 8 * n + 4096
+    cand = [(torch.zeros(4 * n, dtype=torch.int32, device="cuda"), torch.zeros(pcap, dtype=torch.int32, device="cuda")) for _ in range(2)]
+    d_ir = torch.zeros(4 * n, dtype=torch.int32, device="cuda")
+    d_ia = torch.zeros(2 * pcap, dtype=torch.int32, device="cuda")
+    sb = max(al.pairs_scratch_bytes(n), al.strands_scratch_bytes(n))
+    d_scr = torch.empty(sb + 256, dtype=torch.uint8, device="cuda")
+    scr = (d_scr.data_ptr() + 255) & ~255
+    counts = torch.zeros(al.counts_len(), dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    last = {}
+
+    def two_combines():   # S = (mate 1, rc mate 2), R = (rc mate 1, mate 2), both uncounted
+        for c, (x, y) in enumerate(((0, 1), (1, 0))):
+            al.pairs_combine_device(mate[0][3][x].data_ptr(), mate[0][4][x].data_ptr(), mate[1][3][y].data_ptr(), mate[1][4][y].data_ptr(), n, cand[c][0].data_ptr(),
+                                    cand[c][1].data_ptr(), pcap, scr, sb)
+            al.pairs_finish(scr)
+    out["two_combines_ms"], _ = timed(two_combines)
+
+    def merge(d_counts):
+        al.strands_merge_device(cand[0][0].data_ptr(), cand[0][1].data_ptr(), cand[1][0].data_ptr(), cand[1][1].data_ptr(), n, d_ir.data_ptr(), d_ia.data_ptr(), 2 * pcap,
+                                scr, sb, d_counts=d_counts)
+        last["stats"], last["used"], _ = al.strands_finish(scr)
+    out["merge_ms"], _ = timed(lambda: merge(0))
+    ovf = pa.Overflow(0, 1 << 22, 1 << 26)
+    al.set_overflow(ovf)
+    out["merge_table_overflow_ms"], _ = timed(lambda: merge(counts.data_ptr()))
+    al.set_overflow(None)
+    out["stats"] = last["stats"]
+    out["merge_arena_ids"] = int(last["used"])
+    out["merge_over_two_combines"] = out["merge_ms"] / out["two_combines_ms"]
+    out["merge_over_four_maps"] = out["merge_ms"] / out["four_maps_ms"]
+    out["count_pairs"] = count_pairs_leg(a, al, m1, m2, ["fr", "un"])
+    out["count_pairs_un_over_fr"] = out["count_pairs"]["un"]["pairs_per_s"] / out["count_pairs"]["fr"]["pairs_per_s"]
+    Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(a.out).write_text(json.dumps(out, indent=1) + "\n")
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=10_000_000)
     ap.add_argument("--index", choices=["config3", "17k"], default="config3")
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--file-pairs", type=int, default=2_000_000, help="pairs written to FASTQ for the count_pairs leg")
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "r10_pairs_bench.json"))
+    ap.add_argument("--orient", choices=["fr", "un"], default="fr", help="un: the pairs as an unstranded library, through the unstranded stage")
+    ap.add_argument("--out", default=None)
     pairs_input.add_args(ap)   # the count_pairs leg on BGZF files / on the host path / timed several times
     a = ap.parse_args()
+    a.out = a.out or str(ROOT / "profiles" / ("r10_pairs_bench.json" if a.orient == "fr" else "r13_strands_bench.json"))
     pairs_input.apply(a)
     n = a.pairs
     tx = pa.Txome.synthesize(20000, 200000, 7) if a.index == "config3" else pa.Txome.synthesize(5000, 17000, 7)
@@ -98,6 +191,8 @@ def main():
     al = pa.Pseudoaligner(host)
     frag = fragments(tx, n, 11)
     m1, m2 = frag[:, :MATE], revcomp_rows(frag[:, -MATE:])
+    if a.orient == "un":
+        return unstranded(a, al, tx, m1, m2)
     t1, l1, wpr = to_tiles(m1)
     t2, l2, _ = to_tiles(m2)
     d_t1, d_t2, d_l1, d_l2 = up(t1), up(t2), up(l1), up(l2)
@@ -147,22 +242,7 @@ def main():
     out["combine_over_two_maps"] = out["combine_ms"] / out["two_maps_ms"]
     out["combine_GBps_of_must_move"] = out["combine_bytes"] / out["combine_ms"] / 1e6
 
-    # count_pairs from files in the page cache
-    fn = min(a.file_pairs, n)
-    lut = np.frombuffer(b"ACGT", np.uint8)
-    with tempfile.TemporaryDirectory(dir=os.environ.get("TMPDIR")) as d:
-        paths = []
-        for k, mate in enumerate((m1, m2)):
-            p = os.path.join(d, "R%d.fq%s" % (k + 1, pairs_input.suffix(a)))
-            with pairs_input.Writer(p, a.input) as f:
-                for lo in range(0, fn, 1 << 18):
-                    rows = lut[mate[lo:min(fn, lo + (1 << 18))]]
-                    f.write(b"".join(b"@p%d/%d\n%s\n+\n%s\n" % (lo + i, k + 1, r.tobytes(), b"I" * MATE) for i, r in enumerate(rows)))
-            paths.append(p)
-        al.count_pairs(paths[0], paths[1], "fr", num_threads=a.threads)          # warm: page cache, buffers
-        secs, (_, st) = pairs_input.timed_calls(lambda: al.count_pairs(paths[0], paths[1], "fr", num_threads=a.threads), a.calls)
-        dt = secs[-1]
-        out["count_pairs"] = {"pairs": fn, "pairs_per_s": fn / dt, "stage_seconds": pa.process_reads_stage_seconds(), "stats": st, **pairs_input.report(pa, a, fn, secs)}
+    out["count_pairs"] = count_pairs_leg(a, al, m1, m2, ["fr"])["fr"]
     Path(a.out).parent.mkdir(parents=True, exist_ok=True)
     Path(a.out).write_text(json.dumps(out, indent=1) + "\n")
     print(json.dumps(out))
