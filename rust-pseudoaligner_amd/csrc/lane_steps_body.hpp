@@ -734,6 +734,28 @@ struct FwdLoad {     // what fwd_issue leaves in flight
     U4 s0, s1, s2, s3;
     Q2 s01, s23, s45;
 };
+// Where the 16-byte load of sequence words w and w + 1 of a block goes (sq = its eight words). A pair that would start at the block's
+// LAST word — a lane that stayed in its block far into the window (fwd_next_block) — is loaded one word lower: the word behind a
+// block's last is never looked at, and the load would have been a request for the next 128-byte line. fwd_seq_first picks the word
+// back out of what was loaded — in the finishing half of the step: nothing between the loads of fwd_issue may wait for one of them.
+constexpr uint32_t CH_SEQ_LAST = CH_WINDOW / 32 - 1;
+PA_HD const Q2* fwd_seq_pair(const uint64_t* sq, uint32_t w) { return reinterpret_cast<const Q2*>(sq + (w == CH_SEQ_LAST ? CH_SEQ_LAST - 1 : w)); }
+PA_HD uint64_t fwd_seq_first(const Q2& v, uint32_t w) { return w == CH_SEQ_LAST ? v.b : v.a; }
+// A lane that goes on in its chain — at window position x (>= 1) of block h, `rest` (>= 1) read bases still to compare — names the block
+// its next step reads; returns whether that is the block it holds (then the slot of its node's record stays known).
+// It STAYS when everything the remaining steps can look at lies in this block's window: the bases x .. x + rest - 1 (x + rest is the same
+// at every step of a walk through one chain, so such a lane never leaves the block), and with them the record of every node that
+// overlaps them and the edge or link slot of a node that ends among them (device_layout.hpp: a block lists every node that overlaps
+// its window). The step then re-reads the line the lane loaded one step earlier instead of the neighbouring, overlapping block — a
+// fresh line — and does not have to look for its record there. Which block a base is read from is not observable: 64 h + x is the same.
+// Else: the block whose window starts at most 64 bases before x (a position that is a multiple of 64 stays the 64th of the block
+// before: a node that ends exactly there is still on that block's list), where the next step looks for the node's record.
+PA_HD bool fwd_next_block(uint32_t& h, uint32_t& x, uint32_t rest) {
+    const uint32_t adv = x + rest <= CH_WINDOW ? 0u : (x - 1) >> CH_STRIDE_LOG2;
+    h += adv;
+    x -= adv << CH_STRIDE_LOG2;
+    return adv == 0;
+}
 #endif   // PA_LS_COMMON
 #if PA_LS_LANE
 PA_HD void fwd_issue(const Lane& s, const DevIndexView& ix, FwdLoad& f) {
@@ -748,13 +770,14 @@ PA_HD void fwd_issue(const Lane& s, const DevIndexView& ix, FwdLoad& f) {
     const uint32_t rot = l_cur(s);
     f.s0 = PA_LD(8, sp + rot); f.s1 = PA_LD(8, sp + ((rot + 1) & 3u)); f.s2 = PA_LD(8, sp + ((rot + 2) & 3u)); f.s3 = PA_LD(8, sp + ((rot + 3) & 3u));
     // sequence words this step can need, known before the block arrives: at most the rest of the read, 128 bases per step
-    // (the second and third 16-byte load only go out for the lanes that can need them: every load is an access of the vector L1)
-    const uint32_t most = pa_min(L - kp0, 128u), nwords = ((xs & 31) + most + 31) >> 5;
-    const Q2* sq2 = reinterpret_cast<const Q2*>(blk + CH_SEQ_BYTES + 8u * (xs >> 5));
-    f.s01 = PA_LD(8, sq2);
+    // (the second 16-byte load and the load of the fifth word only go out for the lanes that can need them: every load is an access of
+    // the vector L1; none of them reaches beyond the block's 128 bytes when the words the step needs lie in it: fwd_seq_pair)
+    const uint32_t most = pa_min(L - kp0, 128u), nwords = ((xs & 31) + most + 31) >> 5, w0 = xs >> 5;
+    const uint64_t* sq = reinterpret_cast<const uint64_t*>(blk + CH_SEQ_BYTES);
+    f.s01 = PA_LD(8, fwd_seq_pair(sq, w0));
     f.s23 = f.s45 = Q2{0ull, 0ull};
-    if (nwords > 2) f.s23 = PA_LD(8, sq2 + 1);
-    if (nwords > 4) f.s45 = PA_LD(8, sq2 + 2);
+    if (nwords > 2) f.s23 = PA_LD(8, fwd_seq_pair(sq, w0 + 2));
+    if (nwords > 4) f.s45.a = PA_LD(8, sq + (w0 + 4));                // (a step looks at five words at most: one word, never beyond the block)
 }
 #endif   // PA_LS_LANE
 
@@ -786,7 +809,8 @@ PA_HD void fwd_finish_general(Lane& s, const DevIndexView& ix, ReadRef rd, ColRe
     const uint32_t xs = x, kp0 = kp;
     uint32_t snp = s.rr >> 24, cov = l_cov(s), mism = l_mism(s);
     const uint32_t most = pa_min(L - kp0, 128u), nwords = ((xs & 31) + most + 31) >> 5;   // as in fwd_issue
-    const uint64_t a[5] = {f.s01.a, f.s01.b, nwords > 2 ? f.s23.a : 0ull, nwords > 2 ? f.s23.b : 0ull, nwords > 4 ? f.s45.a : 0ull};
+    const uint64_t a[5] = {fwd_seq_first(f.s01, xs >> 5), f.s01.b, nwords > 2 ? fwd_seq_first(f.s23, (xs >> 5) + 2) : 0ull, nwords > 2 ? f.s23.b : 0ull,
+                           nwords > 4 ? f.s45.a : 0ull};
     const Slots sl{f.s0, f.s1, f.s2, f.s3};                           // (rotated by l_cur(s): fwd_issue)
     const bool known = s.of & OF_CUR_KNOWN;
     const uint32_t rot = l_cur(s);
@@ -896,11 +920,9 @@ PA_HD void fwd_finish_general(Lane& s, const DevIndexView& ix, ReadRef rd, ColRe
     }
     nfl |= l_flags(s) & (F_SMALL_BASE | F_SPILL_OVERFLOW);           // (what push_node may have set)
     if (st == ST_SEEK) nfl |= F_SPEC;                                 // a re-seek starts at the base the visit broke off at: a probable miss
-    if (st == ST_FWD && !hopped) {                                    // goes on in this chain: the block whose window starts at most 64 bases before x
-        const uint32_t adv = (x - 1) >> CH_STRIDE_LOG2;               // (x >= 1; a position that is a multiple of 64 stays the 64th of the block before:
-        h += adv;                                                     //  a node that ends exactly there is still on that block's list)
-        x -= adv << CH_STRIDE_LOG2;
-        ncur = of_cur((rot + cur) & 3u, adv == 0);                    // the same block: the node's slot is known; another block: the next step looks for it
+    if (st == ST_FWD && !hopped) {                                    // goes on in this chain (x >= 1, kp < L): in the block it holds when the rest of the read fits it
+        const bool same = fwd_next_block(h, x, L - kp);
+        ncur = of_cur((rot + cur) & 3u, same);                        // the same block: the node's slot is known; another block: the next step looks for it
     }
     s.h = h;
     l_set_lk(s, L, kp, st);
@@ -948,7 +970,8 @@ PA_HD void fwd_finish(Lane& s, const DevIndexView& ix, ReadRef rd, ColRef cols, 
     const uint32_t kadd = fresh ? K : 0u;
     const uint32_t x0 = l_off(s) + kadd, kp0 = l_kp(s) + kadd;       // ref_offset (:227), kmer_pos += kmer_length (:215)
     const uint32_t snp0 = fresh ? 0u : s.rr >> 24;                    // :235
-    const uint64_t a0 = f.s01.a, a1 = f.s01.b, a2 = f.s23.a, a3 = f.s23.b, a4 = f.s45.a;   // (words fwd_issue did not load are zero there; never looked at)
+    // (words fwd_issue did not load are zero there; never looked at)
+    const uint64_t a0 = fwd_seq_first(f.s01, x0 >> 5), a1 = f.s01.b, a2 = fwd_seq_first(f.s23, (x0 >> 5) + 2), a3 = f.s23.b, a4 = f.s45.a;
     // t0 = the record of the node this step starts in. A lane that knows its slot had the block's slots loaded rotated by it
     // (fwd_issue); one that does not (it moved on to another block of its chain) finds the record — the first one that ends beyond
     // x0 - 1 — and rotates what it loaded
@@ -1070,10 +1093,8 @@ PA_HD void fwd_finish(Lane& s, const DevIndexView& ix, ReadRef rd, ColRef cols, 
     // (nx.z); in this block it is A's or B's slot; in another block of this chain the next step has to look for it
     uint32_t ncur = linkA ? ed.z : of_cur(0u, true);
     if (st == ST_FWD && !hop_chain) {                                 // goes on in this chain (fwd_finish_general)
-        const uint32_t adv = (x - 1) >> CH_STRIDE_LOG2;
-        h += adv;
-        x -= adv << CH_STRIDE_LOG2;
-        ncur = of_cur((curp + (hopB ? 1u + (wideA ? 1u : 0u) + (branchA ? 1u : 0u) : 0u)) & 3u, adv == 0);
+        const bool same = fwd_next_block(h, x, L - kp);
+        ncur = of_cur((curp + (hopB ? 1u + (wideA ? 1u : 0u) + (branchA ? 1u : 0u) : 0u)) & 3u, same);
     }
     s.h = h;
     l_set_lk(s, L, kp, st);

@@ -4,10 +4,17 @@
 // memory system moves and the mapping kernel is bound by.
 //
 //   g++ -O2 -std=c++17 -pthread tools/chain_stats.cpp rust-pseudoaligner_amd/csrc/{host_index,dbg_build,device_flatten,synth}.cpp -lz -o /tmp/chain_stats
-//   /tmp/chain_stats <k> <read_len> <ppm> <n_reads> [fasta]
+//   /tmp/chain_stats [--kernel] [--no-cache] <k> <read_len> <ppm> <n_reads> [fasta]
+//
+// The forward step has two texts (lane_steps.hpp): the GENERAL one (any number of nodes per step; traced batches, careful and list mode)
+// and the straight-line one the kernel's common lanes take (two nodes per step). The figures above are those of the general step, which
+// also yields the node trace the hop statistics need. --kernel steps the reads a second time as the kernel does (fwd_step<false>) and
+// prints both side by side: forward steps, distinct blocks, what the later steps of a walk do, and the steps that have to look for
+// their node's slot. --no-cache builds the index instead of reusing /tmp/chain_stats_*.idx (which is keyed by k only, not by the FASTA).
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <vector>
 
@@ -18,21 +25,95 @@
 
 using namespace pa;
 
+struct PassStats {
+    uint64_t n_unknown = 0, n_seek = 0, n_fwd = 0, n_left = 0, n_blocks = 0, n_nodes = 0, n_lists = 0, hop_edges = 0, hop_unique = 0, hop_unique_rem = 0;
+    // forward steps after which the lane goes on FORWARD, by where its next step reads: a chain entered over an edge, another chain
+    // through a link, the block it holds, another block of its chain (re-based) — and of the latter those whose rest of the read
+    // would have fitted the block the lane held
+    uint64_t next_edge = 0, next_link = 0, next_same = 0, next_rebased = 0, rebased_fits = 0;
+    std::map<uint32_t, uint64_t> rem_hist, fwd_hist;
+};
+
+// every read of the batch stepped to the end of its walk; KERNEL: the forward step as the kernel's common lanes take it
+template <bool KERNEL>
+static void run_pass(const DevIndexView& ix, const pa_flat_index& f, const std::vector<uint64_t>& tiles, const std::vector<uint32_t>& lens, uint32_t wpr,
+                     uint32_t read_len, PassStats& st) {
+    const uint64_t n = lens.size();
+    std::vector<uint64_t> rd(wpr + 2);
+    alignas(16) uint32_t refs[4], lens4[4], cids4[4], win4[4];
+    uint32_t wcand[2];
+    std::vector<uint32_t> spill(8 * read_len + 64), trace(8 * read_len + 64), pend(8 * read_len + 64);
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t t = i >> 6, r = i & 63;
+        for (uint32_t w = 0; w < wpr; ++w) rd[w] = tiles[(t * wpr + w) * 64 + r];
+        rd[wpr] = rd[wpr + 1] = 0;
+        Lane s;
+        lane_start(s, (uint32_t)i, lens[i], ix.k);
+        const ReadRef rr{rd.data(), 1, wpr};
+        const ColRef cr{win4, wcand, refs, lens4, cids4, spill.data(), (uint32_t)spill.size(), pend.data(), trace.data()};
+        std::vector<uint32_t> blocks;
+        uint32_t nf = 0;
+        for (;;) {
+            while (l_st(s) == ST_SEEK || l_st(s) == ST_FWD || l_st(s) == ST_LEFT) {
+                if (l_st(s) == ST_SEEK) { seek_step(s, ix, rr); ++st.n_seek; }
+                else if (l_st(s) == ST_FWD) {
+                    blocks.push_back(s.h);
+                    if (!(s.of & OF_CUR_KNOWN)) ++st.n_unknown;
+                    const uint32_t h0 = s.h;
+                    fwd_step<!KERNEL>(s, ix, rr, cr, 2);
+                    ++st.n_fwd; ++nf;
+                    if (l_st(s) == ST_FWD) {
+                        if (l_flags(s) & F_FRESH) ++st.next_edge;
+                        else if (s.h == h0) ++st.next_same;
+                        else if (s.of & OF_CUR_KNOWN) ++st.next_link;
+                        else {
+                            ++st.next_rebased;
+                            const uint32_t x_held = l_off(s) + ((s.h - h0) << CH_STRIDE_LOG2);   // the same base as a position of the block the lane held
+                            if (x_held + (l_L(s) - l_kp(s)) <= CH_WINDOW) ++st.rebased_fits;
+                        }
+                    }
+                    if (!KERNEL && l_st(s) == ST_FWD && (l_flags(s) & F_FRESH) && l_ntrace(s)) {   // left its chain over an edge
+                        ++st.hop_edges;
+                        const uint32_t from = trace[l_ntrace(s) - 1], re = f.node_exts[from] & 15u;
+                        if (!(re & (re - 1))) { ++st.hop_unique; st.hop_unique_rem += l_L(s) - (l_kp(s) + ix.k); st.rem_hist[(l_L(s) - (l_kp(s) + ix.k)) / 16]++; }
+                    }
+                }
+                else { blocks.push_back(s.ph); left_step<!KERNEL>(s, ix, rr, cr, 2); ++st.n_left; }
+            }
+            if (l_st(s) != ST_ISECT || (l_flags(s) & F_LISTS)) break;
+            if (window_todo(s) == 2) { restart_lists(s, ix.k); ++st.n_lists; continue; }
+            break;
+        }
+        st.fwd_hist[nf]++;
+        st.n_nodes += l_ntrace(s);
+        std::sort(blocks.begin(), blocks.end());
+        st.n_blocks += std::unique(blocks.begin(), blocks.end()) - blocks.begin();
+    }
+}
+
 int main(int argc, char** argv) {
-    const uint32_t k = argc > 1 ? atoi(argv[1]) : 24, read_len = argc > 2 ? atoi(argv[2]) : 150, ppm = argc > 3 ? atoi(argv[3]) : 0;
-    const uint64_t n = argc > 4 ? atoll(argv[4]) : 100000;
+    bool kernel = false, no_cache = false;
+    std::vector<char*> pos;
+    for (int i = 1; i < argc; ++i) {
+        if (!strcmp(argv[i], "--kernel")) kernel = true;
+        else if (!strcmp(argv[i], "--no-cache")) no_cache = true;
+        else pos.push_back(argv[i]);
+    }
+    const uint32_t k = pos.size() > 0 ? atoi(pos[0]) : 24, read_len = pos.size() > 1 ? atoi(pos[1]) : 150, ppm = pos.size() > 2 ? atoi(pos[2]) : 0;
+    const uint64_t n = pos.size() > 3 ? atoll(pos[3]) : 100000;
+    const char* fasta = pos.size() > 4 ? pos[4] : nullptr;
     pa_txome* tx = nullptr;
-    if (argc > 5) { if (pa_txome_from_fasta(argv[5], &tx)) { fprintf(stderr, "%s\n", pa_last_error()); return 1; } }
+    if (fasta) { if (pa_txome_from_fasta(fasta, &tx)) { fprintf(stderr, "%s\n", pa_last_error()); return 1; } }
     else if (pa_txome_synthesize(58000, 203000, 7, &tx)) { fprintf(stderr, "%s\n", pa_last_error()); return 1; }
     const uint64_t *packed, *tx_start;
     uint32_t num_tx;
     pa_txome_view(tx, &packed, &tx_start, &num_tx);
     char cache[256];
-    snprintf(cache, sizeof cache, "/tmp/chain_stats_%s_k%u.idx", argc > 5 ? "fasta" : "synth", k);
+    snprintf(cache, sizeof cache, "/tmp/chain_stats_%s_k%u.idx", fasta ? "fasta" : "synth", k);
     pa_host_index* h = nullptr;
-    if (pa_host_index_load(cache, &h) != PA_OK) {
+    if (no_cache || pa_host_index_load(cache, &h) != PA_OK) {
         if (pa_host_index_build_packed(packed, tx_start, num_tx, k, 8, &h)) { fprintf(stderr, "%s\n", pa_last_error()); return 1; }
-        pa_host_index_save(h, cache);
+        if (!no_cache) pa_host_index_save(h, cache);
     }
     pa_flat_index f;
     pa_host_index_view(h, &f);
@@ -42,7 +123,6 @@ int main(int argc, char** argv) {
     uint64_t mergeable = 0;
     {
         // nodes whose only right extension leads to a node whose only left extension leads back (what a chain may merge)
-        std::vector<uint32_t> cnt(4, 0);
         for (uint32_t i = 0; i < f.num_nodes; ++i) {
             const uint32_t re = f.node_exts[i] & 15u;
             if (re && !(re & (re - 1))) ++mergeable;   // upper bound (the successor's left side is not checked here)
@@ -67,55 +147,37 @@ int main(int argc, char** argv) {
     std::vector<uint64_t> tiles(((n + 63) / 64) * wpr * 64);
     std::vector<uint32_t> lens(n);
     pa_simulate_reads_host(tx, read_len, k == 31 ? 4 : 2, ppm, 0, n, wpr, tiles.data(), lens.data());
-    std::vector<uint64_t> rd(wpr + 2);
-    alignas(16) uint32_t refs[4], lens4[4], cids4[4], win4[4];
-    uint32_t wcand[2];
-    std::vector<uint32_t> spill(8 * read_len + 64), trace(8 * read_len + 64), pend(8 * read_len + 64);
-    uint64_t n_unknown = 0, n_seek = 0, n_fwd = 0, n_left = 0, n_blocks = 0, n_nodes = 0, n_lists = 0, hop_edges = 0, hop_unique = 0, hop_unique_rem = 0;
-    std::map<uint32_t, uint64_t> rem_hist;
-    std::map<uint32_t, uint64_t> fwd_hist;
-    for (uint64_t i = 0; i < n; ++i) {
-        const uint64_t t = i >> 6, r = i & 63;
-        for (uint32_t w = 0; w < wpr; ++w) rd[w] = tiles[(t * wpr + w) * 64 + r];
-        rd[wpr] = rd[wpr + 1] = 0;
-        Lane s;
-        lane_start(s, (uint32_t)i, lens[i], ix.k);
-        const ReadRef rr{rd.data(), 1, wpr};
-        const ColRef cr{win4, wcand, refs, lens4, cids4, spill.data(), (uint32_t)spill.size(), pend.data(), trace.data()};
-        std::vector<uint32_t> blocks;
-        uint32_t nf = 0;
-        for (;;) {
-            while (l_st(s) == ST_SEEK || l_st(s) == ST_FWD || l_st(s) == ST_LEFT) {
-                if (l_st(s) == ST_SEEK) { seek_step(s, ix, rr); ++n_seek; }
-                else if (l_st(s) == ST_FWD) {
-                    blocks.push_back(s.h);
-                    if (!(s.of & OF_CUR_KNOWN)) ++n_unknown;
-                    fwd_step<true>(s, ix, rr, cr, 2);
-                    ++n_fwd; ++nf;
-                    if (l_st(s) == ST_FWD && (l_flags(s) & F_FRESH) && l_ntrace(s)) {   // left its chain over an edge
-                        ++hop_edges;
-                        const uint32_t from = trace[l_ntrace(s) - 1], re = f.node_exts[from] & 15u;
-                        if (!(re & (re - 1))) { ++hop_unique; hop_unique_rem += l_L(s) - (l_kp(s) + ix.k); rem_hist[(l_L(s) - (l_kp(s) + ix.k)) / 16]++; }
-                    }
-                }
-                else { blocks.push_back(s.ph); left_step<true>(s, ix, rr, cr, 2); ++n_left; }
-            }
-            if (l_st(s) != ST_ISECT || (l_flags(s) & F_LISTS)) break;
-            if (window_todo(s) == 2) { restart_lists(s, ix.k); ++n_lists; continue; }
-            break;
-        }
-        fwd_hist[nf]++;
-        n_nodes += l_ntrace(s);
-        std::sort(blocks.begin(), blocks.end());
-        n_blocks += std::unique(blocks.begin(), blocks.end()) - blocks.begin();
-    }
-    printf("per read: %.3f probes, %.3f forward steps, %.3f left steps, %.3f distinct chain blocks, %.3f nodes pushed, %.4f list-mode restarts\n", (double)n_seek / n,
-           (double)n_fwd / n, (double)n_left / n, (double)n_blocks / n, (double)n_nodes / n, (double)n_lists / n);
-    printf("per read: %.3f hops over an edge, %.3f of them from a node with ONE right extension (mean read bases left then: %.1f)\n", (double)hop_edges / n,
-           (double)hop_unique / n, hop_unique ? (double)hop_unique_rem / hop_unique : 0.0);
-    printf("forward steps that had to look for their node's slot: %.4f per read\n", (double)n_unknown / n);
+    PassStats g;
+    run_pass<false>(ix, f, tiles, lens, wpr, read_len, g);
+    printf("per read: %.3f probes, %.3f forward steps, %.3f left steps, %.3f distinct chain blocks, %.3f nodes pushed, %.4f list-mode restarts\n", (double)g.n_seek / n,
+           (double)g.n_fwd / n, (double)g.n_left / n, (double)g.n_blocks / n, (double)g.n_nodes / n, (double)g.n_lists / n);
+    printf("per read: %.3f hops over an edge, %.3f of them from a node with ONE right extension (mean read bases left then: %.1f)\n", (double)g.hop_edges / n,
+           (double)g.hop_unique / n, g.hop_unique ? (double)g.hop_unique_rem / g.hop_unique : 0.0);
+    printf("forward steps that had to look for their node's slot: %.4f per read\n", (double)g.n_unknown / n);
     printf("forward steps per read:");
-    for (auto& kv : fwd_hist) printf(" %u:%.3f", kv.first, (double)kv.second / n);
+    for (auto& kv : g.fwd_hist) printf(" %u:%.3f", kv.first, (double)kv.second / n);
     printf("\n");
+    if (kernel) {
+        PassStats q;
+        run_pass<true>(ix, f, tiles, lens, wpr, read_len, q);
+        const double d = (double)n;
+        printf("\nper read                                                      general step   as the kernel steps\n");
+#define ROW(label, field) printf("%-60s %13.4f %21.4f\n", label, (double)g.field / d, (double)q.field / d);
+        ROW("forward steps", n_fwd)
+        ROW("distinct 128-byte chain blocks fetched", n_blocks)
+        ROW("later steps that hop over an edge", next_edge)
+        ROW("later steps that follow a link", next_link)
+        ROW("later steps in the same block", next_same)
+        ROW("later steps RE-BASED to another block of the same chain", next_rebased)
+        ROW("... of which the rest of the read fits the block held", rebased_fits)
+        ROW("forward steps that have to LOOK FOR their node's slot", n_unknown)
+#undef ROW
+        // one line for scripts and tests: exact counts
+        printf("kernel_step_counts reads=%llu fwd=%llu blocks=%llu unknown=%llu rebased=%llu rebased_fits=%llu general_fwd=%llu general_blocks=%llu general_unknown=%llu\n",
+               (unsigned long long)n, (unsigned long long)q.n_fwd, (unsigned long long)q.n_blocks, (unsigned long long)q.n_unknown, (unsigned long long)q.next_rebased,
+               (unsigned long long)q.rebased_fits, (unsigned long long)g.n_fwd, (unsigned long long)g.n_blocks, (unsigned long long)g.n_unknown);
+    }
+    pa_host_index_destroy(h);
+    pa_txome_destroy(tx);
     return 0;
 }
