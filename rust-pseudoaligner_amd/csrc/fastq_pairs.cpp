@@ -5,7 +5,7 @@
 // b - 1 is on the GPU. The streams they launch on are IndexStreams, a mapping that ran out of arena goes through map_finish_regrow
 // (hip_buffer.hpp).
 // PairReader has two forms. In the DEVICE form the host does not look at the text: each file is a WindowFeed (window_feed.hpp: raw or compressed
-// windows to HBM, records found by fastq_scan.hip), and the ids are compared and R2 / the R1 prefix gathered on the GPU (pair_scan.hip), straight into
+// windows to HBM, records found by fastq_scan.hip — the window steps of text_window.hpp, which pa_process_reads runs too), and the ids are compared and R2 / the R1 prefix gathered on the GPU (pair_scan.hip), straight into
 // the buffers that encode, counter and BUS stage read. It is the default when BOTH files are BGZF (the host form inflates them whole through one zlib
 // stream each). With a plain text file on either side it is taken only on request, PA_PAIRS_DEVICE_PLAIN=1: its rate on plain text has not been
 // measured against the host form's yet. An ordinary-gzip file on either side, or PA_PAIRS_HOST_SCAN=1, keeps the HOST form for the
@@ -264,9 +264,7 @@ struct PairReader {
             return PA_OK;
         }
         device = true;
-        uint64_t window = 64ull << 20;
-        if ((v = getenv("PA_INGEST_WINDOW"))) { const long long x = atoll(v); if (x >= 1) window = (uint64_t)x; }
-        window = std::min<uint64_t>(std::min<uint64_t>(window, batch_pairs * 256), 1ull << 31);
+        const uint64_t window = window_from_env(batch_pairs);   // (PA_INGEST_BATCH as the paired drivers read it: any value >= 1)
         PA_HIP_TRY(hipStreamCreateWithFlags(&gs, hipStreamNonBlocking));
         if ((rc = d_ctl.alloc(PA_PAIRS_CTL_WORDS)) != PA_OK || (rc = h_ctl.alloc(PA_PAIRS_CTL_WORDS)) != PA_OK) return rc;
         for (int i = 0; i < 2; ++i) {
@@ -281,7 +279,7 @@ struct PairReader {
             uint64_t* const is = last_pairs_input();
             for (int i = 0; i < 2; ++i) {
                 if (!feed[i]) continue;
-                const FeedStats fs = feed[i]->stats();
+                const InputStats fs = feed[i]->stats();
                 memcpy(is + i * PA_INGEST_INPUT_STATS, &fs, sizeof fs);
                 feed[i].reset();
             }

@@ -2,24 +2,19 @@
 // read out, in INPUT order, with the flag rule of :455 as it is (true iff coverage >= 32 and the class is EMPTY). The pipeline over windows of
 // raw text is described where it starts, below; the text itself is fastq_text.cpp's.
 #include <hip/hip_runtime.h>
-#include <emmintrin.h>
-#include <sys/mman.h>
-#include <unistd.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <string>
 #include <cerrno>
 #include <condition_variable>
 #include <cstdio>
-#include <chrono>
 #include <cstdlib>
 #include <deque>
 #include <mutex>
 #include <thread>
 
-#include "fastq_text.hpp"
+#include "text_window.hpp"
 
 using namespace pa;
 using namespace pa::ingest;
@@ -110,7 +105,7 @@ std::string rust_f32(float v) {
 
 // ---- process_reads over WINDOWS of raw text ----
 // The host does not look at the text: worker threads copy a window of the file into pinned memory (out of the file's mapping, page tables
-// filled and dropped piece by piece: TextPipe::read_piece), the window goes to HBM as it is on a copy stream, the GPU finds its records (fastq_scan.hip) and the encode /
+// filled and dropped piece by piece: read_piece), the window goes to HBM as it is on a copy stream, the GPU finds its records (fastq_scan.hip) and the encode /
 // map / render kernels read sequences and ids where they lie. A lane has FOUR streams: copy (text in), scan (a window's records: waits for its
 // text and the scan before, not for the kernels of the window before), the kernels' stream, and back (the tuples' 14 MB per window to the host):
 // on one stream the chain scan | encode | map | render | copy back + two host round trips was as long as a window's copy, and every hiccup a gap on the link. A window ends where the file offset says, not where a record does: the
@@ -121,14 +116,17 @@ std::string rust_f32(float v) {
 // blank lines, an empty last record) and text that is not in four-line shape (wrapped records: rewritten first).
 // process_reads_impl names the steps in order: open_lanes | gpu_windows (start_read, send_window, resolve, reread_from, enqueue_scan per window) | host_tail
 // (host_batch per batch) | finish.
+// What those steps do to a window — the pieces into pinned memory, the copies and the inflate, head and scan, the wait with its regrow, the window-size rule,
+// the host-scanned batch — is text_window.hpp's (window_fill, window_send, window_enqueue_scan, window_scan_wait, window_rule, host_tail_cut, window_fill_host),
+// shared with the paired drivers' WindowFeed. TextPipe is the scheduler: lanes and slots, reads that run behind the caller's back (window_fill without wait:
+// the link is the bound and the host's read has no margin), the writer, the copy timer, the lane-serial wait, and the kernels of a window.
 constexpr int LANE_SLOTS = 4;            // windows of a lane in flight: read | scan | map + render | write
 constexpr uint32_t FLAG_BUCKETS = PA_RENDER_FLAG_BUCKETS;
-constexpr uint64_t PIECE = 2ull << 20;   // bytes of a window that one task of the pool copies
 
 struct Options {   // every switch the environment has for this driver, read once at the top of a call
     bool bgzf;              // PA_INGEST_BGZF=0 (diagnosis and A/B): a BGZF file is inflated on the host like any other .gz
-    uint64_t batch_reads = DEFAULT_BATCH_READS;   // PA_INGEST_BATCH
-    uint64_t window = 64ull << 20;   // bytes of a window the GPU scans (64 MiB: 128 MiB leaves more of the first read and the last kernels unoverlapped, 16 MiB costs launches) (PA_INGEST_WINDOW; never more than 256 bytes per read of a batch: the tests' small batches give small windows)
+    uint64_t batch_reads = DEFAULT_BATCH_READS;   // PA_INGEST_BATCH, rounded down to whole tiles of 64 reads; values below 64 are ignored
+    uint64_t window;        // bytes of a window the GPU scans (window_from_env: PA_INGEST_WINDOW, clamped by the batch)
     bool verbose;           // PA_VERBOSE
     bool lane_serial;       // PA_LANE_SERIAL (knobs builds: A/B of the one-window-at-a-time rule for lanes that share a GPU)
     bool host_only;         // PA_INGEST_HOST_SCAN (diagnosis: every window through the host's scan)
@@ -137,20 +135,13 @@ struct Options {   // every switch the environment has for this driver, read onc
         const char* v = getenv("PA_INGEST_BGZF");
         bgzf = !(v && *v && atoi(v) == 0);
         if ((v = getenv("PA_INGEST_BATCH"))) { const long long x = atoll(v); if (x >= 64) batch_reads = (uint64_t)x / 64 * 64; }
-        if ((v = getenv("PA_INGEST_WINDOW"))) { const long long x = atoll(v); if (x >= 1) window = (uint64_t)x; }
-        window = std::min<uint64_t>(std::min<uint64_t>(window, batch_reads * 256), 1ull << 31);
+        window = window_from_env(batch_reads);
         verbose = getenv("PA_VERBOSE") != nullptr;
         lane_serial = knob_int("PA_LANE_SERIAL", 1) != 0;
         host_only = getenv("PA_INGEST_HOST_SCAN") != nullptr;
         use_pread = knob_int("PA_INGEST_PREAD", 0) != 0;
     }
-    uint64_t window_of(const FastqText& t) const { return t.bgzf ? std::max<uint64_t>(window, PA_BGZF_MAX_ISIZE) : window; }   // a BGZF window's own text is a run of whole members
 };
-
-struct InputStats {   // pa_process_reads_input_stats, in the ABI's order: filled as the run goes, written once (TextPipe::finish)
-    uint64_t text_kind = 0, members_total = 0, members_gpu = 0, members_host = 0, bytes_h2d = 0, text_bytes_gpu = 0;
-};
-static_assert(sizeof(InputStats) == sizeof(uint64_t) * PA_INGEST_INPUT_STATS, "one field per entry of the ABI's array");
 
 uint64_t* last_input_stats() {   // pa_process_reads_input_stats: of this thread's last call
     static thread_local uint64_t st[PA_INGEST_INPUT_STATS] = {0};
@@ -194,14 +185,9 @@ struct Win {
     bool launched = false;      // its kernels are on the lane's stream
 };
 
-struct Pre {   // a window whose text is being read into its slot, or has been
-    WindowPlan plan;
-    uint64_t id = 0;
-    BatchCtx* c = nullptr;
+struct LanePre : Pre {   // a window whose text is being read into its slot, or has been: on this lane
     Lane* l = nullptr;
 };
-
-constexpr int WIN_ODD = 1, WIN_EMPTY = 2;   // what resolve() answers besides a pa_status
 
 struct TextPipe {
     const char* fastq_path;
@@ -213,20 +199,19 @@ struct TextPipe {
     const double t_enter, t_begin;
     std::deque<Win> wins;       // launched or about to be, in order; the front is written first
     uint64_t next_id = 0, launched_reads = 0, reported = 0, flagged = 0, next_report = 1000000;
-    double t_scan = 0, t_read = 0, t_wait = 0, t_launch = 0, t_text = 0, t_push = 0;
-    uint64_t gpu_wins = 0, host_wins = 0, rescans = 0;   // windows whose records the GPU found, batches of the host's scan, scans run again
-    InputStats stats{text.bgzf ? 2u : !text.inflated.empty() ? 1u : 0u, text.members.size()};
+    double st[6] = {0, 0, 0, 0, 0, 0};   // the call's stage seconds, by ST_*: the window steps add to the first four
+    WindowCtx x{fastq_path, text, pool, st, opt.use_pread};   // the file as the window steps see it: input statistics, rescans, the read-error flag
+    uint64_t gpu_wins = 0, host_wins = 0;   // windows whose records the GPU found, batches of the host's scan
     CopyTimer timer{opt.verbose};
-    uint64_t W = opt.window_of(text);
-    const uint64_t KEEP = std::max<uint64_t>(4096, std::min<uint64_t>(W / 4, 1ull << 20));   // the end of the text is the host's: its rules for the last record live there
+    uint64_t W = window_of(text, opt.window);
+    const uint64_t KEEP = keep_of(W);
     uint64_t rec_start = 0;     // text offset of the first record no window has taken yet (known once the window before has been scanned)
     uint64_t read_to = 0;       // text read so far
     bool gpu_mode = false;      // windows are still handed to the GPU's scan
     bool have_pending = false;
     Win pending;                // the window whose records the GPU is finding
-    Pre cur, nxt;               // the window being sent and scanned; the one whose text is being read behind it
+    LanePre cur, nxt;           // the window being sent and scanned; the one whose text is being read behind it
 
-    static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
     int L() const { return (int)lanes.size(); }
     Lane& lane_of(uint64_t id) { return lanes[(size_t)(id % (uint64_t)L())]; }
     int slot_of(uint64_t id) const { return (int)((id / (uint64_t)L()) % LANE_SLOTS); }
@@ -252,89 +237,6 @@ struct TextPipe {
         return PA_OK;
     }
 
-    // [0, len) dealt in pieces of PIECE bytes: fn(a, b) copies bytes [a, b). One piece is copied by the caller, here. More go to the pool: all of them done on return
-    // (wait), or left with the pool's workers (the answer is true: read_end waits for them)
-    template <class F>
-    bool deal_pieces(uint64_t len, bool wait, F fn) {
-        if (len == 0) return false;
-        const int ntask = (int)std::min<uint64_t>((len + PIECE - 1) / PIECE, 1u << 20);
-        auto piece = [fn, len, ntask](int t) { fn(len * (uint64_t)t / (uint64_t)ntask, len * (uint64_t)(t + 1) / (uint64_t)ntask); };
-        if (ntask == 1) { piece(0); return false; }
-        if (wait) { pool.run(ntask, piece); return false; }
-        pool.begin(ntask, piece);
-        return true;
-    }
-
-    // bytes [off, off + len) of the text into dst (pinned): out of the file's mapping (read_piece), memcpy for text in memory (inflated gzip).
-    // read_begin hands the pieces to the worker pool and returns; read_end waits for them (small reads are done at once by the caller)
-    std::atomic<int> read_bad{0};
-    bool read_async = false;
-    // bytes of the mapping into a pinned window with streaming stores: the window is read next by the copy engine, never by this CPU, so no line of it
-    // has to be fetched for ownership or kept in a cache
-    static void copy_streaming(uint8_t* d, const uint8_t* s, size_t n) {
-        size_t head = (64 - ((uintptr_t)d & 63)) & 63;
-        if (head > n) head = n;
-        memcpy(d, s, head);
-        d += head; s += head; n -= head;
-        const size_t body = n & ~(size_t)63;
-        for (size_t i = 0; i < body; i += 64) {
-            const __m128i v0 = _mm_loadu_si128((const __m128i*)(s + i)), v1 = _mm_loadu_si128((const __m128i*)(s + i + 16));
-            const __m128i v2 = _mm_loadu_si128((const __m128i*)(s + i + 32)), v3 = _mm_loadu_si128((const __m128i*)(s + i + 48));
-            _mm_stream_si128((__m128i*)(d + i), v0); _mm_stream_si128((__m128i*)(d + i + 16), v1);
-            _mm_stream_si128((__m128i*)(d + i + 32), v2); _mm_stream_si128((__m128i*)(d + i + 48), v3);
-        }
-        _mm_sfence();
-        memcpy(d + body, s + body, n - body);
-    }
-    void read_piece(uint64_t a, uint64_t b, uint8_t* dst) {   // text bytes [a, b) to dst
-        if (text.mapped && text.data == text.map_base && !opt.use_pread) {
-            // A file: out of its MAPPING. pread copies at 65 - 75 GB/s on 16 threads of the target host (one copy_to_user per page, the file's page-cache
-            // lock) — 1.2 x the link, no margin — the same bytes out of the mapping at 127 GB/s INCLUDING the page tables of the piece, which are
-            // filled in one call before the copy (MADV_POPULATE_READ, Linux 5.14; without it the copy faults them in: 115 GB/s) and dropped behind it
-            // (a 100 GB file would otherwise keep 25 M entries mapped until the call ends)
-            constexpr uint64_t PAGE = 4096;
-            const bool big = b - a >= (256u << 10);
-            if (big) {
-                const uint64_t pa = a & ~(PAGE - 1), pb = std::min<uint64_t>((b + PAGE - 1) & ~(PAGE - 1), text.map_size);
-#ifdef MADV_POPULATE_READ
-                (void)madvise((void*)(text.map_base + pa), (size_t)(pb - pa), MADV_POPULATE_READ);
-#else
-                (void)madvise((void*)(text.map_base + pa), (size_t)(pb - pa), 22);
-#endif
-            }
-            copy_streaming(dst, (const uint8_t*)text.data + a, (size_t)(b - a));
-            if (big) {
-                const uint64_t qa = (a + PAGE - 1) & ~(PAGE - 1), qb = b & ~(PAGE - 1);
-                if (qb > qa) (void)madvise((void*)(text.map_base + qa), (size_t)(qb - qa), MADV_DONTNEED);
-            }
-        } else if (text.mapped && text.fd >= 0 && text.data == text.map_base) {
-            uint64_t p = a;
-            while (p < b) {
-                const ssize_t got = pread(text.fd, dst + (p - a), (size_t)(b - p), (off_t)p);
-                if (got < 0 && errno == EINTR) continue;
-                if (got <= 0) { read_bad.store(1); return; }
-                p += (uint64_t)got;
-            }
-        } else memcpy(dst, text.data + a, (size_t)(b - a));
-    }
-    void read_begin(uint64_t off, uint64_t len, uint8_t* dst) {
-        read_async = deal_pieces(len, false, [this, off, dst](uint64_t a, uint64_t b) { read_piece(off + a, off + b, dst + a); });
-    }
-    int read_end() {
-        if (read_async) { pool.end(); read_async = false; }
-        return read_bad.exchange(0) ? fail(PA_ERR_IO, "%s: read failed: %s", fastq_path, strerror(errno)) : PA_OK;
-    }
-    // a BGZF window: bytes [off, off + len) of the COMPRESSED file into dst (pinned), by the pool, with streaming stores
-    void read_comp_begin(uint64_t off, uint64_t len, uint8_t* dst) {
-        const uint8_t* src = (const uint8_t*)text.map_base + off;
-        read_async = deal_pieces(len, false, [src, dst](uint64_t a, uint64_t b) { copy_streaming(dst + a, src + a, (size_t)(b - a)); });
-    }
-    int read_small(uint64_t off, uint64_t len, uint8_t* dst) {   // by the caller itself, whatever the pool is doing (a window's head: <= 1 MiB)
-        if (text.bgzf) return len ? bgzf_read_host(text, fastq_path, off, len, dst) : PA_OK;   // (the members that hold the unfinished record: inflated by this thread)
-        if (len) read_piece(off, off + len, dst);
-        return read_bad.load() ? fail(PA_ERR_IO, "%s: read failed: %s", fastq_path, strerror(errno)) : PA_OK;
-    }
-
     // the kernels of the window launched before on this lane's stream: waited for (they share the stream's launch context inside the index)
     int finish_lane(Lane& l) {
         if (l.unfinished < 0) return PA_OK;
@@ -343,7 +245,7 @@ struct TextPipe {
                 const double t0 = now();
                 int e = use(l);
                 if (e == PA_OK) e = batch_finish(l.idx, ctx_of(w), l.cache->stream);
-                t_wait += now() - t0;
+                st[ST_WAIT] += now() - t0;
                 l.unfinished = -1;
                 return e;
             }
@@ -367,7 +269,7 @@ struct TextPipe {
             const double t0 = now();
             int e = use(l);
             if (e == PA_OK) e = batch_text_wait(c);
-            t_text += now() - t0;
+            st[ST_TEXT] += now() - t0;
             if (e != PA_OK) return e;
             uint64_t cum = 0, bucket = 0;
             while (next_report <= w.first_read + c.n) {   // :497-503: the counts of exactly the first 10^6 m reads
@@ -412,7 +314,7 @@ struct TextPipe {
         if ((e = retire_finished(0)) != PA_OK) return e;
         double t0 = now();
         if (l.text_job[w.slot]) { writer.wait(l.text_job[w.slot]); l.text_job[w.slot] = 0; }   // (the launch ends with the speculative copy of the tuples into the slot's pinned text)
-        t_push += now() - t0; t0 = now();
+        st[ST_PUSH] += now() - t0; t0 = now();
         if ((e = use(l)) != PA_OK) return e;
         c.in_place = true;
         w.first_read = launched_reads;
@@ -422,94 +324,52 @@ struct TextPipe {
         l.unfinished = (int64_t)w.id;
         w.launched = true;
         launched_reads += c.n;
-        t_launch += now() - t0;
+        st[ST_LAUNCH] += now() - t0;
         return PA_OK;
     }
 
     // the next window (plan_window: none when the text in front of the host's part has been read) gets its slot, and the pool's workers start to copy its bytes
-    // into the slot's pinned memory: the text itself, or a BGZF window's compressed members with their rows of the member table
-    int start_read(Pre& p, uint64_t id) {
+    // into the slot's pinned memory (window_fill without wait: the read goes on behind this thread's back until send_window asks for it)
+    int start_read(LanePre& p, uint64_t id) {
         p.plan = gpu_mode ? plan_window(text, read_to, W, KEEP) : WindowPlan();
-        const WindowPlan& plan = p.plan;
-        if (!plan.active) return PA_OK;
+        if (!p.plan.active) return PA_OK;
         p.id = id;
         int e = acquire(id, &p.c);
         if (e != PA_OK) return e;
         p.l = &lane_of(id);
-        if ((e = window_ensure_raw(*p.c, WINDOW_HEAD_ROOM + plan.text_len)) != PA_OK) return e;
-        if (plan.n_members) {
-            if ((e = window_ensure_comp(*p.c, plan.comp_len, plan.n_members)) != PA_OK) return e;
-            for (uint64_t i = 0; i < plan.n_members; ++i) {
-                pa_bgzf_member r = text.members[plan.first_member + i];
-                r.in_off -= plan.comp_from;
-                p.c->h_mrows.get()[i] = r;
-            }
-            read_comp_begin(plan.comp_from, plan.comp_len, p.c->h_comp.get());
-        } else read_begin(plan.text_from, plan.text_len, p.c->h_raw.get() + WINDOW_HEAD_ROOM);
-        read_to = plan.text_from + plan.text_len;
+        if ((e = window_fill(x, p.plan, *p.c, false)) != PA_OK) return e;
+        read_to = p.plan.text_from + p.plan.text_len;
         return PA_OK;
     }
 
-    // the window's bytes, now in pinned memory, go to the GPU on the lane's copy stream; a BGZF window's members are inflated there, behind their copy,
-    // and their statuses come back ahead of ev_h2d
-    int send_window(const Pre& p) {
-        const WindowPlan& plan = p.plan;
-        BatchCtx& c = *p.c;
+    // the window's bytes, now in pinned memory, go to the GPU on the lane's copy stream (window_send), timed for PA_VERBOSE
+    int send_window(const LanePre& p) {
         Lane& l = *p.l;
         const hipStream_t copy = l.cache->copy_stream;
-        const double t0 = now();
-        int e = read_end();
+        int e = window_fill_end(x);
         if (e != PA_OK) return e;
-        t_read += now() - t0;
         if ((e = use(l)) != PA_OK) return e;
-        timer.begin(p.id, copy, plan.n_members ? plan.comp_len : plan.text_len);
+        timer.begin(p.id, copy, p.plan.n_members ? p.plan.comp_len : p.plan.text_len);
         // lanes that share a GPU (a handle listed twice) send their windows one at a time: with two copies of one direction queued at once the runtime
         // runs one of them as a blit kernel, at a fraction of the DMA engine's rate (host_batch.cpp has the measurement)
         for (size_t o = 0; o < lanes.size() && opt.lane_serial; ++o)
             if (&lanes[o] != &l && lanes[o].device == l.device && lanes[o].last_h2d) PA_HIP_TRY(hipStreamWaitEvent(copy, lanes[o].last_h2d, 0));
-        c.n_members = plan.n_members;
-        if (plan.n_members) {   // BGZF: the compressed members cross the link, the text first exists in HBM
-            PA_HIP_TRY(hipMemcpyAsync(c.d_comp.get(), c.h_comp.get(), plan.comp_len, hipMemcpyHostToDevice, copy));
-            PA_HIP_TRY(hipMemcpyAsync(c.d_mrows.get(), c.h_mrows.get(), plan.n_members * sizeof(pa_bgzf_member), hipMemcpyHostToDevice, copy));
-            if ((e = bgzf_inflate_launch(c.d_comp.get(), plan.comp_len, c.d_mrows.get(), plan.n_members, c.d_raw.get() + WINDOW_HEAD_ROOM, plan.text_len, c.d_mstat.get(), copy)) != PA_OK) return e;
-            PA_HIP_TRY(hipMemcpyAsync(c.h_mstat.get(), c.d_mstat.get(), plan.n_members * sizeof(uint32_t), hipMemcpyDeviceToHost, copy));
-            stats.members_gpu += plan.n_members;
-            stats.bytes_h2d += plan.comp_len + plan.n_members * sizeof(pa_bgzf_member);
-            stats.text_bytes_gpu += plan.text_len;
-        } else {
-            PA_HIP_TRY(hipMemcpyAsync(c.d_raw.get() + WINDOW_HEAD_ROOM, c.h_raw.get() + WINDOW_HEAD_ROOM, plan.text_len, hipMemcpyHostToDevice, copy));
-            stats.bytes_h2d += plan.text_len;
-        }
-        PA_HIP_TRY(hipEventRecord(c.ev_h2d, copy));
-        l.last_h2d = c.ev_h2d;
+        if ((e = window_send(x, p.plan, *p.c, copy)) != PA_OK) return e;
+        l.last_h2d = p.c->ev_h2d;
         timer.end(p.id, copy);
         return PA_OK;
     }
 
-    // the pending window's scan: waited for; its records are launched, the next window's first record is known
+    // the pending window's scan: waited for (window_scan_wait); its records are launched, the next window's first record is known
     int resolve() {
         Lane& l = lanes[(size_t)pending.lane];
         BatchCtx& c = l.cache->ctx[pending.slot];
-        const FqInfo& info = *c.h_info.get();
         have_pending = false;
         int e = use(l);
         if (e != PA_OK) return e;
-        for (int attempt = 0;; ++attempt) {
-            const double t0 = now();
-            PA_HIP_TRY(hipEventSynchronize(c.ev_info));
-            t_wait += now() - t0;
-            if (!info.overflow) break;
-            if (attempt == 2) return fail(PA_ERR_INTERNAL, "FASTQ scan: line table too small after regrowing");
-            ++rescans;   // more lines than guessed (short reads): grow the line table, fill it again from the counts already there
-            if ((e = window_ensure_scan(c, info.lines)) != PA_OK) return e;
-            if ((e = window_scan_enqueue(c, true, l.cache->scan_stream)) != PA_OK) return e;
-        }
-        for (uint64_t i = 0; i < c.n_members; ++i)   // (they came back on the copy stream ahead of ev_h2d, which the scan waited for)
-            if (c.h_mstat.get()[i] != PA_INFLATE_OK)
-                return fail(PA_ERR_FORMAT, "%s: corrupt gzip stream: member at byte %llu: %s", fastq_path, (unsigned long long)c.h_mrows.get()[i].file_off,
-                            pa_inflate_status_name(c.h_mstat.get()[i]));
-        if (info.odd) return WIN_ODD;
-        if (info.n == 0) return WIN_EMPTY;
+        if ((e = window_scan_wait(x, c, l.cache->scan_stream)) != WIN_OK) return e;
+        const FqInfo& info = *c.h_info.get();
+        // (every read of this driver is encoded whole. The feed has no such line: its consumers refuse a long read where they encode it — WindowFeed::resolve)
         if (info.max_seq > PA_MAX_READ_LEN) return fail(PA_ERR_UNSUPPORTED, "read longer than %u bases", PA_MAX_READ_LEN);
         c.n = info.n;
         c.wpr = pa_words_per_read(info.max_seq ? info.max_seq : 1);
@@ -519,40 +379,23 @@ struct TextPipe {
         return launch(wins.back());
     }
 
-    // a window is dropped: its text (and what was being read behind it) is read again, from the first record not yet taken
-    int reread_from(uint64_t from) {
-        if (nxt.plan.active) { (void)read_end(); nxt.plan.active = false; }
+    // a window is dropped: its text (and what was being read behind it) is read again, from the first record not yet taken — unless the host's scan takes over there
+    int reread_from(uint64_t from, bool host) {
+        if (nxt.plan.active) { (void)window_fill_end(x); nxt.plan.active = false; }
         (void)hipStreamSynchronize(cur.l->cache->copy_stream);
         read_to = from;
-        if (W > (1ull << 31)) gpu_mode = false;   // (a record of gigabytes: the host's scan says what it is)
+        if (host) gpu_mode = false;
         return start_read(cur, next_id);
     }
 
-    // the window's records are to be found: the unfinished record of the window before goes in front of the window's own text as its head (on the scan stream,
-    // which then waits for the text itself: ev_h2d only), the scan follows and the window is the pending one
-    int enqueue_scan(const Pre& p, uint64_t head, uint64_t skip) {
-        BatchCtx& c = *p.c;
-        const hipStream_t scan = p.l->cache->scan_stream;
-        double t0 = now();
-        if (head) {
-            uint8_t* const h = c.h_raw.get() + WINDOW_HEAD_ROOM - head;
-            const int e = read_small(rec_start, head, h);
-            if (e != PA_OK) return e;
-            PA_HIP_TRY(hipMemcpyAsync(c.d_raw.get() + WINDOW_HEAD_ROOM - head, h, head, hipMemcpyHostToDevice, scan));
-            stats.bytes_h2d += head;
-        }
-        t_read += now() - t0; t0 = now();
-        c.raw_begin = WINDOW_HEAD_ROOM - head + skip;
-        c.raw_end = WINDOW_HEAD_ROOM + p.plan.text_len;
-        int e = window_ensure_scan(c, 0);
-        if (e != PA_OK) return e;
-        PA_HIP_TRY(hipStreamWaitEvent(scan, c.ev_h2d, 0));
-        if ((e = window_scan_enqueue(c, false, scan)) != PA_OK) return e;
-        t_launch += now() - t0;
+    // the window's records are to be found (window_enqueue_scan: head, then the scan behind ev_h2d), and the window is the pending one. WIN_HEAD: it is not
+    int enqueue_scan(const LanePre& p) {
+        const int r = window_enqueue_scan(x, p.plan, *p.c, rec_start, p.l->cache->scan_stream);
+        if (r != WIN_OK) return r;
         pending = win_of(p.id, rec_start);
         have_pending = true;
         next_id = p.id + 1;
-        return PA_OK;
+        return WIN_OK;
     }
 
     // ---- windows the GPU scans ----
@@ -563,20 +406,20 @@ struct TextPipe {
         while (e == PA_OK && cur.plan.active) {
             if ((e = send_window(cur)) != PA_OK) break;
             if ((e = start_read(nxt, cur.id + 1)) != PA_OK) break;      // the next window's text starts to arrive
-            const uint64_t main_from = cur.plan.text_from;
-            bool discard = false;
+            int r = WIN_OK;   // what became of the pending window, then of cur
             if (have_pending) {
-                const int r = resolve();
-                if (r == WIN_ODD) { gpu_mode = false; discard = true; rec_start = pending.from; next_id = pending.id; }               // not four-line text from here on: the host's scan takes over
-                else if (r == WIN_EMPTY) { W = std::max<uint64_t>(2 * W, 2 * (main_from - pending.from)); discard = true; rec_start = pending.from; next_id = pending.id; }   // no whole record in the window: a longer one
-                else if (r != PA_OK) { e = r; break; }
+                r = resolve();
+                if (r == WIN_ODD || r == WIN_EMPTY) { rec_start = pending.from; next_id = pending.id; }   // the pending window is dropped, and cur behind it
+                else if (r != WIN_OK) { e = r; break; }
             }
             if ((e = use(*cur.l)) != PA_OK) break;
-            const uint64_t head = main_from > rec_start ? main_from - rec_start : 0;   // the unfinished record of the window before
-            const uint64_t skip = rec_start > main_from ? rec_start - main_from : 0;   // (BGZF behind a discarded window: the first record starts inside the first member)
-            if (!discard && head > WINDOW_HEAD_ROOM) { W = std::max<uint64_t>(W, 2 * head); discard = true; }
-            if (discard) { e = reread_from(rec_start); continue; }
-            if ((e = enqueue_scan(cur, head, skip)) != PA_OK) break;
+            if (r == WIN_OK && (r = enqueue_scan(cur)) < 0) { e = r; break; }
+            if (r != WIN_OK) {   // odd, empty, or cur's head beyond the head room: a longer window from rec_start on, or the host's scan from there
+                const WindowRule rule = window_rule(r, W, cur.plan.text_from, rec_start, true);
+                W = rule.W;
+                e = reread_from(rec_start, rule.host);
+                continue;
+            }
             if ((e = retire_finished(0)) != PA_OK) break;
             cur = nxt;
             nxt.plan.active = false;
@@ -586,9 +429,9 @@ struct TextPipe {
     int gpu_windows() {
         gpu_mode = !opt.host_only && text.fsize > KEEP;
         int e = gpu_windows_loop();
-        (void)read_end();   // (an error path: nothing of the pool's job is left behind)
+        (void)window_fill_end(x);   // (an error path: nothing of the pool's job is left behind)
         gpu_mode = false;
-        if (e == PA_OK && have_pending) {
+        if (e == PA_OK && have_pending) {   // (no window behind the last one: odd or empty, the rest is the host's)
             const int r = resolve();
             if (r == WIN_ODD || r == WIN_EMPTY) { rec_start = pending.from; next_id = pending.id; }
             else e = r;
@@ -596,48 +439,20 @@ struct TextPipe {
         return e;
     }
 
-    // a batch of the host-scanned text: records rp[0, n), whose text ends at `end` (ws's offsets). Text and records go to the GPU, the same kernels follow
-    int host_batch(const WindowScan& ws, const RecPos* rp, uint64_t n, uint64_t end) {
-        const uint64_t first = rp[0].start, bytes = end - first, id = next_id;
-        if (bytes > (3ull << 30)) return fail(PA_ERR_UNSUPPORTED, "%s: record %llu is longer than 3 GiB", fastq_path, (unsigned long long)launched_reads);
+    // a batch of the host-scanned text: records rp[i0, i1) of ws. Text and records go to the GPU (window_fill_host, window_send_host), the same kernels follow
+    int host_batch(const WindowScan& ws, const RecPos* rp, uint64_t i0, uint64_t i1) {
+        const uint64_t id = next_id, n = i1 - i0;
         BatchCtx* cp = nullptr;
         int e = acquire(id, &cp);
         if (e != PA_OK) return e;
         BatchCtx& c = *cp;
-        if ((e = window_ensure_raw(c, WINDOW_HEAD_ROOM + bytes)) != PA_OK) return e;
-        if ((e = window_ensure_recs(c, n, true)) != PA_OK) return e;
-        const double t0 = now();
-        // the batch's text (plain memcpy: the bytes were just read by the scan and lie in the caches) and where its records lie in it
-        const char* const src = ws.base + first;
-        uint8_t* const dst = c.h_raw.get() + WINDOW_HEAD_ROOM;
-        deal_pieces(bytes, true, [src, dst](uint64_t a, uint64_t b) { memcpy(dst + a, src + a, (size_t)(b - a)); });
-        const int T4 = pool.size() * 4;
-        std::vector<uint32_t> tmax((size_t)T4, 0);
-        pool.run(T4, [&](int t) {
-            uint32_t mx = 0;
-            for (uint64_t i = n * (uint64_t)t / (uint64_t)T4; i < n * (uint64_t)(t + 1) / (uint64_t)T4; ++i) {
-                const RecPos& r = rp[i];
-                const uint64_t seq_off = std::min<uint64_t>(r.start + r.hdr + 1, ws.size);
-                const uint32_t seq_len = (uint32_t)std::min<uint64_t>(r.seq_len, ws.size - seq_off);
-                c.h_rec.get()[i] = make_uint4((uint32_t)(WINDOW_HEAD_ROOM + r.start + 1 - first), r.id_len, (uint32_t)(WINDOW_HEAD_ROOM + seq_off - first), seq_len);
-                mx = std::max(mx, seq_len);
-            }
-            tmax[(size_t)t] = mx;
-        });
-        uint32_t maxlen = 1;
-        for (uint32_t m : tmax) maxlen = std::max(maxlen, m);
-        t_read += now() - t0;
+        uint32_t maxlen = 0;
+        if ((e = window_fill_host(x, ws, rp, i0, i1, launched_reads, c, &maxlen)) != PA_OK) return e;
         if (maxlen > PA_MAX_READ_LEN) return fail(PA_ERR_UNSUPPORTED, "read longer than %u bases", PA_MAX_READ_LEN);
         // (the copies ride on the lane's kernel stream: this path is bound by the host's scan, not by the link)
-        const hipStream_t stream = lane_of(id).cache->stream;
-        PA_HIP_TRY(hipMemcpyAsync(c.d_raw.get() + WINDOW_HEAD_ROOM, dst, bytes, hipMemcpyHostToDevice, stream));
-        PA_HIP_TRY(hipMemcpyAsync(c.d_rec.get(), c.h_rec.get(), n * sizeof(uint4), hipMemcpyHostToDevice, stream));
-        stats.bytes_h2d += bytes + n * sizeof(uint4);
-        c.n_members = 0;
-        c.raw_begin = WINDOW_HEAD_ROOM;
-        c.raw_end = WINDOW_HEAD_ROOM + bytes;
+        if ((e = window_send_host(x, c, n, lane_of(id).cache->stream)) != PA_OK) return e;
         c.n = n;
-        c.wpr = pa_words_per_read(maxlen);
+        c.wpr = pa_words_per_read(maxlen ? maxlen : 1);   // (a batch of empty reads still has a word per read)
         next_id = id + 1;
         wins.push_back(win_of(id, 0));
         ++host_wins;
@@ -656,16 +471,13 @@ struct TextPipe {
         for (;;) {
             const double t0 = now();
             e = ws.next(fastq_path, records_before, pool, hc->rec_pos, hc->brk);
-            t_scan += now() - t0;
+            st[ST_SCAN] += now() - t0;
             if (e != PA_OK || ws.nrec == 0) return e;
             records_before += ws.nrec;
             const RecPos* const rp = hc->rec_pos.data();
-            auto end_of = [&](uint64_t i) { return i < ws.nrec ? rp[i].start : ws.size; };
             for (uint64_t i0 = 0; i0 < ws.nrec;) {
-                // a batch of whole records whose text fits a window of 2 GiB (offsets into it are 32 bits)
-                uint64_t i1 = std::min<uint64_t>(ws.nrec, i0 + opt.batch_reads);
-                while (i1 > i0 + 1 && end_of(i1) - rp[i0].start > (1ull << 31)) i1 = i0 + (i1 - i0) / 2;
-                if ((e = host_batch(ws, rp + i0, i1 - i0, end_of(i1))) != PA_OK) return e;
+                const uint64_t i1 = host_tail_cut(rp, ws.nrec, ws.size, i0, opt.batch_reads);
+                if ((e = host_batch(ws, rp, i0, i1)) != PA_OK) return e;
                 i0 = i1;
             }
         }
@@ -674,14 +486,14 @@ struct TextPipe {
     // the end of a call, good or bad (rc): the figures of the call are left for their getters, every stream is waited for, the writer ends, and the lanes' buffers
     // are parked on their handles (or destroyed behind an error, whose message is kept)
     int finish(int rc, const char* out_path) {
-        const double st[PA_INGEST_STAGES] = {t_scan, t_read, t_wait, t_launch, t_text, t_push, now() - t_begin, (double)reported};
-        memcpy(pa::ingest::last_stage_seconds(), st, sizeof st);
-        if (stats.text_kind == 2) stats.members_host = text.members_host;
+        const double all[PA_INGEST_STAGES] = {st[ST_SCAN], st[ST_READ], st[ST_WAIT], st[ST_LAUNCH], st[ST_TEXT], st[ST_PUSH], now() - t_begin, (double)reported};
+        memcpy(pa::ingest::last_stage_seconds(), all, sizeof all);
+        const InputStats stats = x.final_stats();
         memcpy(last_input_stats(), &stats, sizeof stats);
         if (opt.verbose)
             fprintf(stderr, "\n[pa ingest] %llu reads, %d threads, %d lane(s): %llu windows scanned on the GPU (%llu scanned twice), %llu batches by the host; host scan %.3f s, read %.3f s, wait GPU %.3f s, launch %.3f s, wait text %.3f s, wait writer %.3f s, total %.3f s (before the first window %.3f s)\n",
-                    (unsigned long long)reported, pool.size(), L(), (unsigned long long)gpu_wins, (unsigned long long)rescans, (unsigned long long)host_wins, t_scan, t_read, t_wait,
-                    t_launch, t_text, t_push, now() - t_begin, t_begin - t_enter);
+                    (unsigned long long)reported, pool.size(), L(), (unsigned long long)gpu_wins, (unsigned long long)x.rescans, (unsigned long long)host_wins, st[ST_SCAN], st[ST_READ], st[ST_WAIT],
+                    st[ST_LAUNCH], st[ST_TEXT], st[ST_PUSH], now() - t_begin, t_begin - t_enter);
         if (opt.verbose && timer.ms > 0) fprintf(stderr, "[pa ingest] windows to the GPU: %.1f MB in %.2f ms of copies = %.1f GB/s\n", timer.total / 1e6, timer.ms, timer.total / timer.ms / 1e6);
         timer.release();
         if (reported >= 1000000) fputc('\n', stderr);   // (`eprintln!()` behind the progress line, :508)
@@ -723,7 +535,7 @@ int process_reads_impl(pa_index* const* idxs, int nidx, const char* fastq_path, 
     if (!idxs || nidx < 1 || !fastq_path || !out_path) return fail(PA_ERR_INVALID_ARG, "null argument");
     for (int i = 0; i < nidx; ++i)
         if (!idxs[i]) return fail(PA_ERR_INVALID_ARG, "null index handle");
-    const double t_enter = TextPipe::now();
+    const double t_enter = now();
     if (num_threads < 1) num_threads = 1;
     if (n_reads_out) *n_reads_out = 0;
     if (n_flagged_out) *n_flagged_out = 0;
@@ -741,7 +553,7 @@ int process_reads_impl(pa_index* const* idxs, int nidx, const char* fastq_path, 
     std::vector<char> obuf(out != stdout ? (size_t)1 << 22 : 0);
     if (out != stdout) setvbuf(out, obuf.data(), _IOFBF, obuf.size());
 
-    const double t_begin = TextPipe::now();
+    const double t_begin = now();
     Pool pool(num_threads);
     std::vector<Lane> lanes((size_t)nidx);
     Writer writer(out);

@@ -1,6 +1,7 @@
 // The text of a FASTQ file as the host sees it (fastq_text.cpp): opened (mapped, or inflated when gzip'ed), scanned for its records a window
 // at a time with the tolerant rules of bio's reader. What the file drivers share: pa_process_reads (fastq_reads.cpp) hands the host's scan
-// the text its GPU scan does not take, pa_count_cells / pa_count_pairs (fastq_pairs.cpp) walk their two files with it.
+// the text its GPU scan does not take, pa_count_cells / pa_count_pairs (fastq_pairs.cpp) walk their two files with it. What is done to a window of
+// this text on its way to the GPU and behind it — for both of them — is text_window.hpp's.
 #pragma once
 #include <sys/mman.h>
 #include <unistd.h>
