@@ -1,7 +1,7 @@
 // The FASTQ text on the host: a file opened (mapped; gzip inflated), its records found by counting lines — every host thread its byte
 // range, nobody parses a byte twice or takes a lock — with the tolerances of bio's fastq::Reader (the reference's reader): CRLF, trailing
 // blank lines, a last record without its quality line, wrapped sequence / quality lines (rewritten first). pa_fastq_scan_host runs the scan
-// alone; the file drivers (fastq_reads.cpp, fastq_pairs.cpp) take their windows of records from it (fastq_text.hpp).
+// alone; the file drivers (fastq_reads.cpp, pair_reader.cpp) take their windows of records from it (fastq_text.hpp).
 #include <fcntl.h>
 #include <emmintrin.h>
 #include <sys/mman.h>

@@ -1,6 +1,6 @@
 // The text of a FASTQ file as the host sees it (fastq_text.cpp): opened (mapped, or inflated when gzip'ed), scanned for its records a window
 // at a time with the tolerant rules of bio's reader. What the file drivers share: pa_process_reads (fastq_reads.cpp) hands the host's scan
-// the text its GPU scan does not take, pa_count_cells / pa_count_pairs (fastq_pairs.cpp) walk their two files with it. What is done to a window of
+// the text its GPU scan does not take, the paired drivers (pair_reader.cpp under fastq_cells.cpp and fastq_pairs.cpp) walk their two files with it. What is done to a window of
 // this text on its way to the GPU and behind it — for both of them — is text_window.hpp's.
 #pragma once
 #include <sys/mman.h>
@@ -27,7 +27,7 @@ struct FastqText {   // the text of a FASTQ file as the scan sees it: the mapped
     const char* map_base = nullptr; // the mapping as mmap returned it (data moves on when the rest of a file is rewritten)
     uint64_t map_size = 0;
     int fd = -1;                    // of a mapped file (kept open for the call)
-    // A BGZF file (pa_bgzf_scan accepts it; pa_process_reads only): the mapping is the COMPRESSED file (map_base / map_size, `mapped` stays false: nothing
+    // A BGZF file (pa_bgzf_scan accepts it; pa_process_reads and the paired drivers' window feeds): the mapping is the COMPRESSED file (map_base / map_size, `mapped` stays false: nothing
     // may read text out of it), fsize = the bytes of text (sum of ISIZE), offsets everywhere are text offsets, `members` finds the bytes behind them.
     // data stays null until materialise() has inflated the text's tail on the host (the part the GPU windows do not take).
     bool bgzf = false;
@@ -45,7 +45,7 @@ struct FastqText {   // the text of a FASTQ file as the scan sees it: the mapped
 };
 
 int open_fastq(const char* fastq_path, FastqText& t);
-// bgzf.cpp (pa_process_reads only): a file that is BGZF from first byte to last is opened as the BGZF kind above (t.bgzf set); anything else, an unreadable
+// bgzf.cpp (pa_process_reads, and the paired drivers when they take the device form): a file that is BGZF from first byte to last is opened as the BGZF kind above (t.bgzf set); anything else, an unreadable
 // file included, leaves t untouched for open_fastq, with its results and its errors
 void open_bgzf(const char* fastq_path, FastqText& t);
 // BGZF kind: the index of the member that holds text offset `off` (the last member that starts at or before it: empty members in front are skipped)
@@ -83,6 +83,13 @@ struct WindowScan {
     // the next window with records in it (nrec = 0: the text has ended). records_before: records of the windows before (error messages)
     int next(const char* fastq_path, uint64_t records_before, Pool& pool, std::vector<RecPos>& rec_pos, std::vector<std::vector<uint32_t>>& brk);
 };
+
+// The id under which the two records of a pair are compared: record.id() of `len` bytes at s with one trailing "/1" or "/2" cut, and only from an id of at
+// least two bytes. The host's pair reader calls it per record (pair_reader.cpp), tests/pairplan drives it over ids in buffers of exactly their length, and
+// tests/pairscan_model.py states the same rule for the GPU's pair scan (pair_scan.hip)
+inline uint32_t pair_id_len(const char* s, uint32_t len) {
+    return len >= 2 && s[len - 2] == '/' && (s[len - 1] == '1' || s[len - 1] == '2') ? len - 2 : len;
+}
 
 // The C ABI's edge of a file driver: nothing thrown crosses it (std::bad_alloc out of the growable buffers, std::system_error out of thread creation)
 template <class F>

@@ -130,6 +130,30 @@ inline PairParams stage_params(const PairIndexView& v, uint64_t n, pa_read_resul
     return p;
 }
 
+// the arena bound of both stages: `kernel` sums what the n records of a and b can need into the first 8 bytes of d_scratch; synchronises `stream`.
+// too_many: the text for a batch beyond one launch
+using BoundKernel = void (*)(const pa_read_result*, const pa_read_result*, uint64_t, unsigned long long*);
+inline int stage_arena_bound(pa_index* idx, BoundKernel kernel, const pa_read_result* d_a, const pa_read_result* d_b, uint64_t n, void* d_scratch, void* stream, uint64_t* bound,
+                             const char* too_many) {
+    if (!idx || !d_scratch || !bound || (n && (!d_a || !d_b))) return fail(PA_ERR_INVALID_ARG, "null argument");
+    PairIndexView v;
+    index_pair_view(idx, &v);
+    PA_HIP_TRY(hipSetDevice(v.device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    PA_HIP_TRY(hipMemsetAsync(d_scratch, 0, 8, s));
+    if (n) {
+        const uint32_t blocks = grid_for(n);
+        if (blocks == 0) return fail(PA_ERR_UNSUPPORTED, "%s", too_many);
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, s, d_a, d_b, n, static_cast<unsigned long long*>(d_scratch));
+        PA_HIP_TRY(hipGetLastError());
+    }
+    unsigned long long h = 0;
+    PA_HIP_TRY(hipMemcpyAsync(&h, d_scratch, 8, hipMemcpyDeviceToHost, s));
+    PA_HIP_TRY(hipStreamSynchronize(s));
+    *bound = h;
+    return PA_OK;
+}
+
 // the finish of both stages: the control block to the host behind the launch; `what` names the arena in the message
 inline int stage_finish(pa_index* idx, void* d_scratch, void* stream, uint64_t* stats, uint64_t* arena_used, uint64_t* arena_needed, const char* what) {
     if (!idx || !d_scratch) return fail(PA_ERR_INVALID_ARG, "null argument");

@@ -356,23 +356,7 @@ extern "C" int pa_pairs_combine_device(pa_index* idx, const pa_read_result* d_re
 }
 
 int pa::pairs_arena_bound(pa_index* idx, const pa_read_result* d_res1, const pa_read_result* d_res2, uint64_t n_pairs, void* d_scratch, void* stream, uint64_t* bound) {
-    if (!idx || !d_scratch || !bound || (n_pairs && (!d_res1 || !d_res2))) return fail(PA_ERR_INVALID_ARG, "null argument");
-    PairIndexView v;
-    index_pair_view(idx, &v);
-    PA_HIP_TRY(hipSetDevice(v.device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    PA_HIP_TRY(hipMemsetAsync(d_scratch, 0, 8, s));
-    if (n_pairs) {
-        const uint32_t blocks = grid_for(n_pairs);
-        if (blocks == 0) return fail(PA_ERR_UNSUPPORTED, "too many pairs for one launch");
-        hipLaunchKernelGGL(pa_pairs_bound_kernel, dim3(blocks), dim3(256), 0, s, d_res1, d_res2, n_pairs, static_cast<unsigned long long*>(d_scratch));
-        PA_HIP_TRY(hipGetLastError());
-    }
-    unsigned long long h = 0;
-    PA_HIP_TRY(hipMemcpyAsync(&h, d_scratch, 8, hipMemcpyDeviceToHost, s));
-    PA_HIP_TRY(hipStreamSynchronize(s));
-    *bound = h;
-    return PA_OK;
+    return stage_arena_bound(idx, pa_pairs_bound_kernel, d_res1, d_res2, n_pairs, d_scratch, stream, bound, "too many pairs for one launch");
 }
 
 extern "C" int pa_pairs_finish(pa_index* idx, void* d_scratch, void* stream, uint64_t stats[PA_PAIR_STATS], uint64_t* arena_used, uint64_t* arena_needed) {

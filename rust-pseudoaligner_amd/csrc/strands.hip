@@ -346,23 +346,7 @@ extern "C" int pa_strands_merge_device(pa_index* idx, const pa_read_result* d_re
 }
 
 int pa::strands_arena_bound(pa_index* idx, const pa_read_result* d_resS, const pa_read_result* d_resR, uint64_t n, void* d_scratch, void* stream, uint64_t* bound) {
-    if (!idx || !d_scratch || !bound || (n && (!d_resS || !d_resR))) return fail(PA_ERR_INVALID_ARG, "null argument");
-    PairIndexView v;
-    index_pair_view(idx, &v);
-    PA_HIP_TRY(hipSetDevice(v.device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    PA_HIP_TRY(hipMemsetAsync(d_scratch, 0, 8, s));
-    if (n) {
-        const uint32_t blocks = grid_for(n);
-        if (blocks == 0) return fail(PA_ERR_UNSUPPORTED, "too many items for one launch");
-        hipLaunchKernelGGL(pa_strands_bound_kernel, dim3(blocks), dim3(256), 0, s, d_resS, d_resR, n, static_cast<unsigned long long*>(d_scratch));
-        PA_HIP_TRY(hipGetLastError());
-    }
-    unsigned long long h = 0;
-    PA_HIP_TRY(hipMemcpyAsync(&h, d_scratch, 8, hipMemcpyDeviceToHost, s));
-    PA_HIP_TRY(hipStreamSynchronize(s));
-    *bound = h;
-    return PA_OK;
+    return stage_arena_bound(idx, pa_strands_bound_kernel, d_resS, d_resR, n, d_scratch, stream, bound, "too many items for one launch");
 }
 
 extern "C" int pa_strands_finish(pa_index* idx, void* d_scratch, void* stream, uint64_t stats[PA_STRAND_STATS], uint64_t* arena_used, uint64_t* arena_needed) {

@@ -20,6 +20,7 @@ constexpr uint64_t PIECE = 2ull << 20;   // bytes of a window that one task of t
 
 enum { WIN_OK = 0, WIN_ODD = 1, WIN_EMPTY = 2, WIN_HEAD = 3 };   // what a step answers besides a pa_status (those are negative): not four-line text | no whole record | the head does not fit the head room
 enum { ST_SCAN = 0, ST_READ = 1, ST_WAIT = 2, ST_LAUNCH = 3, ST_TEXT = 4, ST_PUSH = 5 };   // stage seconds a step or a scheduler adds to (pa_process_reads_stage_seconds: [6] whole call, [7] reads)
+enum { ST_TALLY = 4, ST_WRITE = 5, ST_CALL = 6, ST_RECORDS = 7 };   // the paired drivers' names for the same array: [ST_READ] is their host gather, then count | output files | whole call | pairs
 
 struct InputStats {   // pa_process_reads_input_stats, in the ABI's order: filled as the call goes
     uint64_t text_kind = 0, members_total = 0, members_gpu = 0, members_host = 0, bytes_h2d = 0, text_bytes_gpu = 0;

@@ -3,7 +3,7 @@
 // that TextPipe (fastq_reads.cpp) runs; the feed is the scheduler around them for a consumer that pulls: three slots, a slot taken again behind an event of its
 // consumer, reads of a window's text synchronous on the pool (two feeds share it, and the pool runs one job at a time), next() handing out a window while the
 // one behind it is scanned and the one behind that read and sent. FqInfo.odd or nothing left to plan -> the rest of the file through bgzf_materialise and the
-// host's WindowScan, uploaded as windows of the same form. The paired drivers (fastq_pairs.cpp) run two of them side by side.
+// host's WindowScan, uploaded as windows of the same form. The paired drivers' device reader (pair_reader.cpp) runs two of them side by side.
 #pragma once
 #include <memory>
 

@@ -1,14 +1,17 @@
 // The arithmetic of the paired drivers' device path that needs no GPU (csrc/window_feed.hpp: segment_pairs, feed_slot_of), driven over made-up sequences
-// of window record counts the way PairReader::gather_device drives it: windows are refilled when they are used up, a batch is built from segments, a window
+// of window record counts the way DevicePairReader::gather (csrc/pair_reader.cpp) drives it: windows are refilled when they are used up, a batch is built from segments, a window
 // is released when its last segment has been launched. Checked: every pair is taken exactly once and in order, a batch never exceeds batch_pairs, a window
 // is never released before its last segment, the two files end together or the longer one is named, and the slot of a window is not taken again while the
 // window and the two windows behind it (being scanned, being read) are alive. Stand-alone host program, built with -fsanitize=address,undefined.
 // What this pins is the ARITHMETIC only: segment_pairs() and feed_slot_of() are the product's, the loop around them and the model of which slots are busy
-// are written here after gather_device and WindowFeed::next. The order in which WindowFeed::next itself takes slots (the window after next read into its
+// are written here after that gather and WindowFeed::next. The order in which WindowFeed::next itself takes slots (the window after next read into its
 // slot before the next one is resolved, the ids taken again after an empty or odd window) is not seen by this program: it runs on the GPU tier only
 // (tests/test_gpu_pairs_ingest.py with windows of 700 bytes).
+// Also pinned here: pair_id_len (csrc/fastq_text.hpp), the rule under which the host's reader compares the ids of a pair, the product's own inline function.
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
+#include <memory>
 #include <vector>
 
 #include "window_feed.hpp"
@@ -105,9 +108,21 @@ void expect(const char* name, std::vector<uint64_t> c1, std::vector<uint64_t> c2
     printf("%s: %llu pairs, batch %llu, longer %d\n", name, (unsigned long long)got, (unsigned long long)batch, longer);
 }
 
+// pair_id_len over an id in a heap buffer of exactly its length (a look in front of a one-byte or empty id is a sanitizer finding); silent unless it misses
+void expect_id(const char* id, uint32_t want) {
+    const uint32_t len = (uint32_t)strlen(id);
+    std::unique_ptr<char[]> buf(new char[len]);
+    memcpy(buf.get(), id, len);
+    const uint32_t got = pair_id_len(buf.get(), len);
+    CHECK(got == want, "pair_id_len(\"%s\") = %u, not %u", id, got, want);
+}
+
 }  // namespace
 
 int main() {
+    // the cases of test_id_cut (tests/test_pairscan_model.py): "/1" or "/2" is cut once, and only from an id of at least two bytes
+    expect_id("read7/1", 5); expect_id("read7/2", 5); expect_id("read7/3", 7); expect_id("read7/", 6); expect_id("read71", 6);
+    expect_id("/1", 0); expect_id("/2", 0); expect_id("1", 1); expect_id("/", 1); expect_id("", 0); expect_id("a/1/1", 3);
     expect("equal windows", {100, 100, 100}, {100, 100, 100}, 64);
     expect("different windows", {7, 300, 1, 1, 91}, {150, 150, 100}, 64);
     expect("batch larger than everything", {5, 5, 5}, {15}, 1000);

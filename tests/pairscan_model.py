@@ -1,5 +1,5 @@
 """A pure-Python model of the pair scan (csrc/pair_scan.hip, pa_pairs_gather_device): record i of an R1 text against record i of an R2
-text. The rules are the ones the host's PairReader applies per pair today (csrc/fastq_pairs.cpp: PairCursor::id and gather()):
+text. The rules are the ones the host's pair reader applies per pair (csrc/pair_reader.cpp: HostPairReader::gather, with pair_id_len of csrc/fastq_text.hpp):
 
   id          record.id() with a trailing "/1" or "/2" cut, when the id has at least two bytes ("/1" alone becomes empty, "/3" stays)
   first bad   the smallest batch position whose two cut ids differ in length or in a byte
@@ -11,10 +11,10 @@ text. The rules are the ones the host's PairReader applies per pair today (csrc/
 and two rules that only the device entry point has: a record row that points outside its text gives two empty pieces (first outside = its
 batch position), and a piece that would end beyond the capacity of its output is not written while the byte counts still include it.
 
-PairCursor::id and gather() sit in an unnamed namespace of the library and cannot be called from a test, so no CPU-tier test runs this model beside
-them: tests/test_pairscan_model.py pins the model on cases written by hand. Agreement with the real host code is established on the GPU tier, in two
-steps: the kernels equal this model bit for bit (tests/test_gpu_pairscan_edges.py), and the drivers on the device path equal the same call on the host
-path, which is PairCursor::id and gather() (tests/test_gpu_pairs_ingest.py)."""
+The id rule is the inline function pair_id_len (csrc/fastq_text.hpp): tests/pairplan/pairplan_check.cpp runs the product's own function over the id
+cases that tests/test_pairscan_model.py pins this model on. The gather sits in an unnamed namespace of the library and cannot be called from a test:
+agreement with it is established on the GPU tier, in two steps: the kernels equal this model bit for bit (tests/test_gpu_pairscan_edges.py), and the
+drivers on the device path equal the same call on the host path, which is HostPairReader::gather (tests/test_gpu_pairs_ingest.py)."""
 
 WHOLE_READ = 0xFFFFFFFF
 NONE = 0xFFFFFFFFFFFFFFFF

@@ -87,7 +87,7 @@ def run(kind, p1, p2, tmp_path, tag, whitelist=None):
         files = [(out / f).read_bytes() for f in ("output.bus", "matrix.ec", "transcripts.txt")]
     else:
         host, al = _pairs_aligner()
-        counts, st = al.count_pairs(str(p1), str(p2), "fr")
+        counts, st = al.count_pairs(str(p1), str(p2), "un" if kind == "un" else "fr")
         files = [counts.tobytes()]
     n_pairs = int(list(pa.process_reads_stage_seconds().values())[7])
     return st, files, n_pairs, pa.pairs_input_stats()
@@ -134,7 +134,7 @@ def test_windows(kind, mix, window, tmp_path, monkeypatch):
     assert stats["r2"]["bytes_h2d"] > 0 and (f2 != "bgzf" or window is None or stats["r2"]["members_gpu"] > 0)
 
 
-@pytest.mark.parametrize("kind", ["cells", "bus", "pairs"])
+@pytest.mark.parametrize("kind", ["cells", "bus", "pairs", "un"])   # ("un": four streams, the gathered bytes consumed on two of them)
 def test_batch_seam_inside_small_windows(kind, tmp_path, monkeypatch):
     r1, r2, wl = _reads(kind, 2000)
     ids = ["p%d" % i for i in range(len(r1))]

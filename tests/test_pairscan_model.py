@@ -1,6 +1,7 @@
 """tests/pairscan_model.py pinned on hand-written cases: the id cut, the first bad position, lengths, offsets, bytes and maxima, as
-PairCursor::id and PairReader::gather of csrc/fastq_pairs.cpp define them (their rules are spelled out here case by case: both live in an
-unnamed namespace of the library and cannot be called from a test), and the two rules of the device entry point (rows outside the text,
+pair_id_len (csrc/fastq_text.hpp) and HostPairReader::gather (csrc/pair_reader.cpp) define them (spelled out here case by case: the gather lives in an
+unnamed namespace of the library; the id rule is an inline function, which tests/pairplan/pairplan_check.cpp runs over the cases of test_id_cut),
+and the two rules of the device entry point (rows outside the text,
 pieces beyond the capacity). The GPU tests compare pa_pairs_gather_device with this model bit for bit."""
 import pairscan_model as pm
 
