@@ -1,9 +1,10 @@
 // The emulator's per-read loop: every unqualified Lane / l_* / *_step name is that of the packing whose namespace includes this file
 // (emu_map.cpp: pa::narrow for reads of up to 512 bases, pa::wide beyond — as launch_map_pool picks its kernels).
-// results as pa_read_result; class ids as malloc'd CSR in read order; optional step counters [5] = seek, fwd, left steps, spills, reads whose pending classes were masked
+// results as pa_read_result; class ids as malloc'd CSR in read order; optional step counters [5] = seek, fwd, left steps, spills, reads whose pending classes were masked;
+// optional path_out[n][EMU_PATH_WORDS] = which way the read took to its class (emu_map.cpp, EMU_PATH_*)
 static int emu_map_batch_impl(const emu_index* e, const uint64_t* tiles, uint32_t wpr, const uint32_t* lens, uint64_t n, uint32_t allowed,
                   uint32_t col_cap, pa_read_result* results, uint64_t* class_offsets, uint32_t** class_ids, uint32_t* colour_out,
-                  uint64_t* steps, uint32_t* nodes_out, uint32_t nodes_stride, uint32_t* nodes_len) {
+                  uint64_t* steps, uint32_t* nodes_out, uint32_t nodes_stride, uint32_t* nodes_len, uint32_t* path_out) {
     const DevIndexView ix = e->fd.host_view();
     std::vector<uint32_t> all;
     std::vector<uint64_t> rd(wpr + 2);
@@ -24,6 +25,7 @@ static int emu_map_batch_impl(const emu_index* e, const uint64_t* tiles, uint32_
         lane_start(s, (uint32_t)i, L, ix.k);
         const ReadRef rr{rd.data(), 1, wpr};
         const ColRef cr{win4, wcand, refs, lens4, cids4, spill.data(), (uint32_t)spill.size(), pend.data(), trace.data()};
+        uint32_t path[EMU_PATH_WORDS] = {EMU_PATH_NONE, 0xFFFFFFFFu, 0, 0, 0};
         for (;;) {
             while (l_st(s) == ST_SEEK || l_st(s) == ST_FWD || l_st(s) == ST_LEFT) {
                 if (l_st(s) == ST_SEEK) { seek_step(s, ix, rr); ++st_seek; }
@@ -38,7 +40,7 @@ static int emu_map_batch_impl(const emu_index* e, const uint64_t* tiles, uint32_
             if (l_st(s) != ST_ISECT || (l_flags(s) & F_LISTS)) break;
             const uint32_t todo = window_todo(s);   // window mode: classes without windows still to apply?
             if (todo == 2) { restart_lists(s, ix.k); continue; }
-            if (todo == 1) { mask_pending(s, ix, cr); ++st_mask; }
+            if (todo == 1) { path[3] = l_npend(s); mask_pending(s, ix, cr); ++st_mask; }
             break;
         }
         if (l_flags(s) & F_SPILL_OVERFLOW) return PA_ERR_INTERNAL;
@@ -52,6 +54,7 @@ static int emu_map_batch_impl(const emu_index* e, const uint64_t* tiles, uint32_
         uint32_t colour = 0xFFFFFFFFu;
         if (l_st(s) == ST_ISECT && !(l_flags(s) & F_LISTS)) {   // window mode: {base1, mask1, base2, mask2} + class id or NO_CLASS
             const uint32_t cand = wcand[0];
+            path[0] = path[3] ? EMU_PATH_MASKED : EMU_PATH_WINDOW;
             const uint32_t count = (uint32_t)(__builtin_popcount(win4[1]) + __builtin_popcount(win4[3]));
             const size_t o = all.size();
             all.resize(o + count);
@@ -77,6 +80,11 @@ static int emu_map_batch_impl(const emu_index* e, const uint64_t* tiles, uint32_
             }
         } else if (l_st(s) == ST_ISECT) {
             const Isect is = isect_count(s, ix, cr);
+            Isect pick;
+            path[0] = EMU_PATH_LISTS;
+            path[1] = isect_pick(s, cr, pick);   // 0 ST_F_LIGHT, 1 ST_F_SCAN, 2 ST_F_COOP (map_pool_kernel.inc, queue_of and the hand-over in ST_F_LIGHT)
+            path[2] = l_ncol(s);
+            path[4] = pick.base_len;
             const size_t o = all.size();
             all.resize(o + is.count);
             res.coverage = l_cov(s);
@@ -95,6 +103,7 @@ static int emu_map_batch_impl(const emu_index* e, const uint64_t* tiles, uint32_
         }
         results[i] = res;
         if (colour_out) colour_out[i] = colour;
+        if (path_out) memcpy(path_out + EMU_PATH_WORDS * i, path, sizeof path);
     }
     class_offsets[n] = all.size();
     uint32_t* p = (uint32_t*)malloc((all.size() ? all.size() : 1) * 4);

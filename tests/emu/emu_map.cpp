@@ -86,6 +86,10 @@ uint64_t emu_index_info(const emu_index* e, int what) {
 }  // extern "C"
 
 struct emu_index;
+// path_out of emu_map_batch, per read: {EMU_PATH_*, tier isect_pick chose (list mode; else 0xFFFFFFFF), l_ncol (list mode: classes collected),
+// pending classes that were masked (window mode), base_len (list mode)}
+constexpr uint32_t EMU_PATH_WORDS = 5;
+enum : uint32_t { EMU_PATH_NONE = 0, EMU_PATH_WINDOW = 1, EMU_PATH_MASKED = 2, EMU_PATH_LISTS = 3 };   // unmapped / two-window AND / pending classes masked / restarted in list mode
 namespace pa {
 namespace narrow {
 #include "emu_loop.inc"
@@ -99,14 +103,14 @@ extern "C" {
 
 // results as pa_read_result; class ids as malloc'd CSR in read order; optional step counters [5] = seek, fwd, left steps, spills, reads whose pending
 // classes were masked. The lane packing follows the kernel's choice: reads of more than PA_LDS_READ_WORDS (16) words take the WIDE lane state
-// (lane_steps.hpp), PA_EMU_WIDE=1 forces it for every batch (the wide text on short reads too)
+// (lane_steps.hpp), PA_EMU_WIDE=1 forces it for every batch (the wide text on short reads too). path_out: optional, [n][EMU_PATH_WORDS]
 int emu_map_batch(const emu_index* e, const uint64_t* tiles, uint32_t wpr, const uint32_t* lens, uint64_t n, uint32_t allowed,
                   uint32_t col_cap, pa_read_result* results, uint64_t* class_offsets, uint32_t** class_ids, uint32_t* colour_out,
-                  uint64_t* steps, uint32_t* nodes_out, uint32_t nodes_stride, uint32_t* nodes_len) {
+                  uint64_t* steps, uint32_t* nodes_out, uint32_t nodes_stride, uint32_t* nodes_len, uint32_t* path_out) {
     const char* force = getenv("PA_EMU_WIDE");
     if (wpr > 16 || (force && *force == '1'))
-        return pa::wide::emu_map_batch_impl(e, tiles, wpr, lens, n, allowed, col_cap, results, class_offsets, class_ids, colour_out, steps, nodes_out, nodes_stride, nodes_len);
-    return pa::narrow::emu_map_batch_impl(e, tiles, wpr, lens, n, allowed, col_cap, results, class_offsets, class_ids, colour_out, steps, nodes_out, nodes_stride, nodes_len);
+        return pa::wide::emu_map_batch_impl(e, tiles, wpr, lens, n, allowed, col_cap, results, class_offsets, class_ids, colour_out, steps, nodes_out, nodes_stride, nodes_len, path_out);
+    return pa::narrow::emu_map_batch_impl(e, tiles, wpr, lens, n, allowed, col_cap, results, class_offsets, class_ids, colour_out, steps, nodes_out, nodes_stride, nodes_len, path_out);
 }
 
 void emu_free(void* p) { free(p); }

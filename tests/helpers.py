@@ -94,7 +94,7 @@ def emu_lib():
         L.emu_index_info.restype = C.c_uint64
         L.emu_index_info.argtypes = [C.c_void_p, C.c_int]
         L.emu_map_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p,
-                                    C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+                                    C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         L.emu_free.argtypes = [C.c_void_p]
         _emu_lib = L
     return _emu_lib
@@ -279,8 +279,13 @@ class Emu:
                     bad_blocks=L.emu_index_info(self._h, 6), branch_records=L.emu_index_info(self._h, 7),
                     num_bitmaps=L.emu_index_info(self._h, 8), bitmap_min=L.emu_index_info(self._h, 9))
 
-    def map_tiles(self, tiles, lens, wpr, allowed=2, col_cap=8, want_nodes=False):
+    PATHS = {0: None, 1: "window", 2: "masked", 3: "lists"}
+
+    def map_tiles(self, tiles, lens, wpr, allowed=2, col_cap=8, want_nodes=False, want_path=False):
+        """want_path: result["path"] = per read {path: None (unmapped) / "window" / "masked" / "lists", tier, ncol, npend, base_len}, the
+        way the read took to its class (tests/class_cases.py names them)"""
         n = len(lens)
+        path = np.zeros((max(n, 1), 5), np.uint32) if want_path else None
         res = np.zeros(n, pa.RESULT_DTYPE)
         coff = np.zeros(n + 1, np.uint64)
         ids = C.c_void_p()
@@ -292,12 +297,13 @@ class Emu:
         nlen = np.zeros(max(n, 1), np.uint32)
         rc = emu_lib().emu_map_batch(self._h, tiles.ctypes.data, wpr, lens.ctypes.data, n, allowed, col_cap, res.ctypes.data, coff.ctypes.data,
                                      C.byref(ids), colour.ctypes.data, steps.ctypes.data, nodes.ctypes.data if want_nodes else None, stride,
-                                     nlen.ctypes.data)
+                                     nlen.ctypes.data, path.ctypes.data if want_path else None)
         assert rc == 0, (rc, emu_lib().emu_last_error())
         total = int(coff[-1])
         out = np.frombuffer((C.c_uint32 * max(total, 1)).from_address(ids.value), np.uint32)[:total].copy()
         emu_lib().emu_free(ids)
-        return dict(results=res, coff=coff, ids=out, colour=colour[:n], steps=steps, nodes=nodes, nodes_len=nlen[:n])
+        paths = [dict(path=self.PATHS[int(p[0])], tier=-1 if int(p[1]) == 0xFFFFFFFF else int(p[1]), ncol=int(p[2]), npend=int(p[3]), base_len=int(p[4])) for p in path[:n]] if want_path else None
+        return dict(results=res, coff=coff, ids=out, colour=colour[:n], steps=steps, nodes=nodes, nodes_len=nlen[:n], path=paths)
 
     def __del__(self):
         try:
