@@ -579,6 +579,81 @@ void pa_bus_destroy(pa_bus* b);
 int pa_write_bus(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, uint32_t bc_len, uint32_t umi_len,
                  const char* out_dir, int num_threads, uint64_t stats[PA_BUS_STATS]);
 
+/* ---------------- cells x genes from BUS records: multi-gene UMIs shared out by EM ----------------
+ * The `bustools count --genecounts --em` step on the records where they lie: where pa_cell_counter drops a read whose class spans two
+ * genes, this keeps the molecule and lets a per-cell EM divide it among its genes.
+ *   inputs     n BUS records, STRICTLY ascending by (barcode, UMI, ec) as pa_bus_finish leaves them; the ec table as a CSR (ec e =
+ *              ids[offsets[e] .. offsets[e + 1]), ascending ids < T); tx_gene[T] < num_genes; bc_len, umi_len
+ *   G(e)       the gene set of an ec: the ascending distinct tx_gene[t] over t in e (an ec without ids: the empty set)
+ *   molecule   a maximal run of records with equal (barcode, UMI). Its gene set is the intersection of G(e) over its records. An empty
+ *              intersection drops the molecule (stats[2]). A molecule counts 1 whatever its records' read counts. There is NO barcode
+ *              or UMI correction here: that is bustools correct's job, or the cell counter's
+ *   cell       a distinct barcode with at least one kept molecule; cells are numbered in ascending barcode value
+ *   rows       of a cell: the distinct gene sets S of its molecules, each with n_S = its molecules. u_g = n_{{g}} (the singleton
+ *              rows); the multi rows are those with |S| >= 2; E = the union of the multi rows; M = sum of n_S over the multi rows
+ *   PA_GENES_UNIQUE   entry (cell, g) = u_g; the multi rows are dropped (stats[4] counts their molecules); every value is an exact
+ *              integer and no iteration is run
+ *   PA_GENES_EM (default)
+ *     start          alpha_g = u_g + M / |E| for g in E; alpha_g = u_g otherwise, fixed from then on
+ *     one iteration  d_S = sum_{g in S} alpha_g over the multi rows;  alpha'_g = u_g + alpha_g * sum_{multi S with g} n_S / d_S
+ *                    (a term with d_S = 0 is 0). A cell without multi rows runs no iteration and has alpha_g = u_g exactly
+ *     stop           per cell, pa_quant_run's rule on the genes of E: after iteration i >= min_iters when no g has both
+ *                    alpha'_g > alpha_change_limit and |alpha'_g - alpha_g| / alpha'_g > alpha_change; looked at every check_every
+ *                    iterations (i a multiple of check_every) and at max_iters. A cell that meets it is frozen at that iterate,
+ *                    whatever the other cells still do
+ *     truncation     after the run every alpha_g < alpha_limit (of E or not) becomes 0 and leaves the matrix
+ *     defaults       pa_quant_default_params' (1e-7, 1e-2, 1e-2, 50, 10 000, 10). Nobody has tuned them for single-cell data
+ *   matrix     (cell, gene, f64 value) sorted by (cell, gene), zeros left out
+ *   independence   what a cell yields (every iterate, its iteration count, its entries) depends on its own records, the tables and the
+ *              params alone, not on the other cells; two runs give the same bits. The order of a cell's multi rows (which fixes the
+ *              order of every sum) is that of the 64-bit content hashes of their gene sets
+ *   errors     records not strictly ascending, an ec outside [0, n_ecs), tx_gene[t] >= num_genes, an ec id >= num_tx or not ascending,
+ *              bc_len / umi_len outside pa_bus_create's limits, params not finite, negative, check_every 0 or an unknown mode:
+ *              PA_ERR_INVALID_ARG; for a record the message names the first offending one. More than 2^31 - 1 records:
+ *              PA_ERR_UNSUPPORTED. Host arguments are checked before any device call; without a GPU pa_genes_create returns
+ *              PA_ERR_NO_DEVICE after those checks (before idx, as pa_quant_create). Two different gene sets of one cell under one
+ *              64-bit content hash are PA_ERR_INTERNAL naming the hash (never expected).
+ * pa_genes_step: every cell with multi rows, exactly n iterations, no stop rule, no freeze. pa_genes_run: stop rule + truncation from
+ * the current alpha, its iterations counted from 1; a second call only reports the same numbers, and pa_genes_step after it is
+ * PA_ERR_INVALID_ARG. pa_genes_values: the current alpha of every (cell, gene) that has a row, sorted by (cell, gene), zeros kept;
+ * barcode[n_cells] the cells' barcodes; any output may be NULL; cap < n_values: PA_ERR_BUFFER_TOO_SMALL. pa_genes_cell_iters: the
+ * iterations every cell has run so far (step and run). pa_genes_matrix: after pa_genes_run, else PA_ERR_INVALID_ARG.
+ * stats[PA_GENES_STATS]: [0] records, [1] molecules, [2] molecules dropped, [3] unique-gene molecules, [4] multi-gene molecules, [5] cells,
+ * [6] cells with multi rows, [7] multi rows after merging equal sets, [8] ids in multi rows, [9] longest multi row, [10] largest degree
+ * (multi rows of one cell that hold one gene), [11] largest cell (|E| + multi rows), [12] most iterations run by a cell, [13] cells
+ * not converged, [14] matrix entries, [15] cells that took the HBM variant of the EM kernel ([12] .. [15] after pa_genes_run).
+ * pa_genes_write (after run): out_dir/matrix.mtx ("%%MatrixMarket matrix coordinate real general", genes x cells, 1-based "gene cell
+ * value" lines in (cell, gene) order, doubles as pa_write_abundance_tsv prints them), barcodes.tsv (the cells' barcodes decoded, first
+ * base most significant) and features.tsv (as pa_count_cells writes it; h names the genes and must number num_genes of them). */
+#define PA_GENES_EM 0
+#define PA_GENES_UNIQUE 1
+#define PA_GENES_STATS 16
+typedef struct pa_genes pa_genes;
+typedef struct pa_genes_params { double alpha_limit, alpha_change_limit, alpha_change;
+                                 uint32_t min_iters, max_iters, check_every, mode, reserved; } pa_genes_params;
+void pa_genes_default_params(pa_genes_params* p);
+/* host arrays of any origin (an output.bus + matrix.ec read back, for instance); idx names the GPU; NULL p = defaults */
+int  pa_genes_create(pa_index* idx, const pa_bus_record* records, uint64_t n, const uint64_t* ec_offsets, const uint32_t* ec_ids,
+                     uint32_t n_ecs, uint32_t num_tx, const uint32_t* tx_gene, uint32_t num_genes, uint32_t bc_len, uint32_t umi_len,
+                     const pa_genes_params* p, pa_genes** out);
+/* the records of a finished writer, taken where they lie in HBM, with the writer's ec table; tx_gene[the index's transcripts]. The
+ * writer is read only during this call */
+int  pa_genes_create_from_bus(const pa_bus* finished, const uint32_t* tx_gene, uint32_t num_genes, const pa_genes_params* p, pa_genes** out);
+int  pa_genes_step(pa_genes* g, uint32_t n_iters);
+int  pa_genes_run(pa_genes* g, uint32_t* max_iters_run, uint64_t* cells_not_converged);   /* either may be NULL */
+int  pa_genes_layout(const pa_genes* g, uint64_t* n_cells, uint64_t* n_values);
+int  pa_genes_values(const pa_genes* g, uint64_t* barcode, uint32_t* cell, uint32_t* gene, double* alpha, uint64_t cap);
+int  pa_genes_cell_iters(const pa_genes* g, uint32_t* iters);   /* [n_cells] */
+int  pa_genes_matrix(const pa_genes* g, uint32_t* cell, uint32_t* gene, double* value, uint64_t cap, uint64_t* n_entries);   /* arrays NULL: only *n_entries */
+int  pa_genes_stats(const pa_genes* g, uint64_t stats[PA_GENES_STATS]);
+int  pa_genes_write(const pa_genes* g, const pa_host_index* h, const char* out_dir);
+void pa_genes_destroy(pa_genes* g);
+/* The whole chain from two FASTQ files: pa_write_bus's reader, batches and stage seconds up to pa_bus_finish (no BUS file is written),
+ * then pa_genes_create_from_bus with pa_host_index_genes(h), pa_genes_run and pa_genes_write into out_dir. Stage seconds [4] = add_device
+ * + finish + the gene stage, [5] = writing. stats may be NULL. */
+int  pa_count_cells_em(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, uint32_t bc_len, uint32_t umi_len,
+                       const pa_genes_params* p, const char* out_dir, int num_threads, uint64_t stats[PA_GENES_STATS]);
+
 /* ---------------- transcript abundances: EM over the class-count table (bulk RNA-seq) ----------------
  * The reference stops at equivalence classes; this is the standard abundance model over them (the EM of kallisto / salmon) on the
  * GPU, in f64. Inputs: the dense table class_counts[pa_counts_len] and, optionally, the serialised overflow words (format below,

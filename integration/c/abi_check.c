@@ -156,6 +156,42 @@ int main(int argc, char** argv) {
         pa_quant_destroy(NULL);
     }
 
+    {   /* cells x genes from BUS records, host side: the defaults, the struct's layout, and the refusals that come before any device call, on a two-cell hand-made input */
+        pa_genes_params gp;
+        pa_genes* gg = NULL;
+        uint64_t gst[PA_GENES_STATS], gnc = 0, gnv = 0;
+        uint32_t git = 1;
+        /* cell 1: a molecule of gene 0, one of genes {0, 1}; cell 2: one molecule of two records whose genes meet in gene 1 */
+        const pa_bus_record two_cells[4] = {{1, 0, 0, 1, 0, 0}, {1, 1, 2, 3, 0, 0}, {2, 0, 2, 1, 0, 0}, {2, 0, 3, 1, 0, 0}};
+        pa_bus_record bad[4];
+        const uint64_t goff[5] = {0, 1, 2, 4, 6};
+        const uint32_t gids[6] = {0, 1, 0, 1, 1, 2}, gtx[3] = {0, 1, 2}, gtx_bad[3] = {0, 1, 3};
+        LAYOUT_STRUCT(pa_genes_params);
+        LAYOUT_FIELD(pa_genes_params, alpha_limit); LAYOUT_FIELD(pa_genes_params, alpha_change_limit); LAYOUT_FIELD(pa_genes_params, alpha_change);
+        LAYOUT_FIELD(pa_genes_params, min_iters); LAYOUT_FIELD(pa_genes_params, max_iters); LAYOUT_FIELD(pa_genes_params, check_every);
+        LAYOUT_FIELD(pa_genes_params, mode); LAYOUT_FIELD(pa_genes_params, reserved);
+        pa_genes_default_params(NULL);
+        pa_genes_default_params(&gp);
+        EXPECT(gp.min_iters == 50 && gp.max_iters == 10000 && gp.check_every == 10 && gp.alpha_limit == 1e-7 && gp.alpha_change == 1e-2 && gp.mode == PA_GENES_EM);
+        EXPECT(pa_genes_create(NULL, two_cells, 4, goff, gids, 4, 3, gtx, 3, 4, 4, &gp, NULL) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_genes_create(NULL, two_cells, 4, goff, gids, 4, 3, gtx, 3, 17, 16, &gp, &gg) == PA_ERR_INVALID_ARG && gg == NULL);
+        EXPECT(pa_genes_create(NULL, two_cells, 4, goff, gids, 4, 3, gtx_bad, 3, 4, 4, &gp, &gg) == PA_ERR_INVALID_ARG && strstr(pa_last_error(), "tx_gene[2]"));
+        EXPECT(pa_genes_create(NULL, two_cells, 4, goff, gids, 3, 3, gtx, 3, 4, 4, &gp, &gg) == PA_ERR_INVALID_ARG && strstr(pa_last_error(), "record 3"));
+        memcpy(bad, two_cells, sizeof bad);
+        bad[2].barcode = 1; bad[2].umi = 1;   /* equal to the record before it */
+        EXPECT(pa_genes_create(NULL, bad, 4, goff, gids, 4, 3, gtx, 3, 4, 4, &gp, &gg) == PA_ERR_INVALID_ARG && strstr(pa_last_error(), "record 2"));
+        gp.mode = 7;
+        EXPECT(pa_genes_create(NULL, two_cells, 4, goff, gids, 4, 3, gtx, 3, 4, 4, &gp, &gg) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_genes_create(NULL, two_cells, 4, goff, gids, 4, 3, gtx, 3, 4, 4, NULL, &gg) == (ndev < 1 ? PA_ERR_NO_DEVICE : PA_ERR_INVALID_ARG) && gg == NULL);
+        EXPECT(pa_genes_create_from_bus(NULL, gtx, 3, NULL, &gg) == PA_ERR_INVALID_ARG && gg == NULL);
+        EXPECT(pa_genes_step(NULL, 1) == PA_ERR_INVALID_ARG && pa_genes_run(NULL, &git, &gnc) == PA_ERR_INVALID_ARG && git == 0);
+        EXPECT(pa_genes_layout(NULL, &gnc, &gnv) == PA_ERR_INVALID_ARG && pa_genes_values(NULL, NULL, NULL, NULL, NULL, 0) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_genes_cell_iters(NULL, &git) == PA_ERR_INVALID_ARG && pa_genes_matrix(NULL, NULL, NULL, NULL, 0, &gnv) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_genes_stats(NULL, gst) == PA_ERR_INVALID_ARG && pa_genes_write(NULL, h, dir) == PA_ERR_INVALID_ARG);
+        pa_genes_destroy(NULL);
+        EXPECT(pa_count_cells_em(NULL, h, fastq, fastq, 4, 4, NULL, dir, 1, gst) == PA_ERR_INVALID_ARG);
+    }
+
     {   /* paired-end reads, host side: the checks that come before any device call */
         uint64_t pst[PA_PAIR_STATS], pu = 0, pn = 0, poff[2] = {0, 0};
         pa_read_result pr[1];
@@ -587,6 +623,34 @@ int main(int argc, char** argv) {
                 EXPECT(pa_bus_ecs(bus, eoff, eids, nids, &nids) == PA_OK && eoff[0] == 0 && eoff[necs] == nids && eids[0] == 0);
                 EXPECT(pa_bus_stats(bus, bst) == PA_OK && bst[0] == nsim && bst[0] == bst[1] + bst[2] + bst[3] + bst[4] + bst[5] + bst[6] && bst[7] == nrec);
                 EXPECT(pa_bus_write(bus, dir) == PA_OK);
+                {   /* the gene stage on those records where they lie, then on the two-cell hand-made input, then from the files */
+                    pa_genes* gg = NULL;
+                    uint64_t gst[PA_GENES_STATS], gnc = 0, gnv = 0, gne = 0, gnot = 0, gbc[2];
+                    uint32_t git = 0, gcell[4], ggene[4], giter[2];
+                    double gval[4];
+                    const pa_bus_record two_cells[4] = {{1, 0, 0, 1, 0, 0}, {1, 1, 2, 3, 0, 0}, {2, 0, 2, 1, 0, 0}, {2, 0, 3, 1, 0, 0}};
+                    const uint64_t goff[5] = {0, 1, 2, 4, 6};
+                    const uint32_t gids[6] = {0, 1, 0, 1, 1, 2}, gtx[3] = {0, 1, 2};
+                    EXPECT(pa_genes_create_from_bus(bus, tx_gene, ngenes, NULL, &gg) == PA_OK && gg);
+                    EXPECT(pa_genes_run(gg, &git, &gnot) == PA_OK && pa_genes_stats(gg, gst) == PA_OK && gst[0] == nrec && gst[1] == gst[2] + gst[3] + gst[4]);
+                    EXPECT(pa_genes_matrix(gg, NULL, NULL, NULL, 0, &gne) == PA_OK && gne == gst[14]);
+                    pa_genes_destroy(gg);
+                    gg = NULL;
+                    EXPECT(pa_genes_create(idx, two_cells, 4, goff, gids, 4, 3, gtx, 3, 4, 4, NULL, &gg) == PA_OK && gg);
+                    EXPECT(pa_genes_layout(gg, &gnc, &gnv) == PA_OK && gnc == 2 && gnv == 3);
+                    EXPECT(pa_genes_values(gg, gbc, gcell, ggene, gval, 2) == PA_ERR_BUFFER_TOO_SMALL);
+                    EXPECT(pa_genes_values(gg, gbc, gcell, ggene, gval, 4) == PA_OK && gbc[0] == 1 && gbc[1] == 2 && gcell[2] == 1 && ggene[2] == 1 && gval[2] == 1.0);
+                    EXPECT(gval[0] == 1.5 && gval[1] == 0.5);   /* u = (1, 0), M = 1 over |E| = 2 */
+                    EXPECT(pa_genes_matrix(gg, gcell, ggene, gval, 4, &gne) == PA_ERR_INVALID_ARG);
+                    EXPECT(pa_genes_step(gg, 1) == PA_OK && pa_genes_cell_iters(gg, giter) == PA_OK && giter[0] == 1 && giter[1] == 0);
+                    EXPECT(pa_genes_values(gg, NULL, NULL, NULL, gval, 4) == PA_OK && gval[0] > 1.74 && gval[0] < 1.76 && gval[0] + gval[1] > 1.999 && gval[0] + gval[1] < 2.001);
+                    EXPECT(pa_genes_run(gg, &git, &gnot) == PA_OK && git >= 51 && gnot == 0 && pa_genes_step(gg, 1) == PA_ERR_INVALID_ARG);
+                    EXPECT(pa_genes_matrix(gg, gcell, ggene, gval, 4, &gne) == PA_OK && gne >= 2 && gne <= 3 && gval[0] > 1.9);
+                    EXPECT(pa_genes_stats(gg, gst) == PA_OK && gst[0] == 4 && gst[1] == 3 && gst[5] == 2 && gst[6] == 1 && gst[7] == 1 && gst[14] == gne);
+                    EXPECT(pa_genes_write(gg, h, dir) == (ngenes == 3 ? PA_OK : PA_ERR_INVALID_ARG));
+                    pa_genes_destroy(gg);
+                    EXPECT(pa_count_cells_em(idx, h, fastq, fastq, 4, 4, NULL, dir, 2, gst) == PA_OK && gst[0] >= 1 && gst[1] == gst[2] + gst[3] + gst[4]);
+                }
                 EXPECT(pa_bus_add_device(bus, (const pa_read_result*)d_res, (const uint32_t*)d_arena, arena_cap, (const uint8_t*)d_r1, (const uint64_t*)d_r1o, nsim, NULL) == PA_ERR_INVALID_ARG);
                 pa_bus_destroy(bus);
                 free(rec); free(eoff); free(eids);

@@ -1,4 +1,4 @@
-//! Exporter + drop-in `process_reads` for the reference crate. Add `mod amd_ffi; mod amd;` to src/lib.rs (and `mod amd_pairs_ffi;` for `map_pairs`, `mod amd_strands_ffi;` for `map_pairs_unstranded`, `mod amd_bgzf_ffi;` for `bgzf_members`, `mod amd_bus_ffi;` for `write_bus`).
+//! Exporter + drop-in `process_reads` for the reference crate. Add `mod amd_ffi; mod amd;` to src/lib.rs (and `mod amd_pairs_ffi;` for `map_pairs`, `mod amd_strands_ffi;` for `map_pairs_unstranded`, `mod amd_bgzf_ffi;` for `bgzf_members`, `mod amd_bus_ffi;` for `write_bus`, `mod amd_genes_ffi;` for `count_cells_em`).
 //! The exporter only reads `pub` fields of `Pseudoaligner<K>` (src/pseudoaligner.rs:27-33); `dbg_index` (the boomphf MPHF,
 //! :30) is not exported: every hit is verified against the node sequence (:99-107), which makes it an exact dictionary that
 //! the library rebuilds. Not compiled in the image of this repository (no rustc): kept in step with
@@ -356,6 +356,35 @@ pub fn write_bus<P: AsRef<Path>>(index_file: P, r1_fastq: P, r2_fastq: P, out_di
     let mut stats = [0u64; PA_BUS_STATS];
     if rc >= 0 {
         rc = unsafe { pa_write_bus(idx, h, r1.as_ptr(), r2.as_ptr(), bc_len, umi_len, out.as_ptr(), num_threads as i32, stats.as_mut_ptr()) };
+    }
+    let result = check(rc).map(|_| stats);   // (the message is read before the handles go)
+    unsafe {
+        if !idx.is_null() { pa_index_destroy(idx); }
+        pa_host_index_destroy(h);
+    }
+    result
+}
+
+/// Cells x genes with fractional counts from files (pa_count_cells_em): `write_bus`'s records, never written, then per cell the
+/// molecules whose records agree on one gene counted for it and the others shared out by an EM (the `bustools count --genecounts --em`
+/// step) -> `out_dir`/matrix.mtx (real values), barcodes.tsv, features.tsv. No whitelist and no correction. `params`: None = the
+/// library's defaults (pa_quant_default_params', not tuned for single-cell data). Returns the sixteen counters of PA_GENES_STATS.
+pub fn count_cells_em<P: AsRef<Path>>(index_file: P, r1_fastq: P, r2_fastq: P, out_dir: P, bc_len: u32, umi_len: u32,
+                                      params: Option<crate::amd_genes_ffi::PaGenesParams>, num_threads: usize,
+                                      device: i32) -> Result<[u64; crate::amd_genes_ffi::PA_GENES_STATS], Error> {
+    use crate::amd_genes_ffi::*;
+    let cstr = |p: &P| CString::new(p.as_ref().to_string_lossy().into_owned());
+    let (ix, r1, r2, out) = (cstr(&index_file)?, cstr(&r1_fastq)?, cstr(&r2_fastq)?, cstr(&out_dir)?);
+    let mut h = std::ptr::null_mut();
+    check(unsafe { pa_host_index_load(ix.as_ptr(), &mut h) })?;
+    let mut view: PaFlatIndex = unsafe { std::mem::zeroed() };
+    let mut idx = std::ptr::null_mut();
+    let mut rc = unsafe { pa_host_index_view(h, &mut view) };
+    if rc >= 0 { rc = unsafe { pa_index_create(&view, device, &mut idx) }; }
+    let mut stats = [0u64; PA_GENES_STATS];
+    if rc >= 0 {
+        let p = params.as_ref().map_or(std::ptr::null(), |p| p as *const PaGenesParams);
+        rc = unsafe { pa_count_cells_em(idx, h, r1.as_ptr(), r2.as_ptr(), bc_len, umi_len, p, out.as_ptr(), num_threads as i32, stats.as_mut_ptr()) };
     }
     let result = check(rc).map(|_| stats);   // (the message is read before the handles go)
     unsafe {

@@ -23,7 +23,7 @@ from ._ffi import (PA_DEFAULT_ALLOWED_MISMATCHES, PA_ERR_ARENA_FULL, PA_MAPPED_B
 __all__ = ["HostIndex", "Txome", "Pseudoaligner", "build_index", "process_reads", "process_reads_multi", "PaError", "lib", "concat_reads",
            "gather_classes", "unpack_compact", "unpack_tiles", "RESULT_DTYPE", "PA_MAPPED_BIT", "PA_DEFAULT_ALLOWED_MISMATCHES",
            "PA_READ_COVERAGE_THRESHOLD", "PA_CLASS_REF", "Overflow", "Comm", "parse_overflow", "serialise_overflow", "overflow_merge",
-           "CellCounter", "load_whitelist", "Quantifier", "BusWriter", "BUS_RECORD_DTYPE"]
+           "CellCounter", "load_whitelist", "Quantifier", "BusWriter", "BUS_RECORD_DTYPE", "GeneCounter"]
 
 PA_CLASS_REF = 0x80000000
 RESULT_DTYPE = np.dtype([("coverage", "<u4"), ("mismatches", "<u4"), ("class_off", "<u4"), ("class_len", "<u4")])
@@ -478,6 +478,17 @@ class Pseudoaligner:
                                  st.ctypes.data))
         return dict(zip(_ffi.BUS_STAT_NAMES, (int(x) for x in st)))
 
+    def count_cells_em(self, host_index: HostIndex, r1: str, r2: str, out_dir: str, bc_len: int = 16, umi_len: int = 12, num_threads: int = 0,
+                       **params) -> dict:
+        """Paired R1 (barcode + UMI) / R2 (cDNA) FASTQ -> out_dir/matrix.mtx (real values), barcodes.tsv, features.tsv (pa_count_cells_em):
+        write_bus's records, never written, shared out over genes by a per-cell EM (GeneCounter). params: GeneCounter's. Returns the stats
+        (GeneCounter.stats)."""
+        p = _genes_params(params)
+        st = np.zeros(_ffi.PA_GENES_STATS, np.uint64)
+        check(lib().pa_count_cells_em(self._h, host_index._h, str(r1).encode(), str(r2).encode(), bc_len, umi_len, C.byref(p), str(out_dir).encode(), num_threads,
+                                      st.ctypes.data))
+        return dict(zip(_ffi.GENES_STAT_NAMES, (int(x) for x in st)))
+
     def quantify(self, d_counts: int, overflow: Optional["Overflow"] = None, **params) -> "Quantifier":
         """Transcript abundances from a class-count table on this GPU (d_counts: the device pointer the count launches accumulated into,
         their streams synchronised) and, optionally, the overflow table that was attached: copies the table back, fetches the overflow,
@@ -709,6 +720,115 @@ class BusWriter:
         try:
             if self._h:
                 lib().pa_bus_destroy(self._h)
+                self._h = vp()
+        except Exception:
+            pass
+
+
+def _genes_params(params: dict) -> "_ffi.GenesParams":
+    p = _ffi.GenesParams()
+    lib().pa_genes_default_params(C.byref(p))
+    for name, value in params.items():
+        if name not in dict(_ffi.GenesParams._fields_) or name == "reserved":
+            raise TypeError("unknown gene counter parameter %r" % name)
+        setattr(p, name, _ffi.GENES_MODES[value] if name == "mode" and isinstance(value, str) else value)
+    return p
+
+
+class GeneCounter:
+    """Cells x genes from BUS records on the index's GPU (pa_genes): molecules whose records agree on one gene count for it, the others
+    are shared out by an EM per cell. from_bus() / from_arrays(), then step() / run(), then values() / matrix() / write(). params: the fields
+    of pa_genes_params (alpha_limit, alpha_change_limit, alpha_change, min_iters, max_iters, check_every, mode = "em" | "unique"); what is
+    not given keeps the library's default."""
+
+    def __init__(self):
+        self._h = vp()
+        self._keep = ()
+
+    @classmethod
+    def from_bus(cls, writer: "BusWriter", tx_gene, num_genes: int, **params) -> "GeneCounter":
+        """the records of a BusWriter (finished here if it is not yet) where they lie in HBM, with the writer's ec table;
+        tx_gene[transcripts] < num_genes (HostIndex.genes())"""
+        g = cls()
+        if writer is not None:
+            writer.finish()
+        p = _genes_params(params)
+        tg = np.ascontiguousarray(tx_gene, np.uint32)
+        g.params = p
+        check(lib().pa_genes_create_from_bus(writer._h if writer is not None else None, tg.ctypes.data if len(tg) else None, num_genes, C.byref(p), C.byref(g._h)))
+        g._keep = (writer._aligner,)
+        return g
+
+    @classmethod
+    def from_arrays(cls, aligner: "Pseudoaligner", records, ec_offsets, ec_ids, tx_gene, num_genes: int, bc_len: int, umi_len: int, **params) -> "GeneCounter":
+        """host arrays of any origin: records (BUS_RECORD_DTYPE, strictly ascending by barcode, UMI, ec), the ec table as a CSR, tx_gene.
+        The files of a BUS run, for instance:
+            records = np.fromfile("output.bus", BUS_RECORD_DTYPE, offset=20)        # 20 header bytes when tlen = 0
+            lists = [[int(t) for t in line.split("\t")[1].split(",")] for line in open("matrix.ec")]
+            ec_offsets = np.cumsum([0] + [len(l) for l in lists]); ec_ids = np.concatenate(lists)"""
+        g = cls()
+        p = _genes_params(params)
+        rec = np.ascontiguousarray(records, BUS_RECORD_DTYPE)
+        off = np.ascontiguousarray(ec_offsets, np.uint64)
+        ids = np.ascontiguousarray(ec_ids, np.uint32)
+        tg = np.ascontiguousarray(tx_gene, np.uint32)
+        g.params = p
+        check(lib().pa_genes_create(aligner._h if aligner is not None else None, rec.ctypes.data if len(rec) else None, len(rec), off.ctypes.data if len(off) else None,
+                                    ids.ctypes.data if len(ids) else None, max(len(off), 1) - 1, len(tg), tg.ctypes.data if len(tg) else None, num_genes, bc_len, umi_len,
+                                    C.byref(p), C.byref(g._h)))
+        g._keep = (aligner,)
+        return g
+
+    def step(self, n_iters: int = 1) -> None:
+        """every cell with multi rows, exactly n iterations: no stop rule, no freeze"""
+        check(lib().pa_genes_step(self._h, n_iters))
+
+    def run(self) -> Tuple[int, int]:
+        """the stop rule per cell + truncation -> (most iterations run by a cell, cells not converged)"""
+        it, nc = C.c_uint32(), C.c_uint64()
+        check(lib().pa_genes_run(self._h, C.byref(it), C.byref(nc)))
+        return it.value, nc.value
+
+    def layout(self) -> Tuple[int, int]:
+        """(cells, values)"""
+        nc, nv = C.c_uint64(), C.c_uint64()
+        check(lib().pa_genes_layout(self._h, C.byref(nc), C.byref(nv)))
+        return nc.value, nv.value
+
+    def values(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """(barcode[cells], cell, gene, alpha): the current alpha of every (cell, gene) that has a row, sorted, zeros kept"""
+        nc, nv = self.layout()
+        bc, cell, gene, alpha = np.zeros(max(nc, 1), np.uint64), np.zeros(max(nv, 1), np.uint32), np.zeros(max(nv, 1), np.uint32), np.zeros(max(nv, 1), np.float64)
+        check(lib().pa_genes_values(self._h, bc.ctypes.data, cell.ctypes.data, gene.ctypes.data, alpha.ctypes.data, nv))
+        return bc[:nc], cell[:nv], gene[:nv], alpha[:nv]
+
+    def cell_iters(self) -> np.ndarray:
+        nc, _ = self.layout()
+        it = np.zeros(max(nc, 1), np.uint32)
+        check(lib().pa_genes_cell_iters(self._h, it.ctypes.data))
+        return it[:nc]
+
+    def matrix(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """after run(): (cell, gene, value) sorted by (cell, gene), zeros dropped"""
+        n = C.c_uint64()
+        check(lib().pa_genes_matrix(self._h, None, None, None, 0, C.byref(n)))
+        cell, gene, value = np.zeros(max(n.value, 1), np.uint32), np.zeros(max(n.value, 1), np.uint32), np.zeros(max(n.value, 1), np.float64)
+        check(lib().pa_genes_matrix(self._h, cell.ctypes.data, gene.ctypes.data, value.ctypes.data, n.value, C.byref(n)))
+        return cell[:n.value], gene[:n.value], value[:n.value]
+
+    def stats(self) -> dict:
+        st = np.zeros(_ffi.PA_GENES_STATS, np.uint64)
+        check(lib().pa_genes_stats(self._h, st.ctypes.data))
+        return dict(zip(_ffi.GENES_STAT_NAMES, (int(x) for x in st)))
+
+    def write(self, host_index: HostIndex, out_dir: str) -> None:
+        """after run(): out_dir/matrix.mtx, barcodes.tsv, features.tsv"""
+        check(lib().pa_genes_write(self._h, host_index._h if host_index is not None else None, str(out_dir).encode()))
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib().pa_genes_destroy(self._h)
                 self._h = vp()
         except Exception:
             pass

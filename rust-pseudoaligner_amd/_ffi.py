@@ -64,6 +64,11 @@ class QuantParams(C.Structure):
                 ("min_iters", C.c_uint32), ("max_iters", C.c_uint32), ("check_every", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class GenesParams(C.Structure):
+    _fields_ = [("alpha_limit", C.c_double), ("alpha_change_limit", C.c_double), ("alpha_change", C.c_double),
+                ("min_iters", C.c_uint32), ("max_iters", C.c_uint32), ("check_every", C.c_uint32), ("mode", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class BgzfMember(C.Structure):
     _fields_ = [("in_off", C.c_uint64), ("out_off", C.c_uint64), ("file_off", C.c_uint64), ("in_len", C.c_uint32), ("out_len", C.c_uint32),
                 ("crc32", C.c_uint32), ("reserved", C.c_uint32)]
@@ -72,6 +77,11 @@ class BgzfMember(C.Structure):
 INFLATE_STATUS_NAMES = ("OK", "BAD_MEMBER", "BAD_BLOCK_TYPE", "STORED_LEN", "TOO_MANY_SYMBOLS", "BAD_CODE_LENGTHS", "BAD_REPEAT", "NO_END_OF_BLOCK", "BAD_SYMBOL",
                         "DISTANCE_TOO_FAR", "INPUT_EXHAUSTED", "TRAILING_INPUT", "OUTPUT_TOO_LONG", "OUTPUT_TOO_SHORT", "CRC_MISMATCH")   # PA_INFLATE_*: the index is the code
 PA_QUANT_STATS = 8
+PA_GENES_EM, PA_GENES_UNIQUE = 0, 1
+GENES_MODES = {"em": PA_GENES_EM, "unique": PA_GENES_UNIQUE}
+PA_GENES_STATS = 16
+GENES_STAT_NAMES = ("records", "molecules", "molecules_dropped", "unique_gene_molecules", "multi_gene_molecules", "cells", "cells_with_multi_rows", "multi_rows",
+                    "multi_row_ids", "longest_multi_row", "largest_degree", "largest_cell", "most_iterations", "cells_not_converged", "matrix_entries", "cells_in_hbm")
 PA_PAIR_FR, PA_PAIR_RF, PA_PAIR_FF = 0, 1, 2
 PAIR_ORIENTATIONS = {"fr": PA_PAIR_FR, "rf": PA_PAIR_RF, "ff": PA_PAIR_FF}
 PA_PAIR_STATS = 8
@@ -177,6 +187,19 @@ SIGNATURES = {
     "pa_bus_write": (C.c_int, [vp, C.c_char_p]),
     "pa_bus_destroy": (None, [vp]),
     "pa_write_bus": (C.c_int, [vp, vp, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, vp]),
+    "pa_genes_default_params": (None, [C.POINTER(GenesParams)]),
+    "pa_genes_create": (C.c_int, [vp, vp, C.c_uint64, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(GenesParams), C.POINTER(vp)]),
+    "pa_genes_create_from_bus": (C.c_int, [vp, vp, C.c_uint32, C.POINTER(GenesParams), C.POINTER(vp)]),
+    "pa_genes_step": (C.c_int, [vp, C.c_uint32]),
+    "pa_genes_run": (C.c_int, [vp, u32p, u64p]),
+    "pa_genes_layout": (C.c_int, [vp, u64p, u64p]),
+    "pa_genes_values": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint64]),
+    "pa_genes_cell_iters": (C.c_int, [vp, vp]),
+    "pa_genes_matrix": (C.c_int, [vp, vp, vp, vp, C.c_uint64, u64p]),
+    "pa_genes_stats": (C.c_int, [vp, vp]),
+    "pa_genes_write": (C.c_int, [vp, vp, C.c_char_p]),
+    "pa_genes_destroy": (None, [vp]),
+    "pa_count_cells_em": (C.c_int, [vp, vp, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(GenesParams), C.c_char_p, C.c_int, vp]),
     "pa_quant_default_params": (None, [C.POINTER(QuantParams)]),
     "pa_quant_create": (C.c_int, [vp, vp, C.POINTER(QuantParams), C.POINTER(vp)]),
     "pa_quant_set_counts": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64]),

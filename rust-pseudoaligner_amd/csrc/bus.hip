@@ -426,6 +426,14 @@ int bus_finish(pa_bus* b) {
 
 }  // namespace
 
+int pa::bus_finished_view(const pa_bus* b, int* device, const pa_bus_record** d_records, uint64_t* n_records, const bus::EcTable** table, uint32_t* bc_len,
+                          uint32_t* umi_len, uint32_t* num_tx) {
+    if (!b->finished) return fail(PA_ERR_INVALID_ARG, "the records exist after pa_bus_finish");
+    *device = b->device; *d_records = b->d_records.get(); *n_records = b->n_records; *table = &b->table;
+    *bc_len = b->bc_len; *umi_len = b->umi_len; *num_tx = b->num_tx;
+    return PA_OK;
+}
+
 extern "C" {
 
 int pa_bus_create(pa_index* idx, const pa_host_index* h, uint32_t bc_len, uint32_t umi_len, pa_bus** out) {

@@ -48,4 +48,10 @@ int write_files(const char* out_dir, uint32_t bc_len, uint32_t umi_len, const pa
                 const std::vector<std::string>& names);
 
 }  // namespace bus
+
+// bus.hip: what a finished writer holds, for the gene counter (genes.hip): its device, the records in HBM, the ec table, the lengths and the
+// index's transcripts. PA_ERR_INVALID_ARG before pa_bus_finish
+int bus_finished_view(const pa_bus* b, int* device, const pa_bus_record** d_records, uint64_t* n_records, const bus::EcTable** table, uint32_t* bc_len, uint32_t* umi_len,
+                      uint32_t* num_tx);
+
 }  // namespace pa

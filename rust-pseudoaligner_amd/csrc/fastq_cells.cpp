@@ -1,5 +1,6 @@
 // The barcoded drivers over PAIRED FASTQ files: R1 is a prefix of barcode + UMI bytes that is never encoded or mapped, R2 is mapped. pa_count_cells -> the
-// cells x genes UMI matrix (pa_cell_counter), pa_write_bus -> sorted (barcode, UMI, class) records (pa_bus); with the barcode whitelist's reader. Reader,
+// cells x genes UMI matrix (pa_cell_counter), pa_write_bus -> sorted (barcode, UMI, class) records (pa_bus), pa_count_cells_em -> those records shared out
+// over genes by a per-cell EM (pa_genes); with the barcode whitelist's reader. Reader,
 // batches, loop and call frame are pair_reader.hpp's; a mapping that ran out of arena goes through map_finish_regrow (hip_buffer.hpp).
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
@@ -212,9 +213,11 @@ int count_cells_impl(pa_index* idx, const pa_host_index* h, const char* r1_path,
     return PA_OK;
 }
 
-// ---- pa_write_bus: the same two files -> sorted (barcode, UMI, ec) records, output.bus + matrix.ec + transcripts.txt ----
-int write_bus_impl(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, uint32_t bc_len, uint32_t umi_len, const char* out_dir,
-                   int num_threads, uint64_t* stats) {
+// ---- pa_write_bus / pa_count_cells_em: the same two files -> sorted (barcode, UMI, ec) records in HBM, then `after(bus, st)`: the writer's three files, or
+// the gene stage and its three files (after() adds its own seconds to st[ST_TALLY] / st[ST_WRITE]) ----
+template <class After>
+int bus_run(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, uint32_t bc_len, uint32_t umi_len, const char* out_dir, int num_threads,
+            After&& after) {
     std::unique_ptr<pa_bus, void (*)(pa_bus*)> own(nullptr, pa_bus_destroy);   // (in front of the frame: destroyed behind its streams)
     PairedCall call(num_threads);
     double* const st = call.st;
@@ -238,12 +241,43 @@ int write_bus_impl(pa_index* idx, const pa_host_index* h, const char* r1_path, c
     uint32_t n_ecs = 0;
     if ((rc = pa_bus_finish(bus, &n_records, &n_ecs)) != PA_OK) return rc;
     st[ST_TALLY] += now() - t0;
-    t0 = now();
-    if ((rc = pa_bus_write(bus, out_dir)) != PA_OK) return rc;
-    st[ST_WRITE] = now() - t0;
-    if (stats) (void)pa_bus_stats(bus, stats);
+    if ((rc = after(bus, st)) != PA_OK) return rc;
     call.done();
     return PA_OK;
+}
+
+int write_bus_impl(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, uint32_t bc_len, uint32_t umi_len, const char* out_dir,
+                   int num_threads, uint64_t* stats) {
+    return bus_run(idx, h, r1_path, r2_path, bc_len, umi_len, out_dir, num_threads, [&](pa_bus* bus, double* st) {
+        const double t0 = now();
+        const int rc = pa_bus_write(bus, out_dir);
+        if (rc != PA_OK) return rc;
+        st[ST_WRITE] = now() - t0;
+        if (stats) (void)pa_bus_stats(bus, stats);
+        return (int)PA_OK;
+    });
+}
+
+int count_cells_em_impl(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, uint32_t bc_len, uint32_t umi_len, const pa_genes_params* p,
+                        const char* out_dir, int num_threads, uint64_t* stats) {
+    return bus_run(idx, h, r1_path, r2_path, bc_len, umi_len, out_dir, num_threads, [&](pa_bus* bus, double* st) {
+        double t0 = now();
+        const uint32_t ntx = pa_host_index_num_transcripts(h);
+        std::vector<uint32_t> tx_gene(ntx ? ntx : 1);
+        uint32_t num_genes = 0;
+        int rc = pa_host_index_genes(h, tx_gene.data(), &num_genes);
+        if (rc != PA_OK) return rc;
+        pa_genes* g = nullptr;
+        if ((rc = pa_genes_create_from_bus(bus, tx_gene.data(), num_genes, p, &g)) != PA_OK) return rc;
+        std::unique_ptr<pa_genes, void (*)(pa_genes*)> own(g, pa_genes_destroy);
+        if ((rc = pa_genes_run(g, nullptr, nullptr)) != PA_OK) return rc;
+        st[ST_TALLY] += now() - t0;
+        t0 = now();
+        if ((rc = pa_genes_write(g, h, out_dir)) != PA_OK) return rc;
+        st[ST_WRITE] = now() - t0;
+        if (stats) (void)pa_genes_stats(g, stats);
+        return (int)PA_OK;
+    });
 }
 
 }  // namespace
@@ -256,4 +290,9 @@ extern "C" int pa_count_cells(pa_index* idx, const pa_host_index* h, const char*
 extern "C" int pa_write_bus(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, uint32_t bc_len, uint32_t umi_len, const char* out_dir,
                             int num_threads, uint64_t stats[PA_BUS_STATS]) {
     return no_throw("pa_write_bus", [&] { return write_bus_impl(idx, h, r1_path, r2_path, bc_len, umi_len, out_dir, num_threads, stats); });
+}
+
+extern "C" int pa_count_cells_em(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, uint32_t bc_len, uint32_t umi_len, const pa_genes_params* p,
+                                 const char* out_dir, int num_threads, uint64_t stats[PA_GENES_STATS]) {
+    return no_throw("pa_count_cells_em", [&] { return count_cells_em_impl(idx, h, r1_path, r2_path, bc_len, umi_len, p, out_dir, num_threads, stats); });
 }
