@@ -579,6 +579,52 @@ void pa_bus_destroy(pa_bus* b);
 int pa_write_bus(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, uint32_t bc_len, uint32_t umi_len,
                  const char* out_dir, int num_threads, uint64_t stats[PA_BUS_STATS]);
 
+/* ---------------- BUS barcode correction against a whitelist, then the collapse again ----------------
+ * The `bustools correct` + re-sort step between pa_bus_finish and the gene counter, on the records where they lie.
+ *   whitelist  n_whitelist barcodes of bc_len bases in BUS packing (2 bits per base, A=0 C=1 G=2 T=3, first base most significant),
+ *              1 <= n_whitelist <= 2^31 - 1. A value >= 4^bc_len or a value that comes twice is PA_ERR_INVALID_ARG; the message names the
+ *              entry, for a duplicate the smaller index of the two. bc_len / umi_len limits are pa_bus_create's (else PA_ERR_UNSUPPORTED)
+ *   barcode    per DISTINCT barcode of the input, the first rule that applies decides (the wording is the cell counter's):
+ *                exact      it is in the whitelist: it stays
+ *                corrected  exactly one of its 3 bc_len single substitutions is in the whitelist: it becomes that one
+ *                none       no such substitution: every record of it is dropped
+ *                ambiguous  two or more: every record of it is dropped
+ *              A BUS record never holds an N (pa_bus drops such reads), so the cell counter's rule for one N has no counterpart here
+ *   output     every surviving record carries its target barcode; records that now share (barcode, UMI, ec) become one whose count is the
+ *              64-bit sum clamped at 2^32 - 1 (pa_bus_finish's rule); strictly ascending by (barcode, UMI, ec), flags = pad = 0. The ec
+ *              table is untouched: an ec that no longer occurs stays in matrix.ec, as with bustools. There is NO UMI correction
+ *   stats[PA_BUS_CORRECT_STATS]: [0] records in, [1] reads in (the sum of the counts, u64), [2] distinct barcodes in, [3] barcodes exact,
+ *              [4] barcodes corrected, [5] barcodes without a neighbour, [6] barcodes ambiguous, [7] records of exact barcodes, [8] records
+ *              of corrected barcodes, [9] records dropped, [10] reads dropped, [11] records out, [12] distinct barcodes out;
+ *              [2] = [3] + [4] + [5] + [6], [0] = [7] + [8] + [9], [11] <= [7] + [8]
+ *   independence  the result is a pure function of (records, whitelist as a set): the order of the whitelist does not matter, and two
+ *              runs give the same bytes
+ * pa_bus_whitelist_pack (host): n * bc_len bytes without separators, as pa_whitelist_load leaves them -> packed[n]; a byte that is not
+ * A, C, G or T is PA_ERR_INVALID_ARG naming the entry; bc_len outside 1..31 PA_ERR_UNSUPPORTED.
+ * pa_bus_correct_records: host arrays of any origin; idx names the GPU, as for pa_genes_create. in[n] must be strictly ascending by
+ * (barcode, UMI, ec) with every barcode < 4^bc_len and every UMI < 4^umi_len, else PA_ERR_INVALID_ARG naming the first offending record;
+ * n = 0 is legal. out NULL: only *n_out and the stats; cap < *n_out: PA_ERR_BUFFER_TOO_SMALL (*n_out is set). More than 2^31 - 1
+ * records: PA_ERR_UNSUPPORTED. Every host argument is checked before any device call; without a GPU a valid call returns
+ * PA_ERR_NO_DEVICE (before idx is looked at). stats may be NULL.
+ * pa_bus_correct: in place on a finished writer (PA_ERR_INVALID_ARG before pa_bus_finish). Afterwards pa_bus_records, pa_bus_write and
+ * pa_genes_create_from_bus see the corrected records, and a second pa_bus_finish and pa_bus_stats[7] report their number. A failing call
+ * leaves the writer as it was. A second call with the same whitelist changes nothing: every barcode is exact.
+ * pa_bus_correct_phase_ms: the GPU milliseconds of this thread's last correction: [0] whitelist table (upload, sort, insert), [1] distinct
+ * barcodes + the exact probe + the miss list, [2] the neighbour probes of the missed barcodes, [3] rewrite + sort + collapse + records.
+ * pa_write_bus_corrected: pa_write_bus with pa_whitelist_load(whitelist_path) -> pa_bus_whitelist_pack -> pa_bus_correct after
+ * pa_bus_finish (stage seconds [4] include it). pa_whitelist_load stops at 16 bases: bc_len > 16 is PA_ERR_UNSUPPORTED for the file-level
+ * calls only. Either stats may be NULL; bus_stats[7] is the number of corrected records. */
+#define PA_BUS_CORRECT_STATS 13
+#define PA_BUS_CORRECT_PHASES 4
+int pa_bus_whitelist_pack(const char* whitelist, uint64_t n, uint32_t bc_len, uint64_t* packed);
+int pa_bus_correct_records(pa_index* idx, const pa_bus_record* in, uint64_t n, uint32_t bc_len, uint32_t umi_len, const uint64_t* whitelist,
+                           uint64_t n_whitelist, pa_bus_record* out, uint64_t cap, uint64_t* n_out, uint64_t stats[PA_BUS_CORRECT_STATS]);
+int pa_bus_correct(pa_bus* finished, const uint64_t* whitelist, uint64_t n_whitelist, uint64_t stats[PA_BUS_CORRECT_STATS]);
+int pa_bus_correct_phase_ms(float out[PA_BUS_CORRECT_PHASES]);
+int pa_write_bus_corrected(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const char* whitelist_path,
+                           uint32_t bc_len, uint32_t umi_len, const char* out_dir, int num_threads, uint64_t bus_stats[PA_BUS_STATS],
+                           uint64_t correct_stats[PA_BUS_CORRECT_STATS]);
+
 /* ---------------- cells x genes from BUS records: multi-gene UMIs shared out by EM ----------------
  * The `bustools count --genecounts --em` step on the records where they lie: where pa_cell_counter drops a read whose class spans two
  * genes, this keeps the molecule and lets a per-cell EM divide it among its genes.
@@ -653,6 +699,11 @@ void pa_genes_destroy(pa_genes* g);
  * + finish + the gene stage, [5] = writing. stats may be NULL. */
 int  pa_count_cells_em(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, uint32_t bc_len, uint32_t umi_len,
                        const pa_genes_params* p, const char* out_dir, int num_threads, uint64_t stats[PA_GENES_STATS]);
+/* ... with the barcodes corrected against a whitelist file between pa_bus_finish and the gene stage (the BUS barcode correction section
+ * above; pa_write_bus_corrected's rules for whitelist_path and bc_len). Either stats may be NULL. */
+int  pa_count_cells_em_corrected(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const char* whitelist_path,
+                                 uint32_t bc_len, uint32_t umi_len, const pa_genes_params* p, const char* out_dir, int num_threads,
+                                 uint64_t genes_stats[PA_GENES_STATS], uint64_t correct_stats[PA_BUS_CORRECT_STATS]);
 
 /* ---------------- transcript abundances: EM over the class-count table (bulk RNA-seq) ----------------
  * The reference stops at equivalence classes; this is the standard abundance model over them (the EM of kallisto / salmon) on the

@@ -192,6 +192,34 @@ int main(int argc, char** argv) {
         EXPECT(pa_count_cells_em(NULL, h, fastq, fastq, 4, 4, NULL, dir, 1, gst) == PA_ERR_INVALID_ARG);
     }
 
+    {   /* BUS barcode correction, host side: the packer, and every refusal that comes before a device call */
+        uint64_t wlp[3] = {0, 0, 0}, cst13[PA_BUS_CORRECT_STATS], cn = 7;
+        float cms[PA_BUS_CORRECT_PHASES];
+        const uint64_t cwl[3] = {27, 255, 164}, cwl_dup[3] = {27, 255, 27}, cwl_big[3] = {27, 256, 164};   /* ACGT TTTT GGCA */
+        const pa_bus_record crec[3] = {{26, 0, 0, 1, 0, 0}, {27, 0, 0, 2, 0, 0}, {27, 1, 0, 1, 0, 0}};
+        pa_bus_record cbad[3], cout[3];
+        EXPECT(PA_BUS_CORRECT_STATS == 13 && PA_BUS_CORRECT_PHASES == 4);
+        EXPECT(pa_bus_whitelist_pack("ACGTTTTTGGCA", 3, 4, wlp) == PA_OK && wlp[0] == 27 && wlp[1] == 255 && wlp[2] == 164);
+        EXPECT(pa_bus_whitelist_pack("ACGTTTNTGGCA", 3, 4, wlp) == PA_ERR_INVALID_ARG && strstr(pa_last_error(), "entry 1"));
+        EXPECT(pa_bus_whitelist_pack("ACGT", 1, 32, wlp) == PA_ERR_UNSUPPORTED);
+        EXPECT(pa_bus_correct_records(NULL, crec, 3, 4, 4, cwl, 3, cout, 3, NULL, cst13) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_bus_correct_records(NULL, crec, 3, 17, 16, cwl, 3, cout, 3, &cn, cst13) == PA_ERR_UNSUPPORTED && cn == 0);
+        EXPECT(pa_bus_correct_records(NULL, crec, 3, 4, 4, cwl_dup, 3, cout, 3, &cn, cst13) == PA_ERR_INVALID_ARG && strstr(pa_last_error(), "entry 0"));
+        EXPECT(pa_bus_correct_records(NULL, crec, 3, 4, 4, cwl_big, 3, cout, 3, &cn, cst13) == PA_ERR_INVALID_ARG && strstr(pa_last_error(), "entry 1"));
+        EXPECT(pa_bus_correct_records(NULL, crec, 3, 4, 4, cwl, 0, cout, 3, &cn, cst13) == PA_ERR_INVALID_ARG);
+        memcpy(cbad, crec, sizeof cbad);
+        cbad[2].umi = 0;   /* equal to the record before it */
+        EXPECT(pa_bus_correct_records(NULL, cbad, 3, 4, 4, cwl, 3, cout, 3, &cn, cst13) == PA_ERR_INVALID_ARG && strstr(pa_last_error(), "record 2"));
+        cbad[2].umi = 256;   /* no UMI of 4 bases */
+        EXPECT(pa_bus_correct_records(NULL, cbad, 3, 4, 4, cwl, 3, cout, 3, &cn, cst13) == PA_ERR_INVALID_ARG && strstr(pa_last_error(), "record 2"));
+        EXPECT(pa_bus_correct_records(NULL, crec, 3, 4, 4, cwl, 3, cout, 3, &cn, cst13) == (ndev < 1 ? PA_ERR_NO_DEVICE : PA_ERR_INVALID_ARG) && cn == 0);
+        EXPECT(pa_bus_correct(NULL, cwl, 3, cst13) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_bus_correct_phase_ms(NULL) == PA_ERR_INVALID_ARG && pa_bus_correct_phase_ms(cms) == PA_OK);
+        snprintf(path, sizeof path, "%s/abi_check_whitelist.txt", dir);
+        EXPECT(pa_write_bus_corrected(NULL, h, fastq, fastq, path, 4, 4, dir, 1, NULL, cst13) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_count_cells_em_corrected(NULL, h, fastq, fastq, path, 4, 4, NULL, dir, 1, NULL, cst13) == PA_ERR_INVALID_ARG);
+    }
+
     {   /* paired-end reads, host side: the checks that come before any device call */
         uint64_t pst[PA_PAIR_STATS], pu = 0, pn = 0, poff[2] = {0, 0};
         pa_read_result pr[1];
@@ -623,6 +651,18 @@ int main(int argc, char** argv) {
                 EXPECT(pa_bus_ecs(bus, eoff, eids, nids, &nids) == PA_OK && eoff[0] == 0 && eoff[necs] == nids && eids[0] == 0);
                 EXPECT(pa_bus_stats(bus, bst) == PA_OK && bst[0] == nsim && bst[0] == bst[1] + bst[2] + bst[3] + bst[4] + bst[5] + bst[6] && bst[7] == nrec);
                 EXPECT(pa_bus_write(bus, dir) == PA_OK);
+                {   /* corrected in place against every barcode of 4 bases but the first record's: nothing else changes; then the identity */
+                    uint64_t* all = (uint64_t*)calloc(256, 8);
+                    uint64_t cst13[PA_BUS_CORRECT_STATS], n_all = 0, nrec2 = 0;
+                    uint32_t necs2 = 0;
+                    for (uint64_t v = 0; v < 256; ++v) if (v != rec[0].barcode) all[n_all++] = v;
+                    EXPECT(pa_bus_correct(bus, all, n_all, cst13) == PA_OK && cst13[0] == nrec && cst13[6] == 1 && cst13[4] == 0 && cst13[11] < nrec);
+                    EXPECT(pa_bus_finish(bus, &nrec2, &necs2) == PA_OK && nrec2 == cst13[11] && necs2 == necs);
+                    EXPECT(pa_bus_correct(bus, all, n_all, cst13) == PA_OK && cst13[0] == nrec2 && cst13[11] == nrec2 && cst13[3] == cst13[2]);
+                    EXPECT(pa_bus_stats(bus, bst) == PA_OK && bst[7] == nrec2);
+                    nrec = nrec2;
+                    free(all);
+                }
                 {   /* the gene stage on those records where they lie, then on the two-cell hand-made input, then from the files */
                     pa_genes* gg = NULL;
                     uint64_t gst[PA_GENES_STATS], gnc = 0, gnv = 0, gne = 0, gnot = 0, gbc[2];
@@ -655,6 +695,24 @@ int main(int argc, char** argv) {
                 pa_bus_destroy(bus);
                 free(rec); free(eoff); free(eids);
                 EXPECT(pa_write_bus(idx, h, fastq, fastq, 4, 4, dir, 2, bst) == PA_OK && bst[0] == nreads && bst[0] == bst[1] + bst[2] + bst[3] + bst[4] + bst[5] + bst[6]);
+                {   /* barcode correction: three hand-made records against ACGT TTTT GGCA, then the file-level entries with the whitelist file */
+                    const uint64_t cwl[3] = {27, 255, 164};
+                    const pa_bus_record crec[4] = {{26, 0, 0, 1, 0, 0}, {27, 0, 0, 2, 0, 0}, {27, 1, 0, 1, 0, 0}, {90, 0, 0, 5, 0, 0}};   /* ACGG -> ACGT; ACGT; CCGG: none */
+                    pa_bus_record cout[4];
+                    uint64_t cn = 0, cst13[PA_BUS_CORRECT_STATS], gst[PA_GENES_STATS];
+                    float cms[PA_BUS_CORRECT_PHASES];
+                    EXPECT(pa_bus_correct_records(idx, crec, 4, 4, 4, cwl, 3, cout, 1, &cn, cst13) == PA_ERR_BUFFER_TOO_SMALL && cn == 2);
+                    EXPECT(pa_bus_correct_records(idx, crec, 4, 4, 4, cwl, 3, cout, 4, &cn, cst13) == PA_OK && cn == 2);
+                    EXPECT(cout[0].barcode == 27 && cout[0].umi == 0 && cout[0].count == 3 && cout[1].umi == 1 && cout[1].count == 1 && cout[1].flags == 0);
+                    EXPECT(cst13[0] == 4 && cst13[1] == 9 && cst13[2] == 3 && cst13[3] == 1 && cst13[4] == 1 && cst13[5] == 1 && cst13[6] == 0 && cst13[9] == 1 && cst13[10] == 5 &&
+                           cst13[11] == 2 && cst13[12] == 1);
+                    EXPECT(pa_bus_correct_phase_ms(cms) == PA_OK && cms[0] >= 0.0f);
+                    snprintf(path, sizeof path, "%s/abi_check_whitelist.txt", dir);
+                    EXPECT(pa_write_bus_corrected(idx, h, fastq, fastq, path, 4, 4, dir, 2, bst, cst13) == PA_OK && bst[0] == nreads && cst13[11] == bst[7] &&
+                           cst13[2] == cst13[3] + cst13[4] + cst13[5] + cst13[6] && cst13[0] == cst13[7] + cst13[8] + cst13[9]);
+                    EXPECT(pa_write_bus_corrected(idx, h, fastq, fastq, path, 17, 4, dir, 2, bst, cst13) == PA_ERR_UNSUPPORTED);
+                    EXPECT(pa_count_cells_em_corrected(idx, h, fastq, fastq, path, 4, 4, NULL, dir, 2, gst, cst13) == PA_OK && gst[0] == cst13[11]);
+                }
             }
             free(mc); free(mg); free(mu); free(r1); free(r1o);
             EXPECT(pa_device_free(d_r1) == PA_OK && pa_device_free(d_r1o) == PA_OK);

@@ -1,4 +1,4 @@
-//! Exporter + drop-in `process_reads` for the reference crate. Add `mod amd_ffi; mod amd;` to src/lib.rs (and `mod amd_pairs_ffi;` for `map_pairs`, `mod amd_strands_ffi;` for `map_pairs_unstranded`, `mod amd_bgzf_ffi;` for `bgzf_members`, `mod amd_bus_ffi;` for `write_bus`, `mod amd_genes_ffi;` for `count_cells_em`).
+//! Exporter + drop-in `process_reads` for the reference crate. Add `mod amd_ffi; mod amd;` to src/lib.rs (and `mod amd_pairs_ffi;` for `map_pairs`, `mod amd_strands_ffi;` for `map_pairs_unstranded`, `mod amd_bgzf_ffi;` for `bgzf_members`, `mod amd_bus_ffi;` for `write_bus`, `mod amd_genes_ffi;` for `count_cells_em`, `mod amd_correct_ffi;` for `write_bus_corrected` / `count_cells_em_corrected`).
 //! The exporter only reads `pub` fields of `Pseudoaligner<K>` (src/pseudoaligner.rs:27-33); `dbg_index` (the boomphf MPHF,
 //! :30) is not exported: every hit is verified against the node sequence (:99-107), which makes it an exact dictionary that
 //! the library rebuilds. Not compiled in the image of this repository (no rustc): kept in step with
@@ -387,6 +387,63 @@ pub fn count_cells_em<P: AsRef<Path>>(index_file: P, r1_fastq: P, r2_fastq: P, o
         rc = unsafe { pa_count_cells_em(idx, h, r1.as_ptr(), r2.as_ptr(), bc_len, umi_len, p, out.as_ptr(), num_threads as i32, stats.as_mut_ptr()) };
     }
     let result = check(rc).map(|_| stats);   // (the message is read before the handles go)
+    unsafe {
+        if !idx.is_null() { pa_index_destroy(idx); }
+        pa_host_index_destroy(h);
+    }
+    result
+}
+
+/// `write_bus` with the barcodes corrected against a whitelist file on the GPU before the files are written (pa_write_bus_corrected): a
+/// barcode stays when it is whitelisted, moves to the one whitelisted barcode a single substitution away, and is dropped with its records
+/// otherwise; records that meet are joined. bc_len <= 16. Returns (PA_BUS_STATS, PA_BUS_CORRECT_STATS).
+pub fn write_bus_corrected<P: AsRef<Path>>(index_file: P, r1_fastq: P, r2_fastq: P, whitelist: P, out_dir: P, bc_len: u32, umi_len: u32, num_threads: usize,
+                                           device: i32) -> Result<([u64; crate::amd_bus_ffi::PA_BUS_STATS], [u64; crate::amd_correct_ffi::PA_BUS_CORRECT_STATS]), Error> {
+    use crate::amd_bus_ffi::*;
+    use crate::amd_correct_ffi::*;
+    let cstr = |p: &P| CString::new(p.as_ref().to_string_lossy().into_owned());
+    let (ix, r1, r2, wl, out) = (cstr(&index_file)?, cstr(&r1_fastq)?, cstr(&r2_fastq)?, cstr(&whitelist)?, cstr(&out_dir)?);
+    let mut h = std::ptr::null_mut();
+    check(unsafe { pa_host_index_load(ix.as_ptr(), &mut h) })?;
+    let mut view: PaFlatIndex = unsafe { std::mem::zeroed() };
+    let mut idx = std::ptr::null_mut();
+    let mut rc = unsafe { pa_host_index_view(h, &mut view) };
+    if rc >= 0 { rc = unsafe { pa_index_create(&view, device, &mut idx) }; }
+    let (mut stats, mut cstats) = ([0u64; PA_BUS_STATS], [0u64; PA_BUS_CORRECT_STATS]);
+    if rc >= 0 {
+        rc = unsafe { pa_write_bus_corrected(idx, h, r1.as_ptr(), r2.as_ptr(), wl.as_ptr(), bc_len, umi_len, out.as_ptr(), num_threads as i32, stats.as_mut_ptr(),
+                                             cstats.as_mut_ptr()) };
+    }
+    let result = check(rc).map(|_| (stats, cstats));   // (the message is read before the handles go)
+    unsafe {
+        if !idx.is_null() { pa_index_destroy(idx); }
+        pa_host_index_destroy(h);
+    }
+    result
+}
+
+/// `count_cells_em` with the barcodes corrected against a whitelist file between the BUS records and the gene stage
+/// (pa_count_cells_em_corrected; `write_bus_corrected`'s rule). Returns (PA_GENES_STATS, PA_BUS_CORRECT_STATS).
+pub fn count_cells_em_corrected<P: AsRef<Path>>(index_file: P, r1_fastq: P, r2_fastq: P, whitelist: P, out_dir: P, bc_len: u32, umi_len: u32,
+                                                params: Option<crate::amd_genes_ffi::PaGenesParams>, num_threads: usize,
+                                                device: i32) -> Result<([u64; crate::amd_genes_ffi::PA_GENES_STATS], [u64; crate::amd_correct_ffi::PA_BUS_CORRECT_STATS]), Error> {
+    use crate::amd_correct_ffi::*;
+    use crate::amd_genes_ffi::*;
+    let cstr = |p: &P| CString::new(p.as_ref().to_string_lossy().into_owned());
+    let (ix, r1, r2, wl, out) = (cstr(&index_file)?, cstr(&r1_fastq)?, cstr(&r2_fastq)?, cstr(&whitelist)?, cstr(&out_dir)?);
+    let mut h = std::ptr::null_mut();
+    check(unsafe { pa_host_index_load(ix.as_ptr(), &mut h) })?;
+    let mut view: PaFlatIndex = unsafe { std::mem::zeroed() };
+    let mut idx = std::ptr::null_mut();
+    let mut rc = unsafe { pa_host_index_view(h, &mut view) };
+    if rc >= 0 { rc = unsafe { pa_index_create(&view, device, &mut idx) }; }
+    let (mut stats, mut cstats) = ([0u64; PA_GENES_STATS], [0u64; PA_BUS_CORRECT_STATS]);
+    if rc >= 0 {
+        let p = params.as_ref().map_or(std::ptr::null(), |p| p as *const PaGenesParams);
+        rc = unsafe { pa_count_cells_em_corrected(idx, h, r1.as_ptr(), r2.as_ptr(), wl.as_ptr(), bc_len, umi_len, p, out.as_ptr(), num_threads as i32,
+                                                  stats.as_mut_ptr(), cstats.as_mut_ptr()) };
+    }
+    let result = check(rc).map(|_| (stats, cstats));   // (the message is read before the handles go)
     unsafe {
         if !idx.is_null() { pa_index_destroy(idx); }
         pa_host_index_destroy(h);

@@ -23,7 +23,8 @@ from ._ffi import (PA_DEFAULT_ALLOWED_MISMATCHES, PA_ERR_ARENA_FULL, PA_MAPPED_B
 __all__ = ["HostIndex", "Txome", "Pseudoaligner", "build_index", "process_reads", "process_reads_multi", "PaError", "lib", "concat_reads",
            "gather_classes", "unpack_compact", "unpack_tiles", "RESULT_DTYPE", "PA_MAPPED_BIT", "PA_DEFAULT_ALLOWED_MISMATCHES",
            "PA_READ_COVERAGE_THRESHOLD", "PA_CLASS_REF", "Overflow", "Comm", "parse_overflow", "serialise_overflow", "overflow_merge",
-           "CellCounter", "load_whitelist", "Quantifier", "BusWriter", "BUS_RECORD_DTYPE", "GeneCounter"]
+           "CellCounter", "load_whitelist", "Quantifier", "BusWriter", "BUS_RECORD_DTYPE", "GeneCounter", "bus_whitelist_pack", "bus_correct", "bus_correct_phase_ms",
+           "CORRECT_STAT_NAMES"]
 
 PA_CLASS_REF = 0x80000000
 RESULT_DTYPE = np.dtype([("coverage", "<u4"), ("mismatches", "<u4"), ("class_off", "<u4"), ("class_len", "<u4")])
@@ -470,21 +471,39 @@ class Pseudoaligner:
                                    str(out_dir).encode(), num_threads, st.ctypes.data))
         return dict(zip(_ffi.CELL_STAT_NAMES, (int(x) for x in st)))
 
-    def write_bus(self, host_index: HostIndex, r1: str, r2: str, out_dir: str, bc_len: int = 16, umi_len: int = 12, num_threads: int = 0) -> dict:
+    def write_bus(self, host_index: HostIndex, r1: str, r2: str, out_dir: str, bc_len: int = 16, umi_len: int = 12, num_threads: int = 0,
+                  whitelist: Optional[str] = None) -> dict:
         """Paired R1 (barcode + UMI) / R2 (cDNA) FASTQ -> out_dir/output.bus (sorted, collapsed BUS v1 records), matrix.ec and
-        transcripts.txt (pa_write_bus): the input of the kallisto | bustools family. Returns the stats (BusWriter.stats)."""
+        transcripts.txt (pa_write_bus): the input of the kallisto | bustools family. Returns the stats (BusWriter.stats). With `whitelist`
+        (the path of a barcode whitelist file) the barcodes are corrected against it before the files are written
+        (pa_write_bus_corrected), and the stats hold the correction's under "correct" (BusWriter.correct)."""
         st = np.zeros(_ffi.PA_BUS_STATS, np.uint64)
+        if whitelist is not None:
+            cs = np.zeros(_ffi.PA_BUS_CORRECT_STATS, np.uint64)
+            check(lib().pa_write_bus_corrected(self._h, host_index._h, str(r1).encode(), str(r2).encode(), str(whitelist).encode(), bc_len, umi_len,
+                                               str(out_dir).encode(), num_threads, st.ctypes.data, cs.ctypes.data))
+            out = dict(zip(_ffi.BUS_STAT_NAMES, (int(x) for x in st)))
+            out["correct"] = dict(zip(_ffi.CORRECT_STAT_NAMES, (int(x) for x in cs)))
+            return out
         check(lib().pa_write_bus(self._h, host_index._h, str(r1).encode(), str(r2).encode(), bc_len, umi_len, str(out_dir).encode(), num_threads,
                                  st.ctypes.data))
         return dict(zip(_ffi.BUS_STAT_NAMES, (int(x) for x in st)))
 
     def count_cells_em(self, host_index: HostIndex, r1: str, r2: str, out_dir: str, bc_len: int = 16, umi_len: int = 12, num_threads: int = 0,
-                       **params) -> dict:
+                       whitelist: Optional[str] = None, **params) -> dict:
         """Paired R1 (barcode + UMI) / R2 (cDNA) FASTQ -> out_dir/matrix.mtx (real values), barcodes.tsv, features.tsv (pa_count_cells_em):
         write_bus's records, never written, shared out over genes by a per-cell EM (GeneCounter). params: GeneCounter's. Returns the stats
-        (GeneCounter.stats)."""
+        (GeneCounter.stats). With `whitelist` (the path of a barcode whitelist file) the barcodes are corrected against it before the
+        gene stage (pa_count_cells_em_corrected), and the stats hold the correction's under "correct"."""
         p = _genes_params(params)
         st = np.zeros(_ffi.PA_GENES_STATS, np.uint64)
+        if whitelist is not None:
+            cs = np.zeros(_ffi.PA_BUS_CORRECT_STATS, np.uint64)
+            check(lib().pa_count_cells_em_corrected(self._h, host_index._h, str(r1).encode(), str(r2).encode(), str(whitelist).encode(), bc_len, umi_len, C.byref(p),
+                                                    str(out_dir).encode(), num_threads, st.ctypes.data, cs.ctypes.data))
+            out = dict(zip(_ffi.GENES_STAT_NAMES, (int(x) for x in st)))
+            out["correct"] = dict(zip(_ffi.CORRECT_STAT_NAMES, (int(x) for x in cs)))
+            return out
         check(lib().pa_count_cells_em(self._h, host_index._h, str(r1).encode(), str(r2).encode(), bc_len, umi_len, C.byref(p), str(out_dir).encode(), num_threads,
                                       st.ctypes.data))
         return dict(zip(_ffi.GENES_STAT_NAMES, (int(x) for x in st)))
@@ -711,6 +730,15 @@ class BusWriter:
         check(lib().pa_bus_stats(self._h, st.ctypes.data))
         return dict(zip(_ffi.BUS_STAT_NAMES, (int(x) for x in st)))
 
+    def correct(self, whitelist) -> dict:
+        """pa_bus_correct: the barcodes of the finished records (finished here if they are not yet) corrected against `whitelist` (barcode
+        strings, or packed values as bus_whitelist_pack gives them) in place, collapsed again -> the stats (CORRECT_STAT_NAMES)"""
+        self.finish()
+        wl = _packed_whitelist(whitelist)
+        st = np.zeros(_ffi.PA_BUS_CORRECT_STATS, np.uint64)
+        check(lib().pa_bus_correct(self._h, wl.ctypes.data if len(wl) else None, len(wl), st.ctypes.data))
+        return dict(zip(_ffi.CORRECT_STAT_NAMES, (int(x) for x in st)))
+
     def write(self, out_dir: str) -> None:
         """out_dir/output.bus, matrix.ec, transcripts.txt"""
         self.finish()
@@ -723,6 +751,47 @@ class BusWriter:
                 self._h = vp()
         except Exception:
             pass
+
+
+CORRECT_STAT_NAMES = _ffi.CORRECT_STAT_NAMES
+
+
+def bus_whitelist_pack(whitelist: Sequence[str]) -> np.ndarray:
+    """pa_bus_whitelist_pack: barcode strings of one length -> uint64, 2 bits per base, A=0 C=1 G=2 T=3, first base most significant"""
+    wl = list(whitelist)
+    bc_len = len(wl[0]) if wl else 1
+    if any(len(b) != bc_len for b in wl):
+        raise ValueError("the barcodes of a whitelist have one length")
+    out = np.zeros(max(len(wl), 1), np.uint64)
+    check(lib().pa_bus_whitelist_pack("".join(wl).encode(), len(wl), bc_len, out.ctypes.data))
+    return out[:len(wl)]
+
+
+def _packed_whitelist(whitelist) -> np.ndarray:
+    if isinstance(whitelist, np.ndarray):
+        return np.ascontiguousarray(whitelist, np.uint64)
+    wl = list(whitelist)
+    return bus_whitelist_pack(wl) if wl and isinstance(wl[0], str) else np.ascontiguousarray(wl, np.uint64)
+
+
+def bus_correct(records, whitelist, bc_len: int, umi_len: int, index: Optional["Pseudoaligner"]) -> Tuple[np.ndarray, dict]:
+    """pa_bus_correct_records: host records (BUS_RECORD_DTYPE, strictly ascending by barcode, UMI, ec) corrected against `whitelist`
+    (barcode strings or packed values) on `index`'s GPU -> (the corrected records, collapsed and sorted again; the stats)"""
+    rec = np.ascontiguousarray(records, BUS_RECORD_DTYPE)
+    wl = _packed_whitelist(whitelist)
+    st = np.zeros(_ffi.PA_BUS_CORRECT_STATS, np.uint64)
+    out = np.zeros(max(len(rec), 1), BUS_RECORD_DTYPE)
+    n = C.c_uint64()
+    check(lib().pa_bus_correct_records(index._h if index is not None else None, rec.ctypes.data if len(rec) else None, len(rec), bc_len, umi_len,
+                                       wl.ctypes.data if len(wl) else None, len(wl), out.ctypes.data, len(rec), C.byref(n), st.ctypes.data))
+    return out[:n.value], dict(zip(_ffi.CORRECT_STAT_NAMES, (int(x) for x in st)))
+
+
+def bus_correct_phase_ms() -> dict:
+    """pa_bus_correct_phase_ms: the GPU milliseconds of this thread's last correction, by phase"""
+    ms = (C.c_float * _ffi.PA_BUS_CORRECT_PHASES)()
+    check(lib().pa_bus_correct_phase_ms(ms))
+    return dict(zip(_ffi.CORRECT_PHASE_NAMES, (float(x) for x in ms)))
 
 
 def _genes_params(params: dict) -> "_ffi.GenesParams":

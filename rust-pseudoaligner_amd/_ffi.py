@@ -22,6 +22,11 @@ CELL_STAT_NAMES = ("reads", "barcode_exact", "barcode_corrected", "barcode_inval
                    "umis_corrected", "molecules_lost_to_conflicts", "umis_in_matrix")
 PA_BUS_STATS = 8
 BUS_STAT_NAMES = ("reads", "r1_short", "barcode_n", "umi_n", "unmapped", "bad_class", "recorded", "records")
+PA_BUS_CORRECT_STATS = 13
+CORRECT_STAT_NAMES = ("records_in", "reads_in", "barcodes_in", "barcodes_exact", "barcodes_corrected", "barcodes_none", "barcodes_ambiguous", "records_exact",
+                      "records_corrected", "records_dropped", "reads_dropped", "records_out", "barcodes_out")
+PA_BUS_CORRECT_PHASES = 4
+CORRECT_PHASE_NAMES = ("table_ms", "classify_exact_ms", "classify_neighbours_ms", "rewrite_ms")
 PA_MAPPED_BIT = 0x80000000
 PA_DEFAULT_ALLOWED_MISMATCHES = 2
 PA_READ_COVERAGE_THRESHOLD = 32
@@ -187,6 +192,11 @@ SIGNATURES = {
     "pa_bus_write": (C.c_int, [vp, C.c_char_p]),
     "pa_bus_destroy": (None, [vp]),
     "pa_write_bus": (C.c_int, [vp, vp, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, vp]),
+    "pa_bus_whitelist_pack": (C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, vp]),
+    "pa_bus_correct_records": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, u64p, vp]),
+    "pa_bus_correct": (C.c_int, [vp, vp, C.c_uint64, vp]),
+    "pa_bus_correct_phase_ms": (C.c_int, [C.POINTER(C.c_float)]),
+    "pa_write_bus_corrected": (C.c_int, [vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, vp, vp]),
     "pa_genes_default_params": (None, [C.POINTER(GenesParams)]),
     "pa_genes_create": (C.c_int, [vp, vp, C.c_uint64, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(GenesParams), C.POINTER(vp)]),
     "pa_genes_create_from_bus": (C.c_int, [vp, vp, C.c_uint32, C.POINTER(GenesParams), C.POINTER(vp)]),
@@ -200,6 +210,7 @@ SIGNATURES = {
     "pa_genes_write": (C.c_int, [vp, vp, C.c_char_p]),
     "pa_genes_destroy": (None, [vp]),
     "pa_count_cells_em": (C.c_int, [vp, vp, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(GenesParams), C.c_char_p, C.c_int, vp]),
+    "pa_count_cells_em_corrected": (C.c_int, [vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(GenesParams), C.c_char_p, C.c_int, vp, vp]),
     "pa_quant_default_params": (None, [C.POINTER(QuantParams)]),
     "pa_quant_create": (C.c_int, [vp, vp, C.POINTER(QuantParams), C.POINTER(vp)]),
     "pa_quant_set_counts": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64]),

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "bus_host.hpp"
+#include "bus_state.hpp"
 #include "device_prims.hpp"
 #include "hip_buffer.hpp"
 #include "kernel_utils.hpp"
@@ -22,16 +23,10 @@ using namespace pa;
 
 namespace {
 
-typedef unsigned long long ull;
-constexpr uint32_t BUS_BLOCK = 256;               // 4 waves
 constexpr uint64_t BUS_WRITE_PIECE = 1u << 18;    // records (8 MiB) per piece of pa_bus_write
 constexpr ull BUS_LIST_BIT = 1ull << 63;          // low key word: the hash of an arena list, not an ec
-enum : uint32_t { BS_READS = 0, BS_R1_SHORT, BS_BARCODE_N, BS_UMI_N, BS_UNMAPPED, BS_BAD_CLASS, BS_RECORDED, BS_RECORDS };
 
-__host__ __device__ inline ull bus_low_mask(uint32_t bits) { return bits >= 64 ? ~0ull : (1ull << bits) - 1; }
 __device__ inline uint32_t bus_base(uint8_t c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u; }
-__device__ inline ull key_lo(u128 k) { return (ull)k; }
-__device__ inline ull key_hi(u128 k) { return (ull)(k >> 64); }
 
 struct BusKeyParams {
     const pa_read_result* results;
@@ -118,36 +113,6 @@ __global__ __launch_bounds__(BUS_BLOCK) void pa_bus_keys_kernel(const BusKeyPara
     }
 }
 
-// ---- collapse of sorted keys: flag the first of every run, scan, scatter ----
-template <class K>
-__global__ __launch_bounds__(BUS_BLOCK) void pa_bus_heads_kernel(const K* __restrict__ keys, uint32_t n, uint32_t* __restrict__ heads) {
-    const uint32_t i = blockIdx.x * BUS_BLOCK + threadIdx.x;
-    if (i < n) heads[i] = (i == 0 || keys[i] != keys[i - 1]) ? 1u : 0u;
-}
-// pos = inclusive scan of heads: run r = pos[i] - 1 begins at its head i; start[runs] = n
-template <class K>
-__global__ __launch_bounds__(BUS_BLOCK) void pa_bus_scatter_kernel(const K* __restrict__ keys, const uint32_t* __restrict__ heads, const uint32_t* __restrict__ pos,
-                                                                    uint32_t n, K* __restrict__ unique, uint32_t* __restrict__ start) {
-    const uint32_t i = blockIdx.x * BUS_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    if (heads[i]) {
-        unique[pos[i] - 1] = keys[i];
-        start[pos[i] - 1] = i;
-    }
-    if (i == n - 1) start[pos[i]] = n;
-}
-// reads of every run: its length, or the sum of its members' counts (in 64 bits, clamped at 2^32 - 1)
-__global__ __launch_bounds__(BUS_BLOCK) void pa_bus_run_counts_kernel(const uint32_t* __restrict__ start, uint32_t runs, const uint32_t* __restrict__ counts_in,
-                                                                       uint32_t* __restrict__ counts) {
-    const uint32_t r = blockIdx.x * BUS_BLOCK + threadIdx.x;
-    if (r >= runs) return;
-    const uint32_t a = start[r], b = start[r + 1];
-    if (!counts_in) { counts[r] = b - a; return; }
-    ull sum = 0;
-    for (uint32_t j = a; j < b; ++j) sum += counts_in[j];
-    counts[r] = sum > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)sum;
-}
-
 // ---- the arena lists of a batch ----
 __device__ inline bool same_list(const pa_read_result a, const pa_read_result b, const uint32_t* __restrict__ arena) {
     if (a.class_len != b.class_len) return false;
@@ -219,18 +184,6 @@ __global__ __launch_bounds__(BUS_BLOCK) void pa_bus_remap_kernel(u128* __restric
     if (a < table_n && table_hash[a] == lo) keys[i] = ((u128)key_hi(k) << 64) | table_ec[a];
     else *err = lo;
 }
-// whole records: 32 bytes as two 16-byte stores
-__global__ __launch_bounds__(BUS_BLOCK) void pa_bus_records_kernel(const u128* __restrict__ keys, const uint32_t* __restrict__ counts, uint32_t n, uint32_t umi_bits,
-                                                                    pa_bus_record* __restrict__ out) {
-    const uint32_t i = blockIdx.x * BUS_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const u128 k = keys[i];
-    const ull w = key_hi(k), bc = w >> umi_bits, umi = w & bus_low_mask(umi_bits);
-    uint4* o = reinterpret_cast<uint4*>(out + i);
-    o[0] = make_uint4((uint32_t)bc, (uint32_t)(bc >> 32), (uint32_t)umi, (uint32_t)(umi >> 32));
-    o[1] = make_uint4((uint32_t)key_lo(k), counts[i], 0u, 0u);
-}
-
 template <class T>
 int fetch(const T* d, hipStream_t s, T& out) {
     PA_HIP_TRY(hipMemcpyAsync(&out, d, sizeof(T), hipMemcpyDeviceToHost, s));
@@ -239,34 +192,6 @@ int fetch(const T* d, hipStream_t s, T& out) {
 }
 
 }  // namespace
-
-struct pa_bus {
-    int device = 0;
-    uint32_t bc_len = 0, umi_len = 0, num_classes = 0, num_tx = 0;
-    const pa_host_index* host = nullptr;
-    DeviceBuffer<uint32_t> d_class_ec;
-    DeviceBuffer<ull> d_stats, d_err;
-    // (key, reads) entries of every batch so far, unsorted across batches
-    DeviceBuffer<u128> acc_keys;
-    DeviceBuffer<uint32_t> acc_counts;
-    uint64_t acc_n = 0;
-    // scratch of a batch, kept between batches
-    DeviceBuffer<u128> keys, sorted;
-    DeviceBuffer<uint32_t> vals, svals, heads, pos, start, which, lread, lread_s, d_n, pool_ids;
-    DeviceBuffer<ull> lhash, lhash_s, lhash_u, lens, loff;
-    DeviceBuffer<uint8_t> tmp;
-    // one list per distinct hash of the run, on the host: list l = list_ids[list_off[l] .. list_off[l + 1])
-    std::unordered_map<ull, uint64_t> list_of_hash;
-    std::vector<ull> list_hash;
-    std::vector<uint64_t> list_off{0};
-    std::vector<uint32_t> list_ids;
-    bool finished = false;
-    uint64_t stats[PA_BUS_STATS] = {};
-    DeviceBuffer<pa_bus_record> d_records;   // the records after finish: they stay in HBM until they are asked for or written
-    uint64_t n_records = 0;
-    bus::EcTable table;
-    uint32_t key_bits() const { return 64 + 2 * (bc_len + umi_len); }
-};
 
 namespace {
 

@@ -214,19 +214,37 @@ int count_cells_impl(pa_index* idx, const pa_host_index* h, const char* r1_path,
 }
 
 // ---- pa_write_bus / pa_count_cells_em: the same two files -> sorted (barcode, UMI, ec) records in HBM, then `after(bus, st)`: the writer's three files, or
-// the gene stage and its three files (after() adds its own seconds to st[ST_TALLY] / st[ST_WRITE]) ----
+// the gene stage and its three files (after() adds its own seconds to st[ST_TALLY] / st[ST_WRITE]). With a whitelist file (the *_corrected calls) the
+// barcodes of the finished records are corrected against it in HBM before `after` sees them (pa_bus_correct; its seconds go to st[ST_TALLY]) ----
+struct BusWhitelist {
+    const char* path = nullptr;   // nullptr: no correction
+    uint64_t* stats = nullptr;    // [PA_BUS_CORRECT_STATS], may be nullptr
+};
+
 template <class After>
-int bus_run(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, uint32_t bc_len, uint32_t umi_len, const char* out_dir, int num_threads,
-            After&& after) {
+int bus_run(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const BusWhitelist& wl, uint32_t bc_len, uint32_t umi_len, const char* out_dir,
+            int num_threads, After&& after) {
     std::unique_ptr<pa_bus, void (*)(pa_bus*)> own(nullptr, pa_bus_destroy);   // (in front of the frame: destroyed behind its streams)
     PairedCall call(num_threads);
     double* const st = call.st;
     if (!idx || !h || !r1_path || !r2_path || !out_dir) return fail(PA_ERR_INVALID_ARG, "null argument");
     struct stat sd;
     if (stat(out_dir, &sd) != 0 || !S_ISDIR(sd.st_mode)) return fail(PA_ERR_IO, "%s is no directory", out_dir);
+    int rc = PA_OK;
+    std::vector<uint64_t> packed;
+    if (wl.path) {   // the whitelist first: a file that cannot be used is refused before a read is mapped
+        if (bc_len > 16) return fail(PA_ERR_UNSUPPORTED, "barcode length %u: a whitelist file holds barcodes of at most 16 bases", bc_len);
+        uint64_t n_wl = 0;
+        if ((rc = pa_whitelist_load(wl.path, bc_len, nullptr, 0, &n_wl)) != PA_OK) return rc;
+        std::vector<char> text((size_t)n_wl * bc_len + 1);
+        packed.resize((size_t)n_wl + 1);
+        if ((rc = pa_whitelist_load(wl.path, bc_len, text.data(), n_wl, &n_wl)) != PA_OK || (rc = pa_bus_whitelist_pack(text.data(), n_wl, bc_len, packed.data())) != PA_OK)
+            return rc;
+        packed.resize((size_t)n_wl);
+        if (packed.empty()) return fail(PA_ERR_INVALID_ARG, "%s holds no barcode", wl.path);
+    }
     pa_bus* bus = nullptr;
-    int rc = pa_bus_create(idx, h, bc_len, umi_len, &bus);
-    if (rc != PA_OK) return rc;
+    if ((rc = pa_bus_create(idx, h, bc_len, umi_len, &bus)) != PA_OK) return rc;
     own.reset(bus);
 
     if ((rc = call.open(idx, r1_path, r2_path, bc_len + umi_len, 1, 1)) != PA_OK) return rc;
@@ -240,15 +258,16 @@ int bus_run(pa_index* idx, const pa_host_index* h, const char* r1_path, const ch
     uint64_t n_records = 0;
     uint32_t n_ecs = 0;
     if ((rc = pa_bus_finish(bus, &n_records, &n_ecs)) != PA_OK) return rc;
+    if (wl.path && (rc = pa_bus_correct(bus, packed.data(), packed.size(), wl.stats)) != PA_OK) return rc;
     st[ST_TALLY] += now() - t0;
     if ((rc = after(bus, st)) != PA_OK) return rc;
     call.done();
     return PA_OK;
 }
 
-int write_bus_impl(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, uint32_t bc_len, uint32_t umi_len, const char* out_dir,
-                   int num_threads, uint64_t* stats) {
-    return bus_run(idx, h, r1_path, r2_path, bc_len, umi_len, out_dir, num_threads, [&](pa_bus* bus, double* st) {
+int write_bus_impl(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const BusWhitelist& wl, uint32_t bc_len, uint32_t umi_len,
+                   const char* out_dir, int num_threads, uint64_t* stats) {
+    return bus_run(idx, h, r1_path, r2_path, wl, bc_len, umi_len, out_dir, num_threads, [&](pa_bus* bus, double* st) {
         const double t0 = now();
         const int rc = pa_bus_write(bus, out_dir);
         if (rc != PA_OK) return rc;
@@ -258,9 +277,9 @@ int write_bus_impl(pa_index* idx, const pa_host_index* h, const char* r1_path, c
     });
 }
 
-int count_cells_em_impl(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, uint32_t bc_len, uint32_t umi_len, const pa_genes_params* p,
-                        const char* out_dir, int num_threads, uint64_t* stats) {
-    return bus_run(idx, h, r1_path, r2_path, bc_len, umi_len, out_dir, num_threads, [&](pa_bus* bus, double* st) {
+int count_cells_em_impl(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const BusWhitelist& wl, uint32_t bc_len, uint32_t umi_len,
+                        const pa_genes_params* p, const char* out_dir, int num_threads, uint64_t* stats) {
+    return bus_run(idx, h, r1_path, r2_path, wl, bc_len, umi_len, out_dir, num_threads, [&](pa_bus* bus, double* st) {
         double t0 = now();
         const uint32_t ntx = pa_host_index_num_transcripts(h);
         std::vector<uint32_t> tx_gene(ntx ? ntx : 1);
@@ -289,10 +308,27 @@ extern "C" int pa_count_cells(pa_index* idx, const pa_host_index* h, const char*
 
 extern "C" int pa_write_bus(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, uint32_t bc_len, uint32_t umi_len, const char* out_dir,
                             int num_threads, uint64_t stats[PA_BUS_STATS]) {
-    return no_throw("pa_write_bus", [&] { return write_bus_impl(idx, h, r1_path, r2_path, bc_len, umi_len, out_dir, num_threads, stats); });
+    return no_throw("pa_write_bus", [&] { return write_bus_impl(idx, h, r1_path, r2_path, BusWhitelist{}, bc_len, umi_len, out_dir, num_threads, stats); });
 }
 
 extern "C" int pa_count_cells_em(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, uint32_t bc_len, uint32_t umi_len, const pa_genes_params* p,
                                  const char* out_dir, int num_threads, uint64_t stats[PA_GENES_STATS]) {
-    return no_throw("pa_count_cells_em", [&] { return count_cells_em_impl(idx, h, r1_path, r2_path, bc_len, umi_len, p, out_dir, num_threads, stats); });
+    return no_throw("pa_count_cells_em", [&] { return count_cells_em_impl(idx, h, r1_path, r2_path, BusWhitelist{}, bc_len, umi_len, p, out_dir, num_threads, stats); });
+}
+
+extern "C" int pa_write_bus_corrected(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const char* whitelist_path, uint32_t bc_len,
+                                      uint32_t umi_len, const char* out_dir, int num_threads, uint64_t bus_stats[PA_BUS_STATS], uint64_t correct_stats[PA_BUS_CORRECT_STATS]) {
+    return no_throw("pa_write_bus_corrected", [&] {
+        if (!whitelist_path) return fail(PA_ERR_INVALID_ARG, "null argument");
+        return write_bus_impl(idx, h, r1_path, r2_path, BusWhitelist{whitelist_path, correct_stats}, bc_len, umi_len, out_dir, num_threads, bus_stats);
+    });
+}
+
+extern "C" int pa_count_cells_em_corrected(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const char* whitelist_path, uint32_t bc_len,
+                                           uint32_t umi_len, const pa_genes_params* p, const char* out_dir, int num_threads, uint64_t genes_stats[PA_GENES_STATS],
+                                           uint64_t correct_stats[PA_BUS_CORRECT_STATS]) {
+    return no_throw("pa_count_cells_em_corrected", [&] {
+        if (!whitelist_path) return fail(PA_ERR_INVALID_ARG, "null argument");
+        return count_cells_em_impl(idx, h, r1_path, r2_path, BusWhitelist{whitelist_path, correct_stats}, bc_len, umi_len, p, out_dir, num_threads, genes_stats);
+    });
 }
