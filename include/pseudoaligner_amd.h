@@ -625,6 +625,86 @@ int pa_write_bus_corrected(pa_index* idx, const pa_host_index* h, const char* r1
                            uint32_t bc_len, uint32_t umi_len, const char* out_dir, int num_threads, uint64_t bus_stats[PA_BUS_STATS],
                            uint64_t correct_stats[PA_BUS_CORRECT_STATS]);
 
+/* ---------------- cell calling on BUS records: barcode table, rank knee, filter ----------------
+ * The `bustools whitelist` step (a library without a whitelist file) and the "filtered matrix" step (a whitelist lists possible barcodes,
+ * not cells) on the records where they lie: one table over the records, a ranking, a threshold, a compaction.
+ *   input      n BUS records, STRICTLY ascending by (barcode, UMI, ec), as pa_bus_finish and pa_bus_correct leave them. bc_len / umi_len
+ *              limits are pa_bus_create's (else PA_ERR_UNSUPPORTED)
+ *   table      one row per distinct barcode, in ascending barcode order:
+ *                records = the number of the barcode's records
+ *                umis    = its distinct (barcode, UMI) runs, i.e. molecules. A molecule counts 1 whatever its records' read counts, as
+ *                          in pa_genes_*
+ *                reads   = the u64 sum of its records' count, not clamped
+ *   rank       the 0-based position of the row in the order (umis descending, barcode ascending)
+ *   curve      the distinct umis values v_0 > v_1 > ... > v_{D-1}; R_j = the number of barcodes with umis >= v_j
+ *   threshold  an integer t >= 1. A barcode is CALLED iff umis >= t. pa_knee_default_params: mode PA_KNEE_CURVE, lower 10, divisor 10,
+ *              expected_cells 3000, min_umis 1. Nobody has tuned these defaults on a real library
+ *     PA_KNEE_MIN       t = min_umis
+ *     PA_KNEE_EXPECTED  the Cell Ranger 2.2 / STARsolo rule, integers only: r = expected_cells / 100 (integer division), lowered to B - 1
+ *                       when it is beyond the last of the B rows; m = umis of the row at rank r = v_j for the smallest j with R_j > r;
+ *                       t = (m + 9) / 10. B = 0: t = 1
+ *     PA_KNEE_CURVE     (default) only j < L counts, where L = the number of values >= lower.
+ *                       L = 0: t = lower. L <= 2: k = L - 1. Otherwise x_j = log10(R_j) and y_j = log10(v_j) as doubles;
+ *                       dx = x_{L-1} - x_0; dy = y_{L-1} - y_0; s_j = (y_j - y_0) * dx - (x_j - x_0) * dy (the height of the point above
+ *                       the chord, times a positive constant); k = the smallest j with the greatest s_j if that s_j > 0, else L - 1.
+ *                       t = max(lower, (v_k + divisor - 1) / divisor). The product and difference are evaluated exactly as written, in
+ *                       f64, with floating-point contraction off; log10 is libm's. The knee is the curve's upper shoulder; the divisor
+ *                       carries the threshold below the cell population, as Cell Ranger 2 does with its 99th percentile
+ *   refusals   PA_ERR_INVALID_ARG for lower = 0, divisor = 0, min_umis = 0, expected_cells = 0 or an unknown mode (whatever the mode in
+ *              use); for records that are not strictly ascending or out of range the message is pa_bus_correct_records'. More than
+ *              2^31 - 1 records: PA_ERR_UNSUPPORTED. Host arguments are checked before any device call; without a GPU a valid call
+ *              returns PA_ERR_NO_DEVICE (before idx is looked at)
+ *   independence  rows, called list, threshold and stats are a pure function of (records, params): two runs give the same bytes
+ *   stats[PA_KNEE_STATS]: [0] records, [1] reads, [2] molecules, [3] distinct barcodes (B), [4] D, [5] L (0 outside PA_KNEE_CURVE),
+ *              [6] threshold, [7] barcodes called, [8] molecules of called barcodes, [9] reads of called barcodes;
+ *              [7] <= [3], [8] <= [2], [9] <= [1]
+ * pa_bus_knee_records: host arrays of any origin; idx names the GPU. rows[*n_rows] in ascending barcode order; called[*n_called] the
+ * called barcodes in BUS packing, ascending: it can be passed to pa_bus_correct as it is. rows / called NULL: only the counts and the
+ * stats. A cap that is too small: PA_ERR_BUFFER_TOO_SMALL with both counts (and the stats) set. NULL p: the defaults. n = 0 is legal.
+ * pa_bus_knee: the same on a finished writer (PA_ERR_INVALID_ARG before pa_bus_finish); the records are read where they lie and the
+ * writer is unchanged.
+ * pa_bus_knee_phase_ms: the GPU milliseconds of this thread's last knee: [0] table, [1] rank + curve, [2] threshold (host) + called list
+ * + rows.
+ * pa_bus_keep_records / pa_bus_keep: a pure filter with no neighbour rescue. A record survives iff its barcode is in barcodes[], which must
+ * be strictly ascending with every value < 4^bc_len, else PA_ERR_INVALID_ARG naming the entry; n_barcodes = 0 is legal and keeps nothing.
+ * Survivors stay in order: they are sorted and distinct as they lie, so there is no sort and no collapse. out NULL: only *n_out and the
+ * stats; cap < *n_out: PA_ERR_BUFFER_TOO_SMALL. pa_bus_keep works in place on a finished writer with pa_bus_correct's guarantees: the new
+ * records are built beside the old ones and swapped in at the end, a failing call leaves the writer as it was; afterwards pa_bus_records,
+ * pa_bus_write, pa_genes_create_from_bus, a second pa_bus_finish and pa_bus_stats[7] see the kept records; the ec table is untouched.
+ *   stats[PA_BUS_KEEP_STATS]: [0] records in, [1] reads in, [2] distinct barcodes in, [3] barcodes kept, [4] records out, [5] reads out,
+ *              [6] listed barcodes that no record carries
+ * pa_write_barcode_ranks_tsv (host): header "barcode\trecords\tumis\treads\trank\tcalled", then one line per row in the order given; the
+ * barcode is decoded as barcodes.tsv decodes it (first base most significant).
+ * pa_write_bus_called / pa_count_cells_em_called: pa_write_bus / pa_count_cells_em with cell calling after pa_bus_finish.
+ *   whitelist_path NULL   knee -> pa_bus_correct(called): `bustools whitelist` + `correct`. An uncalled barcode with exactly one called
+ *                         one-substitution neighbour is joined to it, every other uncalled barcode is dropped
+ *   whitelist_path given  pa_bus_correct(whitelist) -> knee -> pa_bus_keep(called). (A second correction would move whitelisted, uncalled
+ *                         barcodes into called neighbours; the pure filter does not.) pa_write_bus_corrected's rules for the file
+ *   Both also write out_dir/barcode_ranks.tsv: the rows of the knee's input table. No barcode called: PA_ERR_FORMAT "no barcode reaches
+ *   the threshold of N molecules", with nothing written. correct_stats are the one correction's that ran; any stats may be NULL. */
+#define PA_KNEE_CURVE 0
+#define PA_KNEE_EXPECTED 1
+#define PA_KNEE_MIN 2
+#define PA_KNEE_STATS 10
+#define PA_KNEE_PHASES 3
+#define PA_BUS_KEEP_STATS 7
+typedef struct pa_knee_params { uint32_t mode, lower, divisor, expected_cells, min_umis, reserved[3]; } pa_knee_params;
+typedef struct pa_bus_barcode_row { uint64_t barcode, reads; uint32_t records, umis, rank, called; } pa_bus_barcode_row;   /* 32 bytes */
+void pa_knee_default_params(pa_knee_params* p);
+int pa_bus_knee_records(pa_index* idx, const pa_bus_record* in, uint64_t n, uint32_t bc_len, uint32_t umi_len, const pa_knee_params* p,
+                        pa_bus_barcode_row* rows, uint64_t rows_cap, uint64_t* n_rows, uint64_t* called, uint64_t called_cap,
+                        uint64_t* n_called, uint64_t stats[PA_KNEE_STATS]);
+int pa_bus_knee(const pa_bus* finished, const pa_knee_params* p, pa_bus_barcode_row* rows, uint64_t rows_cap, uint64_t* n_rows,
+                uint64_t* called, uint64_t called_cap, uint64_t* n_called, uint64_t stats[PA_KNEE_STATS]);
+int pa_bus_knee_phase_ms(float out[PA_KNEE_PHASES]);
+int pa_bus_keep_records(pa_index* idx, const pa_bus_record* in, uint64_t n, uint32_t bc_len, uint32_t umi_len, const uint64_t* barcodes,
+                        uint64_t n_barcodes, pa_bus_record* out, uint64_t cap, uint64_t* n_out, uint64_t stats[PA_BUS_KEEP_STATS]);
+int pa_bus_keep(pa_bus* finished, const uint64_t* barcodes, uint64_t n_barcodes, uint64_t stats[PA_BUS_KEEP_STATS]);
+int pa_write_barcode_ranks_tsv(const pa_bus_barcode_row* rows, uint64_t n, uint32_t bc_len, const char* path);
+int pa_write_bus_called(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const char* whitelist_path,
+                        uint32_t bc_len, uint32_t umi_len, const pa_knee_params* p, const char* out_dir, int num_threads,
+                        uint64_t bus_stats[PA_BUS_STATS], uint64_t correct_stats[PA_BUS_CORRECT_STATS], uint64_t knee_stats[PA_KNEE_STATS]);
+
 /* ---------------- cells x genes from BUS records: multi-gene UMIs shared out by EM ----------------
  * The `bustools count --genecounts --em` step on the records where they lie: where pa_cell_counter drops a read whose class spans two
  * genes, this keeps the molecule and lets a per-cell EM divide it among its genes.
@@ -704,6 +784,11 @@ int  pa_count_cells_em(pa_index* idx, const pa_host_index* h, const char* r1_pat
 int  pa_count_cells_em_corrected(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const char* whitelist_path,
                                  uint32_t bc_len, uint32_t umi_len, const pa_genes_params* p, const char* out_dir, int num_threads,
                                  uint64_t genes_stats[PA_GENES_STATS], uint64_t correct_stats[PA_BUS_CORRECT_STATS]);
+/* ... with cell calling between pa_bus_finish and the gene stage (the cell calling section above; pa_write_bus_called's rules). */
+int  pa_count_cells_em_called(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const char* whitelist_path,
+                              uint32_t bc_len, uint32_t umi_len, const pa_knee_params* kp, const pa_genes_params* p, const char* out_dir,
+                              int num_threads, uint64_t genes_stats[PA_GENES_STATS], uint64_t correct_stats[PA_BUS_CORRECT_STATS],
+                              uint64_t knee_stats[PA_KNEE_STATS]);
 
 /* ---------------- transcript abundances: EM over the class-count table (bulk RNA-seq) ----------------
  * The reference stops at equivalence classes; this is the standard abundance model over them (the EM of kallisto / salmon) on the

@@ -220,6 +220,44 @@ int main(int argc, char** argv) {
         EXPECT(pa_count_cells_em_corrected(NULL, h, fastq, fastq, path, 4, 4, NULL, dir, 1, NULL, cst13) == PA_ERR_INVALID_ARG);
     }
 
+    {   /* cell calling on BUS records, host side: the defaults, the TSV writer, and every refusal that comes before a device call */
+        pa_knee_params kp, kbad;
+        uint64_t kst[PA_KNEE_STATS], pst[PA_BUS_KEEP_STATS], knr = 7, knc = 7, kn = 7;
+        float kms[PA_KNEE_PHASES];
+        const pa_bus_record krec[3] = {{26, 0, 0, 1, 0, 0}, {27, 0, 0, 2, 0, 0}, {27, 1, 0, 1, 0, 0}};
+        const uint64_t klist[2] = {26, 27}, klist_dup[2] = {27, 27}, klist_big[2] = {27, 256};
+        const pa_bus_barcode_row krow[1] = {{27, 3, 2, 2, 0, 1}};
+        pa_bus_record kbadrec[3];
+        EXPECT(PA_KNEE_STATS == 10 && PA_KNEE_PHASES == 3 && PA_BUS_KEEP_STATS == 7 && sizeof(pa_bus_barcode_row) == 32 && sizeof(pa_knee_params) == 32);
+        pa_knee_default_params(NULL);
+        pa_knee_default_params(&kp);
+        EXPECT(kp.mode == PA_KNEE_CURVE && kp.lower == 10 && kp.divisor == 10 && kp.expected_cells == 3000 && kp.min_umis == 1 && kp.reserved[2] == 0);
+        EXPECT(pa_bus_knee_records(NULL, krec, 3, 4, 4, &kp, NULL, 0, NULL, NULL, 0, &knc, kst) == PA_ERR_INVALID_ARG);
+        kbad = kp;
+        kbad.lower = 0;
+        EXPECT(pa_bus_knee_records(NULL, krec, 3, 4, 4, &kbad, NULL, 0, &knr, NULL, 0, &knc, kst) == PA_ERR_INVALID_ARG && strstr(pa_last_error(), "lower") && knr == 0);
+        kbad = kp;
+        kbad.mode = 3;
+        EXPECT(pa_bus_knee_records(NULL, krec, 3, 4, 4, &kbad, NULL, 0, &knr, NULL, 0, &knc, kst) == PA_ERR_INVALID_ARG && strstr(pa_last_error(), "mode"));
+        EXPECT(pa_bus_knee_records(NULL, krec, 3, 17, 16, &kp, NULL, 0, &knr, NULL, 0, &knc, kst) == PA_ERR_UNSUPPORTED);
+        memcpy(kbadrec, krec, sizeof kbadrec);
+        kbadrec[2].umi = 0;   /* equal to the record before it */
+        EXPECT(pa_bus_knee_records(NULL, kbadrec, 3, 4, 4, NULL, NULL, 0, &knr, NULL, 0, &knc, kst) == PA_ERR_INVALID_ARG && strstr(pa_last_error(), "record 2"));
+        EXPECT(pa_bus_knee_records(NULL, krec, 3, 4, 4, NULL, NULL, 0, &knr, NULL, 0, &knc, kst) == (ndev < 1 ? PA_ERR_NO_DEVICE : PA_ERR_INVALID_ARG) && knc == 0);
+        EXPECT(pa_bus_knee(NULL, &kp, NULL, 0, &knr, NULL, 0, &knc, kst) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_bus_knee_phase_ms(NULL) == PA_ERR_INVALID_ARG && pa_bus_knee_phase_ms(kms) == PA_OK);
+        EXPECT(pa_bus_keep_records(NULL, krec, 3, 4, 4, klist, 2, NULL, 0, NULL, pst) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_bus_keep_records(NULL, krec, 3, 4, 4, klist_dup, 2, NULL, 0, &kn, pst) == PA_ERR_INVALID_ARG && strstr(pa_last_error(), "entry 1") && kn == 0);
+        EXPECT(pa_bus_keep_records(NULL, krec, 3, 4, 4, klist_big, 2, NULL, 0, &kn, pst) == PA_ERR_INVALID_ARG && strstr(pa_last_error(), "entry 1"));
+        EXPECT(pa_bus_keep_records(NULL, krec, 3, 4, 4, klist, 2, NULL, 0, &kn, pst) == (ndev < 1 ? PA_ERR_NO_DEVICE : PA_ERR_INVALID_ARG));
+        EXPECT(pa_bus_keep(NULL, klist, 2, pst) == PA_ERR_INVALID_ARG);
+        snprintf(path, sizeof path, "%s/abi_check_ranks.tsv", dir);
+        EXPECT(pa_write_barcode_ranks_tsv(krow, 1, 4, path) == PA_OK && pa_write_barcode_ranks_tsv(krow, 1, 4, NULL) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_write_barcode_ranks_tsv(krow, 1, 32, path) == PA_ERR_UNSUPPORTED && remove(path) == 0);
+        EXPECT(pa_write_bus_called(NULL, h, fastq, fastq, NULL, 4, 4, &kp, dir, 1, NULL, NULL, kst) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_count_cells_em_called(NULL, h, fastq, fastq, NULL, 4, 4, &kp, NULL, dir, 1, NULL, NULL, kst) == PA_ERR_INVALID_ARG);
+    }
+
     {   /* paired-end reads, host side: the checks that come before any device call */
         uint64_t pst[PA_PAIR_STATS], pu = 0, pn = 0, poff[2] = {0, 0};
         pa_read_result pr[1];
@@ -712,6 +750,37 @@ int main(int argc, char** argv) {
                            cst13[2] == cst13[3] + cst13[4] + cst13[5] + cst13[6] && cst13[0] == cst13[7] + cst13[8] + cst13[9]);
                     EXPECT(pa_write_bus_corrected(idx, h, fastq, fastq, path, 17, 4, dir, 2, bst, cst13) == PA_ERR_UNSUPPORTED);
                     EXPECT(pa_count_cells_em_corrected(idx, h, fastq, fastq, path, 4, 4, NULL, dir, 2, gst, cst13) == PA_OK && gst[0] == cst13[11]);
+                }
+                {   /* cell calling: barcode 27 has two molecules, 26 and 90 one each; min_umis 2 calls 27 alone; then the filter; then the file-level entries */
+                    const pa_bus_record krec[5] = {{26, 0, 0, 1, 0, 0}, {27, 0, 0, 2, 0, 0}, {27, 0, 1, 4, 0, 0}, {27, 1, 0, 1, 0, 0}, {90, 0, 0, 5, 0, 0}};
+                    const uint64_t klist[2] = {27, 91};
+                    pa_knee_params kp;
+                    pa_bus_barcode_row krows[3];
+                    pa_bus_record kout[5];
+                    uint64_t kcalled[3], knr = 0, knc = 0, kn = 0, kst[PA_KNEE_STATS], pst[PA_BUS_KEEP_STATS], cst13[PA_BUS_CORRECT_STATS], gst[PA_GENES_STATS];
+                    float kms[PA_KNEE_PHASES];
+                    pa_knee_default_params(&kp);
+                    kp.mode = PA_KNEE_MIN;
+                    kp.min_umis = 2;
+                    EXPECT(pa_bus_knee_records(idx, krec, 5, 4, 4, &kp, krows, 2, &knr, kcalled, 3, &knc, kst) == PA_ERR_BUFFER_TOO_SMALL && knr == 3 && knc == 1);
+                    EXPECT(pa_bus_knee_records(idx, krec, 5, 4, 4, &kp, NULL, 0, &knr, NULL, 0, &knc, kst) == PA_OK && knr == 3 && knc == 1);
+                    EXPECT(pa_bus_knee_records(idx, krec, 5, 4, 4, &kp, krows, 3, &knr, kcalled, 3, &knc, kst) == PA_OK && knr == 3 && knc == 1 && kcalled[0] == 27);
+                    EXPECT(krows[1].barcode == 27 && krows[1].records == 3 && krows[1].umis == 2 && krows[1].reads == 7 && krows[1].rank == 0 && krows[1].called == 1);
+                    EXPECT(krows[0].rank == 1 && krows[2].rank == 2 && krows[0].called == 0 && krows[2].reads == 5);
+                    EXPECT(kst[0] == 5 && kst[1] == 13 && kst[2] == 4 && kst[3] == 3 && kst[4] == 2 && kst[5] == 0 && kst[6] == 2 && kst[7] == 1 && kst[8] == 2 && kst[9] == 7);
+                    EXPECT(pa_bus_knee_phase_ms(kms) == PA_OK && kms[0] >= 0.0f);
+                    EXPECT(pa_bus_keep_records(idx, krec, 5, 4, 4, klist, 2, kout, 2, &kn, pst) == PA_ERR_BUFFER_TOO_SMALL && kn == 3);
+                    EXPECT(pa_bus_keep_records(idx, krec, 5, 4, 4, klist, 2, kout, 5, &kn, pst) == PA_OK && kn == 3 && kout[0].barcode == 27 && kout[2].umi == 1 && kout[1].count == 4);
+                    EXPECT(pst[0] == 5 && pst[1] == 13 && pst[2] == 3 && pst[3] == 1 && pst[4] == 3 && pst[5] == 7 && pst[6] == 1);
+                    kp.min_umis = 1;
+                    EXPECT(pa_write_bus_called(idx, h, fastq, fastq, NULL, 4, 4, &kp, dir, 2, bst, cst13, kst) == PA_OK && bst[0] == nreads && kst[7] == kst[3] &&
+                           cst13[3] == cst13[2] && bst[7] == kst[0]);
+                    snprintf(path, sizeof path, "%s/abi_check_whitelist.txt", dir);
+                    EXPECT(pa_count_cells_em_called(idx, h, fastq, fastq, path, 4, 4, &kp, NULL, dir, 2, gst, cst13, kst) == PA_OK && gst[0] == kst[0] && kst[0] == cst13[11]);
+                    kp.min_umis = 1000000;
+                    EXPECT(pa_write_bus_called(idx, h, fastq, fastq, NULL, 4, 4, &kp, dir, 2, bst, cst13, kst) == PA_ERR_FORMAT && strstr(pa_last_error(), "threshold of 1000000"));
+                    snprintf(path, sizeof path, "%s/barcode_ranks.tsv", dir);
+                    EXPECT(remove(path) == 0);   /* (the two calls that went through wrote it) */
                 }
             }
             free(mc); free(mg); free(mu); free(r1); free(r1o);

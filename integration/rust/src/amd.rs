@@ -1,4 +1,4 @@
-//! Exporter + drop-in `process_reads` for the reference crate. Add `mod amd_ffi; mod amd;` to src/lib.rs (and `mod amd_pairs_ffi;` for `map_pairs`, `mod amd_strands_ffi;` for `map_pairs_unstranded`, `mod amd_bgzf_ffi;` for `bgzf_members`, `mod amd_bus_ffi;` for `write_bus`, `mod amd_genes_ffi;` for `count_cells_em`, `mod amd_correct_ffi;` for `write_bus_corrected` / `count_cells_em_corrected`).
+//! Exporter + drop-in `process_reads` for the reference crate. Add `mod amd_ffi; mod amd;` to src/lib.rs (and `mod amd_pairs_ffi;` for `map_pairs`, `mod amd_strands_ffi;` for `map_pairs_unstranded`, `mod amd_bgzf_ffi;` for `bgzf_members`, `mod amd_bus_ffi;` for `write_bus`, `mod amd_genes_ffi;` for `count_cells_em`, `mod amd_correct_ffi;` for `write_bus_corrected` / `count_cells_em_corrected`, `mod amd_knee_ffi;` for `bus_knee` / `write_bus_called` / `count_cells_em_called`).
 //! The exporter only reads `pub` fields of `Pseudoaligner<K>` (src/pseudoaligner.rs:27-33); `dbg_index` (the boomphf MPHF,
 //! :30) is not exported: every hit is verified against the node sequence (:99-107), which makes it an exact dictionary that
 //! the library rebuilds. Not compiled in the image of this repository (no rustc): kept in step with
@@ -444,6 +444,113 @@ pub fn count_cells_em_corrected<P: AsRef<Path>>(index_file: P, r1_fastq: P, r2_f
                                                   stats.as_mut_ptr(), cstats.as_mut_ptr()) };
     }
     let result = check(rc).map(|_| (stats, cstats));   // (the message is read before the handles go)
+    unsafe {
+        if !idx.is_null() { pa_index_destroy(idx); }
+        pa_host_index_destroy(h);
+    }
+    result
+}
+
+/// Cell calling on BUS records that lie on the host (pa_bus_knee_records; an output.bus read back, for instance): the barcode table ranked by
+/// molecules and the barcodes the threshold rule calls, on GPU `device` of the index in `index_file`. `params`: None = the library's
+/// defaults (curve knee, lower 10, divisor 10). Returns (rows in ascending barcode order, the called barcodes packed and ascending,
+/// PA_KNEE_STATS); the called list can go to pa_bus_correct / pa_bus_keep as it is.
+pub fn bus_knee<P: AsRef<Path>>(index_file: P, records: &[crate::amd_bus_ffi::PaBusRecord], bc_len: u32, umi_len: u32,
+                                params: Option<crate::amd_knee_ffi::PaKneeParams>,
+                                device: i32) -> Result<(Vec<crate::amd_knee_ffi::PaBusBarcodeRow>, Vec<u64>, [u64; crate::amd_knee_ffi::PA_KNEE_STATS]), Error> {
+    use crate::amd_knee_ffi::*;
+    let ix = CString::new(index_file.as_ref().to_string_lossy().into_owned())?;
+    let mut h = std::ptr::null_mut();
+    check(unsafe { pa_host_index_load(ix.as_ptr(), &mut h) })?;
+    let mut view: PaFlatIndex = unsafe { std::mem::zeroed() };
+    let mut idx = std::ptr::null_mut();
+    let mut rc = unsafe { pa_host_index_view(h, &mut view) };
+    if rc >= 0 { rc = unsafe { pa_index_create(&view, device, &mut idx) }; }
+    let mut stats = [0u64; PA_KNEE_STATS];
+    let (mut rows, mut called) = (Vec::<PaBusBarcodeRow>::new(), Vec::<u64>::new());
+    if rc >= 0 {
+        let p = params.as_ref().map_or(std::ptr::null(), |p| p as *const PaKneeParams);
+        let (mut n_rows, mut n_called) = (0u64, 0u64);
+        // the sizes first, then the arrays
+        rc = unsafe { pa_bus_knee_records(idx, records.as_ptr(), records.len() as u64, bc_len, umi_len, p, std::ptr::null_mut(), 0, &mut n_rows,
+                                          std::ptr::null_mut(), 0, &mut n_called, stats.as_mut_ptr()) };
+        if rc >= 0 {
+            rows.resize(n_rows as usize, PaBusBarcodeRow::default());
+            called.resize(n_called as usize, 0);
+            rc = unsafe { pa_bus_knee_records(idx, records.as_ptr(), records.len() as u64, bc_len, umi_len, p, rows.as_mut_ptr(), n_rows, &mut n_rows,
+                                              called.as_mut_ptr(), n_called, &mut n_called, stats.as_mut_ptr()) };
+        }
+    }
+    let result = check(rc).map(|_| (rows, called, stats));   // (the message is read before the handles go)
+    unsafe {
+        if !idx.is_null() { pa_index_destroy(idx); }
+        pa_host_index_destroy(h);
+    }
+    result
+}
+
+/// `write_bus` with cells called on the GPU before the files are written (pa_write_bus_called). `whitelist` None: the called barcodes are
+/// the whitelist of the correction (`bustools whitelist` + `correct`); Some(file): the barcodes are corrected against it, then the records
+/// of uncalled barcodes are dropped. Also writes `out_dir`/barcode_ranks.tsv. Returns (PA_BUS_STATS, PA_BUS_CORRECT_STATS, PA_KNEE_STATS).
+pub fn write_bus_called<P: AsRef<Path>>(index_file: P, r1_fastq: P, r2_fastq: P, whitelist: Option<P>, out_dir: P, bc_len: u32, umi_len: u32,
+                                        knee: Option<crate::amd_knee_ffi::PaKneeParams>, num_threads: usize,
+                                        device: i32) -> Result<([u64; crate::amd_bus_ffi::PA_BUS_STATS], [u64; crate::amd_correct_ffi::PA_BUS_CORRECT_STATS],
+                                                                [u64; crate::amd_knee_ffi::PA_KNEE_STATS]), Error> {
+    use crate::amd_bus_ffi::*;
+    use crate::amd_correct_ffi::*;
+    use crate::amd_knee_ffi::*;
+    let cstr = |p: &P| CString::new(p.as_ref().to_string_lossy().into_owned());
+    let (ix, r1, r2, out) = (cstr(&index_file)?, cstr(&r1_fastq)?, cstr(&r2_fastq)?, cstr(&out_dir)?);
+    let wl = match whitelist.as_ref() { Some(w) => Some(cstr(w)?), None => None };
+    let mut h = std::ptr::null_mut();
+    check(unsafe { pa_host_index_load(ix.as_ptr(), &mut h) })?;
+    let mut view: PaFlatIndex = unsafe { std::mem::zeroed() };
+    let mut idx = std::ptr::null_mut();
+    let mut rc = unsafe { pa_host_index_view(h, &mut view) };
+    if rc >= 0 { rc = unsafe { pa_index_create(&view, device, &mut idx) }; }
+    let (mut stats, mut cstats, mut kstats) = ([0u64; PA_BUS_STATS], [0u64; PA_BUS_CORRECT_STATS], [0u64; PA_KNEE_STATS]);
+    if rc >= 0 {
+        let kp = knee.as_ref().map_or(std::ptr::null(), |p| p as *const PaKneeParams);
+        let wlp = wl.as_ref().map_or(std::ptr::null(), |w| w.as_ptr());
+        rc = unsafe { pa_write_bus_called(idx, h, r1.as_ptr(), r2.as_ptr(), wlp, bc_len, umi_len, kp, out.as_ptr(), num_threads as i32, stats.as_mut_ptr(),
+                                          cstats.as_mut_ptr(), kstats.as_mut_ptr()) };
+    }
+    let result = check(rc).map(|_| (stats, cstats, kstats));   // (the message is read before the handles go)
+    unsafe {
+        if !idx.is_null() { pa_index_destroy(idx); }
+        pa_host_index_destroy(h);
+    }
+    result
+}
+
+/// `count_cells_em` with cells called between the BUS records and the gene stage (pa_count_cells_em_called; `write_bus_called`'s rules): the
+/// matrix is the filtered one. Returns (PA_GENES_STATS, PA_BUS_CORRECT_STATS, PA_KNEE_STATS).
+pub fn count_cells_em_called<P: AsRef<Path>>(index_file: P, r1_fastq: P, r2_fastq: P, whitelist: Option<P>, out_dir: P, bc_len: u32, umi_len: u32,
+                                             knee: Option<crate::amd_knee_ffi::PaKneeParams>, params: Option<crate::amd_genes_ffi::PaGenesParams>,
+                                             num_threads: usize,
+                                             device: i32) -> Result<([u64; crate::amd_genes_ffi::PA_GENES_STATS], [u64; crate::amd_correct_ffi::PA_BUS_CORRECT_STATS],
+                                                                     [u64; crate::amd_knee_ffi::PA_KNEE_STATS]), Error> {
+    use crate::amd_correct_ffi::*;
+    use crate::amd_genes_ffi::*;
+    use crate::amd_knee_ffi::*;
+    let cstr = |p: &P| CString::new(p.as_ref().to_string_lossy().into_owned());
+    let (ix, r1, r2, out) = (cstr(&index_file)?, cstr(&r1_fastq)?, cstr(&r2_fastq)?, cstr(&out_dir)?);
+    let wl = match whitelist.as_ref() { Some(w) => Some(cstr(w)?), None => None };
+    let mut h = std::ptr::null_mut();
+    check(unsafe { pa_host_index_load(ix.as_ptr(), &mut h) })?;
+    let mut view: PaFlatIndex = unsafe { std::mem::zeroed() };
+    let mut idx = std::ptr::null_mut();
+    let mut rc = unsafe { pa_host_index_view(h, &mut view) };
+    if rc >= 0 { rc = unsafe { pa_index_create(&view, device, &mut idx) }; }
+    let (mut stats, mut cstats, mut kstats) = ([0u64; PA_GENES_STATS], [0u64; PA_BUS_CORRECT_STATS], [0u64; PA_KNEE_STATS]);
+    if rc >= 0 {
+        let kp = knee.as_ref().map_or(std::ptr::null(), |p| p as *const PaKneeParams);
+        let p = params.as_ref().map_or(std::ptr::null(), |p| p as *const PaGenesParams);
+        let wlp = wl.as_ref().map_or(std::ptr::null(), |w| w.as_ptr());
+        rc = unsafe { pa_count_cells_em_called(idx, h, r1.as_ptr(), r2.as_ptr(), wlp, bc_len, umi_len, kp, p, out.as_ptr(), num_threads as i32,
+                                               stats.as_mut_ptr(), cstats.as_mut_ptr(), kstats.as_mut_ptr()) };
+    }
+    let result = check(rc).map(|_| (stats, cstats, kstats));   // (the message is read before the handles go)
     unsafe {
         if !idx.is_null() { pa_index_destroy(idx); }
         pa_host_index_destroy(h);

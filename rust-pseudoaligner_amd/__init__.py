@@ -24,7 +24,7 @@ __all__ = ["HostIndex", "Txome", "Pseudoaligner", "build_index", "process_reads"
            "gather_classes", "unpack_compact", "unpack_tiles", "RESULT_DTYPE", "PA_MAPPED_BIT", "PA_DEFAULT_ALLOWED_MISMATCHES",
            "PA_READ_COVERAGE_THRESHOLD", "PA_CLASS_REF", "Overflow", "Comm", "parse_overflow", "serialise_overflow", "overflow_merge",
            "CellCounter", "load_whitelist", "Quantifier", "BusWriter", "BUS_RECORD_DTYPE", "GeneCounter", "bus_whitelist_pack", "bus_correct", "bus_correct_phase_ms",
-           "CORRECT_STAT_NAMES"]
+           "CORRECT_STAT_NAMES", "BARCODE_ROW_DTYPE", "bus_knee", "bus_keep", "bus_knee_phase_ms", "write_barcode_ranks_tsv", "KNEE_STAT_NAMES", "KEEP_STAT_NAMES"]
 
 PA_CLASS_REF = 0x80000000
 RESULT_DTYPE = np.dtype([("coverage", "<u4"), ("mismatches", "<u4"), ("class_off", "<u4"), ("class_len", "<u4")])
@@ -472,12 +472,24 @@ class Pseudoaligner:
         return dict(zip(_ffi.CELL_STAT_NAMES, (int(x) for x in st)))
 
     def write_bus(self, host_index: HostIndex, r1: str, r2: str, out_dir: str, bc_len: int = 16, umi_len: int = 12, num_threads: int = 0,
-                  whitelist: Optional[str] = None) -> dict:
+                  whitelist: Optional[str] = None, call_cells=None) -> dict:
         """Paired R1 (barcode + UMI) / R2 (cDNA) FASTQ -> out_dir/output.bus (sorted, collapsed BUS v1 records), matrix.ec and
         transcripts.txt (pa_write_bus): the input of the kallisto | bustools family. Returns the stats (BusWriter.stats). With `whitelist`
         (the path of a barcode whitelist file) the barcodes are corrected against it before the files are written
-        (pa_write_bus_corrected), and the stats hold the correction's under "correct" (BusWriter.correct)."""
+        (pa_write_bus_corrected), and the stats hold the correction's under "correct" (BusWriter.correct). With `call_cells` (True for the
+        defaults, or a dict of knee params as BusWriter.knee takes them) cells are called (pa_write_bus_called): without a whitelist the called
+        barcodes are the whitelist of the correction, with one the corrected records of uncalled barcodes are dropped; out_dir/barcode_ranks.tsv
+        holds the table, and the stats hold the knee's under "knee"."""
         st = np.zeros(_ffi.PA_BUS_STATS, np.uint64)
+        if call_cells is not None and call_cells is not False:
+            kp = _knee_params(call_cells)
+            cs, ks = np.zeros(_ffi.PA_BUS_CORRECT_STATS, np.uint64), np.zeros(_ffi.PA_KNEE_STATS, np.uint64)
+            check(lib().pa_write_bus_called(self._h, host_index._h, str(r1).encode(), str(r2).encode(), str(whitelist).encode() if whitelist is not None else None, bc_len,
+                                            umi_len, C.byref(kp), str(out_dir).encode(), num_threads, st.ctypes.data, cs.ctypes.data, ks.ctypes.data))
+            out = dict(zip(_ffi.BUS_STAT_NAMES, (int(x) for x in st)))
+            out["correct"] = dict(zip(_ffi.CORRECT_STAT_NAMES, (int(x) for x in cs)))
+            out["knee"] = dict(zip(_ffi.KNEE_STAT_NAMES, (int(x) for x in ks)))
+            return out
         if whitelist is not None:
             cs = np.zeros(_ffi.PA_BUS_CORRECT_STATS, np.uint64)
             check(lib().pa_write_bus_corrected(self._h, host_index._h, str(r1).encode(), str(r2).encode(), str(whitelist).encode(), bc_len, umi_len,
@@ -490,13 +502,24 @@ class Pseudoaligner:
         return dict(zip(_ffi.BUS_STAT_NAMES, (int(x) for x in st)))
 
     def count_cells_em(self, host_index: HostIndex, r1: str, r2: str, out_dir: str, bc_len: int = 16, umi_len: int = 12, num_threads: int = 0,
-                       whitelist: Optional[str] = None, **params) -> dict:
+                       whitelist: Optional[str] = None, call_cells=None, **params) -> dict:
         """Paired R1 (barcode + UMI) / R2 (cDNA) FASTQ -> out_dir/matrix.mtx (real values), barcodes.tsv, features.tsv (pa_count_cells_em):
         write_bus's records, never written, shared out over genes by a per-cell EM (GeneCounter). params: GeneCounter's. Returns the stats
         (GeneCounter.stats). With `whitelist` (the path of a barcode whitelist file) the barcodes are corrected against it before the
-        gene stage (pa_count_cells_em_corrected), and the stats hold the correction's under "correct"."""
+        gene stage (pa_count_cells_em_corrected), and the stats hold the correction's under "correct". With `call_cells` (True or a dict of
+        knee params) cells are called before the gene stage as write_bus calls them (pa_count_cells_em_called): the matrix is the filtered
+        one, out_dir/barcode_ranks.tsv holds the table, and the stats hold the knee's under "knee"."""
         p = _genes_params(params)
         st = np.zeros(_ffi.PA_GENES_STATS, np.uint64)
+        if call_cells is not None and call_cells is not False:
+            kp = _knee_params(call_cells)
+            cs, ks = np.zeros(_ffi.PA_BUS_CORRECT_STATS, np.uint64), np.zeros(_ffi.PA_KNEE_STATS, np.uint64)
+            check(lib().pa_count_cells_em_called(self._h, host_index._h, str(r1).encode(), str(r2).encode(), str(whitelist).encode() if whitelist is not None else None,
+                                                 bc_len, umi_len, C.byref(kp), C.byref(p), str(out_dir).encode(), num_threads, st.ctypes.data, cs.ctypes.data, ks.ctypes.data))
+            out = dict(zip(_ffi.GENES_STAT_NAMES, (int(x) for x in st)))
+            out["correct"] = dict(zip(_ffi.CORRECT_STAT_NAMES, (int(x) for x in cs)))
+            out["knee"] = dict(zip(_ffi.KNEE_STAT_NAMES, (int(x) for x in ks)))
+            return out
         if whitelist is not None:
             cs = np.zeros(_ffi.PA_BUS_CORRECT_STATS, np.uint64)
             check(lib().pa_count_cells_em_corrected(self._h, host_index._h, str(r1).encode(), str(r2).encode(), str(whitelist).encode(), bc_len, umi_len, C.byref(p),
@@ -739,6 +762,24 @@ class BusWriter:
         check(lib().pa_bus_correct(self._h, wl.ctypes.data if len(wl) else None, len(wl), st.ctypes.data))
         return dict(zip(_ffi.CORRECT_STAT_NAMES, (int(x) for x in st)))
 
+    def knee(self, **params) -> Tuple[np.ndarray, np.ndarray, dict]:
+        """pa_bus_knee: the barcode table of the finished records (finished here if they are not yet), ranked by molecules, and the barcodes
+        the threshold rule calls -> (rows as BARCODE_ROW_DTYPE in ascending barcode order, the called barcodes packed and ascending, the
+        stats (KNEE_STAT_NAMES)). params: the fields of pa_knee_params (mode = "curve" | "expected" | "min", lower, divisor, expected_cells,
+        min_umis); what is not given keeps the library's default. The writer is unchanged; correct(called) or keep(called) apply the call."""
+        self.finish()
+        p = _knee_params(params)
+        return _knee_call(lambda *out: lib().pa_bus_knee(self._h, C.byref(p), *out))
+
+    def keep(self, barcodes) -> dict:
+        """pa_bus_keep: only the records whose barcode is in `barcodes` (packed values, strictly ascending) stay, in place; no neighbour is
+        rescued and nothing is sorted or joined -> the stats (KEEP_STAT_NAMES)"""
+        self.finish()
+        bc = np.ascontiguousarray(barcodes, np.uint64)
+        st = np.zeros(_ffi.PA_BUS_KEEP_STATS, np.uint64)
+        check(lib().pa_bus_keep(self._h, bc.ctypes.data if len(bc) else None, len(bc), st.ctypes.data))
+        return dict(zip(_ffi.KEEP_STAT_NAMES, (int(x) for x in st)))
+
     def write(self, out_dir: str) -> None:
         """out_dir/output.bus, matrix.ec, transcripts.txt"""
         self.finish()
@@ -792,6 +833,65 @@ def bus_correct_phase_ms() -> dict:
     ms = (C.c_float * _ffi.PA_BUS_CORRECT_PHASES)()
     check(lib().pa_bus_correct_phase_ms(ms))
     return dict(zip(_ffi.CORRECT_PHASE_NAMES, (float(x) for x in ms)))
+
+
+BARCODE_ROW_DTYPE = np.dtype([("barcode", "<u8"), ("reads", "<u8"), ("records", "<u4"), ("umis", "<u4"), ("rank", "<u4"), ("called", "<u4")])   # pa_bus_barcode_row
+KNEE_STAT_NAMES, KEEP_STAT_NAMES = _ffi.KNEE_STAT_NAMES, _ffi.KEEP_STAT_NAMES
+
+
+def _knee_params(params) -> "_ffi.KneeParams":
+    """True or an empty dict: the defaults; else the fields of pa_knee_params by name"""
+    p = _ffi.KneeParams()
+    lib().pa_knee_default_params(C.byref(p))
+    for name, value in ({} if params is True else dict(params)).items():
+        if name not in dict(_ffi.KneeParams._fields_) or name == "reserved":
+            raise TypeError("unknown knee parameter %r" % name)
+        setattr(p, name, _ffi.KNEE_MODES[value] if name == "mode" and isinstance(value, str) else value)
+    return p
+
+
+def _knee_call(call) -> Tuple[np.ndarray, np.ndarray, dict]:
+    """call(rows, rows_cap, n_rows, called, called_cap, n_called, stats): once for the sizes, once for the arrays"""
+    n_rows, n_called = C.c_uint64(), C.c_uint64()
+    st = np.zeros(_ffi.PA_KNEE_STATS, np.uint64)
+    check(call(None, 0, C.byref(n_rows), None, 0, C.byref(n_called), st.ctypes.data))
+    rows, called = np.zeros(max(n_rows.value, 1), BARCODE_ROW_DTYPE), np.zeros(max(n_called.value, 1), np.uint64)
+    check(call(rows.ctypes.data, n_rows.value, C.byref(n_rows), called.ctypes.data, n_called.value, C.byref(n_called), st.ctypes.data))
+    return rows[:n_rows.value], called[:n_called.value], dict(zip(_ffi.KNEE_STAT_NAMES, (int(x) for x in st)))
+
+
+def bus_knee(records, bc_len: int, umi_len: int, index: Optional["Pseudoaligner"], **params) -> Tuple[np.ndarray, np.ndarray, dict]:
+    """pa_bus_knee_records: host records (BUS_RECORD_DTYPE, strictly ascending by barcode, UMI, ec) on `index`'s GPU -> (rows, called, stats) as
+    BusWriter.knee gives them"""
+    rec = np.ascontiguousarray(records, BUS_RECORD_DTYPE)
+    p = _knee_params(params)
+    return _knee_call(lambda *out: lib().pa_bus_knee_records(index._h if index is not None else None, rec.ctypes.data if len(rec) else None, len(rec), bc_len, umi_len,
+                                                             C.byref(p), *out))
+
+
+def bus_keep(records, barcodes, bc_len: int, umi_len: int, index: Optional["Pseudoaligner"]) -> Tuple[np.ndarray, dict]:
+    """pa_bus_keep_records: the host records whose barcode is in `barcodes` (packed values, strictly ascending), in their order -> (records, stats)"""
+    rec = np.ascontiguousarray(records, BUS_RECORD_DTYPE)
+    bc = np.ascontiguousarray(barcodes, np.uint64)
+    st = np.zeros(_ffi.PA_BUS_KEEP_STATS, np.uint64)
+    out = np.zeros(max(len(rec), 1), BUS_RECORD_DTYPE)
+    n = C.c_uint64()
+    check(lib().pa_bus_keep_records(index._h if index is not None else None, rec.ctypes.data if len(rec) else None, len(rec), bc_len, umi_len,
+                                    bc.ctypes.data if len(bc) else None, len(bc), out.ctypes.data, len(rec), C.byref(n), st.ctypes.data))
+    return out[:n.value], dict(zip(_ffi.KEEP_STAT_NAMES, (int(x) for x in st)))
+
+
+def bus_knee_phase_ms() -> dict:
+    """pa_bus_knee_phase_ms: the GPU milliseconds of this thread's last knee, by phase"""
+    ms = (C.c_float * _ffi.PA_KNEE_PHASES)()
+    check(lib().pa_bus_knee_phase_ms(ms))
+    return dict(zip(_ffi.KNEE_PHASE_NAMES, (float(x) for x in ms)))
+
+
+def write_barcode_ranks_tsv(rows, bc_len: int, path: str) -> None:
+    """pa_write_barcode_ranks_tsv: the rows of a knee as barcode_ranks.tsv"""
+    r = np.ascontiguousarray(rows, BARCODE_ROW_DTYPE)
+    check(lib().pa_write_barcode_ranks_tsv(r.ctypes.data if len(r) else None, len(r), bc_len, str(path).encode()))
 
 
 def _genes_params(params: dict) -> "_ffi.GenesParams":

@@ -27,6 +27,14 @@ CORRECT_STAT_NAMES = ("records_in", "reads_in", "barcodes_in", "barcodes_exact",
                       "records_corrected", "records_dropped", "reads_dropped", "records_out", "barcodes_out")
 PA_BUS_CORRECT_PHASES = 4
 CORRECT_PHASE_NAMES = ("table_ms", "classify_exact_ms", "classify_neighbours_ms", "rewrite_ms")
+PA_KNEE_CURVE, PA_KNEE_EXPECTED, PA_KNEE_MIN = 0, 1, 2
+KNEE_MODES = {"curve": PA_KNEE_CURVE, "expected": PA_KNEE_EXPECTED, "min": PA_KNEE_MIN}
+PA_KNEE_STATS = 10
+KNEE_STAT_NAMES = ("records", "reads", "molecules", "barcodes", "distinct_values", "values_above_lower", "threshold", "barcodes_called", "molecules_called", "reads_called")
+PA_KNEE_PHASES = 3
+KNEE_PHASE_NAMES = ("table_ms", "rank_curve_ms", "called_rows_ms")
+PA_BUS_KEEP_STATS = 7
+KEEP_STAT_NAMES = ("records_in", "reads_in", "barcodes_in", "barcodes_kept", "records_out", "reads_out", "listed_absent")
 PA_MAPPED_BIT = 0x80000000
 PA_DEFAULT_ALLOWED_MISMATCHES = 2
 PA_READ_COVERAGE_THRESHOLD = 32
@@ -72,6 +80,10 @@ class QuantParams(C.Structure):
 class GenesParams(C.Structure):
     _fields_ = [("alpha_limit", C.c_double), ("alpha_change_limit", C.c_double), ("alpha_change", C.c_double),
                 ("min_iters", C.c_uint32), ("max_iters", C.c_uint32), ("check_every", C.c_uint32), ("mode", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class KneeParams(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("lower", C.c_uint32), ("divisor", C.c_uint32), ("expected_cells", C.c_uint32), ("min_umis", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
 class BgzfMember(C.Structure):
@@ -197,6 +209,16 @@ SIGNATURES = {
     "pa_bus_correct": (C.c_int, [vp, vp, C.c_uint64, vp]),
     "pa_bus_correct_phase_ms": (C.c_int, [C.POINTER(C.c_float)]),
     "pa_write_bus_corrected": (C.c_int, [vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, vp, vp]),
+    "pa_knee_default_params": (None, [C.POINTER(KneeParams)]),
+    "pa_bus_knee_records": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(KneeParams), vp, C.c_uint64, u64p, vp, C.c_uint64, u64p, vp]),
+    "pa_bus_knee": (C.c_int, [vp, C.POINTER(KneeParams), vp, C.c_uint64, u64p, vp, C.c_uint64, u64p, vp]),
+    "pa_bus_knee_phase_ms": (C.c_int, [C.POINTER(C.c_float)]),
+    "pa_bus_keep_records": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, u64p, vp]),
+    "pa_bus_keep": (C.c_int, [vp, vp, C.c_uint64, vp]),
+    "pa_write_barcode_ranks_tsv": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_char_p]),
+    "pa_write_bus_called": (C.c_int, [vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(KneeParams), C.c_char_p, C.c_int, vp, vp, vp]),
+    "pa_count_cells_em_called": (C.c_int, [vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(KneeParams), C.POINTER(GenesParams), C.c_char_p, C.c_int,
+                                           vp, vp, vp]),
     "pa_genes_default_params": (None, [C.POINTER(GenesParams)]),
     "pa_genes_create": (C.c_int, [vp, vp, C.c_uint64, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(GenesParams), C.POINTER(vp)]),
     "pa_genes_create_from_bus": (C.c_int, [vp, vp, C.c_uint32, C.POINTER(GenesParams), C.POINTER(vp)]),

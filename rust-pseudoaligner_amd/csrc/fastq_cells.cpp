@@ -13,6 +13,7 @@
 #include <string>
 #include <unordered_set>
 
+#include "bus_knee_host.hpp"
 #include "pair_reader.hpp"
 
 using namespace pa;
@@ -215,15 +216,44 @@ int count_cells_impl(pa_index* idx, const pa_host_index* h, const char* r1_path,
 
 // ---- pa_write_bus / pa_count_cells_em: the same two files -> sorted (barcode, UMI, ec) records in HBM, then `after(bus, st)`: the writer's three files, or
 // the gene stage and its three files (after() adds its own seconds to st[ST_TALLY] / st[ST_WRITE]). With a whitelist file (the *_corrected calls) the
-// barcodes of the finished records are corrected against it in HBM before `after` sees them (pa_bus_correct; its seconds go to st[ST_TALLY]) ----
+// barcodes of the finished records are corrected against it in HBM before `after` sees them (pa_bus_correct; its seconds go to st[ST_TALLY]); with a knee (the
+// *_called calls) cells are called there too (pa_bus_knee, then pa_bus_correct or pa_bus_keep; st[ST_TALLY], the table's file st[ST_WRITE]) ----
 struct BusWhitelist {
     const char* path = nullptr;   // nullptr: no correction
     uint64_t* stats = nullptr;    // [PA_BUS_CORRECT_STATS], may be nullptr
 };
 
+// Cell calling (the *_called calls; pa_bus_knee): without a whitelist file the called barcodes ARE the whitelist of the correction; with one the
+// corrected records are ranked and the uncalled barcodes filtered out (pa_bus_keep). Either way out_dir/barcode_ranks.tsv holds the knee's table
+struct BusKnee {
+    bool on = false;
+    const pa_knee_params* params = nullptr;   // nullptr: the defaults
+    uint64_t* stats = nullptr;                // [PA_KNEE_STATS], may be nullptr
+};
+
+// after pa_bus_finish: correction and cell calling in the order the two inputs ask for; the seconds of the table's file go to *write_seconds
+int bus_call_cells(pa_bus* bus, const BusWhitelist& wl, const std::vector<uint64_t>& packed, const BusKnee& knee, uint32_t bc_len, const char* out_dir, double* write_seconds) {
+    int rc = PA_OK;
+    if (wl.path && (rc = pa_bus_correct(bus, packed.data(), packed.size(), wl.stats)) != PA_OK) return rc;
+    if (!knee.on) return PA_OK;
+    std::vector<pa_bus_barcode_row> rows;
+    std::vector<uint64_t> called;
+    uint64_t ks[PA_KNEE_STATS] = {};
+    if ((rc = pa_bus_knee_vectors(bus, knee.params, rows, called, ks)) != PA_OK) return rc;
+    if (knee.stats) memcpy(knee.stats, ks, sizeof ks);
+    if (called.empty()) return fail(PA_ERR_FORMAT, "no barcode reaches the threshold of %llu molecules", (unsigned long long)ks[6]);
+    // listed barcodes are only filtered (a second correction would move listed, uncalled barcodes into called neighbours); unlisted ones are corrected against the called
+    rc = wl.path ? pa_bus_keep(bus, called.data(), called.size(), nullptr) : pa_bus_correct(bus, called.data(), called.size(), wl.stats);
+    if (rc != PA_OK) return rc;
+    const double t0 = now();
+    if ((rc = pa_write_barcode_ranks_tsv(rows.data(), rows.size(), bc_len, (std::string(out_dir) + "/barcode_ranks.tsv").c_str())) != PA_OK) return rc;
+    *write_seconds = now() - t0;
+    return PA_OK;
+}
+
 template <class After>
-int bus_run(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const BusWhitelist& wl, uint32_t bc_len, uint32_t umi_len, const char* out_dir,
-            int num_threads, After&& after) {
+int bus_run(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const BusWhitelist& wl, const BusKnee& knee, uint32_t bc_len, uint32_t umi_len,
+            const char* out_dir, int num_threads, After&& after) {
     std::unique_ptr<pa_bus, void (*)(pa_bus*)> own(nullptr, pa_bus_destroy);   // (in front of the frame: destroyed behind its streams)
     PairedCall call(num_threads);
     double* const st = call.st;
@@ -231,6 +261,8 @@ int bus_run(pa_index* idx, const pa_host_index* h, const char* r1_path, const ch
     struct stat sd;
     if (stat(out_dir, &sd) != 0 || !S_ISDIR(sd.st_mode)) return fail(PA_ERR_IO, "%s is no directory", out_dir);
     int rc = PA_OK;
+    pa_knee_params knee_checked;
+    if (knee.on && (rc = pa::knee::take_params(knee.params, knee_checked)) != PA_OK) return rc;   // refused before a read is mapped, like the whitelist
     std::vector<uint64_t> packed;
     if (wl.path) {   // the whitelist first: a file that cannot be used is refused before a read is mapped
         if (bc_len > 16) return fail(PA_ERR_UNSUPPORTED, "barcode length %u: a whitelist file holds barcodes of at most 16 bases", bc_len);
@@ -258,16 +290,18 @@ int bus_run(pa_index* idx, const pa_host_index* h, const char* r1_path, const ch
     uint64_t n_records = 0;
     uint32_t n_ecs = 0;
     if ((rc = pa_bus_finish(bus, &n_records, &n_ecs)) != PA_OK) return rc;
-    if (wl.path && (rc = pa_bus_correct(bus, packed.data(), packed.size(), wl.stats)) != PA_OK) return rc;
-    st[ST_TALLY] += now() - t0;
+    double ranks_seconds = 0.0;
+    if ((rc = bus_call_cells(bus, wl, packed, knee, bc_len, out_dir, &ranks_seconds)) != PA_OK) return rc;
+    st[ST_TALLY] += now() - t0 - ranks_seconds;
     if ((rc = after(bus, st)) != PA_OK) return rc;
+    st[ST_WRITE] += ranks_seconds;
     call.done();
     return PA_OK;
 }
 
-int write_bus_impl(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const BusWhitelist& wl, uint32_t bc_len, uint32_t umi_len,
-                   const char* out_dir, int num_threads, uint64_t* stats) {
-    return bus_run(idx, h, r1_path, r2_path, wl, bc_len, umi_len, out_dir, num_threads, [&](pa_bus* bus, double* st) {
+int write_bus_impl(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const BusWhitelist& wl, const BusKnee& knee, uint32_t bc_len,
+                   uint32_t umi_len, const char* out_dir, int num_threads, uint64_t* stats) {
+    return bus_run(idx, h, r1_path, r2_path, wl, knee, bc_len, umi_len, out_dir, num_threads, [&](pa_bus* bus, double* st) {
         const double t0 = now();
         const int rc = pa_bus_write(bus, out_dir);
         if (rc != PA_OK) return rc;
@@ -277,9 +311,9 @@ int write_bus_impl(pa_index* idx, const pa_host_index* h, const char* r1_path, c
     });
 }
 
-int count_cells_em_impl(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const BusWhitelist& wl, uint32_t bc_len, uint32_t umi_len,
-                        const pa_genes_params* p, const char* out_dir, int num_threads, uint64_t* stats) {
-    return bus_run(idx, h, r1_path, r2_path, wl, bc_len, umi_len, out_dir, num_threads, [&](pa_bus* bus, double* st) {
+int count_cells_em_impl(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const BusWhitelist& wl, const BusKnee& knee, uint32_t bc_len,
+                        uint32_t umi_len, const pa_genes_params* p, const char* out_dir, int num_threads, uint64_t* stats) {
+    return bus_run(idx, h, r1_path, r2_path, wl, knee, bc_len, umi_len, out_dir, num_threads, [&](pa_bus* bus, double* st) {
         double t0 = now();
         const uint32_t ntx = pa_host_index_num_transcripts(h);
         std::vector<uint32_t> tx_gene(ntx ? ntx : 1);
@@ -308,19 +342,19 @@ extern "C" int pa_count_cells(pa_index* idx, const pa_host_index* h, const char*
 
 extern "C" int pa_write_bus(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, uint32_t bc_len, uint32_t umi_len, const char* out_dir,
                             int num_threads, uint64_t stats[PA_BUS_STATS]) {
-    return no_throw("pa_write_bus", [&] { return write_bus_impl(idx, h, r1_path, r2_path, BusWhitelist{}, bc_len, umi_len, out_dir, num_threads, stats); });
+    return no_throw("pa_write_bus", [&] { return write_bus_impl(idx, h, r1_path, r2_path, BusWhitelist{}, BusKnee{}, bc_len, umi_len, out_dir, num_threads, stats); });
 }
 
 extern "C" int pa_count_cells_em(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, uint32_t bc_len, uint32_t umi_len, const pa_genes_params* p,
                                  const char* out_dir, int num_threads, uint64_t stats[PA_GENES_STATS]) {
-    return no_throw("pa_count_cells_em", [&] { return count_cells_em_impl(idx, h, r1_path, r2_path, BusWhitelist{}, bc_len, umi_len, p, out_dir, num_threads, stats); });
+    return no_throw("pa_count_cells_em", [&] { return count_cells_em_impl(idx, h, r1_path, r2_path, BusWhitelist{}, BusKnee{}, bc_len, umi_len, p, out_dir, num_threads, stats); });
 }
 
 extern "C" int pa_write_bus_corrected(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const char* whitelist_path, uint32_t bc_len,
                                       uint32_t umi_len, const char* out_dir, int num_threads, uint64_t bus_stats[PA_BUS_STATS], uint64_t correct_stats[PA_BUS_CORRECT_STATS]) {
     return no_throw("pa_write_bus_corrected", [&] {
         if (!whitelist_path) return fail(PA_ERR_INVALID_ARG, "null argument");
-        return write_bus_impl(idx, h, r1_path, r2_path, BusWhitelist{whitelist_path, correct_stats}, bc_len, umi_len, out_dir, num_threads, bus_stats);
+        return write_bus_impl(idx, h, r1_path, r2_path, BusWhitelist{whitelist_path, correct_stats}, BusKnee{}, bc_len, umi_len, out_dir, num_threads, bus_stats);
     });
 }
 
@@ -329,6 +363,23 @@ extern "C" int pa_count_cells_em_corrected(pa_index* idx, const pa_host_index* h
                                            uint64_t correct_stats[PA_BUS_CORRECT_STATS]) {
     return no_throw("pa_count_cells_em_corrected", [&] {
         if (!whitelist_path) return fail(PA_ERR_INVALID_ARG, "null argument");
-        return count_cells_em_impl(idx, h, r1_path, r2_path, BusWhitelist{whitelist_path, correct_stats}, bc_len, umi_len, p, out_dir, num_threads, genes_stats);
+        return count_cells_em_impl(idx, h, r1_path, r2_path, BusWhitelist{whitelist_path, correct_stats}, BusKnee{}, bc_len, umi_len, p, out_dir, num_threads, genes_stats);
+    });
+}
+
+extern "C" int pa_write_bus_called(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const char* whitelist_path, uint32_t bc_len,
+                                   uint32_t umi_len, const pa_knee_params* kp, const char* out_dir, int num_threads, uint64_t bus_stats[PA_BUS_STATS],
+                                   uint64_t correct_stats[PA_BUS_CORRECT_STATS], uint64_t knee_stats[PA_KNEE_STATS]) {
+    return no_throw("pa_write_bus_called", [&] {
+        return write_bus_impl(idx, h, r1_path, r2_path, BusWhitelist{whitelist_path, correct_stats}, BusKnee{true, kp, knee_stats}, bc_len, umi_len, out_dir, num_threads, bus_stats);
+    });
+}
+
+extern "C" int pa_count_cells_em_called(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const char* whitelist_path, uint32_t bc_len,
+                                        uint32_t umi_len, const pa_knee_params* kp, const pa_genes_params* p, const char* out_dir, int num_threads,
+                                        uint64_t genes_stats[PA_GENES_STATS], uint64_t correct_stats[PA_BUS_CORRECT_STATS], uint64_t knee_stats[PA_KNEE_STATS]) {
+    return no_throw("pa_count_cells_em_called", [&] {
+        return count_cells_em_impl(idx, h, r1_path, r2_path, BusWhitelist{whitelist_path, correct_stats}, BusKnee{true, kp, knee_stats}, bc_len, umi_len, p, out_dir, num_threads,
+                                   genes_stats);
     });
 }
