@@ -90,7 +90,6 @@ enum : uint32_t { ST_READS = 0, ST_EXACT, ST_CORRECTED, ST_BC_INVALID, ST_UMI_IN
 
 __host__ __device__ inline unsigned long long shl64(unsigned long long x, uint32_t s) { return s >= 64 ? 0ull : x << s; }
 __host__ __device__ inline unsigned long long shr64(unsigned long long x, uint32_t s) { return s >= 64 ? 0ull : x >> s; }
-__host__ __device__ inline unsigned long long low_mask(uint32_t bits) { return bits >= 64 ? ~0ull : (1ull << bits) - 1; }
 __device__ inline uint32_t cell_base(uint8_t c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u; }
 // two 2-bit codes words at Hamming distance 1: exactly one base differs
 __device__ inline bool hamming1(uint32_t x) { return __popc((x | (x >> 1)) & 0x55555555u) == 1; }

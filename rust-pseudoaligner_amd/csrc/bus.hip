@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "bus_host.hpp"
+#include "bus_records_host.hpp"
 #include "bus_state.hpp"
 #include "device_prims.hpp"
 #include "hip_buffer.hpp"
@@ -184,13 +185,6 @@ __global__ __launch_bounds__(BUS_BLOCK) void pa_bus_remap_kernel(u128* __restric
     if (a < table_n && table_hash[a] == lo) keys[i] = ((u128)key_hi(k) << 64) | table_ec[a];
     else *err = lo;
 }
-template <class T>
-int fetch(const T* d, hipStream_t s, T& out) {
-    PA_HIP_TRY(hipMemcpyAsync(&out, d, sizeof(T), hipMemcpyDeviceToHost, s));
-    PA_HIP_TRY(hipStreamSynchronize(s));
-    return PA_OK;
-}
-
 }  // namespace
 
 namespace {
@@ -211,18 +205,12 @@ int check_err(pa_bus* b, hipStream_t s, const char* what) {
     return PA_OK;
 }
 
-// sorted keys[0 .. n) -> unique[runs], start[runs + 1] (b->heads and b->pos hold the flags and their scan afterwards); n >= 1
+// sorted keys[0 .. n) -> unique[runs], b->start[runs + 1] (b->heads and b->pos hold the flags and their scan afterwards); n >= 1
 template <class K>
-int collapse(pa_bus* b, hipStream_t s, const K* keys, uint32_t n, K* unique, uint32_t& runs) {
+int collapse_keys(pa_bus* b, hipStream_t s, const K* keys, uint32_t n, K* unique, uint32_t& runs) {
     int e;
     if ((e = grow(b->heads, n)) || (e = grow(b->pos, n)) || (e = grow(b->start, (size_t)n + 1)) || (e = b->d_n.reserve(1, 1))) return e;
-    hipLaunchKernelGGL(pa_bus_heads_kernel<K>, dim3(grid_for(n, BUS_BLOCK)), dim3(BUS_BLOCK), 0, s, keys, n, b->heads.get());
-    PA_HIP_TRY(hipGetLastError());
-    if ((e = scan_inclusive(s, b->tmp, (const uint32_t*)b->heads.get(), b->pos.get(), (size_t)n))) return e;
-    hipLaunchKernelGGL(pa_bus_scatter_kernel<K>, dim3(grid_for(n, BUS_BLOCK)), dim3(BUS_BLOCK), 0, s, keys, (const uint32_t*)b->heads.get(), (const uint32_t*)b->pos.get(), n,
-                       unique, b->start.get());
-    PA_HIP_TRY(hipGetLastError());
-    return fetch_u32(b->pos.get() + (n - 1), s, runs);
+    return collapse_runs(s, b->tmp, KeyArray<K>{keys}, n, b->heads.get(), b->pos.get(), unique, b->start.get(), runs);
 }
 
 // the arena lists among the batch's `runs` new accumulator entries at `unique` (sorted reads in b->sorted / b->svals, their runs in
@@ -232,8 +220,7 @@ int collect_lists(pa_bus* b, hipStream_t s, const u128* unique, uint32_t runs, c
     uint32_t n_lists = 0;
     if ((e = grow(b->which, runs)) != PA_OK) return e;
     // (heads is free again: the flags of the runs)
-    hipLaunchKernelGGL(pa_bus_list_flags_kernel, dim3(grid_for(runs, BUS_BLOCK)), dim3(BUS_BLOCK), 0, s, unique, runs, b->heads.get());
-    PA_HIP_TRY(hipGetLastError());
+    if ((e = launch(pa_bus_list_flags_kernel, grid_for(runs, BUS_BLOCK), BUS_BLOCK, s, unique, runs, b->heads.get()))) return e;
     if ((e = select_flagged_indices(s, b->tmp, (const uint32_t*)b->heads.get(), (size_t)runs, b->which.get(), b->d_n.get())) || (e = fetch_u32(b->d_n.get(), s, n_lists)))
         return e;
     if (n_lists == 0) return PA_OK;
@@ -241,15 +228,13 @@ int collect_lists(pa_bus* b, hipStream_t s, const u128* unique, uint32_t runs, c
         (e = grow(b->lread_s, n_lists)) || (e = grow(b->lens, n_lists)) || (e = grow(b->loff, n_lists)))
         return e;
     // `start` is overwritten by the collapse below: the reads that stand for the runs are gathered first
-    hipLaunchKernelGGL(pa_bus_list_gather_kernel, dim3(grid_for(n_lists, BUS_BLOCK)), dim3(BUS_BLOCK), 0, s, unique, (const uint32_t*)b->start.get(),
-                       (const uint32_t*)b->svals.get(), (const uint32_t*)b->which.get(), n_lists, b->lhash.get(), b->lread.get());
-    PA_HIP_TRY(hipGetLastError());
+    if ((e = launch(pa_bus_list_gather_kernel, grid_for(n_lists, BUS_BLOCK), BUS_BLOCK, s, unique, (const uint32_t*)b->start.get(), (const uint32_t*)b->svals.get(),
+            (const uint32_t*)b->which.get(), n_lists, b->lhash.get(), b->lread.get()))) return e;
     if ((e = sort_pairs(s, b->tmp, (const ull*)b->lhash.get(), b->lhash_s.get(), (const uint32_t*)b->lread.get(), b->lread_s.get(), (int)n_lists, 0, 64))) return e;
     uint32_t distinct = 0;
-    if ((e = collapse<ull>(b, s, b->lhash_s.get(), n_lists, b->lhash_u.get(), distinct)) != PA_OK) return e;
-    hipLaunchKernelGGL(pa_bus_verify_runs_kernel, dim3(grid_for(n_lists, BUS_BLOCK)), dim3(BUS_BLOCK), 0, s, (const ull*)b->lhash_s.get(), (const uint32_t*)b->lread_s.get(),
-                       (const uint32_t*)b->pos.get(), (const uint32_t*)b->start.get(), n_lists, d_results, d_arena, b->lens.get(), b->d_err.get());
-    PA_HIP_TRY(hipGetLastError());
+    if ((e = collapse_keys<ull>(b, s, b->lhash_s.get(), n_lists, b->lhash_u.get(), distinct)) != PA_OK) return e;
+    if ((e = launch(pa_bus_verify_runs_kernel, grid_for(n_lists, BUS_BLOCK), BUS_BLOCK, s, (const ull*)b->lhash_s.get(), (const uint32_t*)b->lread_s.get(),
+            (const uint32_t*)b->pos.get(), (const uint32_t*)b->start.get(), n_lists, d_results, d_arena, b->lens.get(), b->d_err.get()))) return e;
     if ((e = scan_exclusive(s, b->tmp, (const ull*)b->lens.get(), b->loff.get(), (size_t)distinct))) return e;
     std::vector<ull> h_hash(distinct), h_off(distinct), h_len(distinct);
     PA_HIP_TRY(hipMemcpyAsync(h_hash.data(), b->lhash_u.get(), distinct * 8ull, hipMemcpyDeviceToHost, s));
@@ -258,9 +243,8 @@ int collect_lists(pa_bus* b, hipStream_t s, const u128* unique, uint32_t runs, c
     if ((e = check_err(b, s, "two different id lists share the content hash")) != PA_OK) return e;   // (synchronises)
     const uint64_t total = h_off[distinct - 1] + h_len[distinct - 1];
     if ((e = grow(b->pool_ids, (size_t)total)) != PA_OK) return e;
-    hipLaunchKernelGGL(pa_bus_pool_copy_kernel, dim3(grid_for(distinct, BUS_BLOCK)), dim3(BUS_BLOCK), 0, s, (const uint32_t*)b->lread_s.get(), (const uint32_t*)b->start.get(),
-                       distinct, d_results, d_arena, (const ull*)b->loff.get(), b->pool_ids.get());
-    PA_HIP_TRY(hipGetLastError());
+    if ((e = launch(pa_bus_pool_copy_kernel, grid_for(distinct, BUS_BLOCK), BUS_BLOCK, s, (const uint32_t*)b->lread_s.get(), (const uint32_t*)b->start.get(), distinct, d_results,
+            d_arena, (const ull*)b->loff.get(), b->pool_ids.get()))) return e;
     std::vector<uint32_t> h_ids((size_t)total);
     PA_HIP_TRY(hipMemcpyAsync(h_ids.data(), b->pool_ids.get(), total * 4, hipMemcpyDeviceToHost, s));
     PA_HIP_TRY(hipStreamSynchronize(s));
@@ -287,10 +271,8 @@ int sort_reduce(pa_bus* b, hipStream_t s, const u128* keys, const uint32_t* coun
                 uint32_t& runs) {
     int e;
     if ((e = sort_pairs(s, b->tmp, keys, k1, counts, c1, (size_t)n, 0, b->key_bits()))) return e;
-    if ((e = collapse<u128>(b, s, k1, (uint32_t)n, out_keys, runs)) != PA_OK) return e;
-    hipLaunchKernelGGL(pa_bus_run_counts_kernel, dim3(grid_for(runs, BUS_BLOCK)), dim3(BUS_BLOCK), 0, s, (const uint32_t*)b->start.get(), runs, (const uint32_t*)c1, out_counts);
-    PA_HIP_TRY(hipGetLastError());
-    return PA_OK;
+    if ((e = collapse_keys<u128>(b, s, k1, (uint32_t)n, out_keys, runs)) != PA_OK) return e;
+    return run_counts(s, b->start.get(), runs, c1, out_counts);
 }
 
 int bus_finish(pa_bus* b) {
@@ -323,9 +305,8 @@ int bus_finish(pa_bus* b) {
             DeviceBuffer<ull> d_th;
             DeviceBuffer<uint32_t> d_te;
             if ((e = upload(d_th, th)) || (e = upload(d_te, te))) return e;
-            hipLaunchKernelGGL(pa_bus_remap_kernel, dim3(grid_for(M, BUS_BLOCK)), dim3(BUS_BLOCK), 0, s, k2.get(), M, (const ull*)d_th.get(), (const uint32_t*)d_te.get(),
-                               (uint32_t)th.size(), b->d_err.get());
-            PA_HIP_TRY(hipGetLastError());
+            if ((e = launch(pa_bus_remap_kernel, grid_for(M, BUS_BLOCK), BUS_BLOCK, s, k2.get(), M, (const ull*)d_th.get(), (const uint32_t*)d_te.get(), (uint32_t)th.size(),
+                    b->d_err.get()))) return e;
             if ((e = check_err(b, s, "no id list was kept for the content hash")) != PA_OK) return e;
             // 3. a list that turned out to be an index class joins that class's record: sort and reduce once more -> (k2, c2)[M]
             DeviceBuffer<u128> k3;
@@ -338,9 +319,8 @@ int bus_finish(pa_bus* b) {
         }
         // 4. whole records
         if ((e = b->d_records.alloc(M)) != PA_OK) return e;
-        hipLaunchKernelGGL(pa_bus_records_kernel, dim3(grid_for(M, BUS_BLOCK)), dim3(BUS_BLOCK), 0, s, (const u128*)k2.get(), (const uint32_t*)c2.get(), M, 2 * b->umi_len,
-                           b->d_records.get());
-        PA_HIP_TRY(hipGetLastError());
+        if ((e = launch(pa_bus_records_kernel<64, 0>, grid_for(M, BUS_BLOCK), BUS_BLOCK, s, (const u128*)k2.get(), (const uint32_t*)c2.get(), M, 2 * b->umi_len,
+                b->d_records.get()))) return e;
         PA_HIP_TRY(hipStreamSynchronize(s));
         b->n_records = M;
     }
@@ -364,13 +344,13 @@ extern "C" {
 int pa_bus_create(pa_index* idx, const pa_host_index* h, uint32_t bc_len, uint32_t umi_len, pa_bus** out) {
     if (out) *out = nullptr;
     if (!idx || !h || !out) return fail(PA_ERR_INVALID_ARG, "null argument");
-    if (bc_len < 1 || umi_len < 1 || (uint64_t)bc_len + umi_len > 32)
-        return fail(PA_ERR_UNSUPPORTED, "barcode length %u / UMI length %u: both at least 1, together at most 32 bases (one 64-bit word)", bc_len, umi_len);
+    int e = bus_records::check_lengths(bc_len, umi_len, PA_ERR_UNSUPPORTED, " (one 64-bit word)");
+    if (e != PA_OK) return e;
     const HostIndex& hi = h->h;
     const uint32_t num_classes = hi.ec_offset.empty() ? 0 : (uint32_t)(hi.ec_offset.size() - 1);
     std::vector<uint32_t> class_ec;
     uint32_t M = 0;
-    int e = bus::class_ecs(hi.num_transcripts, hi.ec_offset.data(), hi.ec_ids.data(), num_classes, class_ec, &M);
+    e = bus::class_ecs(hi.num_transcripts, hi.ec_offset.data(), hi.ec_ids.data(), num_classes, class_ec, &M);
     if (e != PA_OK) return e;
     pa_index_stats ist{};
     if ((e = pa_index_get_stats(idx, &ist)) != PA_OK) return e;
@@ -403,11 +383,10 @@ int pa_bus_add_device(pa_bus* b, const pa_read_result* d_results, const uint32_t
     BusKeyParams p;
     p.results = d_results; p.arena = d_arena; p.arena_len = arena_len; p.r1 = d_r1; p.r1_off = d_r1_offsets; p.n = n_reads;
     p.class_ec = b->d_class_ec.get(); p.num_classes = b->num_classes; p.num_tx = b->num_tx; p.bc_len = b->bc_len; p.umi_len = b->umi_len;
-    p.sentinel = ((u128)bus_low_mask(2 * (b->bc_len + b->umi_len)) << 64) | ~0ull;   // >= every valid key: the dropped reads sort behind the recorded ones
+    p.sentinel = ((u128)low_mask(2 * (b->bc_len + b->umi_len)) << 64) | ~0ull;   // >= every valid key: the dropped reads sort behind the recorded ones
     p.keys = b->keys.get(); p.vals = b->vals.get(); p.stats = b->d_stats.get();
     const uint64_t recorded_before = b->stats[BS_RECORDED];
-    hipLaunchKernelGGL(pa_bus_keys_kernel, dim3(grid_for(n_reads, BUS_BLOCK)), dim3(BUS_BLOCK), 0, s, p);
-    PA_HIP_TRY(hipGetLastError());
+    if ((e = launch(pa_bus_keys_kernel, grid_for(n_reads, BUS_BLOCK), BUS_BLOCK, s, p))) return e;
     if ((e = fetch_stats(b, s)) != PA_OK) return e;
     const uint64_t recorded = b->stats[BS_RECORDED] - recorded_before;
     if (recorded == 0) return PA_OK;
@@ -429,13 +408,10 @@ int pa_bus_add_device(pa_bus* b, const pa_read_result* d_results, const uint32_t
     u128* unique = b->acc_keys.get() + b->acc_n;
     uint32_t runs = 0;
     if ((e = sort_pairs(s, b->tmp, (const u128*)b->keys.get(), b->sorted.get(), (const uint32_t*)b->vals.get(), b->svals.get(), (size_t)n_reads, 0, b->key_bits()))) return e;
-    if ((e = collapse<u128>(b, s, b->sorted.get(), (uint32_t)recorded, unique, runs)) != PA_OK) return e;
-    hipLaunchKernelGGL(pa_bus_run_counts_kernel, dim3(grid_for(runs, BUS_BLOCK)), dim3(BUS_BLOCK), 0, s, (const uint32_t*)b->start.get(), runs, (const uint32_t*)nullptr,
-                       b->acc_counts.get() + b->acc_n);
-    PA_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(pa_bus_verify_members_kernel, dim3(grid_for(recorded, BUS_BLOCK)), dim3(BUS_BLOCK), 0, s, (const u128*)b->sorted.get(), (const uint32_t*)b->svals.get(),
-                       (const uint32_t*)b->pos.get(), (const uint32_t*)b->start.get(), (uint32_t)recorded, d_results, d_arena, b->d_err.get());
-    PA_HIP_TRY(hipGetLastError());
+    if ((e = collapse_keys<u128>(b, s, b->sorted.get(), (uint32_t)recorded, unique, runs)) != PA_OK) return e;
+    if ((e = run_counts(s, b->start.get(), runs, nullptr, b->acc_counts.get() + b->acc_n))) return e;
+    if ((e = launch(pa_bus_verify_members_kernel, grid_for(recorded, BUS_BLOCK), BUS_BLOCK, s, (const u128*)b->sorted.get(), (const uint32_t*)b->svals.get(),
+            (const uint32_t*)b->pos.get(), (const uint32_t*)b->start.get(), (uint32_t)recorded, d_results, d_arena, b->d_err.get()))) return e;
     if ((e = collect_lists(b, s, unique, runs, d_results, d_arena)) != PA_OK) return e;
     if ((e = check_err(b, s, "two different id lists share the content hash")) != PA_OK) return e;   // (synchronises)
     b->acc_n += runs;

@@ -2,7 +2,7 @@
 // they lie. The whitelist becomes an open-addressing table in HBM (8-byte slots, the barcode is the key, linear probing from pa_mix64); the
 // records' distinct barcodes are classified in two launches — one exact probe per barcode, then a group of CORRECT_GROUP lanes per missed
 // barcode that deals its 3 bc_len single substitutions over the lanes and issues every probe before it looks at any; every record takes its
-// barcode's target or is dropped, and the kept ones are sorted and collapsed again as bus.hip collapses a run (skipped when nothing moved).
+// barcode's target or is dropped, and the kept ones are sorted and collapsed again with collapse_runs, as bus.hip collapses a run (skipped when nothing moved).
 // Integer arithmetic only; the stat counters are summed per wave and added with integer atomics, once per wave: the kernels that count run a bounded
 // grid whose lanes stride over their items (a wave per 64 records adding to one address each was most of the rewrite's time).
 #include <hip/hip_runtime.h>
@@ -16,6 +16,7 @@
 #include "hip_buffer.hpp"
 #include "kernel_utils.hpp"
 #include "pa_common.hpp"
+#include "phase_clock.hpp"
 
 using namespace pa;
 
@@ -34,16 +35,6 @@ static_assert(CS_BARCODES_OUT + 1 == PA_BUS_CORRECT_STATS, "the stats of the hea
 static_assert(CORRECT_GROUP * CORRECT_MAX_ROUNDS >= 3 * 31 && 64 % CORRECT_GROUP == 0, "a group holds every candidate and divides a wave");
 
 thread_local float g_phase_ms[PA_BUS_CORRECT_PHASES] = {};
-
-// the sum of v over the wave's 64 lanes, valid in lane 0 (every lane calls)
-__device__ inline ull wave_sum(ull v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
-__device__ inline void wave_add(ull* counter, ull v) {
-    const ull s = wave_sum(v);
-    if ((threadIdx.x & 63) == 0 && s) atomicAdd(counter, s);
-}
 
 // ---- 1. the whitelist table ----
 // sorted whitelist -> table; equal neighbours: the error word names the barcode (+ 1); a table without a free slot: the other error word
@@ -74,23 +65,6 @@ __device__ inline int wl_lookup(const ull* __restrict__ table, ull cap, ull key)
         j = (j + 1) & mask;
     }
     return -1;
-}
-
-// ---- 2. the distinct barcodes of the records ----
-__global__ __launch_bounds__(CORRECT_BLOCK) void pa_correct_heads_kernel(const pa_bus_record* __restrict__ rec, uint32_t n, uint32_t* __restrict__ heads) {
-    const uint32_t i = blockIdx.x * CORRECT_BLOCK + threadIdx.x;
-    if (i < n) heads[i] = (i == 0 || rec[i].barcode != rec[i - 1].barcode) ? 1u : 0u;
-}
-// pos = inclusive scan of heads: barcode run r = pos[i] - 1 begins at its head i; start[runs] = n
-__global__ __launch_bounds__(CORRECT_BLOCK) void pa_correct_scatter_kernel(const pa_bus_record* __restrict__ rec, const uint32_t* __restrict__ heads,
-                                                                            const uint32_t* __restrict__ pos, uint32_t n, ull* __restrict__ ubc, uint32_t* __restrict__ start) {
-    const uint32_t i = blockIdx.x * CORRECT_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    if (heads[i]) {
-        ubc[pos[i] - 1] = rec[i].barcode;
-        start[pos[i] - 1] = i;
-    }
-    if (i == n - 1) start[pos[i]] = n;
 }
 
 // ---- 3a. one lane per distinct barcode: the exact probe ----
@@ -197,24 +171,12 @@ __global__ __launch_bounds__(CORRECT_BLOCK) void pa_correct_compact_kernel(const
                                                                             uint32_t* __restrict__ counts) {
     const uint32_t i = blockIdx.x * CORRECT_BLOCK + threadIdx.x;
     if (i >= n || !kept[i]) return;
-    const uint4* in = reinterpret_cast<const uint4*>(rec + i);
-    const uint4 a = in[0], c = in[1];   // barcode lo hi, umi lo hi | ec, count, flags, pad
-    const ull umi = (ull)a.z | ((ull)a.w << 32);
+    const RecordWords r = load_record(rec + i);
+    const ull umi = (ull)r.a.z | ((ull)r.a.w << 32);
     const ull w = (target[pos[i] - 1] << umi_bits) | umi;
     const uint32_t d = kpos[i] - 1;
-    keys[d] = ((u128)w << 32) | (u128)(c.x ^ EC_BIAS);
-    counts[d] = c.y;
-}
-// whole records from the keys: 32 bytes as two 16-byte stores
-__global__ __launch_bounds__(CORRECT_BLOCK) void pa_correct_records_kernel(const u128* __restrict__ keys, const uint32_t* __restrict__ counts, uint32_t n, uint32_t umi_bits,
-                                                                            pa_bus_record* __restrict__ out) {
-    const uint32_t i = blockIdx.x * CORRECT_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const u128 k = keys[i];
-    const ull w = (ull)(k >> 32), bc = w >> umi_bits, umi = w & bus_low_mask(umi_bits);
-    uint4* o = reinterpret_cast<uint4*>(out + i);
-    o[0] = make_uint4((uint32_t)bc, (uint32_t)(bc >> 32), (uint32_t)umi, (uint32_t)(umi >> 32));
-    o[1] = make_uint4((uint32_t)k ^ EC_BIAS, counts[i], 0u, 0u);
+    keys[d] = ((u128)w << 32) | (u128)(r.c.x ^ EC_BIAS);
+    counts[d] = r.c.y;
 }
 __global__ __launch_bounds__(CORRECT_BLOCK) void pa_correct_barcodes_out_kernel(const pa_bus_record* __restrict__ rec, uint32_t n, ull* __restrict__ stats) {
     ull heads = 0;
@@ -225,26 +187,6 @@ __global__ __launch_bounds__(CORRECT_BLOCK) void pa_correct_barcodes_out_kernel(
 
 // blocks of a kernel whose lanes stride over n items
 uint32_t count_grid(uint64_t n) { return std::min(grid_for(n, CORRECT_BLOCK), CORRECT_MAX_GRID); }
-
-// the milliseconds between the phases of one call, on the null stream
-struct PhaseClock {
-    hipEvent_t ev[PA_BUS_CORRECT_PHASES + 1] = {};
-    int made = 0;
-    ~PhaseClock() { for (int i = 0; i < made; ++i) (void)hipEventDestroy(ev[i]); }
-    int open() {
-        for (; made <= PA_BUS_CORRECT_PHASES; ++made) PA_HIP_TRY(hipEventCreate(&ev[made]));
-        return PA_OK;
-    }
-    int mark(int i) { PA_HIP_TRY(hipEventRecord(ev[i], nullptr)); return PA_OK; }
-    int close(int marked) {   // ev[0 .. marked] were recorded
-        PA_HIP_TRY(hipEventSynchronize(ev[marked]));
-        for (int i = 0; i < PA_BUS_CORRECT_PHASES; ++i) {
-            g_phase_ms[i] = 0.0f;
-            if (i < marked) PA_HIP_TRY(hipEventElapsedTime(&g_phase_ms[i], ev[i], ev[i + 1]));
-        }
-        return PA_OK;
-    }
-};
 
 int check_device_err(const ull* d_err, hipStream_t s) {
     ull err[ERR_WORDS] = {};
@@ -260,7 +202,7 @@ int correct_device(const pa_bus_record* d_in, uint32_t n, uint32_t bc_len, uint3
                    DeviceBuffer<pa_bus_record>& d_out, uint64_t* n_out, uint64_t* stats) {
     hipStream_t s = nullptr;
     int e;
-    PhaseClock clock;
+    PhaseClock<PA_BUS_CORRECT_PHASES> clock;
     if ((e = clock.open()) || (e = clock.mark(0))) return e;
     DeviceBuffer<uint8_t> tmp;
     DeviceBuffer<ull> d_stats, d_err;
@@ -275,43 +217,37 @@ int correct_device(const pa_bus_record* d_in, uint32_t n, uint32_t bc_len, uint3
     if ((e = upload(d_wl, (const ull*)whitelist, (size_t)W)) || (e = d_wl_sorted.alloc(W)) || (e = d_table.alloc((size_t)cap))) return e;
     PA_HIP_TRY(hipMemsetAsync(d_table.get(), 0xFF, (size_t)cap * 8, s));
     if ((e = sort_keys(s, tmp, (const ull*)d_wl.get(), d_wl_sorted.get(), (int)W, 0, 2 * bc_len))) return e;
-    hipLaunchKernelGGL(pa_correct_insert_kernel, dim3(grid_for(W, CORRECT_BLOCK)), dim3(CORRECT_BLOCK), 0, s, (const ull*)d_wl_sorted.get(), W, d_table.get(), cap, d_err.get());
-    PA_HIP_TRY(hipGetLastError());
+    if ((e = launch(pa_correct_insert_kernel, grid_for(W, CORRECT_BLOCK), CORRECT_BLOCK, s, (const ull*)d_wl_sorted.get(), W, d_table.get(), cap, d_err.get()))) return e;
     if ((e = clock.mark(1)) || (e = check_device_err(d_err.get(), s))) return e;
 
-    // 2. the distinct barcodes
+    // 2. the distinct barcodes: the collapse in its two halves, the outputs sized by the run count
     DeviceBuffer<uint32_t> d_heads, d_pos, d_start, d_missed, d_miss, d_n;
     DeviceBuffer<ull> d_ubc, d_target;
     uint32_t B = 0, n_miss = 0;
-    if ((e = d_heads.alloc(n)) || (e = d_pos.alloc(n)) || (e = d_n.alloc(1))) return e;
-    hipLaunchKernelGGL(pa_correct_heads_kernel, dim3(grid_for(n, CORRECT_BLOCK)), dim3(CORRECT_BLOCK), 0, s, d_in, n, d_heads.get());
-    PA_HIP_TRY(hipGetLastError());
-    if ((e = scan_inclusive(s, tmp, (const uint32_t*)d_heads.get(), d_pos.get(), (size_t)n)) || (e = fetch_u32(d_pos.get() + (n - 1), s, B))) return e;
-    if ((e = d_ubc.alloc(B)) || (e = d_target.alloc(B)) || (e = d_start.alloc((size_t)B + 1)) || (e = d_missed.alloc(B)) || (e = d_miss.alloc(B))) return e;
-    hipLaunchKernelGGL(pa_correct_scatter_kernel, dim3(grid_for(n, CORRECT_BLOCK)), dim3(CORRECT_BLOCK), 0, s, d_in, (const uint32_t*)d_heads.get(), (const uint32_t*)d_pos.get(), n,
-                       d_ubc.get(), d_start.get());
-    PA_HIP_TRY(hipGetLastError());
+    if ((e = d_heads.alloc(n)) || (e = d_pos.alloc(n)) || (e = d_n.alloc(1)) || (e = flag_runs(s, tmp, RecordBarcode{d_in}, n, d_heads.get(), d_pos.get(), B))) return e;
+    if ((e = d_ubc.alloc(B)) || (e = d_target.alloc(B)) || (e = d_start.alloc((size_t)B + 1)) || (e = d_missed.alloc(B)) || (e = d_miss.alloc(B)) ||
+        (e = scatter_runs(s, RecordBarcode{d_in}, (const uint32_t*)d_heads.get(), (const uint32_t*)d_pos.get(), n, B, d_ubc.get(), d_start.get())))
+        return e;
 
     // 3a. exact
-    hipLaunchKernelGGL(pa_correct_exact_kernel, dim3(count_grid(B)), dim3(CORRECT_BLOCK), 0, s, (const ull*)d_ubc.get(), (const uint32_t*)d_start.get(), B,
-                       (const ull*)d_table.get(), cap, d_target.get(), d_missed.get(), d_stats.get(), d_err.get());
-    PA_HIP_TRY(hipGetLastError());
+    if ((e = launch(pa_correct_exact_kernel, count_grid(B), CORRECT_BLOCK, s, (const ull*)d_ubc.get(), (const uint32_t*)d_start.get(), B, (const ull*)d_table.get(), cap,
+            d_target.get(), d_missed.get(), d_stats.get(), d_err.get()))) return e;
     if ((e = select_flagged_indices(s, tmp, (const uint32_t*)d_missed.get(), (size_t)B, d_miss.get(), d_n.get())) || (e = clock.mark(2)) || (e = fetch_u32(d_n.get(), s, n_miss)))
         return e;
     // 3b. the neighbours of the missed ones
     if (n_miss) {
         const dim3 grid(count_grid((uint64_t)n_miss * CORRECT_GROUP)), block(CORRECT_BLOCK);
-        auto launch = [&](auto kernel) {
+        auto neighbours = [&](auto kernel) {
             hipLaunchKernelGGL(kernel, grid, block, 0, s, (const ull*)d_ubc.get(), (const uint32_t*)d_start.get(), (const uint32_t*)d_miss.get(), n_miss, 3 * bc_len,
                                (const ull*)d_table.get(), cap, d_target.get(), d_stats.get(), d_err.get());
         };
         switch ((3 * bc_len + CORRECT_GROUP - 1) / CORRECT_GROUP) {   // 1 .. CORRECT_MAX_ROUNDS for bc_len 1 .. 31
-            case 1: launch(pa_correct_neighbours_kernel<1>); break;
-            case 2: launch(pa_correct_neighbours_kernel<2>); break;
-            case 3: launch(pa_correct_neighbours_kernel<3>); break;
-            case 4: launch(pa_correct_neighbours_kernel<4>); break;
-            case 5: launch(pa_correct_neighbours_kernel<5>); break;
-            default: launch(pa_correct_neighbours_kernel<CORRECT_MAX_ROUNDS>); break;
+            case 1: neighbours(pa_correct_neighbours_kernel<1>); break;
+            case 2: neighbours(pa_correct_neighbours_kernel<2>); break;
+            case 3: neighbours(pa_correct_neighbours_kernel<3>); break;
+            case 4: neighbours(pa_correct_neighbours_kernel<4>); break;
+            case 5: neighbours(pa_correct_neighbours_kernel<5>); break;
+            default: neighbours(pa_correct_neighbours_kernel<CORRECT_MAX_ROUNDS>); break;
         }
         PA_HIP_TRY(hipGetLastError());
     }
@@ -323,10 +259,8 @@ int correct_device(const pa_bus_record* d_in, uint32_t n, uint32_t bc_len, uint3
     DeviceBuffer<u128> d_keys;
     uint32_t n_kept = 0;
     if ((e = d_kpos.alloc(n))) return e;
-    hipLaunchKernelGGL(pa_correct_keep_kernel, dim3(count_grid(n)), dim3(CORRECT_BLOCK), 0, s, d_in, (const uint32_t*)d_pos.get(), (const ull*)d_target.get(), n,
-                       d_kept.get(), d_stats.get());
-    PA_HIP_TRY(hipGetLastError());
-    if ((e = scan_inclusive(s, tmp, (const uint32_t*)d_kept.get(), d_kpos.get(), (size_t)n)) || (e = fetch_u32(d_kpos.get() + (n - 1), s, n_kept))) return e;
+    if ((e = launch(pa_correct_keep_kernel, count_grid(n), CORRECT_BLOCK, s, d_in, (const uint32_t*)d_pos.get(), (const ull*)d_target.get(), n, d_kept.get(), d_stats.get()))) return e;
+    if ((e = scan_inclusive_total(s, tmp, (const uint32_t*)d_kept.get(), d_kpos.get(), (size_t)n, n_kept))) return e;
     ull st[PA_BUS_CORRECT_STATS] = {};
     PA_HIP_TRY(hipMemcpyAsync(st, d_stats.get(), sizeof st, hipMemcpyDeviceToHost, s));
     if ((e = check_device_err(d_err.get(), s))) return e;   // (synchronises)
@@ -334,9 +268,8 @@ int correct_device(const pa_bus_record* d_in, uint32_t n, uint32_t bc_len, uint3
     if (n_kept) {
         const uint32_t umi_bits = 2 * umi_len, key_bits = 32 + 2 * (bc_len + umi_len);
         if ((e = d_keys.alloc(n_kept)) || (e = d_counts.alloc(n_kept))) return e;
-        hipLaunchKernelGGL(pa_correct_compact_kernel, dim3(grid_for(n, CORRECT_BLOCK)), dim3(CORRECT_BLOCK), 0, s, d_in, (const uint32_t*)d_pos.get(), (const ull*)d_target.get(),
-                           (const uint32_t*)d_kept.get(), (const uint32_t*)d_kpos.get(), n, umi_bits, d_keys.get(), d_counts.get());
-        PA_HIP_TRY(hipGetLastError());
+        if ((e = launch(pa_correct_compact_kernel, grid_for(n, CORRECT_BLOCK), CORRECT_BLOCK, s, d_in, (const uint32_t*)d_pos.get(), (const ull*)d_target.get(),
+                (const uint32_t*)d_kept.get(), (const uint32_t*)d_kpos.get(), n, umi_bits, d_keys.get(), d_counts.get()))) return e;
         M = n_kept;
         if (st[CS_CORRECTED]) {   // a barcode moved: sort, join equal keys. Otherwise the kept records are sorted and distinct as they were
             DeviceBuffer<u128> k1, k2;
@@ -345,30 +278,22 @@ int correct_device(const pa_bus_record* d_in, uint32_t n, uint32_t bc_len, uint3
                 (e = start.alloc((size_t)n_kept + 1)))
                 return e;
             if ((e = sort_pairs(s, tmp, (const u128*)d_keys.get(), k1.get(), (const uint32_t*)d_counts.get(), c1.get(), (size_t)n_kept, 0, key_bits))) return e;
-            hipLaunchKernelGGL(pa_bus_heads_kernel<u128>, dim3(grid_for(n_kept, BUS_BLOCK)), dim3(BUS_BLOCK), 0, s, (const u128*)k1.get(), n_kept, heads.get());
-            PA_HIP_TRY(hipGetLastError());
-            if ((e = scan_inclusive(s, tmp, (const uint32_t*)heads.get(), pos.get(), (size_t)n_kept))) return e;
-            hipLaunchKernelGGL(pa_bus_scatter_kernel<u128>, dim3(grid_for(n_kept, BUS_BLOCK)), dim3(BUS_BLOCK), 0, s, (const u128*)k1.get(), (const uint32_t*)heads.get(),
-                               (const uint32_t*)pos.get(), n_kept, k2.get(), start.get());
-            PA_HIP_TRY(hipGetLastError());
-            if ((e = fetch_u32(pos.get() + (n_kept - 1), s, M))) return e;
-            hipLaunchKernelGGL(pa_bus_run_counts_kernel, dim3(grid_for(M, BUS_BLOCK)), dim3(BUS_BLOCK), 0, s, (const uint32_t*)start.get(), M, (const uint32_t*)c1.get(), c2.get());
-            PA_HIP_TRY(hipGetLastError());
+            if ((e = collapse_runs(s, tmp, KeyArray<u128>{k1.get()}, n_kept, heads.get(), pos.get(), k2.get(), start.get(), M)) ||
+                (e = run_counts(s, start.get(), M, c1.get(), c2.get())))
+                return e;
             PA_HIP_TRY(hipStreamSynchronize(s));   // (the scratch of this block is freed at its end)
             d_keys = std::move(k2);
             d_counts = std::move(c2);
         }
         if ((e = d_out.alloc(M))) return e;
-        hipLaunchKernelGGL(pa_correct_records_kernel, dim3(grid_for(M, CORRECT_BLOCK)), dim3(CORRECT_BLOCK), 0, s, (const u128*)d_keys.get(), (const uint32_t*)d_counts.get(), M,
-                           umi_bits, d_out.get());
-        PA_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(pa_correct_barcodes_out_kernel, dim3(count_grid(M)), dim3(CORRECT_BLOCK), 0, s, (const pa_bus_record*)d_out.get(), M, d_stats.get());
-        PA_HIP_TRY(hipGetLastError());
+        if ((e = launch(pa_bus_records_kernel<32, EC_BIAS>, grid_for(M, BUS_BLOCK), BUS_BLOCK, s, (const u128*)d_keys.get(), (const uint32_t*)d_counts.get(), M, umi_bits,
+                d_out.get()))) return e;
+        if ((e = launch(pa_correct_barcodes_out_kernel, count_grid(M), CORRECT_BLOCK, s, (const pa_bus_record*)d_out.get(), M, d_stats.get()))) return e;
         PA_HIP_TRY(hipMemcpyAsync(&st[CS_BARCODES_OUT], d_stats.get() + CS_BARCODES_OUT, 8, hipMemcpyDeviceToHost, s));
     } else {
         d_out.release();
     }
-    if ((e = clock.mark(4)) || (e = clock.close(4))) return e;   // (synchronises)
+    if ((e = clock.mark(4)) || (e = clock.close(g_phase_ms, 4))) return e;   // (synchronises)
     st[CS_RECORDS_IN] = n;
     st[CS_BARCODES_IN] = B;
     st[CS_RECORDS_DROPPED] = (ull)n - st[CS_RECORDS_EXACT] - st[CS_RECORDS_CORRECTED];
@@ -377,12 +302,6 @@ int correct_device(const pa_bus_record* d_in, uint32_t n, uint32_t bc_len, uint3
         return fail(PA_ERR_INTERNAL, "barcode correction: the counts of the classes do not add up");
     *n_out = M;
     if (stats) for (uint32_t j = 0; j < PA_BUS_CORRECT_STATS; ++j) stats[j] = st[j];
-    return PA_OK;
-}
-
-int have_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PA_ERR_NO_DEVICE, "no HIP device available; this library has no CPU fallback");
     return PA_OK;
 }
 
@@ -400,37 +319,21 @@ int pa_bus_correct_records(pa_index* idx, const pa_bus_record* in, uint64_t n, u
     int e;
     if ((e = correct::check_lengths(bc_len, umi_len)) || (e = correct::check_whitelist(whitelist, n_whitelist, bc_len))) return e;
     if (n > 0x7FFFFFFFull) return fail(PA_ERR_UNSUPPORTED, "more than 2^31-1 records");
-    if ((e = correct::check_records(in, n, bc_len, umi_len)) || (e = have_device())) return e;
-    if (!idx) return fail(PA_ERR_INVALID_ARG, "null argument");
-    if (n == 0) return PA_OK;
-    const uint32_t *h_ec = nullptr, *h_ref = nullptr;
-    int device = 0;
-    index_host_classes(idx, &h_ec, &h_ref, &device);
-    PA_HIP_TRY(hipSetDevice(device));
-    DeviceBuffer<pa_bus_record> d_in, d_out;
-    if ((e = upload(d_in, in, (size_t)n)) || (e = correct_device(d_in.get(), (uint32_t)n, bc_len, umi_len, whitelist, n_whitelist, d_out, n_out, stats))) return e;
-    if (!out) return PA_OK;
-    if (cap < *n_out) return fail(PA_ERR_BUFFER_TOO_SMALL, "%llu records, room for %llu", (ull)*n_out, (ull)cap);
-    if (*n_out) PA_HIP_TRY(hipMemcpy(out, d_out.get(), *n_out * sizeof(pa_bus_record), hipMemcpyDeviceToHost));
-    return PA_OK;
+    if ((e = correct::check_records(in, n, bc_len, umi_len))) return e;
+    DeviceBuffer<pa_bus_record> d_out;
+    if ((e = on_host_records(idx, in, n, [&](const pa_bus_record* d_in, uint32_t m) { return correct_device(d_in, m, bc_len, umi_len, whitelist, n_whitelist, d_out, n_out, stats); },
+                             empty_ok)))
+        return e;
+    return deliver_records(d_out, *n_out, out, cap);
 }
 
 int pa_bus_correct(pa_bus* b, const uint64_t* whitelist, uint64_t n_whitelist, uint64_t stats[PA_BUS_CORRECT_STATS]) {
     if (stats) memset(stats, 0, PA_BUS_CORRECT_STATS * 8);
-    if (!b) return fail(PA_ERR_INVALID_ARG, "null argument");
-    if (!b->finished) return fail(PA_ERR_INVALID_ARG, "the records are corrected after pa_bus_finish");
     int e;
-    if ((e = correct::check_whitelist(whitelist, n_whitelist, b->bc_len))) return e;
-    if (b->n_records > 0x7FFFFFFFull) return fail(PA_ERR_UNSUPPORTED, "more than 2^31-1 records");
-    if (b->n_records == 0) return PA_OK;
-    PA_HIP_TRY(hipSetDevice(b->device));
-    DeviceBuffer<pa_bus_record> d_out;
-    uint64_t n_out = 0;
-    if ((e = correct_device(b->d_records.get(), (uint32_t)b->n_records, b->bc_len, b->umi_len, whitelist, n_whitelist, d_out, &n_out, stats))) return e;
-    b->d_records = std::move(d_out);   // (a failing call has left the writer as it was)
-    b->n_records = n_out;
-    b->stats[BS_RECORDS] = n_out;
-    return PA_OK;
+    if ((e = finished_writer(b, "the records are corrected after pa_bus_finish")) || (e = correct::check_whitelist(whitelist, n_whitelist, b->bc_len))) return e;
+    return rewrite_writer_records(b, [&](const pa_bus_record* d_in, uint32_t n, DeviceBuffer<pa_bus_record>& d_out, uint64_t* n_out) {
+        return correct_device(d_in, n, b->bc_len, b->umi_len, whitelist, n_whitelist, d_out, n_out, stats);
+    }, empty_ok);
 }
 
 int pa_bus_correct_phase_ms(float out[PA_BUS_CORRECT_PHASES]) {

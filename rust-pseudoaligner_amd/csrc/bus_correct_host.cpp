@@ -5,18 +5,14 @@
 #include <numeric>
 #include <vector>
 
+#include "bus_records_host.hpp"
+
 namespace pa {
 namespace correct {
 
 typedef unsigned long long ull;
 
-static uint64_t value_limit(uint32_t bases) { return bases >= 32 ? ~0ull : (1ull << (2 * bases)); }   // 4^bases (bases <= 31 here)
-
-int check_lengths(uint32_t bc_len, uint32_t umi_len) {
-    if (bc_len < 1 || umi_len < 1 || (uint64_t)bc_len + umi_len > 32)
-        return fail(PA_ERR_UNSUPPORTED, "barcode length %u / UMI length %u: both at least 1, together at most 32 bases (one 64-bit word)", bc_len, umi_len);
-    return PA_OK;
-}
+int check_lengths(uint32_t bc_len, uint32_t umi_len) { return bus_records::check_lengths(bc_len, umi_len, PA_ERR_UNSUPPORTED, " (one 64-bit word)"); }
 
 int pack_whitelist(const char* whitelist, uint64_t n, uint32_t bc_len, uint64_t* packed) {
     if ((n && !whitelist) || (n && !packed)) return fail(PA_ERR_INVALID_ARG, "null argument");
@@ -37,7 +33,7 @@ int pack_whitelist(const char* whitelist, uint64_t n, uint32_t bc_len, uint64_t*
 int check_whitelist(const uint64_t* whitelist, uint64_t n, uint32_t bc_len) {
     if (!whitelist) return fail(PA_ERR_INVALID_ARG, "null argument");
     if (n < 1 || n > 0x7FFFFFFFull) return fail(PA_ERR_INVALID_ARG, "a whitelist of %llu barcodes: 1 .. 2^31-1", (ull)n);
-    const uint64_t limit = value_limit(bc_len);
+    const uint64_t limit = bus_records::value_limit(bc_len);
     for (uint64_t i = 0; i < n; ++i)
         if (whitelist[i] >= limit) return fail(PA_ERR_INVALID_ARG, "whitelist entry %llu: %llu is no barcode of %u bases", (ull)i, (ull)whitelist[i], bc_len);
     // duplicates: the entries ordered by (value, index); of all pairs of equal neighbours the one whose first index is smallest
@@ -51,20 +47,7 @@ int check_whitelist(const uint64_t* whitelist, uint64_t n, uint32_t bc_len) {
     return PA_OK;
 }
 
-int check_records(const pa_bus_record* records, uint64_t n, uint32_t bc_len, uint32_t umi_len) {
-    if (n && !records) return fail(PA_ERR_INVALID_ARG, "null argument");
-    const uint64_t bc_limit = value_limit(bc_len), umi_limit = value_limit(umi_len);
-    for (uint64_t i = 0; i < n; ++i) {
-        const pa_bus_record& r = records[i];
-        if (r.barcode >= bc_limit) return fail(PA_ERR_INVALID_ARG, "record %llu: barcode %llu is no barcode of %u bases", (ull)i, (ull)r.barcode, bc_len);
-        if (r.umi >= umi_limit) return fail(PA_ERR_INVALID_ARG, "record %llu: UMI %llu is no UMI of %u bases", (ull)i, (ull)r.umi, umi_len);
-        if (i == 0) continue;
-        const pa_bus_record& q = records[i - 1];
-        const bool ascending = q.barcode != r.barcode ? q.barcode < r.barcode : q.umi != r.umi ? q.umi < r.umi : q.ec < r.ec;
-        if (!ascending) return fail(PA_ERR_INVALID_ARG, "record %llu: not above record %llu by (barcode, UMI, ec)", (ull)i, (ull)i - 1);
-    }
-    return PA_OK;
-}
+int check_records(const pa_bus_record* records, uint64_t n, uint32_t bc_len, uint32_t umi_len) { return bus_records::check_records(records, n, bc_len, umi_len); }
 
 uint64_t table_capacity(uint64_t n_whitelist) {
     uint64_t cap = 2;

@@ -17,6 +17,7 @@
 #include "hip_buffer.hpp"
 #include "kernel_utils.hpp"
 #include "pa_common.hpp"
+#include "phase_clock.hpp"
 
 using namespace pa;
 
@@ -42,15 +43,6 @@ static_assert(sizeof(KneeHead) == 32, "two 16-byte stores");
 
 thread_local float g_phase_ms[PA_KNEE_PHASES] = {};
 
-// the sum of v over the wave's 64 lanes, valid in lane 0 (every lane calls)
-__device__ inline ull wave_sum(ull v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
-__device__ inline void wave_add(ull* counter, ull v) {
-    const ull s = wave_sum(v);
-    if ((threadIdx.x & 63) == 0 && s) atomicAdd(counter, s);
-}
 // v of lanes 0 .. lane of the wave, summed (every lane calls)
 __device__ inline ull wave_scan(ull v, uint32_t lane) {
 #pragma unroll
@@ -210,7 +202,8 @@ __global__ __launch_bounds__(KNEE_BLOCK) void pa_knee_called_kernel(const KneeHe
 }
 
 // ---- pa_bus_keep ----
-// one lane per record: its barcode-head flag; the reads in
+// one lane per record: its barcode-head flag; the reads in. The flagging half of the collapse with the sum of the reads fused into it, so that
+// the 32-byte records are swept once; the scatter half is the shared one (scatter_runs)
 __global__ __launch_bounds__(KNEE_BLOCK) void pa_keep_heads_kernel(const pa_bus_record* __restrict__ rec, uint32_t n, uint32_t* __restrict__ heads, ull* __restrict__ stats) {
     ull reads = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * KNEE_BLOCK + threadIdx.x; i < n; i += (uint64_t)gridDim.x * KNEE_BLOCK) {
@@ -218,12 +211,6 @@ __global__ __launch_bounds__(KNEE_BLOCK) void pa_keep_heads_kernel(const pa_bus_
         reads += rec[i].count;
     }
     wave_add(stats + KP_READS_IN, reads);
-}
-// pos = the inclusive scan of heads: the distinct barcodes in order
-__global__ __launch_bounds__(KNEE_BLOCK) void pa_keep_distinct_kernel(const pa_bus_record* __restrict__ rec, const uint32_t* __restrict__ heads, const uint32_t* __restrict__ pos,
-                                                                       uint32_t n, uint32_t B, ull* __restrict__ distinct) {
-    const uint32_t i = blockIdx.x * KNEE_BLOCK + threadIdx.x;
-    if (i < n && heads[i] && pos[i] - 1 < B) distinct[pos[i] - 1] = rec[i].barcode;
 }
 // one lane per distinct barcode: a binary search in the ascending list (at most 32 halvings of a list below 2^32)
 __global__ __launch_bounds__(KNEE_BLOCK) void pa_keep_search_kernel(const ull* __restrict__ distinct, uint32_t B, const ull* __restrict__ list, uint32_t n_list,
@@ -260,31 +247,10 @@ __global__ __launch_bounds__(KNEE_BLOCK) void pa_keep_compact_kernel(const pa_bu
                                                                       uint32_t n, uint32_t n_out, pa_bus_record* __restrict__ out) {
     const uint32_t i = blockIdx.x * KNEE_BLOCK + threadIdx.x;
     if (i >= n || !kept[i] || kpos[i] - 1 >= n_out) return;
-    const uint4* in = reinterpret_cast<const uint4*>(rec + i);
-    const uint4 a = in[0], c = in[1];
-    uint4* o = reinterpret_cast<uint4*>(out + (kpos[i] - 1));
-    o[0] = a;
-    o[1] = c;
+    copy_record(out + (kpos[i] - 1), rec + i);
 }
 
 uint32_t strided_grid(uint64_t items) { return std::min(grid_for(items, KNEE_BLOCK), KNEE_MAX_GRID); }
-
-// the milliseconds between the phases of one call, on the null stream
-struct PhaseClock {
-    hipEvent_t ev[PA_KNEE_PHASES + 1] = {};
-    int made = 0;
-    ~PhaseClock() { for (int i = 0; i < made; ++i) (void)hipEventDestroy(ev[i]); }
-    int open() {
-        for (; made <= PA_KNEE_PHASES; ++made) PA_HIP_TRY(hipEventCreate(&ev[made]));
-        return PA_OK;
-    }
-    int mark(int i) { PA_HIP_TRY(hipEventRecord(ev[i], nullptr)); return PA_OK; }
-    int close() {
-        PA_HIP_TRY(hipEventSynchronize(ev[PA_KNEE_PHASES]));
-        for (int i = 0; i < PA_KNEE_PHASES; ++i) PA_HIP_TRY(hipEventElapsedTime(&g_phase_ms[i], ev[i], ev[i + 1]));
-        return PA_OK;
-    }
-};
 
 // the result of one knee, in HBM
 struct KneeResult {
@@ -295,16 +261,17 @@ struct KneeResult {
 };
 
 // the empty table: no device work; the threshold is the rule's on an empty curve
-void knee_empty(const pa_knee_params& p, KneeResult& res) {
+int knee_empty(const pa_knee_params& p, KneeResult& res) {
     uint64_t L = 0;
     res.stats[KS_THRESHOLD] = knee::threshold(p, nullptr, nullptr, 0, &L);
+    return PA_OK;
 }
 
 // d_in[n] (n >= 1, strictly ascending) on the current device -> res
 int knee_device(const pa_bus_record* d_in, uint32_t n, const pa_knee_params& p, KneeResult& res) {
     hipStream_t s = nullptr;
     int e;
-    PhaseClock clock;
+    PhaseClock<PA_KNEE_PHASES> clock;
     if ((e = clock.open()) || (e = clock.mark(0))) return e;
     DeviceBuffer<uint8_t> tmp;
     uint64_t* st = res.stats;
@@ -313,15 +280,11 @@ int knee_device(const pa_bus_record* d_in, uint32_t n, const pa_knee_params& p, 
     const uint32_t n_tiles = grid_for(n, KNEE_TILE), grid = std::min(n_tiles, KNEE_MAX_GRID);
     DeviceBuffer<ull> d_tile_heads, d_tile_reads, d_scan_heads, d_scan_reads;
     if ((e = d_tile_heads.alloc(n_tiles)) || (e = d_tile_reads.alloc(n_tiles)) || (e = d_scan_heads.alloc(n_tiles)) || (e = d_scan_reads.alloc(n_tiles))) return e;
-    hipLaunchKernelGGL(pa_knee_tile_totals_kernel, dim3(grid), dim3(KNEE_BLOCK), 0, s, d_in, n, n_tiles, d_tile_heads.get(), d_tile_reads.get());
-    PA_HIP_TRY(hipGetLastError());
-    if ((e = scan_inclusive(s, tmp, (const ull*)d_tile_heads.get(), d_scan_heads.get(), (size_t)n_tiles)) ||
-        (e = scan_inclusive(s, tmp, (const ull*)d_tile_reads.get(), d_scan_reads.get(), (size_t)n_tiles)))
-        return e;
+    if ((e = launch(pa_knee_tile_totals_kernel, grid, KNEE_BLOCK, s, d_in, n, n_tiles, d_tile_heads.get(), d_tile_reads.get()))) return e;
     ull total_heads = 0, total_reads = 0;
-    PA_HIP_TRY(hipMemcpyAsync(&total_heads, d_scan_heads.get() + (n_tiles - 1), 8, hipMemcpyDeviceToHost, s));
-    PA_HIP_TRY(hipMemcpyAsync(&total_reads, d_scan_reads.get() + (n_tiles - 1), 8, hipMemcpyDeviceToHost, s));
-    PA_HIP_TRY(hipStreamSynchronize(s));
+    if ((e = scan_inclusive_total(s, tmp, (const ull*)d_tile_heads.get(), d_scan_heads.get(), (size_t)n_tiles, total_heads)) ||
+        (e = scan_inclusive_total(s, tmp, (const ull*)d_tile_reads.get(), d_scan_reads.get(), (size_t)n_tiles, total_reads)))
+        return e;
     const uint32_t B = (uint32_t)(total_heads >> 32), molecules = (uint32_t)total_heads;
     if (B < 1 || B > n || molecules < B || molecules > n) return fail(PA_ERR_INTERNAL, "knee: %u barcodes and %u molecules in %u records", B, molecules, n);
     DeviceBuffer<KneeHead> d_heads;
@@ -329,11 +292,9 @@ int knee_device(const pa_bus_record* d_in, uint32_t n, const pa_knee_params& p, 
     DeviceBuffer<ull> d_reads;
     if ((e = d_heads.alloc((size_t)B + 1)) || (e = d_umis.alloc(B)) || (e = d_records.alloc(B)) || (e = d_index.alloc(B)) || (e = d_reads.alloc(B)) || (e = d_max.alloc(1))) return e;
     PA_HIP_TRY(hipMemsetAsync(d_max.get(), 0, 4, s));
-    hipLaunchKernelGGL(pa_knee_heads_kernel, dim3(grid), dim3(KNEE_BLOCK), 0, s, d_in, n, n_tiles, (const ull*)d_scan_heads.get(), (const ull*)d_scan_reads.get(), d_heads.get(), B);
-    PA_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(pa_knee_diff_kernel, dim3(strided_grid(B)), dim3(KNEE_BLOCK), 0, s, (const KneeHead*)d_heads.get(), B, d_umis.get(), d_records.get(), d_reads.get(),
-                       d_index.get(), d_max.get());
-    PA_HIP_TRY(hipGetLastError());
+    if ((e = launch(pa_knee_heads_kernel, grid, KNEE_BLOCK, s, d_in, n, n_tiles, (const ull*)d_scan_heads.get(), (const ull*)d_scan_reads.get(), d_heads.get(), B))) return e;
+    if ((e = launch(pa_knee_diff_kernel, strided_grid(B), KNEE_BLOCK, s, (const KneeHead*)d_heads.get(), B, d_umis.get(), d_records.get(), d_reads.get(), d_index.get(),
+            d_max.get()))) return e;
     uint32_t max_umis = 0;
     if ((e = clock.mark(1)) || (e = fetch_u32(d_max.get(), s, max_umis))) return e;
 
@@ -346,8 +307,7 @@ int knee_device(const pa_bus_record* d_in, uint32_t n, const pa_knee_params& p, 
     if ((e = sort_pairs_desc(s, tmp, (const uint32_t*)d_umis.get(), d_sorted.get(), (const uint32_t*)d_index.get(), d_sorted_index.get(), (int)B, 0,
                              std::max(1u, bits_for(max_umis)))))
         return e;
-    hipLaunchKernelGGL(pa_knee_rank_kernel, dim3(grid_for(B, KNEE_BLOCK)), dim3(KNEE_BLOCK), 0, s, (const uint32_t*)d_sorted_index.get(), B, d_rank.get());
-    PA_HIP_TRY(hipGetLastError());
+    if ((e = launch(pa_knee_rank_kernel, grid_for(B, KNEE_BLOCK), KNEE_BLOCK, s, (const uint32_t*)d_sorted_index.get(), B, d_rank.get()))) return e;
     uint32_t D = 0;
     if ((e = run_length_encode(s, tmp, (const uint32_t*)d_sorted.get(), (size_t)B, d_values.get(), d_counts.get(), d_runs.get())) || (e = fetch_u32(d_runs.get(), s, D))) return e;
     if (D < 1 || D > B) return fail(PA_ERR_INTERNAL, "knee: %u distinct molecule counts over %u barcodes", D, B);
@@ -367,21 +327,19 @@ int knee_device(const pa_bus_record* d_in, uint32_t n, const pa_knee_params& p, 
     DeviceBuffer<ull> d_sums;
     if ((e = res.d_rows.alloc(B)) || (e = d_flags.alloc(B)) || (e = d_selected.alloc(B)) || (e = d_n.alloc(1)) || (e = d_sums.alloc(2))) return e;
     PA_HIP_TRY(hipMemsetAsync(d_sums.get(), 0, 16, s));
-    hipLaunchKernelGGL(pa_knee_rows_kernel, dim3(strided_grid(B)), dim3(KNEE_BLOCK), 0, s, (const KneeHead*)d_heads.get(), (const uint32_t*)d_umis.get(),
-                       (const uint32_t*)d_records.get(), (const ull*)d_reads.get(), (const uint32_t*)d_rank.get(), B, (ull)t, res.d_rows.get(), d_flags.get(), d_sums.get());
-    PA_HIP_TRY(hipGetLastError());
+    if ((e = launch(pa_knee_rows_kernel, strided_grid(B), KNEE_BLOCK, s, (const KneeHead*)d_heads.get(), (const uint32_t*)d_umis.get(), (const uint32_t*)d_records.get(),
+            (const ull*)d_reads.get(), (const uint32_t*)d_rank.get(), B, (ull)t, res.d_rows.get(), d_flags.get(), d_sums.get()))) return e;
     uint32_t n_called = 0;
     if ((e = select_flagged_indices(s, tmp, (const uint32_t*)d_flags.get(), (size_t)B, d_selected.get(), d_n.get())) || (e = fetch_u32(d_n.get(), s, n_called))) return e;
     if (n_called > B) return fail(PA_ERR_INTERNAL, "knee: %u of %u barcodes called", n_called, B);
     if ((e = res.d_called.alloc(n_called ? n_called : 1))) return e;
     if (n_called) {
-        hipLaunchKernelGGL(pa_knee_called_kernel, dim3(grid_for(n_called, KNEE_BLOCK)), dim3(KNEE_BLOCK), 0, s, (const KneeHead*)d_heads.get(), (const uint32_t*)d_selected.get(),
-                           n_called, B, res.d_called.get());
-        PA_HIP_TRY(hipGetLastError());
+        if ((e = launch(pa_knee_called_kernel, grid_for(n_called, KNEE_BLOCK), KNEE_BLOCK, s, (const KneeHead*)d_heads.get(), (const uint32_t*)d_selected.get(), n_called, B,
+                res.d_called.get()))) return e;
     }
     ull sums[2] = {};
     PA_HIP_TRY(hipMemcpyAsync(sums, d_sums.get(), 16, hipMemcpyDeviceToHost, s));
-    if ((e = clock.mark(3)) || (e = clock.close())) return e;   // (synchronises)
+    if ((e = clock.mark(3)) || (e = clock.close(g_phase_ms))) return e;   // (synchronises)
     st[KS_RECORDS] = n;
     st[KS_READS] = total_reads;
     st[KS_MOLECULES] = molecules;
@@ -422,29 +380,24 @@ int keep_device(const pa_bus_record* d_in, uint32_t n, const uint64_t* barcodes,
         (e = d_kpos.alloc(n)))
         return e;
     PA_HIP_TRY(hipMemsetAsync(d_stats.get(), 0, PA_BUS_KEEP_STATS * 8, s));
-    hipLaunchKernelGGL(pa_keep_heads_kernel, dim3(strided_grid(n)), dim3(KNEE_BLOCK), 0, s, d_in, n, d_heads.get(), d_stats.get());
-    PA_HIP_TRY(hipGetLastError());
+    if ((e = launch(pa_keep_heads_kernel, strided_grid(n), KNEE_BLOCK, s, d_in, n, d_heads.get(), d_stats.get()))) return e;
     uint32_t B = 0, kept = 0;
-    if ((e = scan_inclusive(s, tmp, (const uint32_t*)d_heads.get(), d_pos.get(), (size_t)n)) || (e = fetch_u32(d_pos.get() + (n - 1), s, B))) return e;
+    if ((e = scan_inclusive_total(s, tmp, (const uint32_t*)d_heads.get(), d_pos.get(), (size_t)n, B))) return e;
     if (B < 1 || B > n) return fail(PA_ERR_INTERNAL, "keep: %u barcodes in %u records", B, n);
-    if ((e = d_distinct.alloc(B)) || (e = d_listed.alloc(B))) return e;
-    hipLaunchKernelGGL(pa_keep_distinct_kernel, dim3(grid_for(n, KNEE_BLOCK)), dim3(KNEE_BLOCK), 0, s, d_in, (const uint32_t*)d_heads.get(), (const uint32_t*)d_pos.get(), n, B,
-                       d_distinct.get());
-    PA_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(pa_keep_search_kernel, dim3(strided_grid(B)), dim3(KNEE_BLOCK), 0, s, (const ull*)d_distinct.get(), B, (const ull*)d_list.get(), (uint32_t)n_barcodes,
-                       d_listed.get(), d_stats.get());
-    PA_HIP_TRY(hipGetLastError());
+    if ((e = d_distinct.alloc(B)) || (e = d_listed.alloc(B)) ||
+        (e = scatter_runs(s, RecordBarcode{d_in}, (const uint32_t*)d_heads.get(), (const uint32_t*)d_pos.get(), n, B, d_distinct.get(), nullptr)))
+        return e;
+    if ((e = launch(pa_keep_search_kernel, strided_grid(B), KNEE_BLOCK, s, (const ull*)d_distinct.get(), B, (const ull*)d_list.get(), (uint32_t)n_barcodes, d_listed.get(),
+            d_stats.get()))) return e;
     DeviceBuffer<uint32_t>& d_kept = d_heads;   // (the heads are used up)
-    hipLaunchKernelGGL(pa_keep_flag_kernel, dim3(strided_grid(n)), dim3(KNEE_BLOCK), 0, s, d_in, (const uint32_t*)d_pos.get(), (const uint32_t*)d_listed.get(), n, B, d_kept.get(),
-                       d_stats.get());
-    PA_HIP_TRY(hipGetLastError());
-    if ((e = scan_inclusive(s, tmp, (const uint32_t*)d_kept.get(), d_kpos.get(), (size_t)n)) || (e = fetch_u32(d_kpos.get() + (n - 1), s, kept))) return e;
+    if ((e = launch(pa_keep_flag_kernel, strided_grid(n), KNEE_BLOCK, s, d_in, (const uint32_t*)d_pos.get(), (const uint32_t*)d_listed.get(), n, B, d_kept.get(),
+            d_stats.get()))) return e;
+    if ((e = scan_inclusive_total(s, tmp, (const uint32_t*)d_kept.get(), d_kpos.get(), (size_t)n, kept))) return e;
     if (kept > n) return fail(PA_ERR_INTERNAL, "keep: %u of %u records kept", kept, n);
     if (kept) {
         if ((e = d_out.alloc(kept))) return e;
-        hipLaunchKernelGGL(pa_keep_compact_kernel, dim3(grid_for(n, KNEE_BLOCK)), dim3(KNEE_BLOCK), 0, s, d_in, (const uint32_t*)d_kept.get(), (const uint32_t*)d_kpos.get(), n, kept,
-                           d_out.get());
-        PA_HIP_TRY(hipGetLastError());
+        if ((e = launch(pa_keep_compact_kernel, grid_for(n, KNEE_BLOCK), KNEE_BLOCK, s, d_in, (const uint32_t*)d_kept.get(), (const uint32_t*)d_kpos.get(), n, kept,
+                d_out.get()))) return e;
     } else {
         d_out.release();
     }
@@ -461,22 +414,17 @@ int keep_device(const pa_bus_record* d_in, uint32_t n, const uint64_t* barcodes,
     return PA_OK;
 }
 
-int have_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PA_ERR_NO_DEVICE, "no HIP device available; this library has no CPU fallback");
+// no records: every listed barcode is absent
+int keep_empty(uint64_t n_barcodes, uint64_t* stats) {
+    if (stats) stats[KP_LISTED_ABSENT] = n_barcodes;
     return PA_OK;
 }
 
 int knee_of_writer(const pa_bus* b, const pa_knee_params* p, KneeResult& res) {
-    if (!b) return fail(PA_ERR_INVALID_ARG, "null argument");
-    if (!b->finished) return fail(PA_ERR_INVALID_ARG, "cells are called after pa_bus_finish");
     pa_knee_params params;
     int e;
-    if ((e = knee::take_params(p, params))) return e;
-    if (b->n_records > 0x7FFFFFFFull) return fail(PA_ERR_UNSUPPORTED, "more than 2^31-1 records");
-    if (b->n_records == 0) { knee_empty(params, res); return PA_OK; }
-    PA_HIP_TRY(hipSetDevice(b->device));
-    return knee_device(b->d_records.get(), (uint32_t)b->n_records, params, res);
+    if ((e = finished_writer(b, "cells are called after pa_bus_finish")) || (e = knee::take_params(p, params))) return e;
+    return on_writer_records(b, [&](const pa_bus_record* d_in, uint32_t n) { return knee_device(d_in, n, params, res); }, [&] { return knee_empty(params, res); });
 }
 
 }  // namespace
@@ -503,19 +451,10 @@ int pa_bus_knee_records(pa_index* idx, const pa_bus_record* in, uint64_t n, uint
     int e;
     if ((e = knee::take_params(p, params))) return e;
     if (n > 0x7FFFFFFFull) return fail(PA_ERR_UNSUPPORTED, "more than 2^31-1 records");
-    if ((e = knee::check_records(in, n, bc_len, umi_len)) || (e = have_device())) return e;
-    if (!idx) return fail(PA_ERR_INVALID_ARG, "null argument");
     KneeResult res;
-    if (n == 0) {
-        knee_empty(params, res);
-    } else {
-        const uint32_t *h_ec = nullptr, *h_ref = nullptr;
-        int device = 0;
-        index_host_classes(idx, &h_ec, &h_ref, &device);
-        PA_HIP_TRY(hipSetDevice(device));
-        DeviceBuffer<pa_bus_record> d_in;
-        if ((e = upload(d_in, in, (size_t)n)) || (e = knee_device(d_in.get(), (uint32_t)n, params, res))) return e;
-    }
+    if ((e = knee::check_records(in, n, bc_len, umi_len)) ||
+        (e = on_host_records(idx, in, n, [&](const pa_bus_record* d_in, uint32_t m) { return knee_device(d_in, m, params, res); }, [&] { return knee_empty(params, res); })))
+        return e;
     return knee_deliver(res, rows, rows_cap, n_rows, called, called_cap, n_called, stats);
 }
 
@@ -545,44 +484,23 @@ int pa_bus_keep_records(pa_index* idx, const pa_bus_record* in, uint64_t n, uint
     int e;
     if (n > 0x7FFFFFFFull) return fail(PA_ERR_UNSUPPORTED, "more than 2^31-1 records");
     if (n_barcodes > 0x7FFFFFFFull) return fail(PA_ERR_UNSUPPORTED, "a list of more than 2^31-1 barcodes");
-    if ((e = knee::check_records(in, n, bc_len, umi_len)) || (e = knee::check_list(barcodes, n_barcodes, bc_len)) || (e = have_device())) return e;
-    if (!idx) return fail(PA_ERR_INVALID_ARG, "null argument");
-    if (n == 0) {
-        if (stats) stats[KP_LISTED_ABSENT] = n_barcodes;
-        return PA_OK;
-    }
-    const uint32_t *h_ec = nullptr, *h_ref = nullptr;
-    int device = 0;
-    index_host_classes(idx, &h_ec, &h_ref, &device);
-    PA_HIP_TRY(hipSetDevice(device));
-    DeviceBuffer<pa_bus_record> d_in, d_out;
-    if ((e = upload(d_in, in, (size_t)n)) || (e = keep_device(d_in.get(), (uint32_t)n, barcodes, n_barcodes, d_out, n_out, stats))) return e;
-    if (!out) return PA_OK;
-    if (cap < *n_out) return fail(PA_ERR_BUFFER_TOO_SMALL, "%llu records, room for %llu", (ull)*n_out, (ull)cap);
-    if (*n_out) PA_HIP_TRY(hipMemcpy(out, d_out.get(), *n_out * sizeof(pa_bus_record), hipMemcpyDeviceToHost));
-    return PA_OK;
+    DeviceBuffer<pa_bus_record> d_out;
+    if ((e = knee::check_records(in, n, bc_len, umi_len)) || (e = knee::check_list(barcodes, n_barcodes, bc_len)) ||
+        (e = on_host_records(idx, in, n, [&](const pa_bus_record* d_in, uint32_t m) { return keep_device(d_in, m, barcodes, n_barcodes, d_out, n_out, stats); },
+                             [&] { return keep_empty(n_barcodes, stats); })))
+        return e;
+    return deliver_records(d_out, *n_out, out, cap);
 }
 
 int pa_bus_keep(pa_bus* b, const uint64_t* barcodes, uint64_t n_barcodes, uint64_t stats[PA_BUS_KEEP_STATS]) {
     if (stats) memset(stats, 0, PA_BUS_KEEP_STATS * 8);
-    if (!b) return fail(PA_ERR_INVALID_ARG, "null argument");
-    if (!b->finished) return fail(PA_ERR_INVALID_ARG, "the records are filtered after pa_bus_finish");
     int e;
+    if ((e = finished_writer(b, "the records are filtered after pa_bus_finish"))) return e;
     if (n_barcodes > 0x7FFFFFFFull) return fail(PA_ERR_UNSUPPORTED, "a list of more than 2^31-1 barcodes");
     if ((e = knee::check_list(barcodes, n_barcodes, b->bc_len))) return e;
-    if (b->n_records > 0x7FFFFFFFull) return fail(PA_ERR_UNSUPPORTED, "more than 2^31-1 records");
-    if (b->n_records == 0) {
-        if (stats) stats[KP_LISTED_ABSENT] = n_barcodes;
-        return PA_OK;
-    }
-    PA_HIP_TRY(hipSetDevice(b->device));
-    DeviceBuffer<pa_bus_record> d_out;
-    uint64_t n_out = 0;
-    if ((e = keep_device(b->d_records.get(), (uint32_t)b->n_records, barcodes, n_barcodes, d_out, &n_out, stats))) return e;
-    b->d_records = std::move(d_out);   // (a failing call has left the writer as it was)
-    b->n_records = n_out;
-    b->stats[BS_RECORDS] = n_out;
-    return PA_OK;
+    return rewrite_writer_records(b, [&](const pa_bus_record* d_in, uint32_t n, DeviceBuffer<pa_bus_record>& d_out, uint64_t* n_out) {
+        return keep_device(d_in, n, barcodes, n_barcodes, d_out, n_out, stats);
+    }, [&] { return keep_empty(n_barcodes, stats); });
 }
 
 }  // extern "C"

@@ -4,7 +4,7 @@
 #include <cmath>
 #include <string>
 
-#include "bus_correct_host.hpp"
+#include "bus_records_host.hpp"
 
 namespace pa {
 namespace knee {
@@ -23,13 +23,13 @@ int take_params(const pa_knee_params* p, pa_knee_params& out) {
 }
 
 int check_records(const pa_bus_record* records, uint64_t n, uint32_t bc_len, uint32_t umi_len) {
-    const int e = correct::check_lengths(bc_len, umi_len);
-    return e != PA_OK ? e : correct::check_records(records, n, bc_len, umi_len);
+    const int e = bus_records::check_lengths(bc_len, umi_len, PA_ERR_UNSUPPORTED, " (one 64-bit word)");
+    return e != PA_OK ? e : bus_records::check_records(records, n, bc_len, umi_len);
 }
 
 int check_list(const uint64_t* barcodes, uint64_t n, uint32_t bc_len) {
     if (n && !barcodes) return fail(PA_ERR_INVALID_ARG, "null argument");
-    const uint64_t limit = bc_len >= 32 ? ~0ull : (1ull << (2 * bc_len));
+    const uint64_t limit = bus_records::value_limit(bc_len);
     for (uint64_t i = 0; i < n; ++i) {
         if (barcodes[i] >= limit) return fail(PA_ERR_INVALID_ARG, "barcode list entry %llu: %llu is no barcode of %u bases", (ull)i, (ull)barcodes[i], bc_len);
         if (i && barcodes[i - 1] >= barcodes[i]) return fail(PA_ERR_INVALID_ARG, "barcode list entry %llu: not above entry %llu", (ull)i, (ull)i - 1);

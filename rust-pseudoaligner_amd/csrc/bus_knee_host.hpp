@@ -16,7 +16,7 @@ constexpr uint32_t EXPECTED_DIVISOR = 10;       // ... and a tenth of its molecu
 // p as the caller gave it (NULL: the defaults) -> out; lower, divisor, min_umis or expected_cells 0 or an unknown mode: PA_ERR_INVALID_ARG
 int take_params(const pa_knee_params* p, pa_knee_params& out);
 
-// bc_len / umi_len as pa_bus_create takes them (PA_ERR_UNSUPPORTED), then bus_correct_host's walk over the records: strictly ascending
+// bc_len / umi_len as pa_bus_create takes them (PA_ERR_UNSUPPORTED), then bus_records_host's walk over the records: strictly ascending
 // by (barcode, UMI, ec), every barcode < 4^bc_len, every UMI < 4^umi_len, else PA_ERR_INVALID_ARG naming the first offending record
 int check_records(const pa_bus_record* records, uint64_t n, uint32_t bc_len, uint32_t umi_len);
 

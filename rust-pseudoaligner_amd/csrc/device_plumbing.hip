@@ -19,6 +19,12 @@ int pa::use_device(int device) {
     return PA_OK;
 }
 
+int pa::have_device() {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PA_ERR_NO_DEVICE, "no HIP device available; this library has no CPU fallback");
+    return PA_OK;
+}
+
 extern "C" {
 
 int pa_device_count(void) {

@@ -1,6 +1,9 @@
 // Device-wide primitives of the host runtime's setup paths (sorts, scans, run-length encodes, reductions by key, compactions):
 // the one place rocPRIM is called from, and the one place its two-phase protocol ("ask for the scratch bytes, allocate, call
-// again") is written. Host side; included by .hip sources only.
+// again") is written; and the "collapse" of sorted items into their runs (collapse_runs and its two kernels), which index_build.hip's
+// own pa_ib_heads_kernel (64-bit counts, other outputs) does not use. Host side; included by .hip sources only: barcode_counts.hip,
+// bus.hip, bus_correct.hip, bus_knee.hip, compact.hip, fastq_scan.hip, genes.hip, index_build.hip, pair_scan.hip, pairs.hip (through
+// pair_stage.hpp too), quant.hip, quant_boot.hip, render.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -33,10 +36,20 @@ inline uint32_t bits_for(uint64_t max_value) {
     return b;
 }
 
-// the word at d once everything before it on the stream is done
-inline int fetch_u32(const uint32_t* d, hipStream_t s, uint32_t& out) {
-    PA_HIP_TRY(hipMemcpyAsync(&out, d, 4, hipMemcpyDeviceToHost, s));
+// the element at d once everything before it on the stream is done
+template <class T>
+int fetch(const T* d, hipStream_t s, T& out) {
+    PA_HIP_TRY(hipMemcpyAsync(&out, d, sizeof(T), hipMemcpyDeviceToHost, s));
     PA_HIP_TRY(hipStreamSynchronize(s));
+    return PA_OK;
+}
+inline int fetch_u32(const uint32_t* d, hipStream_t s, uint32_t& out) { return fetch(d, s, out); }
+
+// kernel<<<blocks, block, 0, s>>>(args...) and the status of the launch
+template <class... P, class... A>
+int launch(void (*kernel)(P...), uint32_t blocks, uint32_t block, hipStream_t s, A... args) {
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(block), 0, s, args...);
+    PA_HIP_TRY(hipGetLastError());
     return PA_OK;
 }
 
@@ -90,6 +103,13 @@ int scan_inclusive(hipStream_t s, DeviceBuffer<uint8_t>& tmp, const In* in, Out*
     return prim_call(tmp, [&](void* t, size_t& b) { return rocprim::inclusive_scan(t, b, in, out, n, rocprim::plus<Out>(), s); });
 }
 
+// ... and total = out[n - 1] on the host (n >= 1; synchronises s)
+template <class In, class Out>
+int scan_inclusive_total(hipStream_t s, DeviceBuffer<uint8_t>& tmp, const In* in, Out* out, size_t n, Out& total) {
+    const int e = scan_inclusive(s, tmp, in, out, n);
+    return e != PA_OK ? e : fetch((const Out*)out + (n - 1), s, total);
+}
+
 // out[i] = in[0] + .. + in[i - 1], summed as Out (out[0] = 0). This is the rocPRIM call itself, for prim_bytes and for callers with
 // a scratch block of their own; scan_exclusive below is the same on `tmp`.
 template <class In, class Out>
@@ -119,6 +139,59 @@ int reduce_by_key_sum(hipStream_t s, DeviceBuffer<uint8_t>& tmp, const K* kin, c
 template <class I>
 int select_flagged_indices(hipStream_t s, DeviceBuffer<uint8_t>& tmp, const uint32_t* flags, size_t n, I* out, uint32_t* d_count) {
     return prim_call(tmp, [&](void* t, size_t& b) { return rocprim::select(t, b, rocprim::counting_iterator<I>(0), flags, out, d_count, n, s); });
+}
+
+// ---- the collapse of sorted items: flag the first of every run, scan, scatter ----
+constexpr uint32_t RUN_BLOCK = 256;   // 4 waves
+
+// key_at(i), the key of item i as a kernel reads it: an array of keys, or the barcode field of BUS records
+template <class K>
+struct KeyArray {
+    typedef K key_type;
+    const K* keys;
+    __device__ K operator()(uint32_t i) const { return keys[i]; }
+};
+struct RecordBarcode {
+    typedef unsigned long long key_type;
+    const pa_bus_record* rec;
+    __device__ key_type operator()(uint32_t i) const { return rec[i].barcode; }
+};
+
+template <class KeyAt>
+__global__ __launch_bounds__(RUN_BLOCK) void pa_run_heads_kernel(const KeyAt key_at, uint32_t n, uint32_t* __restrict__ heads) {
+    const uint32_t i = blockIdx.x * RUN_BLOCK + threadIdx.x;
+    if (i < n) heads[i] = (i == 0 || key_at(i) != key_at(i - 1)) ? 1u : 0u;
+}
+// pos = inclusive scan of heads: run r = pos[i] - 1 begins at its head i; with a start: start[r] = i, start[runs] = n
+template <class KeyAt>
+__global__ __launch_bounds__(RUN_BLOCK) void pa_run_scatter_kernel(const KeyAt key_at, const uint32_t* __restrict__ heads, const uint32_t* __restrict__ pos, uint32_t n,
+                                                                    uint32_t runs, typename KeyAt::key_type* __restrict__ unique, uint32_t* __restrict__ start) {
+    const uint32_t i = blockIdx.x * RUN_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    if (heads[i] && pos[i] - 1 < runs) {   // (the bound is the caller's: unique and start have that many entries)
+        unique[pos[i] - 1] = key_at(i);
+        if (start) start[pos[i] - 1] = i;
+    }
+    if (start && i == n - 1) start[runs] = n;
+}
+// The two halves of the collapse, for a caller that sizes `unique` by the run count or flags the heads in a pass of its own.
+// n >= 1 sorted items -> heads[n] (1 at the first of every run), pos[n] (their inclusive scan), runs = pos[n - 1]; synchronises s
+template <class KeyAt>
+int flag_runs(hipStream_t s, DeviceBuffer<uint8_t>& tmp, KeyAt key_at, uint32_t n, uint32_t* heads, uint32_t* pos, uint32_t& runs) {
+    const int e = launch(pa_run_heads_kernel<KeyAt>, grid_for(n, RUN_BLOCK), RUN_BLOCK, s, key_at, n, heads);
+    return e != PA_OK ? e : scan_inclusive_total(s, tmp, (const uint32_t*)heads, pos, (size_t)n, runs);
+}
+// heads, pos and runs as flag_runs leaves them -> unique[runs] and, unless start is null, start[runs + 1]
+template <class KeyAt>
+int scatter_runs(hipStream_t s, KeyAt key_at, const uint32_t* heads, const uint32_t* pos, uint32_t n, uint32_t runs, typename KeyAt::key_type* unique, uint32_t* start) {
+    return launch(pa_run_scatter_kernel<KeyAt>, grid_for(n, RUN_BLOCK), RUN_BLOCK, s, key_at, heads, pos, n, runs, unique, start);
+}
+// n >= 1 sorted items -> unique[runs], start[runs + 1] (start may be null); heads[n] and pos[n] hold the flags and their scan afterwards
+template <class KeyAt>
+int collapse_runs(hipStream_t s, DeviceBuffer<uint8_t>& tmp, KeyAt key_at, uint32_t n, uint32_t* heads, uint32_t* pos, typename KeyAt::key_type* unique, uint32_t* start,
+                  uint32_t& runs) {
+    const int e = flag_runs(s, tmp, key_at, n, heads, pos, runs);
+    return e != PA_OK ? e : scatter_runs(s, key_at, (const uint32_t*)heads, (const uint32_t*)pos, n, runs, unique, start);
 }
 
 }  // namespace pa

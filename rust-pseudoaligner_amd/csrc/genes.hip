@@ -187,22 +187,6 @@ __global__ __launch_bounds__(B) void gn_counts_f64(const uint32_t* __restrict__ 
     if (i < n) { out[i] = (double)cnt[i]; zero[i] = 0u; }
 }
 
-// ---- collapse of sorted keys: flag the first of every run, scan, scatter ----
-template <class K>
-__global__ __launch_bounds__(B) void gn_heads(const K* __restrict__ keys, uint32_t n, uint32_t* __restrict__ heads) {
-    const uint32_t i = blockIdx.x * B + threadIdx.x;
-    if (i < n) heads[i] = (i == 0 || keys[i] != keys[i - 1]) ? 1u : 0u;
-}
-// pos = inclusive scan of heads: run pos[i] - 1 begins at its head i; start[runs] = n
-template <class K>
-__global__ __launch_bounds__(B) void gn_scatter(const K* __restrict__ keys, const uint32_t* __restrict__ heads, const uint32_t* __restrict__ pos, uint32_t n,
-                                                K* __restrict__ unique, uint32_t* __restrict__ start) {
-    const uint32_t i = blockIdx.x * B + threadIdx.x;
-    if (i >= n) return;
-    if (heads[i]) { unique[pos[i] - 1] = keys[i]; start[pos[i] - 1] = i; }
-    if (i == n - 1) start[pos[i]] = n;
-}
-
 // ---- rows ----
 // every multi-gene molecule against the first of its row (equal hash means the same set only after the contents were compared)
 __global__ __launch_bounds__(B) void gn_verify_rows(const u128* __restrict__ keys, const uint32_t* __restrict__ vals, const uint32_t* __restrict__ pos,
@@ -445,21 +429,7 @@ __global__ __launch_bounds__(B) void gn_run_stats(const uint32_t* __restrict__ i
 template <class T>
 int alloc_n(DeviceBuffer<T>& b, size_t n) { return b.alloc(n ? n : 1); }
 
-#define GN_LAUNCH(kernel, items, s, ...)                                                                      \
-    do {                                                                                                      \
-        hipLaunchKernelGGL(kernel, dim3(grid_for(items, B)), dim3(B), 0, s, __VA_ARGS__);                     \
-        PA_HIP_TRY(hipGetLastError());                                                                        \
-    } while (0)
-
-// sorted keys[0 .. n) -> unique[runs], start[runs + 1]; heads and pos hold the flags and their scan afterwards; n >= 1
-template <class K>
-int collapse(hipStream_t s, DeviceBuffer<uint8_t>& tmp, const K* keys, uint32_t n, uint32_t* heads, uint32_t* pos, K* unique, uint32_t* start, uint32_t& runs) {
-    GN_LAUNCH(gn_heads<K>, n, s, keys, n, heads);
-    int e;
-    if ((e = scan_inclusive(s, tmp, (const uint32_t*)heads, pos, (size_t)n))) return e;
-    GN_LAUNCH(gn_scatter<K>, n, s, keys, (const uint32_t*)heads, (const uint32_t*)pos, n, unique, start);
-    return fetch_u32(pos + (n - 1), s, runs);
-}
+#define GN_LAUNCH(kernel, items, s, ...) do { const int e_ = launch(kernel, grid_for(items, B), B, s, __VA_ARGS__); if (e_ != PA_OK) return e_; } while (0)
 
 // everything up to the start point; d_rec: the n records in HBM (read during this call only)
 int setup(pa_genes* g, const pa_bus_record* d_rec, uint32_t n, const genes::GeneSets& gs) {
@@ -516,7 +486,7 @@ int setup(pa_genes* g, const pa_bus_record* d_rec, uint32_t n, const genes::Gene
     DeviceBuffer<uint32_t> cheads, cpos, single, multi, sel;
     if ((e = cheads.alloc(n_kept)) || (e = cpos.alloc(n_kept)) || (e = single.alloc(n_kept)) || (e = multi.alloc(n_kept)) || (e = sel.alloc(n_kept))) return e;
     GN_LAUNCH(gn_cell_heads, n_kept, s, d_rec, (const uint32_t*)mol_start.get(), (const uint32_t*)kept_idx.get(), n_kept, cheads.get());
-    if ((e = scan_inclusive(s, tmp, (const uint32_t*)cheads.get(), cpos.get(), (size_t)n_kept)) || (e = fetch_u32(cpos.get() + (n_kept - 1), s, g->n_cells))) return e;
+    if ((e = scan_inclusive_total(s, tmp, (const uint32_t*)cheads.get(), cpos.get(), (size_t)n_kept, g->n_cells))) return e;
     const uint32_t n_cells = g->n_cells;
     g->stats[5] = n_cells;
     const uint32_t cell_bits = std::max(1u, bits_for(n_cells - 1));
@@ -556,7 +526,7 @@ int setup(pa_genes* g, const pa_bus_record* d_rec, uint32_t n, const genes::Gene
               mv0.get());
     if ((e = sort_pairs(s, tmp, (const u128*)mk0.get(), mk1.get(), (const uint32_t*)mv0.get(), mv1.get(), (size_t)n_multi, 0, 64 + cell_bits))) return e;
     uint32_t rows = 0;
-    if ((e = collapse<u128>(s, tmp, mk1.get(), n_multi, mheads.get(), mpos.get(), mku.get(), mstart.get(), rows))) return e;
+    if ((e = collapse_runs(s, tmp, KeyArray<u128>{mk1.get()}, n_multi, mheads.get(), mpos.get(), mku.get(), mstart.get(), rows))) return e;
     GN_LAUNCH(gn_verify_rows, n_multi, s, (const u128*)mk1.get(), (const uint32_t*)mv1.get(), (const uint32_t*)mpos.get(), (const uint32_t*)mstart.get(), n_multi,
               (const ull*)mol_off.get(), (const uint32_t*)mol_len.get(), (const uint32_t*)ids.get(), g->d_stats.get() + GS_ERR);
     g->n_rows = rows;
@@ -586,7 +556,7 @@ int setup(pa_genes* g, const pa_bus_record* d_rec, uint32_t n, const genes::Gene
     GN_LAUNCH(gn_expand, n_e, s, (const ull*)g->d_row_ptr.get(), rows, n_e, (const ull*)row_key.get(), (const ull*)row_src.get(), (const uint32_t*)ids.get(), ek0.get(), ev0.get());
     if ((e = sort_pairs(s, tmp, (const ull*)ek0.get(), ek1.get(), (const uint32_t*)ev0.get(), ev1.get(), (size_t)n_e, 0, 32 + cell_bits))) return e;
     uint32_t slots = 0;
-    if ((e = collapse<ull>(s, tmp, ek1.get(), n_e, eheads.get(), epos.get(), g->d_slot_key.get(), g->d_slot_start.get(), slots))) return e;
+    if ((e = collapse_runs(s, tmp, KeyArray<ull>{ek1.get()}, n_e, eheads.get(), epos.get(), g->d_slot_key.get(), g->d_slot_start.get(), slots))) return e;
     g->n_slots = slots;
     GN_LAUNCH(gn_transpose, n_e, s, (const uint32_t*)ev1.get(), (const uint32_t*)epos.get(), n_e, (const ull*)g->d_row_ptr.get(), rows, g->d_row_slot.get(), g->d_t_row.get());
     GN_LAUNCH(gn_cell_bounds<ull>, (uint64_t)n_cells + 1, s, (const ull*)g->d_slot_key.get(), slots, n_cells, g->d_cell_slot.get());
@@ -731,8 +701,7 @@ int pa_genes_create(pa_index* idx, const pa_bus_record* records, uint64_t n, con
     if ((e = resolve_params(p, par)) || (e = genes::check_lengths(bc_len, umi_len)) || (e = genes::check_tables(ec_offsets, ec_ids, n_ecs, num_tx, tx_gene, num_genes))) return e;
     if (n > 0x7FFFFFFFull) return fail(PA_ERR_UNSUPPORTED, "more than 2^31-1 records");
     if ((e = genes::check_records(records, n, n_ecs))) return e;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PA_ERR_NO_DEVICE, "no HIP device available; this library has no CPU fallback");
+    if ((e = have_device())) return e;
     if (!idx) return fail(PA_ERR_INVALID_ARG, "null argument");
     const uint32_t *h_ec = nullptr, *h_ref = nullptr;
     int device = 0;

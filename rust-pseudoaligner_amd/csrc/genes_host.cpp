@@ -9,6 +9,8 @@
 #include <cmath>
 #include <unordered_set>
 
+#include "bus_records_host.hpp"
+
 namespace pa {
 namespace genes {
 
@@ -29,11 +31,7 @@ int check_params(const pa_genes_params& p) {
     return PA_OK;
 }
 
-int check_lengths(uint32_t bc_len, uint32_t umi_len) {
-    if (bc_len < 1 || umi_len < 1 || (uint64_t)bc_len + umi_len > 32)
-        return fail(PA_ERR_INVALID_ARG, "barcode length %u / UMI length %u: both at least 1, together at most 32 bases", bc_len, umi_len);
-    return PA_OK;
-}
+int check_lengths(uint32_t bc_len, uint32_t umi_len) { return bus_records::check_lengths(bc_len, umi_len, PA_ERR_INVALID_ARG, ""); }
 
 int check_tables(const uint64_t* ec_offsets, const uint32_t* ec_ids, uint32_t n_ecs, uint32_t num_tx, const uint32_t* tx_gene, uint32_t num_genes) {
     if (!ec_offsets || (num_tx && !tx_gene)) return fail(PA_ERR_INVALID_ARG, "null argument");
@@ -54,16 +52,8 @@ int check_tables(const uint64_t* ec_offsets, const uint32_t* ec_ids, uint32_t n_
 }
 
 int check_records(const pa_bus_record* records, uint64_t n, uint32_t n_ecs) {
-    if (n && !records) return fail(PA_ERR_INVALID_ARG, "null argument");
-    for (uint64_t i = 0; i < n; ++i) {
-        const pa_bus_record& r = records[i];
-        if (r.ec < 0 || (uint32_t)r.ec >= n_ecs) return fail(PA_ERR_INVALID_ARG, "record %llu: ec %d is outside [0, %u)", (ull)i, r.ec, n_ecs);
-        if (i == 0) continue;
-        const pa_bus_record& q = records[i - 1];
-        const bool ascending = q.barcode != r.barcode ? q.barcode < r.barcode : q.umi != r.umi ? q.umi < r.umi : q.ec < r.ec;
-        if (!ascending) return fail(PA_ERR_INVALID_ARG, "record %llu: not above record %llu by (barcode, UMI, ec)", (ull)i, (ull)i - 1);
-    }
-    return PA_OK;
+    return bus_records::walk(records, n, [&](const pa_bus_record& r) { return r.ec < 0 || (uint32_t)r.ec >= n_ecs; },
+                             [&](uint64_t i, const pa_bus_record& r) { return fail(PA_ERR_INVALID_ARG, "record %llu: ec %d is outside [0, %u)", (ull)i, r.ec, n_ecs); });
 }
 
 void gene_sets(const uint64_t* ec_offsets, const uint32_t* ec_ids, uint32_t n_ecs, const uint32_t* tx_gene, GeneSets& out) {

@@ -81,6 +81,8 @@ template <class T> int upload(DeviceBuffer<T>& dst, const std::vector<T>& src) {
 
 // makes `device` current; PA_ERR_NO_DEVICE without a usable GPU, PA_ERR_INVALID_ARG for a device that does not exist (device_plumbing.hip)
 int use_device(int device);
+// PA_ERR_NO_DEVICE without a usable GPU; the current device stays as it is (device_plumbing.hip)
+int have_device();
 
 // A non-blocking stream that launches on `idx`. The index keeps a launch context per stream (2 GB of list-mode rows): a stream that is
 // destroyed without pa_index_release_stream strands it there. release() and destruction: synchronise, release the context, destroy.

@@ -20,6 +20,17 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
     return v;
 }
 
+// the sum of v over the wave's 64 lanes, valid in lane 0 (every lane calls)
+__device__ inline unsigned long long wave_sum(unsigned long long v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+    return v;
+}
+// ... added to *counter once per wave (a wave whose sum is 0 adds nothing)
+__device__ inline void wave_add(unsigned long long* counter, unsigned long long v) {
+    const unsigned long long s = wave_sum(v);
+    if ((threadIdx.x & 63) == 0 && s) atomicAdd(counter, s);
+}
+
 // hash of a sorted id list; must equal list_hash_host (device_index.hip: pa_index_create)
 __device__ __forceinline__ uint64_t list_hash_dev(const uint32_t* v, uint32_t n) {
     uint64_t h = 0x243f6a8885a308d3ull ^ n;

@@ -113,6 +113,12 @@ static inline uint64_t mix64(uint64_t x) {
 // reference's CLI accepts, src/bin/pseudoaligner.rs:88) ----
 typedef unsigned __int128 u128;
 
+// the low `bits` bits of a word set (64 and more: all of them); for kernels too
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline unsigned long long low_mask(uint32_t bits) { return bits >= 64 ? ~0ull : (1ull << bits) - 1; }
+
 template <class KT> struct KmerOps;
 template <> struct KmerOps<uint64_t> {
     static uint64_t mask(uint32_t k) { return kmer_mask(k); }

@@ -12,7 +12,7 @@ EXE = HERE / "_build" / "correct_host_check"
 
 
 def build_check(force: bool = False) -> Path:
-    deps = [SRC, CSRC / "bus_correct_host.cpp", CSRC / "bus_correct_host.hpp", CSRC / "pa_common.hpp", Path(__file__), ROOT / "include" / "pseudoaligner_amd.h"]
+    deps = [SRC, CSRC / "bus_correct_host.cpp", CSRC / "bus_correct_host.hpp", CSRC / "bus_records_host.hpp", CSRC / "pa_common.hpp", Path(__file__), ROOT / "include" / "pseudoaligner_amd.h"]
     if force or not EXE.exists() or any(d.stat().st_mtime > EXE.stat().st_mtime for d in deps):
         EXE.parent.mkdir(parents=True, exist_ok=True)
         cmd = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-Wno-unused-function", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",

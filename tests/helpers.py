@@ -122,6 +122,15 @@ def prims_lib():
             getattr(L, "probe_scan_" + name).argtypes = [vp, vp, vp, u64]
         for name in ("u32_u32", "u32_u64"):
             getattr(L, "probe_scan_exclusive_on_" + name).argtypes = [vp, vp, u64, vp, u64, u64, vp]
+        L.probe_sort_keys_ull_size.argtypes = [vp, vp, vp, u64, u32, u32]
+        L.probe_sort_pairs_desc_u32_u32_int.argtypes = [vp, vp, vp, vp, vp, u64, u32, u32]
+        for name in ("inclusive_u32_ull", "exclusive_u32_ull"):
+            getattr(L, "probe_scan_" + name).argtypes = [vp, vp, vp, u64]
+        for name in ("u32_u32", "ull_ull", "u32_ull"):
+            getattr(L, "probe_scan_inclusive_total_" + name).argtypes = [vp, vp, vp, u64, vp]
+        for name in ("ull", "u128", "record"):
+            getattr(L, "probe_collapse_runs_" + name).argtypes = [vp, vp, u64, vp, vp, vp, vp, u64, C.c_int, vp]
+        L.probe_run_length_encode_u32.argtypes = [vp, vp, u64, vp, vp, u64, vp]
         L.probe_run_length_encode_ull.argtypes = [vp, vp, u64, vp, vp, u64, vp]
         L.probe_reduce_by_key_sum_ull_u32.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp]
         L.probe_select_flagged_indices_u32.argtypes = [vp, vp, u64, vp, u64, vp]

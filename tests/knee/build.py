@@ -1,6 +1,6 @@
-"""g++ recipe for tests/knee/knee_host_check.cpp: csrc/bus_knee_host.cpp (the host half of the cell calling on BUS records, free of HIP) with
-csrc/bus_correct_host.cpp (whose record walk it reuses) as a stand-alone host program under AddressSanitizer + UndefinedBehaviorSanitizer (run as a
-child process by tests/test_knee_host.py; never loaded into Python, never on a GPU). -ffp-contract=off: the curve's products and differences are
+"""g++ recipe for tests/knee/knee_host_check.cpp: csrc/bus_knee_host.cpp, the host half of the cell calling on BUS records, as a stand-alone host
+program under AddressSanitizer + UndefinedBehaviorSanitizer (run as a child process by tests/test_knee_host.py; never loaded into Python, never on
+a GPU). The source is free of HIP, and the record walk it calls is header-only (csrc/bus_records_host.hpp). -ffp-contract=off: the curve's products and differences are
 single operations, as the clang pragma of the source asks of the product's compiler."""
 import subprocess
 from pathlib import Path
@@ -10,11 +10,11 @@ ROOT = HERE.parent.parent
 CSRC = ROOT / "rust-pseudoaligner_amd" / "csrc"
 SRC = HERE / "knee_host_check.cpp"
 EXE = HERE / "_build" / "knee_host_check"
-SOURCES = [CSRC / "bus_knee_host.cpp", CSRC / "bus_correct_host.cpp"]
+SOURCES = [CSRC / "bus_knee_host.cpp"]
 
 
 def build_check(force: bool = False) -> Path:
-    deps = [SRC, CSRC / "bus_knee_host.hpp", CSRC / "bus_correct_host.hpp", CSRC / "pa_common.hpp", Path(__file__), ROOT / "include" / "pseudoaligner_amd.h"] + SOURCES
+    deps = [SRC, CSRC / "bus_knee_host.hpp", CSRC / "bus_records_host.hpp", CSRC / "pa_common.hpp", Path(__file__), ROOT / "include" / "pseudoaligner_amd.h"] + SOURCES
     if force or not EXE.exists() or any(d.stat().st_mtime > EXE.stat().st_mtime for d in deps):
         EXE.parent.mkdir(parents=True, exist_ok=True)
         cmd = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-Wno-unused-function", "-ffp-contract=off", "-fsanitize=address,undefined",

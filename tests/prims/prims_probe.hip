@@ -5,24 +5,35 @@
 // status. An output of a sort or a scan of n elements has n + PROBE_GUARD elements, so that a write past the end shows
 // (and n = 0 still has something to look at); the outputs of the run and selection entries have `cap` elements.
 //
-// The instantiations, by call site (ull = unsigned long long, u64 = uint64_t = unsigned long: two types to the compiler):
-//   sort_keys<ull, int>                       barcode_counts.hip:66, :447, :514
-//   sort_pairs<ull, u32, int>                 barcode_counts.hip:474, :500
-//   sort_pairs<u32, u32, size_t>              quant.hip:348; index_build.hip:525
-//   sort_pairs<u64, u32, size_t>              index_build.hip:379 (k <= 32)
-//   sort_pairs<u128, u32, size_t>             index_build.hip:379 (k > 32)
-//   sort_pairs<ull, u32, size_t>              index_build.hip:413
-//   sort_pairs_desc<u32, u32, size_t>         quant.hip:330, :352
-//   scan_inclusive<u32, u32>                  barcode_counts.hip:487; index_build.hip:391, :417
-//   scan_exclusive<u32, u32>                  quant.hip:340
-//   scan_exclusive<ull, ull>                  index_build.hip:441, :535
-//   scan_exclusive_on<u32, u32> + prim_bytes  fastq_scan.hip:165, :179
-//   scan_exclusive_on<u32, u64> + prim_bytes  render.hip:158, :169; compact.hip:59, :89
-//   run_length_encode<ull>                    barcode_counts.hip:67, :448, :484, :514
-//   reduce_by_key_sum<ull, u32>               barcode_counts.hip:475, :501
-//   select_flagged_indices<u32>               index_build.hip:507, :508
-//   bits_for                                  barcode_counts.hip:346; quant.hip:348
-//   grid_for                                  every launch of the three; block 256 and (barcode_counts.hip) CELL_BLOCK
+// The instantiations, by the files that make them (ull = unsigned long long, u64 = uint64_t = unsigned long: two types to the compiler):
+//   sort_keys<ull, int>                       barcode_counts.hip, bus_correct.hip
+//   sort_keys<ull, size_t>                    genes.hip
+//   sort_pairs<ull, u32, int>                 barcode_counts.hip, bus.hip
+//   sort_pairs<u32, u32, size_t>              quant.hip, index_build.hip
+//   sort_pairs<u64, u32, size_t>              index_build.hip (k <= 32)
+//   sort_pairs<u128, u32, size_t>             index_build.hip (k > 32), bus.hip, bus_correct.hip, genes.hip
+//   sort_pairs<ull, u32, size_t>              index_build.hip, genes.hip
+//   sort_pairs_desc<u32, u32, size_t>         quant.hip, genes.hip
+//   sort_pairs_desc<u32, u32, int>            bus_knee.hip
+//   scan_inclusive<u32, u32>                  barcode_counts.hip, index_build.hip
+//   scan_inclusive<u32, ull>                  bus_knee.hip
+//   scan_inclusive_total<u32, u32>            bus_correct.hip, bus_knee.hip, genes.hip, and inside flag_runs
+//   scan_inclusive_total<ull, ull>            bus_knee.hip
+//   scan_inclusive_total<u32, ull>            no call site: scan_inclusive<u32, ull> of bus_knee.hip with the fetch, a total wider than its input
+//   scan_exclusive<u32, u32>                  quant.hip
+//   scan_exclusive<u32, ull>                  genes.hip
+//   scan_exclusive<ull, ull>                  index_build.hip, bus.hip
+//   scan_exclusive_on<u32, u32> + prim_bytes  fastq_scan.hip
+//   scan_exclusive_on<u32, u64> + prim_bytes  render.hip, compact.hip
+//   run_length_encode<ull>                    barcode_counts.hip, genes.hip
+//   run_length_encode<u32>                    bus_knee.hip
+//   reduce_by_key_sum<ull, u32>               barcode_counts.hip
+//   select_flagged_indices<u32>               index_build.hip, bus.hip, bus_correct.hip, bus_knee.hip, genes.hip
+//   collapse_runs<KeyArray<ull>>              bus.hip, genes.hip
+//   collapse_runs<KeyArray<u128>>             bus.hip, bus_correct.hip, genes.hip
+//   flag_runs / scatter_runs<RecordBarcode>   bus_correct.hip (both halves, with a start), bus_knee.hip (scatter_runs alone, null start)
+//   bits_for                                  barcode_counts.hip, quant.hip, bus_knee.hip, genes.hip
+//   grid_for                                  every launch of these files; block 256 and (barcode_counts.hip) CELL_BLOCK
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -103,6 +114,41 @@ int do_sort_pairs(Tmp* tmp, const K* kin, K* kout, const V* vin, V* vout, uint64
     return dvo.down(vout);
 }
 
+template <class In, class Out>
+int do_scan_total(Tmp* tmp, const In* in, Out* out, uint64_t n, Out* total) {
+    Dev<In> din;
+    Dev<Out> dout;
+    TRY(din.up(in, n)); TRY(dout.up(out, n + PROBE_GUARD));
+    TRY(scan_inclusive_total(nullptr, *tmp, (const In*)din.get(), dout.get(), (size_t)n, *total));
+    return dout.down(out);
+}
+
+template <class K>
+int do_rle(Tmp* tmp, const K* in, uint64_t n, K* unique, uint32_t* counts, uint64_t cap, uint32_t* runs) {
+    Dev<K> din, du;
+    Dev<uint32_t> dc, dr;
+    TRY(din.up(in, n)); TRY(du.up(unique, cap)); TRY(dc.up(counts, cap)); TRY(dr.up(runs, 1));
+    TRY(run_length_encode(nullptr, *tmp, (const K*)din.get(), (size_t)n, du.get(), dc.get(), dr.get()));
+    TRY(sync());
+    TRY(du.down(unique)); TRY(dc.down(counts));
+    return dr.down(runs);
+}
+
+// collapse_runs over n >= 1 items `In` read through KeyAt: heads and pos have n + PROBE_GUARD elements, unique has cap, start has cap + 1 (with_start
+// 0: the null-start form, and start comes back as it went up)
+template <class KeyAt, class In>
+int do_collapse(Tmp* tmp, const In* in, uint64_t n, uint32_t* heads, uint32_t* pos, typename KeyAt::key_type* unique, uint32_t* start, uint64_t cap, int with_start,
+                uint32_t* runs) {
+    Dev<In> din;
+    Dev<typename KeyAt::key_type> du;
+    Dev<uint32_t> dh, dp, ds;
+    TRY(din.up(in, n)); TRY(dh.up(heads, n + PROBE_GUARD)); TRY(dp.up(pos, n + PROBE_GUARD)); TRY(du.up(unique, cap)); TRY(ds.up(start, cap + 1));
+    TRY(collapse_runs(nullptr, *tmp, KeyAt{din.get()}, (uint32_t)n, dh.get(), dp.get(), du.get(), with_start ? ds.get() : nullptr, *runs));
+    TRY(sync());
+    TRY(dh.down(heads)); TRY(dp.down(pos)); TRY(du.down(unique));
+    return ds.down(start);
+}
+
 template <class In, class Out, bool INCLUSIVE>
 int do_scan(Tmp* tmp, const In* in, Out* out, uint64_t n) {
     Dev<In> din;
@@ -155,6 +201,7 @@ uint64_t probe_tmp_size(void* t) { return static_cast<Tmp*>(t)->size(); }
 
 // ---- sorts ----
 int probe_sort_keys_ull_int(void* t, const ull* in, ull* out, uint64_t n, uint32_t b0, uint32_t b1) { return do_sort_keys<ull, int>(static_cast<Tmp*>(t), in, out, n, b0, b1); }
+int probe_sort_keys_ull_size(void* t, const ull* in, ull* out, uint64_t n, uint32_t b0, uint32_t b1) { return do_sort_keys<ull, size_t>(static_cast<Tmp*>(t), in, out, n, b0, b1); }
 int probe_sort_pairs_ull_u32_int(void* t, const ull* ki, ull* ko, const uint32_t* vi, uint32_t* vo, uint64_t n, uint32_t b0, uint32_t b1) {
     return do_sort_pairs<ull, uint32_t, int, false>(static_cast<Tmp*>(t), ki, ko, vi, vo, n, b0, b1);
 }
@@ -174,8 +221,17 @@ int probe_sort_pairs_u128_u32_size(void* t, const void* ki, void* ko, const uint
 int probe_sort_pairs_desc_u32_u32_size(void* t, const uint32_t* ki, uint32_t* ko, const uint32_t* vi, uint32_t* vo, uint64_t n, uint32_t b0, uint32_t b1) {
     return do_sort_pairs<uint32_t, uint32_t, size_t, true>(static_cast<Tmp*>(t), ki, ko, vi, vo, n, b0, b1);
 }
+int probe_sort_pairs_desc_u32_u32_int(void* t, const uint32_t* ki, uint32_t* ko, const uint32_t* vi, uint32_t* vo, uint64_t n, uint32_t b0, uint32_t b1) {
+    return do_sort_pairs<uint32_t, uint32_t, int, true>(static_cast<Tmp*>(t), ki, ko, vi, vo, n, b0, b1);
+}
 
 // ---- scans ----
+int probe_scan_inclusive_u32_ull(void* t, const uint32_t* in, ull* out, uint64_t n) { return do_scan<uint32_t, ull, true>(static_cast<Tmp*>(t), in, out, n); }
+int probe_scan_exclusive_u32_ull(void* t, const uint32_t* in, ull* out, uint64_t n) { return do_scan<uint32_t, ull, false>(static_cast<Tmp*>(t), in, out, n); }
+// (n >= 1; *total = what the wrapper fetched)
+int probe_scan_inclusive_total_u32_u32(void* t, const uint32_t* in, uint32_t* out, uint64_t n, uint32_t* total) { return do_scan_total(static_cast<Tmp*>(t), in, out, n, total); }
+int probe_scan_inclusive_total_ull_ull(void* t, const ull* in, ull* out, uint64_t n, ull* total) { return do_scan_total(static_cast<Tmp*>(t), in, out, n, total); }
+int probe_scan_inclusive_total_u32_ull(void* t, const uint32_t* in, ull* out, uint64_t n, ull* total) { return do_scan_total(static_cast<Tmp*>(t), in, out, n, total); }
 int probe_scan_inclusive_u32_u32(void* t, const uint32_t* in, uint32_t* out, uint64_t n) { return do_scan<uint32_t, uint32_t, true>(static_cast<Tmp*>(t), in, out, n); }
 int probe_scan_exclusive_u32_u32(void* t, const uint32_t* in, uint32_t* out, uint64_t n) { return do_scan<uint32_t, uint32_t, false>(static_cast<Tmp*>(t), in, out, n); }
 int probe_scan_exclusive_ull_ull(void* t, const ull* in, ull* out, uint64_t n) { return do_scan<ull, ull, false>(static_cast<Tmp*>(t), in, out, n); }
@@ -189,13 +245,10 @@ int probe_scan_exclusive_on_u32_u64(const uint32_t* in, uint64_t* out, uint64_t 
 // ---- runs. unique / counts / sums have `cap` elements (>= the runs the caller expects; what lies behind them must stay as it was);
 // *runs goes up as the caller set it and comes back as the wrapper left it ----
 int probe_run_length_encode_ull(void* t, const ull* in, uint64_t n, ull* unique, uint32_t* counts, uint64_t cap, uint32_t* runs) {
-    Dev<ull> din, du;
-    Dev<uint32_t> dc, dr;
-    TRY(din.up(in, n)); TRY(du.up(unique, cap)); TRY(dc.up(counts, cap)); TRY(dr.up(runs, 1));
-    TRY(run_length_encode(nullptr, *static_cast<Tmp*>(t), (const ull*)din.get(), (size_t)n, du.get(), dc.get(), dr.get()));
-    TRY(sync());
-    TRY(du.down(unique)); TRY(dc.down(counts));
-    return dr.down(runs);
+    return do_rle(static_cast<Tmp*>(t), in, n, unique, counts, cap, runs);
+}
+int probe_run_length_encode_u32(void* t, const uint32_t* in, uint64_t n, uint32_t* unique, uint32_t* counts, uint64_t cap, uint32_t* runs) {
+    return do_rle(static_cast<Tmp*>(t), in, n, unique, counts, cap, runs);
 }
 int probe_reduce_by_key_sum_ull_u32(void* t, const ull* kin, const uint32_t* vin, uint64_t n, ull* unique, uint32_t* sums, uint64_t cap, uint32_t* runs) {
     Dev<ull> dk, du;
@@ -205,6 +258,18 @@ int probe_reduce_by_key_sum_ull_u32(void* t, const ull* kin, const uint32_t* vin
     TRY(sync());
     TRY(du.down(unique)); TRY(ds.down(sums));
     return dr.down(runs);
+}
+
+// ---- the collapse of sorted items (u128 keys as 16 bytes each, low word first; records as the header lays them out) ----
+int probe_collapse_runs_ull(void* t, const ull* keys, uint64_t n, uint32_t* heads, uint32_t* pos, ull* unique, uint32_t* start, uint64_t cap, int with_start, uint32_t* runs) {
+    return do_collapse<KeyArray<ull>>(static_cast<Tmp*>(t), keys, n, heads, pos, unique, start, cap, with_start, runs);
+}
+int probe_collapse_runs_u128(void* t, const void* keys, uint64_t n, uint32_t* heads, uint32_t* pos, void* unique, uint32_t* start, uint64_t cap, int with_start, uint32_t* runs) {
+    return do_collapse<KeyArray<u128>>(static_cast<Tmp*>(t), static_cast<const u128*>(keys), n, heads, pos, static_cast<u128*>(unique), start, cap, with_start, runs);
+}
+int probe_collapse_runs_record(void* t, const pa_bus_record* rec, uint64_t n, uint32_t* heads, uint32_t* pos, ull* unique, uint32_t* start, uint64_t cap, int with_start,
+                               uint32_t* runs) {
+    return do_collapse<RecordBarcode>(static_cast<Tmp*>(t), rec, n, heads, pos, unique, start, cap, with_start, runs);
 }
 
 // ---- selection: out has `cap` elements ----

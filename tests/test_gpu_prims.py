@@ -82,12 +82,14 @@ def test_grid_for(built):
 # name -> (probe entry, key bits, has values, descending)
 SORTS = {
     "keys_ull_int": ("probe_sort_keys_ull_int", 64, False, False),
+    "keys_ull_size": ("probe_sort_keys_ull_size", 64, False, False),
     "pairs_ull_u32_int": ("probe_sort_pairs_ull_u32_int", 64, True, False),
     "pairs_u32_u32_size": ("probe_sort_pairs_u32_u32_size", 32, True, False),
     "pairs_u64_u32_size": ("probe_sort_pairs_u64_u32_size", 64, True, False),
     "pairs_ull_u32_size": ("probe_sort_pairs_ull_u32_size", 64, True, False),
     "pairs_u128_u32_size": ("probe_sort_pairs_u128_u32_size", 128, True, False),
     "pairs_desc_u32_u32_size": ("probe_sort_pairs_desc_u32_u32_size", 32, True, True),
+    "pairs_desc_u32_u32_int": ("probe_sort_pairs_desc_u32_u32_int", 32, True, True),
 }
 BIT_RANGES = [(0, 1), (0, 48), (0, 62), (0, 32), (0, 33), (0, 64), (7, 19)]   # [0, 2k) for k = 24, 31
 WIDE_RANGES = [(0, 96), (0, 128), (60, 70), (64, 65)]                          # 128-bit keys only (k > 32: up to [0, 128))
@@ -215,6 +217,8 @@ SCANS = {   # name: (entry, in type, out type, inclusive)
     "inclusive_u32_u32": ("probe_scan_inclusive_u32_u32", np.uint32, np.uint32, True),
     "exclusive_u32_u32": ("probe_scan_exclusive_u32_u32", np.uint32, np.uint32, False),
     "exclusive_ull_ull": ("probe_scan_exclusive_ull_ull", np.uint64, np.uint64, False),
+    "inclusive_u32_ull": ("probe_scan_inclusive_u32_ull", np.uint32, np.uint64, True),
+    "exclusive_u32_ull": ("probe_scan_exclusive_u32_ull", np.uint32, np.uint64, False),
 }
 
 
@@ -238,7 +242,7 @@ def test_scan_sizes(name):
         ok(getattr(L(), entry)(tmp.h, ptr(x), ptr(out), n))
         assert np.array_equal(out[:n], scan_reference(x, ot, inclusive)), (name, n)
         assert (out[n:] == FILL[np.dtype(ot)]).all(), (name, n)
-    if it == np.uint32:   # sums in uint32 wrap modulo 2^32 like uint32 arithmetic
+    if it == np.uint32:   # sums in uint32 wrap modulo 2^32 like uint32 arithmetic; into uint64 they are carried past 2^32
         x = rng.integers(0, 2 ** 32, 4097, dtype=np.uint64).astype(np.uint32)
         out = filled(len(x), ot)
         ok(getattr(L(), entry)(tmp.h, ptr(x), ptr(out), len(x)))
@@ -288,6 +292,35 @@ def test_scan_u32_into_u64_is_summed_as_u64():
     assert np.array_equal(out32[:len(x)], want.astype(np.uint32)) and not np.array_equal(out32[:len(x)].astype(np.uint64), want)
 
 
+SCAN_TOTALS = {   # name: (entry, in type, out type)
+    "u32_u32": ("probe_scan_inclusive_total_u32_u32", np.uint32, np.uint32),
+    "ull_ull": ("probe_scan_inclusive_total_ull_ull", np.uint64, np.uint64),
+    "u32_ull": ("probe_scan_inclusive_total_u32_ull", np.uint32, np.uint64),
+}
+
+
+@gpu
+@pytest.mark.parametrize("name", list(SCAN_TOTALS))
+def test_scan_inclusive_total(name):
+    """the scan, and its last element on the host: every size from 1 up; a total wider than the input is carried past 2^32"""
+    entry, it, ot = SCAN_TOTALS[name]
+    rng = np.random.default_rng(13)
+    tmp = Tmp()
+    cases = [rng.integers(0, 4000 if it == np.uint32 else 2 ** 40, n, dtype=np.uint64).astype(it) for n in SIZES]
+    if it == np.uint32:
+        cases.append(rng.integers(2 ** 31, 2 ** 32, 4097, dtype=np.uint64).astype(np.uint32))
+        assert int(cases[-1].astype(np.uint64).sum()) > 2 ** 32
+    for x in cases:
+        n = len(x)
+        out, total = filled(n, ot), np.full(1, FILL[np.dtype(ot)], ot)
+        ok(getattr(L(), entry)(tmp.h, ptr(x), ptr(out), n, ptr(total)))
+        want = scan_reference(x, ot, True)
+        assert np.array_equal(out[:n], want) and (out[n:] == FILL[np.dtype(ot)]).all(), (name, n)
+        assert int(total[0]) == int(want[-1]) == int(out[n - 1]), (name, n)
+    if name == "u32_ull":
+        assert int(total[0]) == int(cases[-1].astype(np.uint64).sum()) > 2 ** 32
+
+
 # ---- run-length encode, reduce by key ----
 def run_shapes(n):
     """lists of run lengths that sum to n"""
@@ -301,14 +334,14 @@ def run_shapes(n):
     return shapes
 
 
-def keys_of_runs(rng, runs):
-    """one random 64-bit key per run, neighbours different, repeated to the run's length (a key may come again in a later run)"""
-    k = rng.integers(0, 2 ** 64, len(runs), dtype=np.uint64)
-    k[1:][k[1:] == k[:-1]] ^= np.uint64(1)
+def keys_of_runs(rng, runs, dtype=np.uint64):
+    """one random key per run (64 bits, or 32), neighbours different, repeated to the run's length (a key may come again in a later run)"""
+    k = rng.integers(0, 2 ** (8 * np.dtype(dtype).itemsize), len(runs), dtype=np.uint64).astype(dtype)
+    k[1:][k[1:] == k[:-1]] ^= dtype(1)
     if len(runs) > 4:
         k[4] = k[0]   # a key that comes again later is a run of its own
         if k[4] == k[3] or (len(runs) > 5 and k[4] == k[5]):
-            k[4] ^= np.uint64(2)
+            k[4] ^= dtype(2)
     return np.repeat(k, runs), k
 
 
@@ -329,6 +362,12 @@ def test_run_length_encode_and_reduce_by_key():
             assert int(cnt[0]) == r, what
             assert np.array_equal(u[:r], uniq) and np.array_equal(c[:r], np.array(runs, np.uint32)), what
             assert (u[r:] == FILL[np.dtype(np.uint64)]).all() and (c[r:] == 0xDEADBEEF).all(), what      # nothing behind the runs
+            # ... of 32-bit keys
+            keys32, uniq32 = keys_of_runs(rng, runs, np.uint32)
+            u, c, cnt = np.full(cap, 0xDEADBEEF, np.uint32), np.full(cap, 0xDEADBEEF, np.uint32), np.full(1, 0xDEADBEEF, np.uint32)
+            ok(lib.probe_run_length_encode_u32(tmp.h, ptr(keys32), n, ptr(u), ptr(c), cap, ptr(cnt)))
+            assert int(cnt[0]) == r and np.array_equal(u[:r], uniq32) and np.array_equal(c[:r], np.array(runs, np.uint32)), what
+            assert (u[r:] == 0xDEADBEEF).all() and (c[r:] == 0xDEADBEEF).all(), what
             # sums of values per run. Values below 1000 and at most 1 000 003 of them: every uint32 sum stays below 2^32.
             vals = rng.integers(0, 1000, n, dtype=np.uint64).astype(np.uint32)
             sums = Counter()
@@ -341,14 +380,82 @@ def test_run_length_encode_and_reduce_by_key():
             assert np.array_equal(u[:r], uniq) and s[:r].tolist() == [sums[j] for j in range(r)], what
             assert (u[r:] == FILL[np.dtype(np.uint64)]).all() and (s[r:] == 0xDEADBEEF).all(), what
     # n = 0: no runs, outputs untouched
-    for entry in ("rle", "rbk"):
-        u, c, cnt = np.full(8, 7, np.uint64), np.full(8, 7, np.uint32), np.full(1, 0xDEADBEEF, np.uint32)
+    for entry in ("rle", "rle32", "rbk"):
+        u, c, cnt = np.full(8, 7, np.uint32 if entry == "rle32" else np.uint64), np.full(8, 7, np.uint32), np.full(1, 0xDEADBEEF, np.uint32)
         k0, v0 = np.zeros(1, np.uint64), np.zeros(1, np.uint32)
         if entry == "rle":
             ok(lib.probe_run_length_encode_ull(tmp.h, ptr(k0), 0, ptr(u), ptr(c), 8, ptr(cnt)))
+        elif entry == "rle32":
+            ok(lib.probe_run_length_encode_u32(tmp.h, ptr(v0), 0, ptr(u), ptr(c), 8, ptr(cnt)))
         else:
             ok(lib.probe_reduce_by_key_sum_ull_u32(tmp.h, ptr(k0), ptr(v0), 0, ptr(u), ptr(c), 8, ptr(cnt)))
         assert int(cnt[0]) == 0 and (u == 7).all() and (c == 7).all(), entry
+
+
+# ---- the collapse of sorted items ----
+BUS_RECORD = np.dtype([("barcode", "<u8"), ("umi", "<u8"), ("ec", "<i4"), ("count", "<u4"), ("flags", "<u4"), ("pad", "<u4")])
+COLLAPSE_SIZES = [1, 2, 255, 256, 257, 4097]
+
+
+def collapse_shapes(n):
+    """lists of run lengths that sum to n: all equal, all distinct, a boundary exactly at item 255, 256, 257 (the seam of two blocks), a last run of one"""
+    shapes = [[n], [1] * n] + [[b, n - b] for b in (255, 256, 257) if b < n]
+    if n > 1:
+        shapes.append([n - 1, 1])
+    if n > 257:
+        shapes.append([255, 1, 1, n - 258, 1])
+    return shapes
+
+
+def collapse_items(kind, rng, runs):
+    """-> (the items as the probe takes them, the key of every run as `unique` holds it: shape (runs,), or (runs, 2) = (low, high) for 128 bits)"""
+    if kind == "u128":
+        k = rng.integers(0, 2 ** 64, (len(runs), 2), dtype=np.uint64)
+        k[:, 1] = k[0, 1]                  # equal high words: the low word decides ...
+        k[1::2, 0] = k[0::2, 0][:len(k[1::2])]
+        k[1::2, 1] ^= np.uint64(1)         # ... and equal low words, where the high word does
+        assert all((k[j] != k[j - 1]).any() for j in range(1, len(k)))
+        return np.ascontiguousarray(np.repeat(k, runs, axis=0)), k
+    items, k = keys_of_runs(rng, runs)
+    if kind == "ull":
+        return items, k
+    rec = np.zeros(len(items), BUS_RECORD)   # equal barcodes with different UMIs and ecs: a run is a run of the barcode field alone
+    rec["barcode"] = items
+    rec["umi"] = rng.integers(0, 2 ** 62, len(items), dtype=np.uint64)
+    rec["ec"] = np.arange(len(items)) % 7
+    rec["count"], rec["flags"], rec["pad"] = 0xFFFFFFFF, 0xFFFFFFFF, 0xFFFFFFFF   # (nothing but the barcode may be read as a key)
+    return rec, k
+
+
+@gpu
+@pytest.mark.parametrize("kind", ["ull", "u128", "record"])
+def test_collapse_runs(kind):
+    """sorted items -> unique[runs], start[runs + 1] with start[runs] = n, heads and pos = the flags and their scan; nothing behind what is written;
+    the null-start form writes the same unique and leaves start alone"""
+    entry = getattr(L(), "probe_collapse_runs_" + kind)
+    rng = np.random.default_rng(14)
+    tmp = Tmp()
+    width = 2 if kind == "u128" else 1
+    for n in COLLAPSE_SIZES:
+        for runs in collapse_shapes(n):
+            items, uniq = collapse_items(kind, rng, runs)
+            r, cap = len(runs), len(runs) + 8
+            want_start = np.concatenate([[0], np.cumsum(runs)]).astype(np.uint32)
+            want_heads = np.zeros(n, np.uint32)
+            want_heads[want_start[:-1]] = 1
+            for with_start in (1, 0):
+                heads, pos = filled(n, np.uint32), filled(n, np.uint32)
+                unique, start, cnt = np.full(cap * width, FILL[np.dtype(np.uint64)], np.uint64), np.full(cap + 1, 0xDEADBEEF, np.uint32), np.full(1, 0xDEADBEEF, np.uint32)
+                ok(entry(tmp.h, ptr(items), n, ptr(heads), ptr(pos), ptr(unique), ptr(start), cap, with_start, ptr(cnt)))
+                what = (kind, n, r, with_start)
+                assert int(cnt[0]) == r, what
+                assert np.array_equal(heads[:n], want_heads) and np.array_equal(pos[:n], np.cumsum(want_heads, dtype=np.uint32)), what
+                assert (heads[n:] == 0xDEADBEEF).all() and (pos[n:] == 0xDEADBEEF).all(), what
+                assert np.array_equal(unique[: r * width].reshape(uniq.shape), uniq) and (unique[r * width:] == FILL[np.dtype(np.uint64)]).all(), what
+                if with_start:
+                    assert np.array_equal(start[: r + 1], want_start) and int(start[r]) == n and (start[r + 1:] == 0xDEADBEEF).all(), what
+                else:
+                    assert (start == 0xDEADBEEF).all(), what
 
 
 # ---- selection ----
