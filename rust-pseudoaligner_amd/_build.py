@@ -91,6 +91,25 @@ def build_maxbins_variant(force: bool = False) -> Path:
     return MAXBINS_SO
 
 
+PAIRKNOBS_SO = OBJ_DIR / "libpseudoaligner_amd_pairknobs.so"
+
+
+def build_pairknobs_variant(force: bool = False) -> Path:
+    """A TEST build of the product: device_flatten.cpp compiled with -DPA_DEBUG_KNOBS, everything else the product's own objects. The choice of the
+    dictionary's format and size (dict_pair_log2, used by the CPU flattener and the GPU filler alike) then reads the test-only sizing hooks
+    PA_PAIR_LOG2 / PA_PAIR_MAX_BLOCKS (tests/test_gpu_dict_pairs.py loads it in a child process through PA_PRODUCT_SO)."""
+    build_product()
+    hipcc = hipcc_path()
+    src = CSRC / "device_flatten.cpp"
+    obj = OBJ_DIR / "device_flatten.pairknobs.o"
+    if force or _stale(obj, _deps_of(src)):
+        _run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread", "-Wall", "-Wno-unused-function", "-DPA_DEBUG_KNOBS", "-x", "hip", "-c", str(src), "-o", str(obj)])
+    objs = [OBJ_DIR / (s + ".o") for s in HOST_SOURCES + HIP_SOURCES if s != "device_flatten.cpp"] + [obj]
+    if force or _stale(PAIRKNOBS_SO, objs):
+        _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-pthread"] + [str(o) for o in objs] + ["-ldl", "-lz", "-o", str(PAIRKNOBS_SO)])
+    return PAIRKNOBS_SO
+
+
 ABI_CHECK_SRC = ROOT / "integration" / "c" / "abi_check.c"
 ABI_CHECK_BIN = ROOT / "integration" / "c" / "abi_check"
 

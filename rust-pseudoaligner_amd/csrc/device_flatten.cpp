@@ -23,6 +23,7 @@ DevIndexView FlatDevice::host_view() const {
     DevIndexView v;
     v.table = table.data();
     v.nbuckets = nbuckets;
+    v.dict_pairs = dict_pairs;
     v.blobs = blobs.data();
     v.ledge = ledge.data();
     v.seg_g = seg_g.data();
@@ -42,6 +43,24 @@ DevIndexView FlatDevice::host_view() const {
     v.bitmap_min = bitmap_min;
     v.bitmap_words = bitmap_words;
     return v;
+}
+
+uint32_t dict_pair_log2(uint32_t k, uint64_t nblocks, uint64_t nk, uint32_t bump) {
+    uint64_t max_blocks = PAIR_MAX_BLOCKS;
+    double load = PAIR_LOAD;
+    uint32_t b = PAIR_MIN_LOG2;
+    if (const char* v = knob_str("PA_PAIR_MAX_BLOCKS")) max_blocks = std::min<uint64_t>(max_blocks, strtoull(v, nullptr, 10));
+    if (const char* v = knob_str("PA_PAIR_LOAD")) { const double x = atof(v); if (x > 0.01 && x <= 1.9) load = x; }   // A/B runs only
+    if (k > PAIR_MAX_K || nblocks >= max_blocks) return 0;
+    if (knob_str("PA_DICT_LOAD")) return 0;   // (names a load of the 16-byte slots: the index keeps them)
+    while (b < PAIR_MAX_LOG2 && (double)nk > load * (double)(1ull << b)) ++b;
+    if (const char* v = knob_str("PA_PAIR_LOG2")) {
+        const uint32_t x = (uint32_t)atoi(v);
+        if (x == 0) return 0;
+        b = std::min(std::max(x, PAIR_MIN_LOG2), PAIR_MAX_LOG2);
+    }
+    b += bump;
+    return b <= PAIR_MAX_LOG2 ? b : 0;   // (a table of more than 2^31 pairs: the 16-byte slots)
 }
 
 namespace {
@@ -102,22 +121,25 @@ struct Dict<u128> {   // k > 32: two whole entries {key word 0..3, handle, off, 
     }
 };
 
-struct HostAtomics {
-    static bool cas(uint32_t* p, uint32_t expect, uint32_t v) { return __atomic_compare_exchange_n(p, &expect, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED); }
-    static void and_(uint32_t* p, uint32_t m) { __atomic_fetch_and(p, m, __ATOMIC_RELAXED); }
-};
-
 template <>
 struct Dict<uint64_t> {   // host-side builder/reader of the 16-byte slots described in device_layout.hpp (dict_slots.hpp)
     static constexpr double LOAD = DICT_LOAD;
     static constexpr uint32_t SLOTS = SLOTS_PER_BUCKET;
     uint32_t* words;
     uint64_t nbuckets;
-    void insert_mt(uint64_t kmer, uint32_t handle, uint32_t off) { dict_insert_home<HostAtomics>(words, (uint32_t)nbuckets, kmer, handle, off); }          // pass 1
-    void insert_rest_mt(uint64_t kmer, uint32_t handle, uint32_t off) { dict_insert_rest<HostAtomics>(words, (uint32_t)nbuckets, kmer, handle, off); }     // pass 2
+    uint32_t pairs = 0;                    // != 0: the pair dictionary of 2^pairs pairs
+    std::atomic<uint32_t>* far = nullptr;  // pair dictionary: set when a key would lie too far from its home
+    void insert_mt(uint64_t kmer, uint32_t handle, uint32_t off) {          // pass 1
+        if (!pairs) dict_insert_home<HostAtomics>(words, (uint32_t)nbuckets, kmer, handle, off);
+        else if (!pair_insert<HostAtomics>(reinterpret_cast<uint64_t*>(words), pairs, kmer, handle, off)) far->store(1);
+    }
+    void insert_rest_mt(uint64_t kmer, uint32_t handle, uint32_t off) {     // pass 2
+        if (!pairs) dict_insert_rest<HostAtomics>(words, (uint32_t)nbuckets, kmer, handle, off);
+        else pair_flag<HostAtomics>(reinterpret_cast<uint64_t*>(words), pairs, kmer);
+    }
     bool find(uint64_t kmer, uint32_t& handle, uint32_t& off, uint32_t* probes_out = nullptr) const {
         uint32_t probes = 0;
-        const bool found = dict_find64(words, (uint32_t)nbuckets, kmer, handle, off, probes);
+        const bool found = dict_find64(words, (uint32_t)nbuckets, pairs, kmer, handle, off, probes);
         if (probes_out) *probes_out = probes;
         return found;
     }
@@ -565,24 +587,32 @@ static int flatten_t(const pa_flat_index& f, int threads, FlatDevice& out, bool 
     }
     double load0 = Dict<KT>::LOAD;
     if (const char* v = knob_str("PA_DICT_LOAD")) { const double x = atof(v); if (x > 0.01 && x <= 0.95) load0 = x; }   // (knobs builds and the test emulator: dense tables exercise the probe's rare paths)
-    for (double load = load0; !device_dict; load *= 0.75) {
-        out.nbuckets = std::max<uint64_t>(1, (uint64_t)((double)nk / (Dict<KT>::SLOTS * load)) + 1);
+    uint32_t bump = 0;
+    std::atomic<uint32_t> pair_far{0};
+    bool try_pairs = sizeof(KT) == 8;
+    for (double load = load0; !device_dict; out.dict_pairs ? (void)++bump : (void)(load *= 0.75)) {   // (each format has its own retry)
+        // the format (device_layout.hpp): pairs of 8-byte entries where the keys and the handles fit them, else the 16-byte slots
+        out.dict_pairs = try_pairs ? dict_pair_log2(k, nblocks, nk, bump) : 0;
+        if (!out.dict_pairs) try_pairs = false;
+        out.nbuckets = out.dict_pairs ? 1ull << out.dict_pairs : std::max<uint64_t>(1, (uint64_t)((double)nk / (Dict<KT>::SLOTS * load)) + 1);
         if (out.nbuckets >= 0xFFFFFFFFull) return fail(PA_ERR_UNSUPPORTED, "dictionary exceeds 2^32 buckets");
-        out.table.assign(out.nbuckets * BUCKET_WORDS, 0xFFFFFFFFu);   // empty slots, no flags
+        out.table.assign(dict_table_words(out.nbuckets, out.dict_pairs), 0xFFFFFFFFu);   // empty slots, no flags
         dict = Dict<KT>{out.table.data(), out.nbuckets};
+        if constexpr (sizeof(KT) == 8) { dict.pairs = out.dict_pairs; dict.far = &pair_far; pair_far.store(0); }
         par_ranges(threads, N, [&](uint64_t a, uint64_t b, int) {
             for (uint64_t i = a; i < b; ++i) node_kmers((uint32_t)i, [&](KT km, uint32_t h, uint32_t o) { dict.insert_mt(km, h, o); });
         });
         par_ranges(threads, N, [&](uint64_t a, uint64_t b, int) {   // k <= 32: keys that did not get their home slot (dict_slots.hpp)
             for (uint64_t i = a; i < b; ++i) node_kmers((uint32_t)i, [&](KT km, uint32_t h, uint32_t o) { dict.insert_rest_mt(km, h, o); });
         });
+        if (pair_far.load()) continue;   // (pair dictionary: a key too far from its home — the next size)
         std::atomic<uint32_t> bad{NO_HANDLE}, far{0};
         par_ranges(threads, N, [&](uint64_t a, uint64_t b, int) {
             for (uint64_t i = a; i < b; ++i)
                 node_kmers((uint32_t)i, [&](KT km, uint32_t h, uint32_t o) {
                     uint32_t fh, fo, probes = 0;
                     if (!dict.find(km, fh, fo, &probes) || fh != h || fo != o) bad.store((uint32_t)i);
-                    if (probes > DICT_MAX_PROBES) far.store(1);
+                    if (!out.dict_pairs && probes > DICT_MAX_PROBES) far.store(1);
                 });
         });
         if (bad.load() != NO_HANDLE) return fail(PA_ERR_FORMAT, "a k-mer of node %u occurs twice in the graph", bad.load());

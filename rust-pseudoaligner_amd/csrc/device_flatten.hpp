@@ -10,8 +10,9 @@
 namespace pa {
 
 struct FlatDevice {
-    std::vector<uint32_t> table;   // nbuckets * BUCKET_WORDS
+    std::vector<uint32_t> table;   // nbuckets * BUCKET_WORDS (pair dictionary: nbuckets = its pairs, 4 words each)
     uint64_t nbuckets = 0;
+    uint32_t dict_pairs = 0;        // != 0: `table` is the pair dictionary of 2^dict_pairs pairs (device_layout.hpp)
     std::vector<uint8_t> blobs;     // chain blocks
     std::vector<uint32_t> handle;   // node id -> handle of its chain
     std::vector<uint32_t> node_s;   // node id -> position of its first base in the chain
@@ -38,10 +39,16 @@ struct FlatDevice {
 // `nbuckets` 0, node_kcum is filled.
 int flatten_for_device(const pa_flat_index& f, int threads, FlatDevice& out, bool device_dict = false);
 
+// The dictionary format of an index of nk k-mers in nblocks chain blocks: log2 of the pairs of the pair dictionary (2k <= 48, handles
+// that fit 24 bits), or 0: the 16-byte slots. `bump`: tables tried before this one that left a key too far from its home (each doubles).
+// Knobs builds only (tests): PA_PAIR_LOG2 forces the size (>= 21; 0 = never the pair format), PA_PAIR_MAX_BLOCKS lowers the block limit.
+uint32_t dict_pair_log2(uint32_t k, uint64_t nblocks, uint64_t nk, uint32_t bump);
+
 #ifdef __HIPCC__
 // index_fill.hip: dictionary fill (CAS into the bucket lines) and verification (duplicate k-mers, probe distance) on the
-// device, from chain blocks already resident in HBM. Hands the dictionary back in `table` (left as it was on failure) and sets *nbuckets.
-int device_fill_index(const FlatDevice& fd, const uint8_t* d_blobs, DeviceBuffer<uint32_t>& table, uint64_t* nbuckets);
+// device, from chain blocks already resident in HBM. Hands the dictionary back in `table` (left as it was on failure) and sets *nbuckets
+// and *dict_pairs (the format: FlatDevice::dict_pairs).
+int device_fill_index(const FlatDevice& fd, const uint8_t* d_blobs, DeviceBuffer<uint32_t>& table, uint64_t* nbuckets, uint32_t* dict_pairs);
 #endif
 
 }  // namespace pa

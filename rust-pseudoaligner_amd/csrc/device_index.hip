@@ -183,7 +183,7 @@ int pa_index_create(const pa_flat_index* flat, int device, pa_index** out) {
     if (idx->num_cus <= 0) idx->num_cus = 256;
     rc = upload(idx->d_blobs, fd.blobs);
     if (rc == PA_OK) rc = upload(idx->d_ledge, fd.ledge);
-    if (rc == PA_OK) rc = device_fill_index(fd, idx->d_blobs.get(), idx->d_table, &fd.nbuckets);
+    if (rc == PA_OK) rc = device_fill_index(fd, idx->d_blobs.get(), idx->d_table, &fd.nbuckets, &fd.dict_pairs);
     if (rc == PA_OK) rc = upload(idx->d_seg_g, fd.seg_g);
     if (rc == PA_OK) rc = upload(idx->d_seg_nid, fd.seg_nid);
     if (rc == PA_OK) rc = upload(idx->d_ec, fd.ec);
@@ -208,11 +208,11 @@ int pa_index_create(const pa_flat_index* flat, int device, pa_index** out) {
     idx->dv.wtable = idx->d_wtable.get();
     // a dictionary beyond the Infinity Cache (256 MB) is streamed past the caches (ld_stream): every line of it is used once per probe,
     // and left to itself it evicts the chain blocks, which every read comes back to
-    idx->dv.stream_nt = (fd.k <= 32 && fd.nbuckets * BUCKET_WORDS * 4 > (512ull << 20)) ? 1u : 0u;   // (the two-word dictionary's probe is four loads of one line: slower with the hint)
+    idx->dv.stream_nt = (fd.k <= 32 && dict_table_words(fd.nbuckets, fd.dict_pairs) * 4 > (512ull << 20)) ? 1u : 0u;   // (the two-word dictionary's probe is four loads of one line: slower with the hint)
     pa_index_stats& s = idx->stats;
     s.num_kmers = fd.num_kmers;
-    s.table_slots = fd.nbuckets * SLOTS_PER_BUCKET;
-    s.bytes_table = fd.nbuckets * BUCKET_WORDS * 4;
+    s.table_slots = dict_table_words(fd.nbuckets, fd.dict_pairs) / SLOT_WORDS;
+    s.bytes_table = dict_table_words(fd.nbuckets, fd.dict_pairs) * 4;
     s.bytes_graph = fd.blobs.size() + fd.ledge.size() * 4 + fd.seg_g.size() * 12;
     s.bytes_classes = (fd.ec.size() + fd.class_ref.size() + fd.class_len.size() + ctab.size() + fd.wtable.size()) * 4;
     s.bytes_total = s.bytes_table + s.bytes_graph + s.bytes_classes;
@@ -241,6 +241,47 @@ int pa_index_create_multi(const pa_flat_index* flat, const int* devices, int nde
         }
     }
     return PA_OK;
+}
+
+// TEST SURFACE, not part of include/pseudoaligner_amd.h: the dictionary of `flat` as the CPU flattener builds it (device < 0) or as the GPU filler
+// builds it on `device`, `builds` times over from the same uploaded blocks. out[cap bytes] receives the first table, *bytes its size, *dict_pairs its
+// format (DevIndexView::dict_pairs), *differing the number of later builds whose bytes are not the first one's.
+int padbg_dict_table(const pa_flat_index* flat, int device, uint32_t builds, void* out, uint64_t cap, uint64_t* bytes, uint32_t* dict_pairs, uint32_t* differing) {
+    if (!flat || !bytes || !dict_pairs || !differing) return fail(PA_ERR_INVALID_ARG, "null argument");
+    FlatDevice fd;
+    int threads = usable_threads();
+    if (threads < 1) threads = 1;
+    *differing = 0;
+    if (device < 0) {
+        const int rc = flatten_for_device(*flat, threads, fd, /*device_dict=*/false);
+        if (rc != PA_OK) return rc;
+        *bytes = fd.table.size() * 4;
+        *dict_pairs = fd.dict_pairs;
+        if (out && cap >= *bytes) memcpy(out, fd.table.data(), *bytes);
+        return PA_OK;
+    }
+    int rc = use_device(device);
+    if (rc == PA_OK) rc = flatten_for_device(*flat, threads, fd, /*device_dict=*/true);
+    DeviceBuffer<uint8_t> d_blobs;
+    if (rc == PA_OK) rc = upload(d_blobs, fd.blobs);
+    std::vector<uint8_t> again;
+    for (uint32_t i = 0; rc == PA_OK && i < builds; ++i) {
+        DeviceBuffer<uint32_t> d_table;
+        rc = device_fill_index(fd, d_blobs.get(), d_table, &fd.nbuckets, &fd.dict_pairs);
+        if (rc != PA_OK) break;
+        const uint64_t n = dict_table_words(fd.nbuckets, fd.dict_pairs) * 4;
+        if (i == 0) {
+            *bytes = n;
+            *dict_pairs = fd.dict_pairs;
+            if (!out || cap < n) return PA_OK;   // (sizing call)
+            if (hipMemcpy(out, d_table.get(), n, hipMemcpyDeviceToHost) != hipSuccess) return fail(PA_ERR_HIP, "hipMemcpy failed");
+        } else {
+            again.resize(n);
+            if (hipMemcpy(again.data(), d_table.get(), n, hipMemcpyDeviceToHost) != hipSuccess) return fail(PA_ERR_HIP, "hipMemcpy failed");
+            if (n != *bytes || memcmp(again.data(), out, n) != 0) ++*differing;
+        }
+    }
+    return rc;
 }
 
 int pa_index_get_stats(const pa_index* idx, pa_index_stats* stats) {

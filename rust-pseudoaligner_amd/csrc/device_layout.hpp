@@ -21,6 +21,26 @@
 //               (profiles/r05_dict_load.txt). One 16-byte load per probe is also what keeps a table of this size usable at all:
 //               beyond ~4 GB of randomly accessed footprint every load instruction is an address-translation miss, and
 //               several loads per random block then run at a quarter of the rate (profiles/r05_tlb_footprint.txt).
+//               PAIR dictionary (2k <= 48 and fewer than 2^24 - 1 chain blocks; chosen when the index is flattened, DevIndexView::dict_pairs):
+//               npairs = 2^b PAIRS of 16 bytes, two 8-byte ENTRIES each, so that the one 16-byte load of a probe returns two whole
+//               entries and a key misses its home only when three or more keys share it (2 % of the keys at 0.39 keys per pair, 6.8 %
+//               at 0.77, against the 11.5 % of the 16-byte slots). m = pair_mix(key) is a bijection on 48 bits (xor-shift, multiply by an
+//               odd constant mod 2^48, two rounds; pair_unmix is its inverse); the HOME pair is q = m >> (48 - b), the remainder r = the
+//               low 48 - b bits of m (b >= 21: at most 27 bits), b the smallest value with kmers / npairs <= PAIR_LOAD. A key that
+//               finds no room in its home pair lies d pairs further on (wrapping at the end). An entry is one u64:
+//                 bits 0..23  handle (0xFFFFFF = empty)     bits 24..34  the 11 bits of `off` below
+//                 bit  35     entry 0 of a pair only, stored inverted: a key that came through this pair lies further on
+//                 bits 36..63 TAG = r | d << (48 - b): what the key is, seen from the pair the entry lies in. (q, r) <-> m <-> key is one
+//                             to one and q = pair - d, so a tag names ONE key: a hit is exact. The displacement must be part of it —
+//                             without it the carried key (q, r) would answer for the key (q + d, r).
+//               d <= pair_max_disp(b) = min(254, 2^(b - 20) - 2): the lane keeps 8 bits of it, the tag has 28 bits, and the all-ones tag is left to the empty entry
+//               (all ones), so a probe compares tags and nothing else. A pair keeps the two SMALLEST entry words homed to or carried
+//               into it (64-bit atomic minimum on entry 0, what that displaces on entry 1, what that displaces goes on with d + 1);
+//               d is the word's top field, so a key at home is never displaced by a carried one, and the table does not depend on the
+//               order of insertion: the CPU flattener and the GPU filler give the same bytes. The flags are set in a second pass
+//               (atomic AND). A lookup that finds neither entry and no flag has proved the key absent; one that finds the flag goes on
+//               to the next pair in its next step with d + 1 (the lane's probe index and the state bits of l_pending), at most pair_max_disp(b) times. A key further
+//               from home than that makes the builders take the next b.
 //               k > 32 (two-word k-mers): a line holds two whole entries {key word 0..3, handle, off, -, -}, handle
 //               0xFFFFFFFF = empty, load <= 1/3, linear probing over lines (a line with a free entry ends the probe sequence).
 //               What an entry says (both forms): handle = the chain BLOCK the k-mer starts in (below), off = where:
@@ -134,6 +154,48 @@ constexpr uint32_t SLOT_FLAG_SHIFT = 24;           // flags 0..2: slot (home + 1
 constexpr uint32_t SLOT_FLAG_OVERFLOW = 8u;
 constexpr double DICT_LOAD = 0.25;                 // k <= 32: keys per slot the builders aim for (see above)
 constexpr uint32_t DICT_MAX_PROBES = 15;           // buckets a key may overflow through (the builders keep every chain shorter)
+// the pair dictionary (layout above)
+constexpr uint32_t PAIR_KEY_BITS = 48, PAIR_MAX_K = 24;
+constexpr uint32_t PAIR_MIN_LOG2 = 21;             // smallest table: 2^21 pairs = 32 MB (the remainder then has 27 bits)
+constexpr uint32_t PAIR_MAX_LOG2 = 31;
+#ifndef PA_PAIR_LOAD   // A/B builds: -DPA_PAIR_LOAD=0.8 (config 3: 2^27 pairs to begin with)
+#define PA_PAIR_LOAD 0.5
+#endif
+constexpr double PAIR_LOAD = PA_PAIR_LOAD;         // keys per pair the sizing allows (config 3: 2^28 pairs, 0.39 keys per pair)
+constexpr uint32_t PAIR_HANDLE_BITS = 24, PAIR_NO_HANDLE = 0xFFFFFFu, PAIR_OFF_SHIFT = 24, PAIR_OFF_MASK = 0x7FFu;
+constexpr uint32_t PAIR_FLAG_BIT = 35, PAIR_TAG_SHIFT = 36, PAIR_TAG_BITS = 28;
+constexpr uint32_t PAIR_MAX_BLOCKS = PAIR_NO_HANDLE;   // the format holds handles below this
+constexpr uint64_t PAIR_EMPTY = ~0ull, PAIR_KEY_MASK = (1ull << PAIR_KEY_BITS) - 1;
+constexpr uint64_t PAIR_MUL1 = 0x9E3779B1ull, PAIR_MUL2 = 0x85EBCA77ull;   // 32-bit odd constants: two multiply instructions per round
+constexpr uint64_t pair_mul_inverse(uint64_t a) {   // of an odd a mod 2^48 (Newton: each round doubles the correct low bits)
+    uint64_t x = a;
+    for (int i = 0; i < 6; ++i) x *= 2 - a * x;
+    return x & PAIR_KEY_MASK;
+}
+constexpr uint64_t PAIR_INV1 = pair_mul_inverse(PAIR_MUL1), PAIR_INV2 = pair_mul_inverse(PAIR_MUL2);
+PA_HD uint64_t pair_mix(uint64_t x) {     // 48 bits -> 48 bits, one to one
+    x ^= x >> 24;
+    x = (x * PAIR_MUL1) & PAIR_KEY_MASK;
+    x ^= x >> 24;
+    return (x * PAIR_MUL2) & PAIR_KEY_MASK;
+}
+PA_HD uint64_t pair_unmix(uint64_t m) {   // (x ^ x >> 24 undoes itself on 48 bits)
+    m = (m * PAIR_INV2) & PAIR_KEY_MASK;
+    m ^= m >> 24;
+    m = (m * PAIR_INV1) & PAIR_KEY_MASK;
+    return m ^ (m >> 24);
+}
+constexpr uint32_t PAIR_MAX_DISP = 254;            // what a lane remembers of a probe that goes on: 8 bits (lane_steps.hpp, l_disp)
+PA_HD uint32_t pair_max_disp(uint32_t b) { return b >= 28 ? PAIR_MAX_DISP : (1u << (b - 20)) - 2u; }
+PA_HD uint64_t pair_entry(uint32_t tag, uint32_t handle, uint32_t off) {   // (flag not set)
+    return ((uint64_t)tag << PAIR_TAG_SHIFT) | (1ull << PAIR_FLAG_BIT) | ((uint64_t)off << PAIR_OFF_SHIFT) | handle;
+}
+PA_HD uint32_t pair_entry_tag(uint64_t e) { return (uint32_t)(e >> PAIR_TAG_SHIFT); }
+PA_HD uint32_t pair_entry_handle(uint64_t e) { return (uint32_t)e & PAIR_NO_HANDLE; }
+PA_HD uint32_t pair_entry_off(uint64_t e) { return (uint32_t)(e >> PAIR_OFF_SHIFT) & PAIR_OFF_MASK; }
+
+// u32 words of a dictionary of `nbuckets` buckets (64-byte lines) or, pair dictionary, pairs (16 bytes)
+PA_HD uint64_t dict_table_words(uint64_t nbuckets, uint32_t dict_pairs) { return nbuckets * (dict_pairs ? 4u : BUCKET_WORDS); }
 
 struct alignas(16) U4 {
     uint32_t x, y, z, w;
@@ -146,7 +208,7 @@ constexpr uint32_t WT_ENTRIES = 3;   // window-table entries per 64-byte line, 5
 
 struct DevIndexView {
     const uint32_t* table;    // nbuckets * 16 words
-    uint64_t nbuckets;
+    uint64_t nbuckets;        // (pair dictionary: its pairs, 2^dict_pairs — the homes a key can have)
     const uint8_t* blobs;     // chain blocks
     const uint32_t* ledge;    // [8 * blocks]: {block handle, y + 1}[4] by chain handle
     const uint64_t* seg_g;    // [num_nodes] 64 * chain handle + node start, ascending (node traces only)
@@ -164,6 +226,7 @@ struct DevIndexView {
     uint32_t stream_nt;       // 1: the dictionary is larger than the caches — its lines and the read words are loaded non-temporal (lane_steps.hpp, ld_stream)
     uint32_t bitmap_min;      // != 0: every class WITHOUT windows of at least this many ids has a membership bitmap behind its record (class_bitmap)
     uint32_t bitmap_words;    // u32 words of such a bitmap (bit t = transcript t is in the class; two spare words: windows are read as 64 bits)
+    uint32_t dict_pairs;      // pair dictionary: log2 of its pairs; 0: the 16-byte slots (or, k > 32, the two-word table)
 };
 
 // 16-byte chunks of the record of a class of `len` ids ({class id, ids..., padding}: at least two)

@@ -640,6 +640,49 @@ PA_HD void seek_complete2(Lane& s, uint32_t K, const SeekProbe& q0, bool two, co
     if (seek_settle(s, K, q0, two)) return;
     (void)seek_settle(s, K, q1, false);
 }
+// ---- the same probe through the PAIR dictionary (device_layout.hpp: ix.dict_pairs != 0). One 16-byte load returns the two entries of the
+// pair d = l_disp(s) pairs behind the key's home; an entry is the key's when its tag — remainder and d — is the key's. The probe struct
+// is the 16-byte format's: klo = the wanted tag where the high word of an entry holds it, khi = the flag bit if the probe may still go on
+// (d < pair_max_disp), else 0. Nothing of a probe is pending between steps but its displacement.
+// the displacement of a probe that goes on: 8 bits, the probe index (low four) and the four state bits l_pending has in the 16-byte format
+PA_HD uint32_t l_disp(const Lane& s) { return l_probe(s) | (l_pending(s) << 4); }
+PA_HD bool seek_two_pair(const Lane& s, uint32_t K) { return (l_flags(s) & F_SPEC) && l_disp(s) == 0 && l_kp(s) + PA_SEEK_STRIDE <= l_L(s) - K; }
+PA_HD void seek_issue_pair(const Lane& s, const DevIndexView& ix, ReadRef rd, SeekProbe& q, uint32_t ahead = 0, bool live = true) {
+    const uint32_t at = live ? l_kp(s) + ahead : l_kp(s);
+    const uint64_t m = pair_mix(read_window_in(rd, at) & ix.kmask);   // read_seq.get_kmer(kmer_pos) (:93); kmer_pos <= L - K
+    const uint32_t b = ix.dict_pairs, rbits = PAIR_KEY_BITS - b, d = ahead ? 0u : l_disp(s);
+    uint32_t pr = ((uint32_t)(m >> rbits) + d) & ((1u << b) - 1u);
+    if (!live) pr = 0;
+    q.v = ld_stream(reinterpret_cast<const U4*>(ix.table) + pr, (PA_NT & 4) || ix.stream_nt);
+    q.klo = (((uint32_t)m & ((1u << rbits) - 1u)) | (d << rbits)) << (PAIR_TAG_SHIFT - 32);
+    q.khi = d < pair_max_disp(b) ? 1u << (PAIR_FLAG_BIT - 32) : 0u;
+    q.pending = 0;
+}
+PA_HD bool seek_settle_pair(Lane& s, uint32_t K, const SeekProbe& q, bool more) {
+    const uint32_t low = (1u << (PAIR_TAG_SHIFT - 32)) - 1u;
+    const bool h0 = (q.v.y ^ q.klo) <= low, h1 = (q.v.w ^ q.klo) <= low;   // (no entry has the tag of an empty one: no handle to look at)
+    const uint32_t lo = h0 ? q.v.x : q.v.z, hi = h0 ? q.v.y : q.v.w;
+    const uint32_t h = (h0 || h1) ? lo & PAIR_NO_HANDLE : NO_HANDLE, off = ((lo >> PAIR_OFF_SHIFT) | (hi << (32 - PAIR_OFF_SHIFT))) & PAIR_OFF_MASK;
+    const bool full = (~q.v.y & q.khi) != 0;   // a key that came through this pair lies further on, and the probe may follow
+    if (h == NO_HANDLE && full) {              // the next pair in the lane's next step
+        const uint32_t d = l_disp(s) + 1u;
+        s.nc = (s.nc & ~(15u << NC_PROBE_SHIFT)) | ((d & 15u) << NC_PROBE_SHIFT);
+        s.rm = (s.rm & ~SK_MASK) | (d >> 4);
+        return true;
+    }
+    if (!more || h != NO_HANDLE) {
+        seek_finish(s, K, h, off, false, 0u);  // (clears the displacement)
+        return true;
+    }
+    l_set_kp(s, l_kp(s) + PA_SEEK_STRIDE);                          // :110 (kmer_pos + 3 <= L - K: seek_two_pair)
+    s.rm &= ~SK_MASK;
+    s.nc &= ~(15u << NC_PROBE_SHIFT);
+    return false;
+}
+PA_HD void seek_complete2_pair(Lane& s, uint32_t K, const SeekProbe& q0, bool two, const SeekProbe& q1) {
+    if (seek_settle_pair(s, K, q0, two)) return;
+    (void)seek_settle_pair(s, K, q1, false);
+}
 // what a probe found -> the lane's next state (the tail of find_kmer_match and of :118-129). `h` = the chain block the k-mer
 // starts in, `off` = the entry's second word (device_layout.hpp: position in the block, first-k-mer-of-its-node flag, blocks
 // before this one in the chain)
@@ -704,7 +747,7 @@ PA_HD void seek_complete_k2(Lane& s, uint32_t K, const SeekProbe2& q) {
                h1 = q.k1.x == q.w0 && q.k1.y == q.w1 && q.k1.z == q.w2 && q.k1.w == q.w3 && q.v1.x != NO_HANDLE;
     seek_finish(s, K, h0 ? q.v0.x : h1 ? q.v1.x : NO_HANDLE, h0 ? q.v0.y : q.v1.y, q.v0.x != NO_HANDLE && q.v1.x != NO_HANDLE, l_probe(s));
 }
-PA_HD void seek_step(Lane& s, const DevIndexView& ix, ReadRef rd) {
+PA_HD void seek_step_slots(Lane& s, const DevIndexView& ix, ReadRef rd) {   // the 16-byte slots, or (K > 32) the two-word table
     const uint32_t K = ix.k;
     if (K > 32) {
         SeekProbe2 q2;
@@ -717,6 +760,18 @@ PA_HD void seek_step(Lane& s, const DevIndexView& ix, ReadRef rd) {
     seek_issue(s, ix, rd, q);
     seek_issue(s, ix, rd, q1, PA_SEEK_STRIDE, two);
     seek_complete2(s, K, q, two, q1);
+}
+PA_HD void seek_step_pair(Lane& s, const DevIndexView& ix, ReadRef rd) {   // the same step through the pair dictionary
+    SeekProbe q, q1;
+    const bool two = seek_two_pair(s, ix.k);
+    seek_issue_pair(s, ix, rd, q);
+    seek_issue_pair(s, ix, rd, q1, PA_SEEK_STRIDE, two);
+    seek_complete2_pair(s, ix.k, q, two, q1);
+}
+// whichever dictionary the index has (the host emulator, tools/chain_stats; the kernel knows the format as a template parameter)
+PA_HD void seek_step(Lane& s, const DevIndexView& ix, ReadRef rd) {
+    if (ix.dict_pairs) seek_step_pair(s, ix, rd);
+    else seek_step_slots(s, ix, rd);
 }
 #endif   // PA_LS_LANE
 

@@ -71,7 +71,7 @@ __device__ __forceinline__ DevIndexView view_of(karg_ptr p) {   // member-wise: 
     DevIndexView v;
     v.table = p->ix.table; v.nbuckets = p->ix.nbuckets; v.blobs = p->ix.blobs; v.ledge = p->ix.ledge;
     v.seg_g = p->ix.seg_g; v.seg_nid = p->ix.seg_nid; v.ec = p->ix.ec; v.class_ref = p->ix.class_ref; v.class_len = p->ix.class_len;
-    v.wtable = p->ix.wtable; v.wbuckets = p->ix.wbuckets; v.kmask = p->ix.kmask; v.kmask_hi = p->ix.kmask_hi; v.k = p->ix.k; v.num_nodes = p->ix.num_nodes; v.num_classes = p->ix.num_classes; v.num_segs = p->ix.num_segs; v.stream_nt = p->ix.stream_nt; v.bitmap_min = p->ix.bitmap_min; v.bitmap_words = p->ix.bitmap_words;
+    v.wtable = p->ix.wtable; v.wbuckets = p->ix.wbuckets; v.kmask = p->ix.kmask; v.kmask_hi = p->ix.kmask_hi; v.k = p->ix.k; v.num_nodes = p->ix.num_nodes; v.num_classes = p->ix.num_classes; v.num_segs = p->ix.num_segs; v.stream_nt = p->ix.stream_nt; v.bitmap_min = p->ix.bitmap_min; v.bitmap_words = p->ix.bitmap_words; v.dict_pairs = p->ix.dict_pairs;
     return v;
 }
 
@@ -302,15 +302,22 @@ static int launch_kernel(K kernel, const MapParams& p, uint32_t grid, size_t lds
 
 int launch_map_pool(const MapParams& p, uint32_t grid, size_t lds_bytes, hipStream_t stream) {
     const bool gread = p.wpr > PA_LDS_READ_WORDS;   // the read stays in its HBM tile: the wide lane state (lane_steps.hpp), reads of up to PA_MAX_READ_LEN bases
+    const bool pair = p.ix.dict_pairs != 0;         // the pair dictionary: a template parameter of every instantiation (the 16-byte ones keep their text)
+    if (gread && pair) return p.trace ? launch_kernel(&wide::pa_map_pool_kernel<true, true, false, false, false, true>, p, grid, lds_bytes, stream)
+                                      : launch_kernel(&wide::pa_map_pool_kernel<false, true, false, false, false, true>, p, grid, lds_bytes, stream);
     if (gread) return p.trace ? launch_kernel(&wide::pa_map_pool_kernel<true, true, false, false>, p, grid, lds_bytes, stream)
                               : launch_kernel(&wide::pa_map_pool_kernel<false, true, false, false>, p, grid, lds_bytes, stream);
-    if (p.trace) return launch_kernel(&narrow::pa_map_pool_kernel<true, false, false, false>, p, grid, lds_bytes, stream);
+    if (p.trace) return pair ? launch_kernel(&narrow::pa_map_pool_kernel<true, false, false, false, false, true>, p, grid, lds_bytes, stream)
+                             : launch_kernel(&narrow::pa_map_pool_kernel<true, false, false, false>, p, grid, lds_bytes, stream);
 #ifdef PA_DEBUG_KNOBS   // the statistics / ablation instantiation exists in A/B builds only
-    if (p.dbg || p.ablate) return launch_kernel(&narrow::pa_map_pool_kernel<false, false, true, false>, p, grid, lds_bytes, stream);
+    if (p.dbg || p.ablate) return pair ? launch_kernel(&narrow::pa_map_pool_kernel<false, false, true, false, false, true>, p, grid, lds_bytes, stream)
+                                       : launch_kernel(&narrow::pa_map_pool_kernel<false, false, true, false>, p, grid, lds_bytes, stream);
 #endif
     if (p.ix.k > 32)   // two-word k-mers: their probes ride in forward iterations through the two-word dictionary's own issue / complete pair
         return p.pool_slots == 128 ? launch_kernel(&narrow::pa_map_pool_kernel<false, false, false, true, true>, p, grid, lds_bytes, stream)
                                    : launch_kernel(&narrow::pa_map_pool_kernel<false, false, false, false, true>, p, grid, lds_bytes, stream);
+    if (pair) return p.pool_slots == 128 ? launch_kernel(&narrow::pa_map_pool_kernel<false, false, false, true, false, true>, p, grid, lds_bytes, stream)
+                                         : launch_kernel(&narrow::pa_map_pool_kernel<false, false, false, false, false, true>, p, grid, lds_bytes, stream);
     if (p.pool_slots == 128) return launch_kernel(&narrow::pa_map_pool_kernel<false, false, false, true>, p, grid, lds_bytes, stream);
     return launch_kernel(&narrow::pa_map_pool_kernel<false, false, false, false>, p, grid, lds_bytes, stream);
 }

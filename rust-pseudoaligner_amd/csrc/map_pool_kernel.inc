@@ -126,7 +126,8 @@ constexpr uint32_t SLOT_FIXED_BYTES = 32 + 16 + 8 + (PA_K_WIDE ? 16 : 0);   // l
 // S128: the pool has 128 slots per wave (reads of up to 5 words: every short-read batch) — the stride of the LDS rows of read words is
 // then a shift instead of a multiply in every step that touches the read (and the compiler keeps fewer scalars: 16 spilled instead of 26).
 // KBIG: the index has two-word k-mers (K > 32) — the probe half of a dual iteration is then the two-word dictionary's (seek_issue_k2)
-template <bool TRACE, bool GREAD, bool DBG, bool S128 = false, bool KBIG = false>
+// PAIR: the index has the pair dictionary (K <= 24: device_layout.hpp) — the probe half is then seek_issue_pair / seek_complete2_pair
+template <bool TRACE, bool GREAD, bool DBG, bool S128 = false, bool KBIG = false, bool PAIR = false>
 __global__ __launch_bounds__(PA_MAP_BLOCK, PA_MAP_MIN_BLOCKS) void pa_map_pool_kernel(const MapParams p_arg) {
     // The ~50 words of parameters are NOT kept in registers across the loop (the allocator would spill most of them to
     // VGPR lanes and pay a v_readlane + hazard nops at every use): each iteration re-reads what its step needs from the
@@ -325,7 +326,10 @@ __global__ __launch_bounds__(PA_MAP_BLOCK, PA_MAP_MIN_BLOCKS) void pa_map_pool_k
             if (active) refill_slot<GREAD>(s, next + lane, slot, kp, rd, wc, S, wpr, K);
             next += n;
         } else if (sel == ST_SEEK) {
-            if (active) seek_step(s, ix, rr);
+            if (active) {
+                if (PAIR) seek_step_pair(s, ix, rr);
+                else seek_step_slots(s, ix, rr);
+            }
         } else if (sel == ST_FWD) {
             // One text for the plain forward step and the DUAL iteration (n2 = 0: the probe half runs on all-zero states and is
             // thrown away). Straight-line issue: every lane executes every load (a lane without a slot carries an all-zero state:
@@ -363,15 +367,17 @@ __global__ __launch_bounds__(PA_MAP_BLOCK, PA_MAP_MIN_BLOCKS) void pa_map_pool_k
                 pq2.k0 = pq2.v0 = pq2.k1 = pq2.v1 = U4{0u, 0u, 0u, 0u}; pq2.v0.x = pq2.v1.x = NO_HANDLE; pq2.w0 = pq2.w1 = pq2.w2 = pq2.w3 = 0;
                 if (n2) seek_issue_k2(s2, ix, rr2, pq2);                // the k-mer's line of the two-word dictionary: four 16-byte loads of one line
             }
-            if (!KBIG && n2) seek_issue(s2, ix, rr2, pq);              // one slot of the k-mer's bucket (HBM); (n2: wave-uniform — a plain forward step skips the probe half)
+            if (PAIR && n2) seek_issue_pair(s2, ix, rr2, pq);          // the two entries of the k-mer's pair (HBM)
+            if (!KBIG && !PAIR && n2) seek_issue(s2, ix, rr2, pq);     // one slot of the k-mer's bucket (HBM); (n2: wave-uniform — a plain forward step skips the probe half)
             // a lane whose scan is past a miss probes the next position of the scan as well (another line, in flight together)
             // (only in steps where at least eight lanes do: the second k-mer and hash are the whole wave's instructions)
-            const bool two_l = !KBIG && active2 && seek_two(s2, K);
+            const bool two_l = !KBIG && active2 && (PAIR ? seek_two_pair(s2, K) : seek_two(s2, K));
             const bool pairs = __popcll(__ballot(two_l)) >= 8;
             const bool two = two_l && pairs;
             SeekProbe pq1;
             pq1.klo = pq1.khi = pq1.pending = 0; pq1.v = U4{0u, 0u, NO_HANDLE, 0u};
-            if (pairs) seek_issue(s2, ix, rr2, pq1, PA_SEEK_STRIDE, two);   // (a wave-uniform branch: the waits behind it stay exact)
+            if (PAIR && pairs) seek_issue_pair(s2, ix, rr2, pq1, PA_SEEK_STRIDE, two);
+            if (!PAIR && pairs) seek_issue(s2, ix, rr2, pq1, PA_SEEK_STRIDE, two);   // (a wave-uniform branch: the waits behind it stay exact)
             fwd_issue(s, ix, fl);                                      // node header + sequence words (MALL / L2)
             __builtin_amdgcn_sched_barrier(0);                         // (left alone the scheduler finishes the probe first and only then issues the node loads)
             PA_MARK("dual_issued");
@@ -379,6 +385,7 @@ __global__ __launch_bounds__(PA_MAP_BLOCK, PA_MAP_MIN_BLOCKS) void pa_map_pool_k
             // not in the slot looked at costs the lane another step: lane_steps.hpp), and its registers are free before the forward half computes
             if (active2) {
                 if (KBIG) seek_complete_k2(s2, K, pq2);
+                else if (PAIR) seek_complete2_pair(s2, K, pq, two, pq1);
                 else seek_complete2(s2, K, pq, two, pq1);
                 nq2 = queue_of(s2, K);   // (may rewrite the state: before the store)
                 lane_store(s2, stA, stB, stC, slot2);

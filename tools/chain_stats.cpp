@@ -130,6 +130,22 @@ int main(int argc, char** argv) {
     }
     printf("index: %u nodes (%llu with one right extension), %u chains, %zu blocks (%.1f MB), %u classes\n", f.num_nodes, (unsigned long long)mergeable,
            fd.num_chains, fd.blobs.size() / CH_BLOCK, fd.blobs.size() / 1e6, f.num_classes);
+    if (fd.dict_pairs) {   // the pair dictionary: where its keys lie (device_layout.hpp: a tag's displacement field)
+        const uint64_t* e = reinterpret_cast<const uint64_t*>(fd.table.data());
+        const uint64_t n = 2ull << fd.dict_pairs;
+        uint64_t keys = 0, off_home = 0;
+        uint32_t furthest = 0;
+        for (uint64_t i = 0; i < n; ++i) {
+            if (e[i] == PAIR_EMPTY) continue;
+            const uint32_t d = pair_entry_tag(e[i]) >> (PAIR_KEY_BITS - fd.dict_pairs);
+            ++keys;
+            off_home += d != 0;
+            furthest = std::max(furthest, d);
+        }
+        printf("pair dictionary: 2^%u pairs (%.2f GB), %.3f keys per pair, %llu of %llu keys off their home pair (%.2f %%), the furthest %u pairs on\n", fd.dict_pairs,
+               16.0 * (double)(1ull << fd.dict_pairs) / 1e9, (double)keys / (double)(1ull << fd.dict_pairs), (unsigned long long)off_home, (unsigned long long)keys,
+               100.0 * (double)off_home / (double)keys, furthest);
+    }
     // slot use per block
     {
         uint64_t hist[5] = {0, 0, 0, 0, 0};
