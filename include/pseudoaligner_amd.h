@@ -592,7 +592,7 @@ int pa_write_bus(pa_index* idx, const pa_host_index* h, const char* r1_path, con
  *              A BUS record never holds an N (pa_bus drops such reads), so the cell counter's rule for one N has no counterpart here
  *   output     every surviving record carries its target barcode; records that now share (barcode, UMI, ec) become one whose count is the
  *              64-bit sum clamped at 2^32 - 1 (pa_bus_finish's rule); strictly ascending by (barcode, UMI, ec), flags = pad = 0. The ec
- *              table is untouched: an ec that no longer occurs stays in matrix.ec, as with bustools. There is NO UMI correction
+ *              table is untouched: an ec that no longer occurs stays in matrix.ec, as with bustools. UMIs are not touched here: that is pa_bus_umi_correct, below
  *   stats[PA_BUS_CORRECT_STATS]: [0] records in, [1] reads in (the sum of the counts, u64), [2] distinct barcodes in, [3] barcodes exact,
  *              [4] barcodes corrected, [5] barcodes without a neighbour, [6] barcodes ambiguous, [7] records of exact barcodes, [8] records
  *              of corrected barcodes, [9] records dropped, [10] reads dropped, [11] records out, [12] distinct barcodes out;
@@ -713,7 +713,7 @@ int pa_write_bus_called(pa_index* idx, const pa_host_index* h, const char* r1_pa
  *   G(e)       the gene set of an ec: the ascending distinct tx_gene[t] over t in e (an ec without ids: the empty set)
  *   molecule   a maximal run of records with equal (barcode, UMI). Its gene set is the intersection of G(e) over its records. An empty
  *              intersection drops the molecule (stats[2]). A molecule counts 1 whatever its records' read counts. There is NO barcode
- *              or UMI correction here: that is bustools correct's job, or the cell counter's
+ *              or UMI correction here: those are pa_bus_correct's and pa_bus_umi_correct's steps, ahead of this one
  *   cell       a distinct barcode with at least one kept molecule; cells are numbered in ascending barcode value
  *   rows       of a cell: the distinct gene sets S of its molecules, each with n_S = its molecules. u_g = n_{{g}} (the singleton
  *              rows); the multi rows are those with |S| >= 2; E = the union of the multi rows; M = sum of n_S over the multi rows
@@ -789,6 +789,70 @@ int  pa_count_cells_em_called(pa_index* idx, const pa_host_index* h, const char*
                               uint32_t bc_len, uint32_t umi_len, const pa_knee_params* kp, const pa_genes_params* p, const char* out_dir,
                               int num_threads, uint64_t genes_stats[PA_GENES_STATS], uint64_t correct_stats[PA_BUS_CORRECT_STATS],
                               uint64_t knee_stats[PA_KNEE_STATS]);
+
+/* ---------------- UMI correction on BUS records, ahead of the gene counter ----------------
+ * The `bustools umicorrect` / Cell Ranger / STARsolo 1MM step on the records where they lie: a UMI that is one substitution away from a
+ * better-supported UMI of the same barcode and can be the same molecule (their gene sets meet) is taken for a sequencing error of it.
+ *   input      as for pa_genes_create: n records STRICTLY ascending by (barcode, UMI, ec), the ec table as a CSR, tx_gene[num_tx] < num_genes,
+ *              bc_len / umi_len within pa_bus_create's limits
+ *   molecule   a maximal run of records with equal (barcode, UMI). n(m) = the u64 sum of its records' counts, not clamped. S(m) = the
+ *              intersection of G(e) over its records (pa_genes_*'s definition, above). A molecule with empty S is INERT: it never moves and is
+ *              nobody's target; the gene stage drops it as before
+ *   neighbours of m = (b, u): the non-inert molecules (b, v) of the SAME barcode with v different from u in exactly one of the umi_len bases and
+ *              S(m) and S(v) sharing a gene
+ *   PA_UMI_GREATEST (0, default; the cell counter's wording)  m moves to the greatest of {m} and its neighbours in the order (n, UMI value). One
+ *              step, not transitive: every decision is taken on the input state. Every move goes to a strictly greater (n, UMI), so there are
+ *              no swaps and no cycles
+ *   PA_UMI_DIRECTIONAL (1)  the same, but a neighbour v is eligible only if n(v) >= 2 n(m) - 1 (UMI-tools' directional threshold, evaluated
+ *              without overflow). Still one step
+ *   output     every record of a moved molecule carries its target's UMI; records that now share (barcode, UMI, ec) become one whose count is
+ *              the 64-bit sum clamped at 2^32 - 1; strictly ascending by (barcode, UMI, ec), flags = pad = 0. The ec table is untouched. When
+ *              u moves to v and v moves to w, u's records end under v and v's own under w: targets are not followed. A second call may
+ *              therefore move molecules again; the step is not idempotent
+ *   purity     the result is a pure function of (records, tables, mode): two runs give the same bytes, and a barcode's output records depend
+ *              on that barcode's input records alone
+ *   stats[PA_BUS_UMI_STATS]: [0] records in, [1] reads in (the u64 sum of the counts), [2] molecules in, [3] distinct barcodes, [4] inert
+ *              molecules, [5] non-inert molecules with any UMI at one substitution present in their barcode (inert or not), [6] molecules with
+ *              at least one neighbour, [7] molecules moved, [8] molecules moved onto a molecule that itself moved, [9] records rewritten (the
+ *              records of moved molecules), [10] reads moved (the sum of n over the moved molecules), [11] records out, [12] molecules out,
+ *              [13] molecules of the largest barcode, [14] barcodes that took the HBM variant of the search;
+ *              [7] <= [6] <= [5] <= [2] - [4], [11] <= [0], [12] <= [2]
+ *   errors     pa_genes_create's checks in pa_genes_create's order, the mode standing where the gene counter checks its params: an unknown mode,
+ *              bc_len / umi_len outside pa_bus_create's limits, tx_gene[t] >= num_genes, an ec id >= num_tx or not ascending:
+ *              PA_ERR_INVALID_ARG; more than 2^31 - 1 records: PA_ERR_UNSUPPORTED; then the records: not strictly ascending, a barcode >=
+ *              4^bc_len or a UMI >= 4^umi_len (pa_bus_correct_records' messages), an ec outside [0, n_ecs): PA_ERR_INVALID_ARG naming the
+ *              first offending record. Every host argument is checked before any device call; without a GPU a valid call returns
+ *              PA_ERR_NO_DEVICE (before idx is looked at). n = 0 is legal. out NULL: only *n_out and the stats; cap < *n_out:
+ *              PA_ERR_BUFFER_TOO_SMALL (*n_out is set). stats may be NULL
+ * pa_bus_umi_correct: in place on a finished writer (PA_ERR_INVALID_ARG before pa_bus_finish) with the writer's ec table and pa_bus_correct's
+ * guarantees: the new records are built beside the old ones, a failing call (a tx_gene entry >= num_genes, for one) leaves the writer as it
+ * was; afterwards pa_bus_records, pa_bus_write, pa_bus_knee, pa_genes_create_from_bus, a second pa_bus_finish and pa_bus_stats[7] see the
+ * corrected records. tx_gene[the index's transcripts].
+ * pa_bus_umi_correct_phase_ms: the GPU milliseconds of this thread's last UMI correction: [0] molecule table (heads, n, S), [1] neighbour
+ * search, [2] rewrite + sort + collapse + records, [3] stats.
+ * pa_write_bus_umi / pa_count_cells_em_umi: the one file-level entry per output that takes every record step. The barcode steps run exactly as
+ * pa_write_bus / _corrected / _called (pa_count_cells_em / ...) run them for that (whitelist_path, call_cells) pair: whitelist_path may be NULL,
+ * call_cells 0 skips cell calling (kp is then ignored; NULL kp = the defaults). Then pa_bus_umi_correct(umi_mode) with pa_host_index_genes(h),
+ * always the last of the record steps, then the files or the gene stage. barcode_ranks.tsv therefore shows molecule counts BEFORE UMI
+ * correction. An unknown umi_mode is refused before a read is mapped. Stage seconds [4] include the UMI correction. The stats of a step that
+ * did not run are left untouched; each may be NULL; bus_stats[7] is the number of records written. */
+#define PA_UMI_GREATEST 0
+#define PA_UMI_DIRECTIONAL 1
+#define PA_BUS_UMI_STATS 15
+#define PA_BUS_UMI_PHASES 4   /* [0] molecule table (heads, n, S), [1] neighbour search, [2] rewrite + sort + collapse + records, [3] stats */
+int pa_bus_umi_correct_records(pa_index* idx, const pa_bus_record* in, uint64_t n, const uint64_t* ec_offsets, const uint32_t* ec_ids,
+                               uint32_t n_ecs, uint32_t num_tx, const uint32_t* tx_gene, uint32_t num_genes, uint32_t bc_len, uint32_t umi_len,
+                               uint32_t mode, pa_bus_record* out, uint64_t cap, uint64_t* n_out, uint64_t stats[PA_BUS_UMI_STATS]);
+int pa_bus_umi_correct(pa_bus* finished, const uint32_t* tx_gene, uint32_t num_genes, uint32_t mode, uint64_t stats[PA_BUS_UMI_STATS]);
+int pa_bus_umi_correct_phase_ms(float out[PA_BUS_UMI_PHASES]);
+int pa_write_bus_umi(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const char* whitelist_path, uint32_t bc_len,
+                     uint32_t umi_len, int call_cells, const pa_knee_params* kp, uint32_t umi_mode, const char* out_dir, int num_threads,
+                     uint64_t bus_stats[PA_BUS_STATS], uint64_t correct_stats[PA_BUS_CORRECT_STATS], uint64_t knee_stats[PA_KNEE_STATS],
+                     uint64_t umi_stats[PA_BUS_UMI_STATS]);
+int pa_count_cells_em_umi(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const char* whitelist_path,
+                          uint32_t bc_len, uint32_t umi_len, int call_cells, const pa_knee_params* kp, uint32_t umi_mode, const pa_genes_params* p,
+                          const char* out_dir, int num_threads, uint64_t genes_stats[PA_GENES_STATS],
+                          uint64_t correct_stats[PA_BUS_CORRECT_STATS], uint64_t knee_stats[PA_KNEE_STATS], uint64_t umi_stats[PA_BUS_UMI_STATS]);
 
 /* ---------------- transcript abundances: EM over the class-count table (bulk RNA-seq) ----------------
  * The reference stops at equivalence classes; this is the standard abundance model over them (the EM of kallisto / salmon) on the

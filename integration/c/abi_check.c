@@ -220,6 +220,33 @@ int main(int argc, char** argv) {
         EXPECT(pa_count_cells_em_corrected(NULL, h, fastq, fastq, path, 4, 4, NULL, dir, 1, NULL, cst13) == PA_ERR_INVALID_ARG);
     }
 
+    {   /* UMI correction on BUS records, host side: every refusal that comes before a device call */
+        uint64_t ust[PA_BUS_UMI_STATS], un = 7;
+        float ums[PA_BUS_UMI_PHASES];
+        const uint64_t uoff[3] = {0, 1, 2};
+        const uint32_t uids[2] = {0, 1}, utg[2] = {0, 1}, utg_bad[2] = {0, 2};
+        const pa_bus_record urec[3] = {{27, 0, 0, 5, 0, 0}, {27, 1, 0, 1, 0, 0}, {27, 4, 1, 1, 0, 0}};
+        pa_bus_record ubad[3], uout[3];
+        EXPECT(PA_BUS_UMI_STATS == 15 && PA_BUS_UMI_PHASES == 4 && PA_UMI_GREATEST == 0 && PA_UMI_DIRECTIONAL == 1);
+        EXPECT(pa_bus_umi_correct_records(NULL, urec, 3, uoff, uids, 2, 2, utg, 2, 4, 4, PA_UMI_GREATEST, uout, 3, NULL, ust) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_bus_umi_correct_records(NULL, urec, 3, uoff, uids, 2, 2, utg, 2, 4, 4, 2, uout, 3, &un, ust) == PA_ERR_INVALID_ARG && un == 0 && strstr(pa_last_error(), "mode 2"));
+        EXPECT(pa_bus_umi_correct_records(NULL, urec, 3, uoff, uids, 2, 2, utg, 2, 17, 16, PA_UMI_GREATEST, uout, 3, &un, ust) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_bus_umi_correct_records(NULL, urec, 3, uoff, uids, 2, 2, utg_bad, 2, 4, 4, PA_UMI_GREATEST, uout, 3, &un, ust) == PA_ERR_INVALID_ARG && strstr(pa_last_error(), "tx_gene[1]"));
+        EXPECT(pa_bus_umi_correct_records(NULL, urec, 1ull << 31, uoff, uids, 2, 2, utg, 2, 4, 4, PA_UMI_DIRECTIONAL, uout, 3, &un, ust) == PA_ERR_UNSUPPORTED);
+        memcpy(ubad, urec, sizeof ubad);
+        ubad[2].ec = 2;   /* no ec of the table */
+        EXPECT(pa_bus_umi_correct_records(NULL, ubad, 3, uoff, uids, 2, 2, utg, 2, 4, 4, PA_UMI_GREATEST, uout, 3, &un, ust) == PA_ERR_INVALID_ARG && strstr(pa_last_error(), "record 2"));
+        ubad[2].ec = 1;
+        ubad[1].umi = 256;   /* no UMI of 4 bases */
+        EXPECT(pa_bus_umi_correct_records(NULL, ubad, 3, uoff, uids, 2, 2, utg, 2, 4, 4, PA_UMI_GREATEST, uout, 3, &un, ust) == PA_ERR_INVALID_ARG && strstr(pa_last_error(), "record 1"));
+        EXPECT(pa_bus_umi_correct_records(NULL, urec, 3, uoff, uids, 2, 2, utg, 2, 4, 4, PA_UMI_DIRECTIONAL, uout, 3, &un, ust) == (ndev < 1 ? PA_ERR_NO_DEVICE : PA_ERR_INVALID_ARG) &&
+               un == 0);
+        EXPECT(pa_bus_umi_correct(NULL, utg, 2, PA_UMI_GREATEST, ust) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_bus_umi_correct_phase_ms(NULL) == PA_ERR_INVALID_ARG && pa_bus_umi_correct_phase_ms(ums) == PA_OK);
+        EXPECT(pa_write_bus_umi(NULL, h, fastq, fastq, NULL, 4, 4, 0, NULL, PA_UMI_GREATEST, dir, 1, NULL, NULL, NULL, ust) == PA_ERR_INVALID_ARG);
+        EXPECT(pa_count_cells_em_umi(NULL, h, fastq, fastq, NULL, 4, 4, 0, NULL, PA_UMI_GREATEST, NULL, dir, 1, NULL, NULL, NULL, ust) == PA_ERR_INVALID_ARG);
+    }
+
     {   /* cell calling on BUS records, host side: the defaults, the TSV writer, and every refusal that comes before a device call */
         pa_knee_params kp, kbad;
         uint64_t kst[PA_KNEE_STATS], pst[PA_BUS_KEEP_STATS], knr = 7, knc = 7, kn = 7;
@@ -781,6 +808,32 @@ int main(int argc, char** argv) {
                     EXPECT(pa_write_bus_called(idx, h, fastq, fastq, NULL, 4, 4, &kp, dir, 2, bst, cst13, kst) == PA_ERR_FORMAT && strstr(pa_last_error(), "threshold of 1000000"));
                     snprintf(path, sizeof path, "%s/barcode_ranks.tsv", dir);
                     EXPECT(remove(path) == 0);   /* (the two calls that went through wrote it) */
+                }
+                {   /* UMI correction: AAAC joins AAAA (one base apart, one gene), AACA has another gene and stays; then the file-level entries */
+                    const uint64_t uoff[3] = {0, 1, 2};
+                    const uint32_t uids[2] = {0, 1}, utg[2] = {0, 1};
+                    const pa_bus_record urec[3] = {{27, 0, 0, 5, 0, 0}, {27, 1, 0, 1, 0, 0}, {27, 4, 1, 1, 0, 0}};
+                    const uint64_t uwant[PA_BUS_UMI_STATS] = {3, 7, 3, 1, 0, 3, 2, 1, 0, 1, 1, 2, 2, 3, 0};
+                    pa_bus_record uout[3];
+                    pa_knee_params kp;
+                    uint64_t un = 0, ust[PA_BUS_UMI_STATS], cst13[PA_BUS_CORRECT_STATS], kst[PA_KNEE_STATS], gst[PA_GENES_STATS];
+                    float ums[PA_BUS_UMI_PHASES];
+                    EXPECT(pa_bus_umi_correct_records(idx, urec, 3, uoff, uids, 2, 2, utg, 2, 4, 4, PA_UMI_GREATEST, uout, 1, &un, ust) == PA_ERR_BUFFER_TOO_SMALL && un == 2);
+                    EXPECT(pa_bus_umi_correct_records(idx, urec, 3, uoff, uids, 2, 2, utg, 2, 4, 4, PA_UMI_GREATEST, uout, 3, &un, ust) == PA_OK && un == 2);
+                    EXPECT(uout[0].umi == 0 && uout[0].count == 6 && uout[1].umi == 4 && uout[1].ec == 1 && uout[1].count == 1 && uout[1].flags == 0);
+                    EXPECT(memcmp(ust, uwant, sizeof ust) == 0);
+                    EXPECT(pa_bus_umi_correct_records(idx, urec, 3, uoff, uids, 2, 2, utg, 2, 4, 4, PA_UMI_DIRECTIONAL, uout, 3, &un, ust) == PA_OK && un == 2 && ust[7] == 1);
+                    EXPECT(pa_bus_umi_correct_phase_ms(ums) == PA_OK && ums[1] >= 0.0f);
+                    EXPECT(pa_write_bus_umi(idx, h, fastq, fastq, NULL, 4, 4, 0, NULL, PA_UMI_GREATEST, dir, 2, bst, cst13, kst, ust) == PA_OK && bst[0] == nreads && ust[11] == bst[7] &&
+                           ust[7] <= ust[6] && ust[6] <= ust[5] && ust[5] <= ust[2] - ust[4]);
+                    EXPECT(pa_write_bus_umi(idx, h, fastq, fastq, NULL, 4, 4, 0, NULL, 2, dir, 2, bst, cst13, kst, ust) == PA_ERR_INVALID_ARG);
+                    pa_knee_default_params(&kp);
+                    kp.mode = PA_KNEE_MIN;
+                    snprintf(path, sizeof path, "%s/abi_check_whitelist.txt", dir);
+                    EXPECT(pa_count_cells_em_umi(idx, h, fastq, fastq, path, 4, 4, 1, &kp, PA_UMI_DIRECTIONAL, NULL, dir, 2, gst, cst13, kst, ust) == PA_OK && gst[0] == ust[11] &&
+                           ust[0] <= kst[0] && kst[0] == cst13[11]);
+                    snprintf(path, sizeof path, "%s/barcode_ranks.tsv", dir);
+                    EXPECT(remove(path) == 0);
                 }
             }
             free(mc); free(mg); free(mu); free(r1); free(r1o);

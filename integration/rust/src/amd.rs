@@ -1,4 +1,4 @@
-//! Exporter + drop-in `process_reads` for the reference crate. Add `mod amd_ffi; mod amd;` to src/lib.rs (and `mod amd_pairs_ffi;` for `map_pairs`, `mod amd_strands_ffi;` for `map_pairs_unstranded`, `mod amd_bgzf_ffi;` for `bgzf_members`, `mod amd_bus_ffi;` for `write_bus`, `mod amd_genes_ffi;` for `count_cells_em`, `mod amd_correct_ffi;` for `write_bus_corrected` / `count_cells_em_corrected`, `mod amd_knee_ffi;` for `bus_knee` / `write_bus_called` / `count_cells_em_called`).
+//! Exporter + drop-in `process_reads` for the reference crate. Add `mod amd_ffi; mod amd;` to src/lib.rs (and `mod amd_pairs_ffi;` for `map_pairs`, `mod amd_strands_ffi;` for `map_pairs_unstranded`, `mod amd_bgzf_ffi;` for `bgzf_members`, `mod amd_bus_ffi;` for `write_bus`, `mod amd_genes_ffi;` for `count_cells_em`, `mod amd_correct_ffi;` for `write_bus_corrected` / `count_cells_em_corrected`, `mod amd_knee_ffi;` for `bus_knee` / `write_bus_called` / `count_cells_em_called`, `mod amd_umi_ffi;` for `bus_umi_correct` / `write_bus_umi` / `count_cells_em_umi`).
 //! The exporter only reads `pub` fields of `Pseudoaligner<K>` (src/pseudoaligner.rs:27-33); `dbg_index` (the boomphf MPHF,
 //! :30) is not exported: every hit is verified against the node sequence (:99-107), which makes it an exact dictionary that
 //! the library rebuilds. Not compiled in the image of this repository (no rustc): kept in step with
@@ -551,6 +551,109 @@ pub fn count_cells_em_called<P: AsRef<Path>>(index_file: P, r1_fastq: P, r2_fast
                                                stats.as_mut_ptr(), cstats.as_mut_ptr(), kstats.as_mut_ptr()) };
     }
     let result = check(rc).map(|_| (stats, cstats, kstats));   // (the message is read before the handles go)
+    unsafe {
+        if !idx.is_null() { pa_index_destroy(idx); }
+        pa_host_index_destroy(h);
+    }
+    result
+}
+
+/// The UMI correction on host records (pa_bus_umi_correct_records): `records` strictly ascending by (barcode, UMI, ec), the ec table as a CSR,
+/// `tx_gene[num_tx] < num_genes`, on the GPU of the index loaded from `index_file`. One step: a molecule moves to the best-supported molecule of
+/// its barcode whose UMI is one substitution away and whose gene set meets its own (`mode`: PA_UMI_GREATEST or PA_UMI_DIRECTIONAL). Returns the
+/// corrected records, collapsed and sorted again, and PA_BUS_UMI_STATS.
+pub fn bus_umi_correct<P: AsRef<Path>>(index_file: P, records: &[crate::amd_bus_ffi::PaBusRecord], ec_offsets: &[u64], ec_ids: &[u32], tx_gene: &[u32],
+                                       num_genes: u32, bc_len: u32, umi_len: u32, mode: u32,
+                                       device: i32) -> Result<(Vec<crate::amd_bus_ffi::PaBusRecord>, [u64; crate::amd_umi_ffi::PA_BUS_UMI_STATS]), Error> {
+    use crate::amd_umi_ffi::*;
+    let ix = CString::new(index_file.as_ref().to_string_lossy().into_owned())?;
+    let mut h = std::ptr::null_mut();
+    check(unsafe { pa_host_index_load(ix.as_ptr(), &mut h) })?;
+    let mut view: PaFlatIndex = unsafe { std::mem::zeroed() };
+    let mut idx = std::ptr::null_mut();
+    let mut rc = unsafe { pa_host_index_view(h, &mut view) };
+    if rc >= 0 { rc = unsafe { pa_index_create(&view, device, &mut idx) }; }
+    let mut out: Vec<crate::amd_bus_ffi::PaBusRecord> = Vec::with_capacity(records.len().max(1));
+    let (mut n_out, mut stats) = (0u64, [0u64; PA_BUS_UMI_STATS]);
+    if rc >= 0 {
+        rc = unsafe { pa_bus_umi_correct_records(idx, records.as_ptr(), records.len() as u64, ec_offsets.as_ptr(), ec_ids.as_ptr(),
+                                                 ec_offsets.len().saturating_sub(1) as u32, tx_gene.len() as u32, tx_gene.as_ptr(), num_genes, bc_len, umi_len, mode,
+                                                 out.as_mut_ptr(), records.len() as u64, &mut n_out, stats.as_mut_ptr()) };
+        if rc >= 0 { unsafe { out.set_len(n_out as usize); } }
+    }
+    let result = check(rc).map(|_| (out, stats));   // (the message is read before the handles go)
+    unsafe {
+        if !idx.is_null() { pa_index_destroy(idx); }
+        pa_host_index_destroy(h);
+    }
+    result
+}
+
+/// `write_bus` with every record step as an option and the UMI correction behind them (pa_write_bus_umi): `whitelist` and `call_cells` run the
+/// barcode steps exactly as `write_bus` / `write_bus_corrected` / `write_bus_called` run them for that pair, then the UMIs are corrected
+/// (`umi_mode`), always last; barcode_ranks.tsv shows the molecule counts before that. Returns (PA_BUS_STATS, PA_BUS_CORRECT_STATS,
+/// PA_KNEE_STATS, PA_BUS_UMI_STATS); the stats of a step that did not run stay 0.
+pub fn write_bus_umi<P: AsRef<Path>>(index_file: P, r1_fastq: P, r2_fastq: P, whitelist: Option<P>, out_dir: P, bc_len: u32, umi_len: u32, call_cells: bool,
+                                     knee: Option<crate::amd_knee_ffi::PaKneeParams>, umi_mode: u32, num_threads: usize,
+                                     device: i32) -> Result<([u64; crate::amd_bus_ffi::PA_BUS_STATS], [u64; crate::amd_correct_ffi::PA_BUS_CORRECT_STATS],
+                                                             [u64; crate::amd_knee_ffi::PA_KNEE_STATS], [u64; crate::amd_umi_ffi::PA_BUS_UMI_STATS]), Error> {
+    use crate::amd_bus_ffi::*;
+    use crate::amd_correct_ffi::*;
+    use crate::amd_knee_ffi::*;
+    use crate::amd_umi_ffi::*;
+    let cstr = |p: &P| CString::new(p.as_ref().to_string_lossy().into_owned());
+    let (ix, r1, r2, out) = (cstr(&index_file)?, cstr(&r1_fastq)?, cstr(&r2_fastq)?, cstr(&out_dir)?);
+    let wl = match whitelist.as_ref() { Some(w) => Some(cstr(w)?), None => None };
+    let mut h = std::ptr::null_mut();
+    check(unsafe { pa_host_index_load(ix.as_ptr(), &mut h) })?;
+    let mut view: PaFlatIndex = unsafe { std::mem::zeroed() };
+    let mut idx = std::ptr::null_mut();
+    let mut rc = unsafe { pa_host_index_view(h, &mut view) };
+    if rc >= 0 { rc = unsafe { pa_index_create(&view, device, &mut idx) }; }
+    let (mut stats, mut cstats, mut kstats, mut ustats) = ([0u64; PA_BUS_STATS], [0u64; PA_BUS_CORRECT_STATS], [0u64; PA_KNEE_STATS], [0u64; PA_BUS_UMI_STATS]);
+    if rc >= 0 {
+        let kp = knee.as_ref().map_or(std::ptr::null(), |p| p as *const PaKneeParams);
+        let wlp = wl.as_ref().map_or(std::ptr::null(), |w| w.as_ptr());
+        rc = unsafe { pa_write_bus_umi(idx, h, r1.as_ptr(), r2.as_ptr(), wlp, bc_len, umi_len, call_cells as i32, kp, umi_mode, out.as_ptr(), num_threads as i32,
+                                       stats.as_mut_ptr(), cstats.as_mut_ptr(), kstats.as_mut_ptr(), ustats.as_mut_ptr()) };
+    }
+    let result = check(rc).map(|_| (stats, cstats, kstats, ustats));   // (the message is read before the handles go)
+    unsafe {
+        if !idx.is_null() { pa_index_destroy(idx); }
+        pa_host_index_destroy(h);
+    }
+    result
+}
+
+/// `count_cells_em` with every record step as an option and the UMI correction between them and the gene stage (pa_count_cells_em_umi;
+/// `write_bus_umi`'s rules). Returns (PA_GENES_STATS, PA_BUS_CORRECT_STATS, PA_KNEE_STATS, PA_BUS_UMI_STATS).
+pub fn count_cells_em_umi<P: AsRef<Path>>(index_file: P, r1_fastq: P, r2_fastq: P, whitelist: Option<P>, out_dir: P, bc_len: u32, umi_len: u32, call_cells: bool,
+                                          knee: Option<crate::amd_knee_ffi::PaKneeParams>, umi_mode: u32, params: Option<crate::amd_genes_ffi::PaGenesParams>,
+                                          num_threads: usize,
+                                          device: i32) -> Result<([u64; crate::amd_genes_ffi::PA_GENES_STATS], [u64; crate::amd_correct_ffi::PA_BUS_CORRECT_STATS],
+                                                                  [u64; crate::amd_knee_ffi::PA_KNEE_STATS], [u64; crate::amd_umi_ffi::PA_BUS_UMI_STATS]), Error> {
+    use crate::amd_correct_ffi::*;
+    use crate::amd_genes_ffi::*;
+    use crate::amd_knee_ffi::*;
+    use crate::amd_umi_ffi::*;
+    let cstr = |p: &P| CString::new(p.as_ref().to_string_lossy().into_owned());
+    let (ix, r1, r2, out) = (cstr(&index_file)?, cstr(&r1_fastq)?, cstr(&r2_fastq)?, cstr(&out_dir)?);
+    let wl = match whitelist.as_ref() { Some(w) => Some(cstr(w)?), None => None };
+    let mut h = std::ptr::null_mut();
+    check(unsafe { pa_host_index_load(ix.as_ptr(), &mut h) })?;
+    let mut view: PaFlatIndex = unsafe { std::mem::zeroed() };
+    let mut idx = std::ptr::null_mut();
+    let mut rc = unsafe { pa_host_index_view(h, &mut view) };
+    if rc >= 0 { rc = unsafe { pa_index_create(&view, device, &mut idx) }; }
+    let (mut stats, mut cstats, mut kstats, mut ustats) = ([0u64; PA_GENES_STATS], [0u64; PA_BUS_CORRECT_STATS], [0u64; PA_KNEE_STATS], [0u64; PA_BUS_UMI_STATS]);
+    if rc >= 0 {
+        let kp = knee.as_ref().map_or(std::ptr::null(), |p| p as *const PaKneeParams);
+        let p = params.as_ref().map_or(std::ptr::null(), |p| p as *const PaGenesParams);
+        let wlp = wl.as_ref().map_or(std::ptr::null(), |w| w.as_ptr());
+        rc = unsafe { pa_count_cells_em_umi(idx, h, r1.as_ptr(), r2.as_ptr(), wlp, bc_len, umi_len, call_cells as i32, kp, umi_mode, p, out.as_ptr(), num_threads as i32,
+                                            stats.as_mut_ptr(), cstats.as_mut_ptr(), kstats.as_mut_ptr(), ustats.as_mut_ptr()) };
+    }
+    let result = check(rc).map(|_| (stats, cstats, kstats, ustats));   // (the message is read before the handles go)
     unsafe {
         if !idx.is_null() { pa_index_destroy(idx); }
         pa_host_index_destroy(h);

@@ -472,15 +472,20 @@ class Pseudoaligner:
         return dict(zip(_ffi.CELL_STAT_NAMES, (int(x) for x in st)))
 
     def write_bus(self, host_index: HostIndex, r1: str, r2: str, out_dir: str, bc_len: int = 16, umi_len: int = 12, num_threads: int = 0,
-                  whitelist: Optional[str] = None, call_cells=None) -> dict:
+                  whitelist: Optional[str] = None, call_cells=None, umi_correct: Optional[str] = None) -> dict:
         """Paired R1 (barcode + UMI) / R2 (cDNA) FASTQ -> out_dir/output.bus (sorted, collapsed BUS v1 records), matrix.ec and
         transcripts.txt (pa_write_bus): the input of the kallisto | bustools family. Returns the stats (BusWriter.stats). With `whitelist`
         (the path of a barcode whitelist file) the barcodes are corrected against it before the files are written
         (pa_write_bus_corrected), and the stats hold the correction's under "correct" (BusWriter.correct). With `call_cells` (True for the
         defaults, or a dict of knee params as BusWriter.knee takes them) cells are called (pa_write_bus_called): without a whitelist the called
         barcodes are the whitelist of the correction, with one the corrected records of uncalled barcodes are dropped; out_dir/barcode_ranks.tsv
-        holds the table, and the stats hold the knee's under "knee"."""
+        holds the table, and the stats hold the knee's under "knee". With `umi_correct` ("greatest" or "directional") the UMIs are corrected
+        after those steps, last of all (pa_write_bus_umi; BusWriter.umi_correct), and the stats hold that step's under "umi"; barcode_ranks.tsv
+        shows the molecule counts before it."""
         st = np.zeros(_ffi.PA_BUS_STATS, np.uint64)
+        if umi_correct is not None:
+            return self._umi_call(lambda *a: lib().pa_write_bus_umi(self._h, host_index._h, str(r1).encode(), str(r2).encode(), *a), st, _ffi.BUS_STAT_NAMES, whitelist,
+                                  bc_len, umi_len, call_cells, umi_correct, (str(out_dir).encode(), num_threads))
         if call_cells is not None and call_cells is not False:
             kp = _knee_params(call_cells)
             cs, ks = np.zeros(_ffi.PA_BUS_CORRECT_STATS, np.uint64), np.zeros(_ffi.PA_KNEE_STATS, np.uint64)
@@ -502,15 +507,20 @@ class Pseudoaligner:
         return dict(zip(_ffi.BUS_STAT_NAMES, (int(x) for x in st)))
 
     def count_cells_em(self, host_index: HostIndex, r1: str, r2: str, out_dir: str, bc_len: int = 16, umi_len: int = 12, num_threads: int = 0,
-                       whitelist: Optional[str] = None, call_cells=None, **params) -> dict:
+                       whitelist: Optional[str] = None, call_cells=None, umi_correct: Optional[str] = None, **params) -> dict:
         """Paired R1 (barcode + UMI) / R2 (cDNA) FASTQ -> out_dir/matrix.mtx (real values), barcodes.tsv, features.tsv (pa_count_cells_em):
         write_bus's records, never written, shared out over genes by a per-cell EM (GeneCounter). params: GeneCounter's. Returns the stats
         (GeneCounter.stats). With `whitelist` (the path of a barcode whitelist file) the barcodes are corrected against it before the
         gene stage (pa_count_cells_em_corrected), and the stats hold the correction's under "correct". With `call_cells` (True or a dict of
         knee params) cells are called before the gene stage as write_bus calls them (pa_count_cells_em_called): the matrix is the filtered
-        one, out_dir/barcode_ranks.tsv holds the table, and the stats hold the knee's under "knee"."""
+        one, out_dir/barcode_ranks.tsv holds the table, and the stats hold the knee's under "knee". With `umi_correct` ("greatest" or
+        "directional") the UMIs are corrected after those steps and before the gene stage (pa_count_cells_em_umi), and the stats hold that
+        step's under "umi"."""
         p = _genes_params(params)
         st = np.zeros(_ffi.PA_GENES_STATS, np.uint64)
+        if umi_correct is not None:
+            return self._umi_call(lambda *a: lib().pa_count_cells_em_umi(self._h, host_index._h, str(r1).encode(), str(r2).encode(), *a), st, _ffi.GENES_STAT_NAMES, whitelist,
+                                  bc_len, umi_len, call_cells, umi_correct, (C.byref(p), str(out_dir).encode(), num_threads))
         if call_cells is not None and call_cells is not False:
             kp = _knee_params(call_cells)
             cs, ks = np.zeros(_ffi.PA_BUS_CORRECT_STATS, np.uint64), np.zeros(_ffi.PA_KNEE_STATS, np.uint64)
@@ -530,6 +540,22 @@ class Pseudoaligner:
         check(lib().pa_count_cells_em(self._h, host_index._h, str(r1).encode(), str(r2).encode(), bc_len, umi_len, C.byref(p), str(out_dir).encode(), num_threads,
                                       st.ctypes.data))
         return dict(zip(_ffi.GENES_STAT_NAMES, (int(x) for x in st)))
+
+    @staticmethod
+    def _umi_call(call, st, names, whitelist, bc_len, umi_len, call_cells, umi_correct, tail) -> dict:
+        """the arguments that pa_write_bus_umi and pa_count_cells_em_umi share, and their stats: "correct" / "knee" only for a step that ran"""
+        calling = call_cells is not None and call_cells is not False
+        kp = _knee_params(call_cells if calling else True)
+        cs, ks, us = np.zeros(_ffi.PA_BUS_CORRECT_STATS, np.uint64), np.zeros(_ffi.PA_KNEE_STATS, np.uint64), np.zeros(_ffi.PA_BUS_UMI_STATS, np.uint64)
+        check(call(str(whitelist).encode() if whitelist is not None else None, bc_len, umi_len, 1 if calling else 0, C.byref(kp), _umi_mode(umi_correct), *tail, st.ctypes.data,
+                   cs.ctypes.data, ks.ctypes.data, us.ctypes.data))
+        out = dict(zip(names, (int(x) for x in st)))
+        if whitelist is not None or calling:
+            out["correct"] = dict(zip(_ffi.CORRECT_STAT_NAMES, (int(x) for x in cs)))
+        if calling:
+            out["knee"] = dict(zip(_ffi.KNEE_STAT_NAMES, (int(x) for x in ks)))
+        out["umi"] = dict(zip(_ffi.UMI_STAT_NAMES, (int(x) for x in us)))
+        return out
 
     def quantify(self, d_counts: int, overflow: Optional["Overflow"] = None, **params) -> "Quantifier":
         """Transcript abundances from a class-count table on this GPU (d_counts: the device pointer the count launches accumulated into,
@@ -780,6 +806,21 @@ class BusWriter:
         check(lib().pa_bus_keep(self._h, bc.ctypes.data if len(bc) else None, len(bc), st.ctypes.data))
         return dict(zip(_ffi.KEEP_STAT_NAMES, (int(x) for x in st)))
 
+    def umi_correct(self, tx_gene=None, mode="greatest", num_genes: Optional[int] = None) -> dict:
+        """pa_bus_umi_correct: the UMIs of the finished records (finished here if they are not yet) corrected in place, one step: a molecule moves
+        to the best-supported molecule of its barcode whose UMI is one substitution away and whose gene set meets its own -> the stats
+        (UMI_STAT_NAMES). tx_gene[transcripts] (with num_genes) defaults to the host index's genes; mode: "greatest" | "directional"."""
+        self.finish()
+        if tx_gene is None:
+            tx_gene, names = self._host.genes()
+            num_genes = len(names)
+        tg = np.ascontiguousarray(tx_gene, np.uint32)
+        if num_genes is None:
+            num_genes = int(tg.max()) + 1 if len(tg) else 0
+        st = np.zeros(_ffi.PA_BUS_UMI_STATS, np.uint64)
+        check(lib().pa_bus_umi_correct(self._h, tg.ctypes.data if len(tg) else None, num_genes, _umi_mode(mode), st.ctypes.data))
+        return dict(zip(_ffi.UMI_STAT_NAMES, (int(x) for x in st)))
+
     def write(self, out_dir: str) -> None:
         """out_dir/output.bus, matrix.ec, transcripts.txt"""
         self.finish()
@@ -833,6 +874,42 @@ def bus_correct_phase_ms() -> dict:
     ms = (C.c_float * _ffi.PA_BUS_CORRECT_PHASES)()
     check(lib().pa_bus_correct_phase_ms(ms))
     return dict(zip(_ffi.CORRECT_PHASE_NAMES, (float(x) for x in ms)))
+
+
+UMI_STAT_NAMES, UMI_PHASE_NAMES = _ffi.UMI_STAT_NAMES, _ffi.UMI_PHASE_NAMES
+
+
+def _umi_mode(mode) -> int:
+    """"greatest" | "directional", or the number itself (an unknown one is the library's to refuse)"""
+    if isinstance(mode, str):
+        if mode not in _ffi.UMI_MODES:
+            raise ValueError("umi_correct: %r is neither 'greatest' nor 'directional'" % mode)
+        return _ffi.UMI_MODES[mode]
+    return int(mode)
+
+
+def bus_umi_correct(records, ec_offsets, ec_ids, tx_gene, num_genes: int, bc_len: int, umi_len: int, aligner: Optional["Pseudoaligner"], mode="greatest") -> Tuple[np.ndarray, dict]:
+    """pa_bus_umi_correct_records: host records (BUS_RECORD_DTYPE, strictly ascending by barcode, UMI, ec) with their ec table as a CSR and
+    tx_gene, as GeneCounter.from_arrays takes them, on `aligner`'s GPU -> (the records with the UMIs corrected, collapsed and sorted again; the
+    stats (UMI_STAT_NAMES))"""
+    rec = np.ascontiguousarray(records, BUS_RECORD_DTYPE)
+    off = np.ascontiguousarray(ec_offsets, np.uint64)
+    ids = np.ascontiguousarray(ec_ids, np.uint32)
+    tg = np.ascontiguousarray(tx_gene, np.uint32)
+    st = np.zeros(_ffi.PA_BUS_UMI_STATS, np.uint64)
+    out = np.zeros(max(len(rec), 1), BUS_RECORD_DTYPE)
+    n = C.c_uint64()
+    check(lib().pa_bus_umi_correct_records(aligner._h if aligner is not None else None, rec.ctypes.data if len(rec) else None, len(rec), off.ctypes.data if len(off) else None,
+                                           ids.ctypes.data if len(ids) else None, max(len(off), 1) - 1, len(tg), tg.ctypes.data if len(tg) else None, num_genes, bc_len, umi_len,
+                                           _umi_mode(mode), out.ctypes.data, len(rec), C.byref(n), st.ctypes.data))
+    return out[:n.value], dict(zip(_ffi.UMI_STAT_NAMES, (int(x) for x in st)))
+
+
+def bus_umi_correct_phase_ms() -> dict:
+    """pa_bus_umi_correct_phase_ms: the GPU milliseconds of this thread's last UMI correction, by phase"""
+    ms = (C.c_float * _ffi.PA_BUS_UMI_PHASES)()
+    check(lib().pa_bus_umi_correct_phase_ms(ms))
+    return dict(zip(_ffi.UMI_PHASE_NAMES, (float(x) for x in ms)))
 
 
 BARCODE_ROW_DTYPE = np.dtype([("barcode", "<u8"), ("reads", "<u8"), ("records", "<u4"), ("umis", "<u4"), ("rank", "<u4"), ("called", "<u4")])   # pa_bus_barcode_row

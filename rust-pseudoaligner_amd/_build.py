@@ -12,8 +12,8 @@ CSRC = PKG / "csrc"
 
 PRODUCT_SO = PKG / "libpseudoaligner_amd.so"
 
-HOST_SOURCES = ["host_index.cpp", "dbg_build.cpp", "device_flatten.cpp", "synth.cpp", "fastq_text.cpp", "fastq_reads.cpp", "pair_reader.cpp", "fastq_cells.cpp", "fastq_pairs.cpp", "record_stream.cpp", "host_batch.cpp", "bgzf.cpp", "bus_host.cpp", "bus_correct_host.cpp", "bus_knee_host.cpp", "genes_host.cpp", "window_feed.cpp", "text_window.cpp"]
-HIP_SOURCES = ["kernels.hip", "map_pool.hip", "device_index.hip", "map_batch.hip", "device_plumbing.hip", "collective.hip", "barcode_counts.hip", "index_build.hip", "index_fill.hip", "count_sort.hip", "resolve.hip", "render.hip", "fastq_scan.hip", "compact.hip", "quant.hip", "quant_boot.hip", "pairs.hip", "strands.hip", "inflate.hip", "bus.hip", "pair_scan.hip", "genes.hip", "bus_correct.hip", "bus_knee.hip"]
+HOST_SOURCES = ["host_index.cpp", "dbg_build.cpp", "device_flatten.cpp", "synth.cpp", "fastq_text.cpp", "fastq_reads.cpp", "pair_reader.cpp", "fastq_cells.cpp", "fastq_pairs.cpp", "record_stream.cpp", "host_batch.cpp", "bgzf.cpp", "bus_host.cpp", "bus_correct_host.cpp", "bus_knee_host.cpp", "genes_host.cpp", "bus_umi_host.cpp", "window_feed.cpp", "text_window.cpp"]
+HIP_SOURCES = ["kernels.hip", "map_pool.hip", "device_index.hip", "map_batch.hip", "device_plumbing.hip", "collective.hip", "barcode_counts.hip", "index_build.hip", "index_fill.hip", "count_sort.hip", "resolve.hip", "render.hip", "fastq_scan.hip", "compact.hip", "quant.hip", "quant_boot.hip", "pairs.hip", "strands.hip", "inflate.hip", "bus.hip", "pair_scan.hip", "genes.hip", "bus_correct.hip", "bus_knee.hip", "bus_umi.hip"]
 
 
 # flags of single sources. map_pool.hip: without LLVM's machine-sinking pass the mapping kernel is 1 % faster at config 3 (7.608 -> 7.536 ms, three interleaved
@@ -108,6 +108,25 @@ def build_pairknobs_variant(force: bool = False) -> Path:
     if force or _stale(PAIRKNOBS_SO, objs):
         _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-pthread"] + [str(o) for o in objs] + ["-ldl", "-lz", "-o", str(PAIRKNOBS_SO)])
     return PAIRKNOBS_SO
+
+
+UMIHBM_SO = OBJ_DIR / "libpseudoaligner_amd_umihbm.so"
+
+
+def build_umi_hbm_variant(force: bool = False) -> Path:
+    """A TEST build of the product: bus_umi.hip compiled with -DPA_UMI_FORCE_HBM, everything else the product's own objects. The barcodes of the UMI
+    correction's block bin (more than UM_LANE_MAX molecules, up to UM_LDS_CAP) then take the HBM variant of the neighbour search, so that the two can be
+    timed on the same barcodes (tools/bench_umi.py loads it in a child process through PA_PRODUCT_SO)."""
+    build_product()
+    hipcc = hipcc_path()
+    src = CSRC / "bus_umi.hip"
+    obj = OBJ_DIR / "bus_umi.umihbm.o"
+    if force or _stale(obj, _deps_of(src)):
+        _run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread", "-Wall", "-Wno-unused-function", "-DPA_UMI_FORCE_HBM", "-x", "hip", "-c", str(src), "-o", str(obj)])
+    objs = [OBJ_DIR / (s + ".o") for s in HOST_SOURCES + HIP_SOURCES if s != "bus_umi.hip"] + [obj]
+    if force or _stale(UMIHBM_SO, objs):
+        _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-pthread"] + [str(o) for o in objs] + ["-ldl", "-lz", "-o", str(UMIHBM_SO)])
+    return UMIHBM_SO
 
 
 ABI_CHECK_SRC = ROOT / "integration" / "c" / "abi_check.c"

@@ -35,6 +35,13 @@ PA_KNEE_PHASES = 3
 KNEE_PHASE_NAMES = ("table_ms", "rank_curve_ms", "called_rows_ms")
 PA_BUS_KEEP_STATS = 7
 KEEP_STAT_NAMES = ("records_in", "reads_in", "barcodes_in", "barcodes_kept", "records_out", "reads_out", "listed_absent")
+PA_UMI_GREATEST, PA_UMI_DIRECTIONAL = 0, 1
+UMI_MODES = {"greatest": PA_UMI_GREATEST, "directional": PA_UMI_DIRECTIONAL}
+PA_BUS_UMI_STATS = 15
+UMI_STAT_NAMES = ("records_in", "reads_in", "molecules_in", "barcodes", "molecules_inert", "molecules_with_hamming1", "molecules_with_neighbour", "molecules_moved",
+                  "molecules_moved_onto_moved", "records_rewritten", "reads_moved", "records_out", "molecules_out", "largest_barcode", "barcodes_hbm")
+PA_BUS_UMI_PHASES = 4
+UMI_PHASE_NAMES = ("molecules_ms", "search_ms", "rewrite_ms", "stats_ms")
 PA_MAPPED_BIT = 0x80000000
 PA_DEFAULT_ALLOWED_MISMATCHES = 2
 PA_READ_COVERAGE_THRESHOLD = 32
@@ -219,6 +226,13 @@ SIGNATURES = {
     "pa_write_bus_called": (C.c_int, [vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(KneeParams), C.c_char_p, C.c_int, vp, vp, vp]),
     "pa_count_cells_em_called": (C.c_int, [vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(KneeParams), C.POINTER(GenesParams), C.c_char_p, C.c_int,
                                            vp, vp, vp]),
+    "pa_bus_umi_correct_records": (C.c_int, [vp, vp, C.c_uint64, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint64, u64p, vp]),
+    "pa_bus_umi_correct": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, vp]),
+    "pa_bus_umi_correct_phase_ms": (C.c_int, [C.POINTER(C.c_float)]),
+    "pa_write_bus_umi": (C.c_int, [vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(KneeParams), C.c_uint32, C.c_char_p, C.c_int, vp, vp, vp,
+                                   vp]),
+    "pa_count_cells_em_umi": (C.c_int, [vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(KneeParams), C.c_uint32, C.POINTER(GenesParams),
+                                        C.c_char_p, C.c_int, vp, vp, vp, vp]),
     "pa_genes_default_params": (None, [C.POINTER(GenesParams)]),
     "pa_genes_create": (C.c_int, [vp, vp, C.c_uint64, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(GenesParams), C.POINTER(vp)]),
     "pa_genes_create_from_bus": (C.c_int, [vp, vp, C.c_uint32, C.POINTER(GenesParams), C.POINTER(vp)]),

@@ -27,7 +27,6 @@ constexpr uint32_t CORRECT_GROUP = 16;         // lanes that share the 3 bc_len 
 constexpr uint32_t CORRECT_MAX_ROUNDS = 6;     // candidates of one lane: ceil(3 * 31 / CORRECT_GROUP)
 constexpr uint32_t CORRECT_MAX_GRID = 2048;    // blocks of a counting kernel: its lanes stride over the items and a wave adds its counters once, at its end
 constexpr ull WL_EMPTY = ~0ull;                // an empty slot, and the target of a dropped barcode (a barcode has at most 62 bits)
-constexpr uint32_t EC_BIAS = 0x80000000u;      // the key holds ec + 2^31: integer order of the key = (barcode, UMI, ec as int32)
 enum : uint32_t { ERR_DUPLICATE = 0, ERR_TABLE = 1, ERR_WORDS = 2 };
 enum : uint32_t { CS_RECORDS_IN = 0, CS_READS_IN, CS_BARCODES_IN, CS_EXACT, CS_CORRECTED, CS_NONE, CS_AMBIGUOUS, CS_RECORDS_EXACT, CS_RECORDS_CORRECTED, CS_RECORDS_DROPPED,
                   CS_READS_DROPPED, CS_RECORDS_OUT, CS_BARCODES_OUT };
@@ -270,24 +269,8 @@ int correct_device(const pa_bus_record* d_in, uint32_t n, uint32_t bc_len, uint3
         if ((e = d_keys.alloc(n_kept)) || (e = d_counts.alloc(n_kept))) return e;
         if ((e = launch(pa_correct_compact_kernel, grid_for(n, CORRECT_BLOCK), CORRECT_BLOCK, s, d_in, (const uint32_t*)d_pos.get(), (const ull*)d_target.get(),
                 (const uint32_t*)d_kept.get(), (const uint32_t*)d_kpos.get(), n, umi_bits, d_keys.get(), d_counts.get()))) return e;
-        M = n_kept;
-        if (st[CS_CORRECTED]) {   // a barcode moved: sort, join equal keys. Otherwise the kept records are sorted and distinct as they were
-            DeviceBuffer<u128> k1, k2;
-            DeviceBuffer<uint32_t> c1, c2, heads, pos, start;
-            if ((e = k1.alloc(n_kept)) || (e = k2.alloc(n_kept)) || (e = c1.alloc(n_kept)) || (e = c2.alloc(n_kept)) || (e = heads.alloc(n_kept)) || (e = pos.alloc(n_kept)) ||
-                (e = start.alloc((size_t)n_kept + 1)))
-                return e;
-            if ((e = sort_pairs(s, tmp, (const u128*)d_keys.get(), k1.get(), (const uint32_t*)d_counts.get(), c1.get(), (size_t)n_kept, 0, key_bits))) return e;
-            if ((e = collapse_runs(s, tmp, KeyArray<u128>{k1.get()}, n_kept, heads.get(), pos.get(), k2.get(), start.get(), M)) ||
-                (e = run_counts(s, start.get(), M, c1.get(), c2.get())))
-                return e;
-            PA_HIP_TRY(hipStreamSynchronize(s));   // (the scratch of this block is freed at its end)
-            d_keys = std::move(k2);
-            d_counts = std::move(c2);
-        }
-        if ((e = d_out.alloc(M))) return e;
-        if ((e = launch(pa_bus_records_kernel<32, EC_BIAS>, grid_for(M, BUS_BLOCK), BUS_BLOCK, s, (const u128*)d_keys.get(), (const uint32_t*)d_counts.get(), M, umi_bits,
-                d_out.get()))) return e;
+        // a barcode moved: sort, join equal keys. Otherwise the kept records are sorted and distinct as they were
+        if ((e = records_from_keys(s, tmp, d_keys, d_counts, n_kept, st[CS_CORRECTED] != 0, key_bits, umi_bits, d_out, M))) return e;
         if ((e = launch(pa_correct_barcodes_out_kernel, count_grid(M), CORRECT_BLOCK, s, (const pa_bus_record*)d_out.get(), M, d_stats.get()))) return e;
         PA_HIP_TRY(hipMemcpyAsync(&st[CS_BARCODES_OUT], d_stats.get() + CS_BARCODES_OUT, 8, hipMemcpyDeviceToHost, s));
     } else {

@@ -1,5 +1,5 @@
-// The BUS writer (pa_bus) as csrc/bus.hip builds it, and what the stages over its records (csrc/bus_correct.hip, csrc/bus_knee.hip) share with it:
-// a record as two 16-byte words, the kernel that writes whole records from sorted keys, and the two call frames of a stage, over records from
+// The BUS writer (pa_bus) as csrc/bus.hip builds it, and what the stages over its records (csrc/bus_correct.hip, csrc/bus_knee.hip, csrc/bus_umi.hip) share with it:
+// a record as two 16-byte words, the kernel that writes whole records from sorted keys, the sort + collapse tail of a stage that rewrote keys, and the two call frames of a stage, over records from
 // the host and over a finished writer's records where they lie. Included by the BUS .hip sources only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -60,6 +60,32 @@ __global__ __launch_bounds__(BUS_BLOCK) void pa_bus_records_kernel(const u128* _
     const u128 k = keys[i];
     const ull w = (ull)(k >> SHIFT), bc = w >> umi_bits, umi = w & pa::low_mask(umi_bits);
     store_record(out + i, RecordWords{make_uint4((uint32_t)bc, (uint32_t)(bc >> 32), (uint32_t)umi, (uint32_t)(umi >> 32)), make_uint4((uint32_t)k ^ EC_FLIP, counts[i], 0u, 0u)});
+}
+
+constexpr uint32_t EC_BIAS = 0x80000000u;      // a rewritten key holds ec + 2^31: integer order of the key = (barcode, UMI, ec as int32)
+
+// The tail of a stage that rewrote barcodes or UMIs (bus_correct.hip, bus_umi.hip): keys[n] = (barcode | UMI) << 32 | ec + 2^31 with their counts,
+// n >= 1 -> d_out[M] whole records. moved: a key changed, so the keys are sorted over their key_bits live bits and equal ones joined (counts summed
+// in 64 bits, clamped); otherwise they are sorted and distinct as they lie. keys and counts are used up
+inline int records_from_keys(hipStream_t s, pa::DeviceBuffer<uint8_t>& tmp, pa::DeviceBuffer<u128>& keys, pa::DeviceBuffer<uint32_t>& counts, uint32_t n, bool moved,
+                             uint32_t key_bits, uint32_t umi_bits, pa::DeviceBuffer<pa_bus_record>& d_out, uint32_t& M) {
+    int e;
+    M = n;
+    if (moved) {
+        pa::DeviceBuffer<u128> k1, k2;
+        pa::DeviceBuffer<uint32_t> c1, c2, heads, pos, start;
+        if ((e = k1.alloc(n)) || (e = k2.alloc(n)) || (e = c1.alloc(n)) || (e = c2.alloc(n)) || (e = heads.alloc(n)) || (e = pos.alloc(n)) || (e = start.alloc((size_t)n + 1)))
+            return e;
+        if ((e = pa::sort_pairs(s, tmp, (const u128*)keys.get(), k1.get(), (const uint32_t*)counts.get(), c1.get(), (size_t)n, 0, key_bits))) return e;
+        if ((e = pa::collapse_runs(s, tmp, pa::KeyArray<u128>{k1.get()}, n, heads.get(), pos.get(), k2.get(), start.get(), M)) ||
+            (e = run_counts(s, start.get(), M, c1.get(), c2.get())))
+            return e;
+        PA_HIP_TRY(hipStreamSynchronize(s));   // (the scratch of this block is freed at its end)
+        keys = std::move(k2);
+        counts = std::move(c2);
+    }
+    if ((e = d_out.alloc(M))) return e;
+    return pa::launch(pa_bus_records_kernel<32, EC_BIAS>, pa::grid_for(M, BUS_BLOCK), BUS_BLOCK, s, (const u128*)keys.get(), (const uint32_t*)counts.get(), M, umi_bits, d_out.get());
 }
 
 }  // namespace

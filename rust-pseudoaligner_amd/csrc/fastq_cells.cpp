@@ -14,6 +14,7 @@
 #include <unordered_set>
 
 #include "bus_knee_host.hpp"
+#include "bus_umi_host.hpp"
 #include "pair_reader.hpp"
 
 using namespace pa;
@@ -217,7 +218,8 @@ int count_cells_impl(pa_index* idx, const pa_host_index* h, const char* r1_path,
 // ---- pa_write_bus / pa_count_cells_em: the same two files -> sorted (barcode, UMI, ec) records in HBM, then `after(bus, st)`: the writer's three files, or
 // the gene stage and its three files (after() adds its own seconds to st[ST_TALLY] / st[ST_WRITE]). With a whitelist file (the *_corrected calls) the
 // barcodes of the finished records are corrected against it in HBM before `after` sees them (pa_bus_correct; its seconds go to st[ST_TALLY]); with a knee (the
-// *_called calls) cells are called there too (pa_bus_knee, then pa_bus_correct or pa_bus_keep; st[ST_TALLY], the table's file st[ST_WRITE]) ----
+// *_called calls) cells are called there too (pa_bus_knee, then pa_bus_correct or pa_bus_keep; st[ST_TALLY], the table's file st[ST_WRITE]); the *_umi calls take
+// both as options and correct the UMIs behind them (pa_bus_umi_correct; st[ST_TALLY]) ----
 struct BusWhitelist {
     const char* path = nullptr;   // nullptr: no correction
     uint64_t* stats = nullptr;    // [PA_BUS_CORRECT_STATS], may be nullptr
@@ -229,6 +231,13 @@ struct BusKnee {
     bool on = false;
     const pa_knee_params* params = nullptr;   // nullptr: the defaults
     uint64_t* stats = nullptr;                // [PA_KNEE_STATS], may be nullptr
+};
+
+// UMI correction (the *_umi calls; pa_bus_umi_correct with the host index's genes): always the last of the record steps, behind correction and cell calling
+struct BusUmi {
+    bool on = false;
+    uint32_t mode = PA_UMI_GREATEST;
+    uint64_t* stats = nullptr;                // [PA_BUS_UMI_STATS], may be nullptr
 };
 
 // after pa_bus_finish: correction and cell calling in the order the two inputs ask for; the seconds of the table's file go to *write_seconds
@@ -252,8 +261,8 @@ int bus_call_cells(pa_bus* bus, const BusWhitelist& wl, const std::vector<uint64
 }
 
 template <class After>
-int bus_run(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const BusWhitelist& wl, const BusKnee& knee, uint32_t bc_len, uint32_t umi_len,
-            const char* out_dir, int num_threads, After&& after) {
+int bus_run(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const BusWhitelist& wl, const BusKnee& knee, const BusUmi& umi, uint32_t bc_len,
+            uint32_t umi_len, const char* out_dir, int num_threads, After&& after) {
     std::unique_ptr<pa_bus, void (*)(pa_bus*)> own(nullptr, pa_bus_destroy);   // (in front of the frame: destroyed behind its streams)
     PairedCall call(num_threads);
     double* const st = call.st;
@@ -263,6 +272,7 @@ int bus_run(pa_index* idx, const pa_host_index* h, const char* r1_path, const ch
     int rc = PA_OK;
     pa_knee_params knee_checked;
     if (knee.on && (rc = pa::knee::take_params(knee.params, knee_checked)) != PA_OK) return rc;   // refused before a read is mapped, like the whitelist
+    if (umi.on && (rc = pa::umi::check_mode(umi.mode)) != PA_OK) return rc;
     std::vector<uint64_t> packed;
     if (wl.path) {   // the whitelist first: a file that cannot be used is refused before a read is mapped
         if (bc_len > 16) return fail(PA_ERR_UNSUPPORTED, "barcode length %u: a whitelist file holds barcodes of at most 16 bases", bc_len);
@@ -292,6 +302,12 @@ int bus_run(pa_index* idx, const pa_host_index* h, const char* r1_path, const ch
     if ((rc = pa_bus_finish(bus, &n_records, &n_ecs)) != PA_OK) return rc;
     double ranks_seconds = 0.0;
     if ((rc = bus_call_cells(bus, wl, packed, knee, bc_len, out_dir, &ranks_seconds)) != PA_OK) return rc;
+    if (umi.on) {
+        const uint32_t ntx = pa_host_index_num_transcripts(h);
+        std::vector<uint32_t> tx_gene(ntx ? ntx : 1);
+        uint32_t num_genes = 0;
+        if ((rc = pa_host_index_genes(h, tx_gene.data(), &num_genes)) != PA_OK || (rc = pa_bus_umi_correct(bus, tx_gene.data(), num_genes, umi.mode, umi.stats)) != PA_OK) return rc;
+    }
     st[ST_TALLY] += now() - t0 - ranks_seconds;
     if ((rc = after(bus, st)) != PA_OK) return rc;
     st[ST_WRITE] += ranks_seconds;
@@ -299,9 +315,9 @@ int bus_run(pa_index* idx, const pa_host_index* h, const char* r1_path, const ch
     return PA_OK;
 }
 
-int write_bus_impl(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const BusWhitelist& wl, const BusKnee& knee, uint32_t bc_len,
-                   uint32_t umi_len, const char* out_dir, int num_threads, uint64_t* stats) {
-    return bus_run(idx, h, r1_path, r2_path, wl, knee, bc_len, umi_len, out_dir, num_threads, [&](pa_bus* bus, double* st) {
+int write_bus_impl(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const BusWhitelist& wl, const BusKnee& knee, const BusUmi& umi,
+                   uint32_t bc_len, uint32_t umi_len, const char* out_dir, int num_threads, uint64_t* stats) {
+    return bus_run(idx, h, r1_path, r2_path, wl, knee, umi, bc_len, umi_len, out_dir, num_threads, [&](pa_bus* bus, double* st) {
         const double t0 = now();
         const int rc = pa_bus_write(bus, out_dir);
         if (rc != PA_OK) return rc;
@@ -311,9 +327,9 @@ int write_bus_impl(pa_index* idx, const pa_host_index* h, const char* r1_path, c
     });
 }
 
-int count_cells_em_impl(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const BusWhitelist& wl, const BusKnee& knee, uint32_t bc_len,
-                        uint32_t umi_len, const pa_genes_params* p, const char* out_dir, int num_threads, uint64_t* stats) {
-    return bus_run(idx, h, r1_path, r2_path, wl, knee, bc_len, umi_len, out_dir, num_threads, [&](pa_bus* bus, double* st) {
+int count_cells_em_impl(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const BusWhitelist& wl, const BusKnee& knee, const BusUmi& umi,
+                        uint32_t bc_len, uint32_t umi_len, const pa_genes_params* p, const char* out_dir, int num_threads, uint64_t* stats) {
+    return bus_run(idx, h, r1_path, r2_path, wl, knee, umi, bc_len, umi_len, out_dir, num_threads, [&](pa_bus* bus, double* st) {
         double t0 = now();
         const uint32_t ntx = pa_host_index_num_transcripts(h);
         std::vector<uint32_t> tx_gene(ntx ? ntx : 1);
@@ -342,19 +358,19 @@ extern "C" int pa_count_cells(pa_index* idx, const pa_host_index* h, const char*
 
 extern "C" int pa_write_bus(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, uint32_t bc_len, uint32_t umi_len, const char* out_dir,
                             int num_threads, uint64_t stats[PA_BUS_STATS]) {
-    return no_throw("pa_write_bus", [&] { return write_bus_impl(idx, h, r1_path, r2_path, BusWhitelist{}, BusKnee{}, bc_len, umi_len, out_dir, num_threads, stats); });
+    return no_throw("pa_write_bus", [&] { return write_bus_impl(idx, h, r1_path, r2_path, BusWhitelist{}, BusKnee{}, BusUmi{}, bc_len, umi_len, out_dir, num_threads, stats); });
 }
 
 extern "C" int pa_count_cells_em(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, uint32_t bc_len, uint32_t umi_len, const pa_genes_params* p,
                                  const char* out_dir, int num_threads, uint64_t stats[PA_GENES_STATS]) {
-    return no_throw("pa_count_cells_em", [&] { return count_cells_em_impl(idx, h, r1_path, r2_path, BusWhitelist{}, BusKnee{}, bc_len, umi_len, p, out_dir, num_threads, stats); });
+    return no_throw("pa_count_cells_em", [&] { return count_cells_em_impl(idx, h, r1_path, r2_path, BusWhitelist{}, BusKnee{}, BusUmi{}, bc_len, umi_len, p, out_dir, num_threads, stats); });
 }
 
 extern "C" int pa_write_bus_corrected(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const char* whitelist_path, uint32_t bc_len,
                                       uint32_t umi_len, const char* out_dir, int num_threads, uint64_t bus_stats[PA_BUS_STATS], uint64_t correct_stats[PA_BUS_CORRECT_STATS]) {
     return no_throw("pa_write_bus_corrected", [&] {
         if (!whitelist_path) return fail(PA_ERR_INVALID_ARG, "null argument");
-        return write_bus_impl(idx, h, r1_path, r2_path, BusWhitelist{whitelist_path, correct_stats}, BusKnee{}, bc_len, umi_len, out_dir, num_threads, bus_stats);
+        return write_bus_impl(idx, h, r1_path, r2_path, BusWhitelist{whitelist_path, correct_stats}, BusKnee{}, BusUmi{}, bc_len, umi_len, out_dir, num_threads, bus_stats);
     });
 }
 
@@ -363,7 +379,7 @@ extern "C" int pa_count_cells_em_corrected(pa_index* idx, const pa_host_index* h
                                            uint64_t correct_stats[PA_BUS_CORRECT_STATS]) {
     return no_throw("pa_count_cells_em_corrected", [&] {
         if (!whitelist_path) return fail(PA_ERR_INVALID_ARG, "null argument");
-        return count_cells_em_impl(idx, h, r1_path, r2_path, BusWhitelist{whitelist_path, correct_stats}, BusKnee{}, bc_len, umi_len, p, out_dir, num_threads, genes_stats);
+        return count_cells_em_impl(idx, h, r1_path, r2_path, BusWhitelist{whitelist_path, correct_stats}, BusKnee{}, BusUmi{}, bc_len, umi_len, p, out_dir, num_threads, genes_stats);
     });
 }
 
@@ -371,7 +387,7 @@ extern "C" int pa_write_bus_called(pa_index* idx, const pa_host_index* h, const 
                                    uint32_t umi_len, const pa_knee_params* kp, const char* out_dir, int num_threads, uint64_t bus_stats[PA_BUS_STATS],
                                    uint64_t correct_stats[PA_BUS_CORRECT_STATS], uint64_t knee_stats[PA_KNEE_STATS]) {
     return no_throw("pa_write_bus_called", [&] {
-        return write_bus_impl(idx, h, r1_path, r2_path, BusWhitelist{whitelist_path, correct_stats}, BusKnee{true, kp, knee_stats}, bc_len, umi_len, out_dir, num_threads, bus_stats);
+        return write_bus_impl(idx, h, r1_path, r2_path, BusWhitelist{whitelist_path, correct_stats}, BusKnee{true, kp, knee_stats}, BusUmi{}, bc_len, umi_len, out_dir, num_threads, bus_stats);
     });
 }
 
@@ -379,7 +395,26 @@ extern "C" int pa_count_cells_em_called(pa_index* idx, const pa_host_index* h, c
                                         uint32_t umi_len, const pa_knee_params* kp, const pa_genes_params* p, const char* out_dir, int num_threads,
                                         uint64_t genes_stats[PA_GENES_STATS], uint64_t correct_stats[PA_BUS_CORRECT_STATS], uint64_t knee_stats[PA_KNEE_STATS]) {
     return no_throw("pa_count_cells_em_called", [&] {
-        return count_cells_em_impl(idx, h, r1_path, r2_path, BusWhitelist{whitelist_path, correct_stats}, BusKnee{true, kp, knee_stats}, bc_len, umi_len, p, out_dir, num_threads,
+        return count_cells_em_impl(idx, h, r1_path, r2_path, BusWhitelist{whitelist_path, correct_stats}, BusKnee{true, kp, knee_stats}, BusUmi{}, bc_len, umi_len, p, out_dir, num_threads,
                                    genes_stats);
+    });
+}
+
+extern "C" int pa_write_bus_umi(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const char* whitelist_path, uint32_t bc_len, uint32_t umi_len,
+                                int call_cells, const pa_knee_params* kp, uint32_t umi_mode, const char* out_dir, int num_threads, uint64_t bus_stats[PA_BUS_STATS],
+                                uint64_t correct_stats[PA_BUS_CORRECT_STATS], uint64_t knee_stats[PA_KNEE_STATS], uint64_t umi_stats[PA_BUS_UMI_STATS]) {
+    return no_throw("pa_write_bus_umi", [&] {
+        return write_bus_impl(idx, h, r1_path, r2_path, BusWhitelist{whitelist_path, correct_stats}, BusKnee{call_cells != 0, kp, knee_stats}, BusUmi{true, umi_mode, umi_stats},
+                              bc_len, umi_len, out_dir, num_threads, bus_stats);
+    });
+}
+
+extern "C" int pa_count_cells_em_umi(pa_index* idx, const pa_host_index* h, const char* r1_path, const char* r2_path, const char* whitelist_path, uint32_t bc_len, uint32_t umi_len,
+                                     int call_cells, const pa_knee_params* kp, uint32_t umi_mode, const pa_genes_params* p, const char* out_dir, int num_threads,
+                                     uint64_t genes_stats[PA_GENES_STATS], uint64_t correct_stats[PA_BUS_CORRECT_STATS], uint64_t knee_stats[PA_KNEE_STATS],
+                                     uint64_t umi_stats[PA_BUS_UMI_STATS]) {
+    return no_throw("pa_count_cells_em_umi", [&] {
+        return count_cells_em_impl(idx, h, r1_path, r2_path, BusWhitelist{whitelist_path, correct_stats}, BusKnee{call_cells != 0, kp, knee_stats},
+                                   BusUmi{true, umi_mode, umi_stats}, bc_len, umi_len, p, out_dir, num_threads, genes_stats);
     });
 }

@@ -1,4 +1,5 @@
 // The gene counter (pa_genes) as csrc/genes.hip builds it: the thresholds of its kernels and the per-cell layout in HBM.
+// (GN_BLOCK and GN_LANE_RECORDS are the molecule stage's, csrc/molecule_stage.hpp, which csrc/bus_umi.hip runs too.)
 #pragma once
 #include <hip/hip_runtime.h>
 
