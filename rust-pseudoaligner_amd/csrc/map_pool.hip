@@ -32,6 +32,15 @@
 #ifndef PA_REFILL_ALIGN   // A/B builds: -DPA_REFILL_ALIGN=16 (refills take whole 128-byte lines of the read tiles; measured and not kept: see the output step)
 #define PA_REFILL_ALIGN 1u
 #endif
+#ifndef PA_SEEK_MIN   // probes ride with a forward step only from this many waiting slots on (or when little forward work is left): the probe half is
+#define PA_SEEK_MIN 32u   // the whole wave's instructions however few lanes it serves (same-box A/B of 1 / 32 / 48: config 3 -1.8 %, config 5 -3.8 % time at 32)
+#endif
+#ifndef PA_PROBE_AT_REFILL   // A/B builds: -DPA_PROBE_AT_REFILL=0 (a fresh read waits in the SEEK queue for its first probe)
+#define PA_PROBE_AT_REFILL 1
+#endif
+#ifndef PA_SEEK_FULL   // with PA_PROBE_AT_REFILL: the SEEK queue weighs as a full wave from this many slots on (0: never; same-box A/B of 8 / 16 / 32: 8 is level with 16 at config 3 and 0.65 % faster at config 5)
+#define PA_SEEK_FULL 8u
+#endif
 #ifndef PA_RARE_MIN   // A/B builds: -DPA_RARE_MIN=0 (rare states compete by population only)
 #define PA_RARE_MIN 16u   // (round 5, same-box A/B of 10 / 16 / 24 on the chain-block layout: config 5 -2.1 % time at 16, config 2 -1.4 %, config 3 -0.5 %; 24 is slower than 10)
 #endif

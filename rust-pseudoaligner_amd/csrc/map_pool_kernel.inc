@@ -91,6 +91,29 @@ __device__ __forceinline__ void refill_slot(Lane& s, uint64_t rid, uint32_t slot
     wc[2 * slot + 1] = (uint32_t)rid;
 }
 
+// PA_PROBE_AT_REFILL: the first dictionary probe of a read in the step that refilled its slot, in the two halves of a dual iteration's probe.
+// A fresh lane (lane_start: k-mer 0, no displacement, no F_SPEC) probes exactly as seek_step_* would with two = false; the k-mer comes from
+// the LDS words refill_slot has just stored. Every lane of the wave executes the load, so that the waits around it stay exact: a lane that
+// took no read, or one shorter than K (ST_NONE), probes with an all-zero state (k-mer 0 of the slot's words: whatever its own state says is
+// not looked at — the state of a slot that never held a read is whatever the LDS held), loads the first line of the table, and its answer
+// is thrown away.
+template <bool PAIR>
+__device__ __forceinline__ bool fresh_probe_issue(const Lane& s, bool fresh, const DevIndexView& ix, ReadRef rr, SeekProbe& q) {
+    const bool live = fresh && l_st(s) == ST_SEEK && (PAIR || ix.k <= 32);
+    Lane t = s;
+    if (!live) l_zero(t);
+    if (PAIR) seek_issue_pair(t, ix, rr, q, 0, live);
+    else seek_issue(t, ix, rr, q, 0, live);
+    return live;
+}
+// ... and its answer: a hit sends the lane to FWD (or LEFT), anything else leaves it in ST_SEEK as seek_step_* would: it goes on from the SEEK queue
+template <bool PAIR>
+__device__ __forceinline__ void fresh_probe_settle(Lane& s, bool live, uint32_t K, const SeekProbe& q) {
+    if (!live) return;
+    if (PAIR) (void)seek_settle_pair(s, K, q, false);
+    else (void)seek_settle(s, K, q, false);
+}
+
 // a slot's lane state in LDS: two 16-byte vectors (and a third for the wide packing's own words)
 __device__ __forceinline__ void lane_load(Lane& s, lds_v4 stA, lds_v4 stB, lds_v4 stC, uint32_t slot) {
     const u32x4 a = stA[slot], b = stB[slot];
@@ -208,6 +231,9 @@ __global__ __launch_bounds__(PA_MAP_BLOCK, PA_MAP_MIN_BLOCKS) void pa_map_pool_k
         const DevIndexView ix = view_of(kp);
         const glb_u32 ec = (glb_u32)ix.ec;
         const uint32_t K = ix.k, allowed = p.allowed, spill_cap = p.spill_cap;
+        // first probes run in the step that refills the slot (PA_PROBE_AT_REFILL): the narrow packing with a one-word dictionary
+        // (a two-word index mapped by a 16-byte instantiation — TRACE and statistics builds — runs the text and probes with no lane)
+        constexpr bool par = PA_PROBE_AT_REFILL && !GREAD && !KBIG;
         if (next == end && more) {   // this wave's chunk is used up: take the next one
             // guided: half of an even share of what was left at this wave's previous grab, 2..16 tiles (the estimate is one
             // chunk old, so the sizes decay geometrically towards the end and the last chunks are ~128 reads)
@@ -246,6 +272,10 @@ __global__ __launch_bounds__(PA_MAP_BLOCK, PA_MAP_MIN_BLOCKS) void pa_map_pool_k
         constexpr uint32_t RARE = (1u << ST_LEFT) | (1u << ST_F_LIGHT) | (1u << ST_F_SCAN) | (1u << ST_F_COOP) | (1u << ST_F_MASK);
         const bool any_rare = __ballot((((RARE >> (st_lo & 31u)) | (RARE >> (st_hi & 31u))) & 1u) != 0) != 0;   // (0xFF, no slot: bit 31, not rare)
         const uint32_t n_bits_q = PA_CNT(ST_F_BITS), n_seek_q = PA_CNT(ST_SEEK), n_fwd_q = PA_CNT(ST_FWD);
+        // with the first probes gone from it (PA_PROBE_AT_REFILL) the SEEK queue holds second looks and restarts only: it competes like a rare
+        // state, a full wave from PA_SEEK_FULL slots on — the rule below would park up to PA_SEEK_MIN - 1 of them
+        const uint32_t seek_min = par && PA_SEEK_FULL ? PA_SEEK_FULL : PA_SEEK_MIN;
+        const uint32_t seek_w = par && PA_SEEK_FULL && n_seek_q >= PA_SEEK_FULL ? 64u + n_seek_q : n_seek_q;
         if (any_rare) {
             PA_CONSIDER_RARE_MIN(ST_F_COOP, PA_CNT(ST_F_COOP), PA_COOP_MIN)   // (the wave takes its reads one at a time: nothing to gain from gathering them)
             PA_CONSIDER_RARE(ST_F_SCAN, PA_CNT(ST_F_SCAN))
@@ -254,12 +284,12 @@ __global__ __launch_bounds__(PA_MAP_BLOCK, PA_MAP_MIN_BLOCKS) void pa_map_pool_k
             PA_CONSIDER(ST_F_BITS, n_bits_q)
             PA_CONSIDER(ST_FWD, n_fwd_q)
             PA_CONSIDER_RARE(ST_LEFT, PA_CNT(ST_LEFT))
-            PA_CONSIDER(ST_SEEK, n_seek_q)
+            if (best < 64 && seek_w > best) { best = seek_w; bestn = n_seek_q; sel = ST_SEEK; }
             PA_CONSIDER(ST_EMPTY, nrefill)
         } else {
             // the common iteration (no slot in a rare state): the same rule on four populations, as scalar min / max — the first of
             // output, forward, probe, refill that fills a wave, else the most populated (ties: the earlier one)
-            const uint32_t cb = min(n_bits_q, 64u), cf = min(n_fwd_q, 64u), cs = min(n_seek_q, 64u), ce = min(nrefill, 64u);
+            const uint32_t cb = min(n_bits_q, 64u), cf = min(n_fwd_q, 64u), cs = min(seek_w, 64u), ce = min(nrefill, 64u);
             best = max(max(cb, cf), max(cs, ce));
             sel = cb == best ? (uint32_t)ST_F_BITS : cf == best ? (uint32_t)ST_FWD : cs == best ? (uint32_t)ST_SEEK : (uint32_t)ST_EMPTY;
             bestn = cb == best ? n_bits_q : cf == best ? n_fwd_q : cs == best ? n_seek_q : nrefill;
@@ -273,10 +303,7 @@ __global__ __launch_bounds__(PA_MAP_BLOCK, PA_MAP_MIN_BLOCKS) void pa_map_pool_k
         // the probe's slot load and the node fetch go out back to back, and does the probe's arithmetic while the
         // node lines are on their way: two round trips in flight per wave instead of one (K <= 32 only: the two-word dictionary's
         // probe is a step of its own).
-#ifndef PA_SEEK_MIN   // probes ride with a forward step only from this many waiting slots on (or when little forward work is left): the probe half is
-#define PA_SEEK_MIN 32u   // the whole wave's instructions however few lanes it serves (same-box A/B of 1 / 32 / 48: config 3 -1.8 %, config 5 -3.8 % time at 32)
-#endif
-        const bool seek_ok = n_seek_q >= PA_SEEK_MIN || n_fwd_q < 24;
+        const bool seek_ok = n_seek_q >= seek_min || n_fwd_q < 24;
         const bool dual = (sel == ST_FWD || sel == ST_SEEK) && (K <= 32 || KBIG) && n_seek_q != 0 && n_fwd_q != 0 && seek_ok && !PA_ABLATE(4u);
         if (dual) sel = ST_FWD;
         uint32_t n_own = dual ? (n_fwd_q < 64 ? n_fwd_q : 64) : bestn < 64 ? bestn : 64;
@@ -325,6 +352,11 @@ __global__ __launch_bounds__(PA_MAP_BLOCK, PA_MAP_MIN_BLOCKS) void pa_map_pool_k
         if (sel == ST_EMPTY) {   // REFILL: free slots take the next reads of this wave's range (coalesced: lane = consecutive read)
             if (active) refill_slot<GREAD>(s, next + lane, slot, kp, rd, wc, S, wpr, K);
             next += n;
+            if (par) {   // ... and probe their first k-mers at once
+                SeekProbe pq;
+                const bool live = fresh_probe_issue<PAIR>(s, active, ix, rr, pq);
+                fresh_probe_settle<PAIR>(s, live, K, pq);
+            }
         } else if (sel == ST_SEEK) {
             if (active) {
                 if (PAIR) seek_step_pair(s, ix, rr);
@@ -435,6 +467,7 @@ __global__ __launch_bounds__(PA_MAP_BLOCK, PA_MAP_MIN_BLOCKS) void pa_map_pool_k
             }
             // ... and the slots that just became free take the wave's next reads in the same step (the tile loads are in
             // flight together with the result stores: one wait instead of an output step and a refill step)
+            bool fresh = false;
             {
                 const uint64_t freed = __ballot(active && s.lk == 0);
                 const uint32_t nfree = (uint32_t)__popcll(freed);
@@ -444,12 +477,18 @@ __global__ __launch_bounds__(PA_MAP_BLOCK, PA_MAP_MIN_BLOCKS) void pa_map_pool_k
                 // config 5 +2 % time. Not the default.)
                 if (PA_REFILL_ALIGN > 1 && take >= PA_REFILL_ALIGN && (uint64_t)take < left) take &= ~(PA_REFILL_ALIGN - 1u);
                 if (take && !PA_ABLATE(8u)) {
-                    if (active && s.lk == 0 && rank_in(freed) < take) refill_slot<GREAD>(s, next + rank_in(freed), slot, kp, rd, wc, S, wpr, K);
+                    fresh = active && s.lk == 0 && rank_in(freed) < take;
+                    if (fresh) refill_slot<GREAD>(s, next + rank_in(freed), slot, kp, rd, wc, S, wpr, K);
                     next += take;
                 }
             }
+            // the fresh reads' first probes: the dictionary lines are on their way while the keys and the deferred entries are appended
+            SeekProbe pq;
+            bool live = false;
+            if (par) live = fresh_probe_issue<PAIR>(s, fresh, ix, rr, pq);
             if (counting && !PA_ABLATE(2u)) append_keys(ckey, lane, kp, kchunk);
             append_deferred(dfr, d0, d1, lane, kp, dchunk);
+            if (par) fresh_probe_settle<PAIR>(s, live, K, pq);
             PA_MARK("bits_end");
         } else if (sel == ST_F_MASK) {
             // Window mode, classes without windows pending (lane_steps.hpp, mask_pending): ONE PENDING CLASS PER LANE. The
