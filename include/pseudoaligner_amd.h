@@ -264,10 +264,17 @@ uint64_t pa_map_arena_hint(const pa_index* idx, uint64_t n_reads);
  *   neither bit: the class is empty (or the read unmapped); both bits: the ids did not fit the launch's arena (pa_map_finish said so)
  * made from a launch's records and arena on the device: d_compact[n_reads] u64, d_packed[packed_cap] u32, *d_packed_words (device u64) =
  * words the packed stream needs (entries that would end beyond packed_cap are not written). d_scratch: pa_compact_scratch_bytes(n_reads)
- * bytes. Asynchronous on `stream`, behind the launch that wrote d_results. */
+ * bytes. Asynchronous on `stream`, behind the launch that wrote d_results. It cannot fail per record: direct callers must not feed it
+ * results of reads longer than PA_COMPACT_MAX_READ_LEN bases — beyond that length the two 14-bit fields hold the low 14 bits of
+ * coverage and mismatches. */
 #define PA_COMPACT_MAPPED 0x10000000u
 #define PA_COMPACT_BY_REF 0x20000000u
 #define PA_COMPACT_PACKED 0x40000000u
+#define PA_COMPACT_MAX_READ_LEN 16383u   /* compact records carry coverage and mismatches in 14 bits each: they are exact only for reads of at most this many
+                                          * bases. Bounding the length bounds both fields: every unit of coverage and every counted mismatch of
+                                          * map_read_to_nodes_with_mismatch (src/pseudoaligner.rs:64-319) belongs to a read base of its own — the left extension
+                                          * compares bases in front of the first matching k-mer, the forward search only bases behind it, each once — so neither
+                                          * exceeds the read's length, whatever allowed_mismatches is. pa_map_tiles_host refuses longer reads. */
 size_t pa_compact_scratch_bytes(uint64_t n_reads);
 int pa_results_compact_device(pa_index* idx, const pa_read_result* d_results, const uint32_t* d_arena, uint64_t arena_cap, uint64_t n_reads,
                               uint64_t* d_compact, uint32_t* d_packed, uint64_t packed_cap, uint64_t* d_packed_words, void* d_scratch,
@@ -279,7 +286,9 @@ int pa_results_compact_device(pa_index* idx, const pa_read_result* d_results, co
  * kernels of chunk i and the copy of chunk i - 1's outputs back overlap. h_lens NULL: every read has uniform_len bases (no length array
  * crosses the link). Outputs in read order: h_compact[n_reads] (the 8-byte records above), h_packed[*packed_words] (their packed classes;
  * PA_ERR_ARENA_FULL when packed_cap is too small), h_counts[pa_counts_len(idx)] (the class-count table of the batch, overwritten; may
- * be NULL). Synchronous: everything has arrived when the call returns. Streams and staging buffers stay parked on the handle. */
+ * be NULL). Synchronous: everything has arrived when the call returns. Streams and staging buffers stay parked on the handle. A read
+ * longer than PA_COMPACT_MAX_READ_LEN bases (uniform_len, or any h_lens[i]) does not fit the compact records: PA_ERR_INVALID_ARG, before
+ * anything is copied or launched. */
 int pa_map_tiles_host(pa_index* idx, const uint64_t* h_tiles, const uint32_t* h_lens, uint32_t uniform_len, uint64_t n_reads,
                       uint32_t words_per_read, uint32_t allowed_mismatches, uint64_t* h_compact, uint32_t* h_packed, uint64_t packed_cap,
                       uint64_t* packed_words, uint64_t* h_counts, uint64_t chunk_reads, int n_streams);

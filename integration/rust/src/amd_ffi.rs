@@ -15,6 +15,7 @@ pub const PA_MAX_ARENA_ENTRIES: u64 = 0x7FFF_FFFF;
 pub const PA_COMPACT_MAPPED: u32 = 0x1000_0000;     // pa_results_compact_device: bit 28 of a record's low word
 pub const PA_COMPACT_BY_REF: u32 = 0x2000_0000;     // the class is index class (record >> 32)
 pub const PA_COMPACT_PACKED: u32 = 0x4000_0000;     // the class is the next {length, ids...} entry of the packed stream
+pub const PA_COMPACT_MAX_READ_LEN: u32 = 16383;     // coverage and mismatches take 14 bits each: longer reads are refused by pa_map_tiles_host
 
 #[repr(C)]
 pub struct PaFlatIndex {            // pa_flat_index

@@ -420,7 +420,8 @@ class Pseudoaligner:
     def map_tiles_host(self, h_tiles: int, n_reads: int, words_per_read: int, h_compact: int, h_packed: int, packed_cap: int, h_lens: int = 0, uniform_len: int = 0,
                        h_counts: int = 0, allowed_mismatches: int = PA_DEFAULT_ALLOWED_MISMATCHES, chunk_reads: int = 0, n_streams: int = 0) -> int:
         """pa_map_tiles_host: a batch in (pinned) host memory -> compact records + packed classes (+ count table) on the host, chunks pipelined
-        over several streams; returns the words of the packed stream. Raw host pointers."""
+        over several streams; returns the words of the packed stream. Raw host pointers. Reads longer than PA_COMPACT_MAX_READ_LEN bases do not fit
+        the compact records: PaError (PA_ERR_INVALID_ARG) before anything is copied."""
         pw = C.c_uint64()
         check(lib().pa_map_tiles_host(self._h, h_tiles, h_lens or None, uniform_len, n_reads, words_per_read, allowed_mismatches, h_compact, h_packed or None, packed_cap,
                                       C.byref(pw), h_counts or None, chunk_reads, n_streams))
@@ -1517,6 +1518,7 @@ def pairs_gather_device(text1, rec1, text2, rec2, prefix: int, base: int, bytes1
 
 
 PA_COMPACT_MAPPED, PA_COMPACT_BY_REF, PA_COMPACT_PACKED = 0x10000000, 0x20000000, 0x40000000
+PA_COMPACT_MAX_READ_LEN = 16383   # coverage and mismatches take 14 bits each: map_tiles_host refuses longer reads (PA_ERR_INVALID_ARG)
 
 
 def unpack_compact(compact: np.ndarray, packed: np.ndarray, index: "HostIndex") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:

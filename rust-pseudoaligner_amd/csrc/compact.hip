@@ -39,6 +39,7 @@ __global__ __launch_bounds__(256) void pa_compact_write_kernel(const pa_read_res
     if (i >= n) return;
     const pa_read_result r = results[i];
     const bool mapped = r.mismatches & PA_MAPPED_BIT;
+    // (14 bits each: exact for reads of at most PA_COMPACT_MAX_READ_LEN bases, which is what pa_map_tiles_host lets through)
     uint32_t lo = (r.coverage & 0x3FFFu) | ((r.mismatches & 0x3FFFu) << 14) | (mapped ? PA_COMPACT_MAPPED : 0u), hi = 0;
     if (mapped && r.class_len != 0) {
         if (r.class_off & PA_CLASS_REF) { lo |= PA_COMPACT_BY_REF; hi = r.class_off & ~PA_CLASS_REF; }

@@ -167,6 +167,14 @@ extern "C" int pa_map_tiles_host(pa_index* idx, const uint64_t* h_tiles, const u
                                  uint64_t chunk_reads, int n_streams) {
     if (!idx || (n_reads && (!h_tiles || !h_compact)) || (packed_cap && !h_packed) || words_per_read == 0) return fail(PA_ERR_INVALID_ARG, "null argument");
     if (!h_lens && (uniform_len == 0 || uniform_len > PA_MAX_READ_LEN || uniform_len > 32ull * words_per_read)) return fail(PA_ERR_INVALID_ARG, "no length array and no usable uniform length");
+    // The compact records hold coverage and mismatches in 14 bits each (PA_COMPACT_MAX_READ_LEN): a longer read would come back wrapped and PA_OK. The length
+    // array is walked only when its tiles have room for such a read at all: not at the 4 - 5 words per read of sequencer batches.
+    if (!h_lens && uniform_len > PA_COMPACT_MAX_READ_LEN)
+        return fail(PA_ERR_INVALID_ARG, "uniform_len %u: the compact records hold reads of at most %u bases", uniform_len, PA_COMPACT_MAX_READ_LEN);
+    if (h_lens && 32ull * words_per_read > PA_COMPACT_MAX_READ_LEN)
+        for (uint64_t i = 0; i < n_reads; ++i)
+            if (h_lens[i] > PA_COMPACT_MAX_READ_LEN)
+                return fail(PA_ERR_INVALID_ARG, "read %llu has %u bases: the compact records hold reads of at most %u bases", (unsigned long long)i, h_lens[i], PA_COMPACT_MAX_READ_LEN);
     if (packed_words) *packed_words = 0;
     if (chunk_reads == 0) chunk_reads = 1000000;   // (1 M reads x 4 streams 71.8 - 73.3 ms per 100 M reads; 2 M 73.9 - 74.7; 4 M 72.3 - 76; 3 or 8 streams slower)
     chunk_reads = std::max<uint64_t>(64, std::min<uint64_t>(chunk_reads, std::max<uint64_t>(n_reads, 64)) / 64 * 64);
