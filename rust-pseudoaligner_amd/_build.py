@@ -110,6 +110,28 @@ def build_pairknobs_variant(force: bool = False) -> Path:
     return PAIRKNOBS_SO
 
 
+DICTKNOBS_SO = OBJ_DIR / "libpseudoaligner_amd_dictknobs.so"
+
+
+def build_dictknobs_variant(force: bool = False) -> Path:
+    """A TEST build of the product: device_flatten.cpp AND index_fill.hip compiled with -DPA_DEBUG_KNOBS, everything else the product's own objects.
+    The CPU flattener and the GPU filler then read PA_DICT_LOAD, the load the 16-byte slots (K <= 32; K <= 24 too: a named load refuses the pair
+    format) and the two-word lines (K > 32) are built at, so that a test can have DENSE tables: keys in named slots, chains of several buckets, the
+    builders' retry (tests/test_dict_model.py and tests/test_gpu_dict_dense.py load it in child processes through PA_PRODUCT_SO)."""
+    build_product()
+    hipcc = hipcc_path()
+    knob_objs = []
+    for name in ("device_flatten.cpp", "index_fill.hip"):
+        src, obj = CSRC / name, OBJ_DIR / (name.rsplit(".", 1)[0] + ".dictknobs.o")
+        if force or _stale(obj, _deps_of(src)):
+            _run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread", "-Wall", "-Wno-unused-function", "-DPA_DEBUG_KNOBS", "-x", "hip", "-c", str(src), "-o", str(obj)])
+        knob_objs.append(obj)
+    objs = [OBJ_DIR / (s + ".o") for s in HOST_SOURCES + HIP_SOURCES if s not in ("device_flatten.cpp", "index_fill.hip")] + knob_objs
+    if force or _stale(DICTKNOBS_SO, objs):
+        _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-pthread"] + [str(o) for o in objs] + ["-ldl", "-lz", "-o", str(DICTKNOBS_SO)])
+    return DICTKNOBS_SO
+
+
 UMIHBM_SO = OBJ_DIR / "libpseudoaligner_amd_umihbm.so"
 
 
