@@ -27,8 +27,10 @@ using namespace pa;
 //   keys[cap]   u64  0 = free, else the content hash of the id list with bit 63 forced
 //   meta[cap]   {u32 pool_off, u32 len, u64 count, u32 ready, u32 pad} (24 bytes as 6 u32)
 //   pool[pool_cap] u32 the id lists, ctl[0] = pool top, ctl[1] = status, ctl[2] = export cursor, ctl[3] = entries
-// Two lanes that insert the same new class at the same moment may both create an entry (a reader can see the other's ids
-// late); entries are merged by content at export time, so the exported table is exact either way.
+// A slot is claimed by one CAS and published behind its ready flag; a lane that meets its own key waits for the flag and then
+// compares the ids, so one content has ONE entry however many lanes bring it at once and the pool holds every list once (max_ids
+// = the sum of the distinct lists' lengths suffices exactly; tests/test_gpu_overflow_edges.py). Only behind a full pool can a
+// content get a second (equally id-less) entry; that table is reported, never exported. The host still merges by content.
 struct pa_overflow {
     int device = 0;
     uint64_t cap = 0, pool_cap = 0;

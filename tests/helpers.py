@@ -1,5 +1,5 @@
 """Test-side plumbing: loads the product package, and wraps the two CHECKERS (oracle/ C restatement, tests/emu lane
-emulator) and the probes of csrc/device_prims.hpp (tests/prims) and of the text kernels (tests/text) with ctypes. Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg use this module."""
+emulator) and the probes of csrc/device_prims.hpp (tests/prims), of the text kernels (tests/text) and of the overflow table (tests/overflow) with ctypes. Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg use this module."""
 from __future__ import annotations
 
 import ctypes as C
@@ -30,12 +30,13 @@ _oracle_build = _load_recipe(ROOT / "oracle" / "build.py", "pa_oracle_build")
 _emu_build = _load_recipe(ROOT / "tests" / "emu" / "build.py", "pa_emu_build")
 _prims_build = _load_recipe(ROOT / "tests" / "prims" / "build.py", "pa_prims_build")
 _text_build = _load_recipe(ROOT / "tests" / "text" / "build.py", "pa_text_build")
+_overflow_build = _load_recipe(ROOT / "tests" / "overflow" / "build.py", "pa_overflow_build")
 
 
 def build_all(force: bool = False):
-    """product (hipcc, gfx950) + the two checkers (gcc / g++) + the device_prims probe and the text probe (hipcc, gfx950)"""
+    """product (hipcc, gfx950) + the two checkers (gcc / g++) + the device_prims probe, the text probe and the overflow probe (hipcc, gfx950)"""
     return (_build.build_product(force), _oracle_build.build_oracle(force), _emu_build.build_emu(force), _prims_build.build_probe(force),
-            _text_build.build_probe(force))
+            _text_build.build_probe(force), _overflow_build.build_probe(force))
 
 GOLDEN = ROOT / "tests" / "golden"
 FASTA = GOLDEN / "gencode_small.fa"
@@ -57,6 +58,7 @@ _oracle_lib = None
 _emu_lib = None
 _prims_lib = None
 _text_lib = None
+_overflow_lib = None
 
 
 def oracle_lib():
@@ -157,6 +159,38 @@ def text_lib():
         L.tp_host_scan.argtypes = [C.c_char_p, C.c_int, vp, vp, vp, vp, vp, u64]
         _text_lib = L
     return _text_lib
+
+
+def overflow_lib():
+    """tests/overflow/overflow_probe.hip: csrc/collective.hip itself (the table's kernels, pa_overflow_*, pa_comm_*) plus the probe's own
+    entries: insert as a map launch does, dump, poke a count, set a status bit, the device's list hash.
+    PA_OVERFLOW_PROBE_SO: another build of the probe to load (a mutated one, when the tests themselves are tested)."""
+    global _overflow_lib
+    if _overflow_lib is None:
+        import os
+        pa.lib()   # the host runtime the probe is linked against
+        L = C.CDLL(os.environ.get("PA_OVERFLOW_PROBE_SO") or str(_overflow_build.build_probe()))
+        vp, u64 = C.c_void_p, C.c_uint64
+        u64p = C.POINTER(u64)
+        for name in ("pa_overflow_create", "pa_overflow_reset", "pa_overflow_fetch", "pa_overflow_allgather", "pa_comm_unique_id", "pa_comm_create"):
+            getattr(L, name).restype = C.c_int
+        L.pa_overflow_create.argtypes = [C.c_int, u64, u64, C.POINTER(vp)]
+        L.pa_overflow_destroy.restype = L.pa_comm_destroy.restype = None
+        L.pa_overflow_destroy.argtypes = L.pa_comm_destroy.argtypes = [vp]
+        L.pa_overflow_reset.argtypes = [vp, vp]
+        L.pa_overflow_fetch.argtypes = [vp, vp, C.POINTER(vp), u64p]
+        L.pa_overflow_allgather.argtypes = [vp, vp, vp, C.POINTER(vp), u64p]
+        L.pa_comm_unique_id.argtypes = [vp]
+        L.pa_comm_create.argtypes = [C.c_int, C.c_int, C.c_int, vp, C.POINTER(vp)]
+        L.ovp_stream_new.argtypes = [C.POINTER(vp)]
+        L.ovp_stream_free.argtypes = [vp]
+        L.ovp_insert.argtypes = [vp, vp, u64, vp, u64, u64, u64, vp]
+        L.ovp_dump.argtypes = [vp, u64p, u64p, vp, vp, vp]
+        L.ovp_poke_count.argtypes = [vp, u64, u64]
+        L.ovp_or_status.argtypes = [vp, u64, vp]
+        L.ovp_hash.argtypes = [vp, u64, vp, u64, vp, vp]
+        _overflow_lib = L
+    return _overflow_lib
 
 
 def pack_read(seq: str) -> np.ndarray:
