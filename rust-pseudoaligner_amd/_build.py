@@ -12,7 +12,7 @@ CSRC = PKG / "csrc"
 
 PRODUCT_SO = PKG / "libpseudoaligner_amd.so"
 
-HOST_SOURCES = ["host_index.cpp", "dbg_build.cpp", "device_flatten.cpp", "synth.cpp", "fastq_text.cpp", "fastq_reads.cpp", "pair_reader.cpp", "fastq_cells.cpp", "fastq_pairs.cpp", "record_stream.cpp", "host_batch.cpp", "bgzf.cpp", "bus_host.cpp", "bus_correct_host.cpp", "bus_knee_host.cpp", "genes_host.cpp", "bus_umi_host.cpp", "window_feed.cpp", "text_window.cpp"]
+HOST_SOURCES = ["host_index.cpp", "dbg_build.cpp", "device_flatten.cpp", "synth.cpp", "fastq_text.cpp", "fastq_reads.cpp", "pair_reader.cpp", "fastq_cells.cpp", "fastq_pairs.cpp", "record_stream.cpp", "host_batch.cpp", "bgzf.cpp", "bus_host.cpp", "bus_correct_host.cpp", "bus_knee_host.cpp", "genes_host.cpp", "bus_umi_host.cpp", "window_feed.cpp", "text_window.cpp", "pairs_host.cpp"]
 HIP_SOURCES = ["kernels.hip", "map_pool.hip", "device_index.hip", "map_batch.hip", "device_plumbing.hip", "collective.hip", "barcode_counts.hip", "index_build.hip", "index_fill.hip", "count_sort.hip", "resolve.hip", "render.hip", "fastq_scan.hip", "compact.hip", "quant.hip", "quant_boot.hip", "pairs.hip", "strands.hip", "inflate.hip", "bus.hip", "pair_scan.hip", "genes.hip", "bus_correct.hip", "bus_knee.hip", "bus_umi.hip"]
 
 

@@ -3,7 +3,7 @@
 // again") is written; and the "collapse" of sorted items into their runs (collapse_runs and its two kernels), which index_build.hip's
 // own pa_ib_heads_kernel (64-bit counts, other outputs) does not use. Host side; included by .hip sources only: barcode_counts.hip,
 // bus.hip, bus_correct.hip, bus_knee.hip, bus_umi.hip, compact.hip, fastq_scan.hip, genes.hip (both through molecule_stage.hpp too), index_build.hip,
-// pair_scan.hip, pairs.hip (through pair_stage.hpp too), quant.hip, quant_boot.hip, render.hip.
+// pair_scan.hip, pairs.hip and strands.hip (through pair_stage.hpp), quant.hip, quant_boot.hip, render.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -150,7 +150,7 @@ int overflow_after_map(pa_overflow* o, const uint32_t* novel_list, const unsigne
                        hipStream_t stream);
 int overflow_device(const pa_overflow* o);
 
-// what the pair stage (pairs.hip) needs of an index handle (device_index.hip), beside index_host_classes
+// what the pair and strand stages (pair_stage.hpp) and the host-buffer paths over them (pairs_host.cpp) need of an index handle (device_index.hip), beside index_host_classes
 struct PairIndexView {
     DevIndexView dv;
     const uint32_t* class_table;

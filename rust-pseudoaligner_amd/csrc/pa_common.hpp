@@ -27,6 +27,8 @@ void classes_to_csr(const pa_index* idx, pa_read_result* results, uint64_t n, co
 void index_host_class_text(pa_index* idx, const uint64_t** off, const char** text);
 // ... and its copy in HBM for the render kernels (render.hip); uploaded on first use. Returns a pa_status
 int index_device_class_text(pa_index* idx, const uint64_t** d_off, const uint8_t** d_text);
+// the most pairs or items in one launch of the pair and strand stages (pair_stage.hpp) and in one call of the host-buffer paths over them (pairs_host.cpp)
+constexpr uint64_t PAIR_MAX_PAIRS = 0x7FFFFFF0ull;   // pair and item indices, and 2 n + 1 flags, are 32-bit
 // pairs.hip: an upper bound on the arena entries pa_pairs_combine_device can need for these mate records (the shorter list of every pair with two
 // mapped mates, the list of a mate mapped alone), summed on the device into the first 8 bytes of d_scratch; synchronises `stream`
 int pairs_arena_bound(pa_index* idx, const pa_read_result* d_res1, const pa_read_result* d_res2, uint64_t n_pairs, void* d_scratch, void* stream, uint64_t* bound);

@@ -1,4 +1,4 @@
-"""The model of the paired-end stage, written from the rules in include/pseudoaligner_amd.h ("paired-end reads"), not from csrc/pairs.hip:
+"""The model of the paired-end stage, written from the rules in include/pseudoaligner_amd.h ("paired-end reads"), not from the stage (the rule of csrc/pairs.hip over the skeleton of csrc/pair_stage.hpp):
 
   * reverse complement on packed 2-bit codes (numpy);
   * the pair rule over two mates' results — from the oracle (an id list, coverage, mismatches or None per mate) or from device-format

@@ -1,4 +1,4 @@
-"""The model of the unstranded stage, written from the rule in include/pseudoaligner_amd.h ("unstranded libraries"), not from csrc/strands.hip:
+"""The model of the unstranded stage, written from the rule in include/pseudoaligner_amd.h ("unstranded libraries"), not from the stage (the rule of csrc/strands.hip over the skeleton of csrc/pair_stage.hpp):
 
   * the merge rule over two candidates of an item (pairs_model mates: None | (sorted id list, coverage, mismatches));
   * its stats vector and the two identities;

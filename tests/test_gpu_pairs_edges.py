@@ -1,4 +1,4 @@
-"""The paired-end stage (csrc/pairs.hip) at its edges, with no aligner in the loop: the tests write the mates' records and arenas by hand, so
+"""The paired-end stage (csrc/pairs.hip over csrc/pair_stage.hpp) at its edges, with no aligner in the loop: the tests write the mates' records and arenas by hand, so
 every row of the pair rule, every list shape and both kernels' boundaries are chosen exactly. Everything is compared with the model
 (tests/pairs_model.py) by CONTENT (which of reference / arena a result takes is the implementation's): all integers, equality."""
 import numpy as np

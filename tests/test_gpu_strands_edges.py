@@ -1,4 +1,4 @@
-"""The unstranded stage (csrc/strands.hip) at its edges, with no aligner in the loop: the tests write the two candidates' records and arenas by
+"""The unstranded stage (csrc/strands.hip over csrc/pair_stage.hpp) at its edges, with no aligner in the loop: the tests write the two candidates' records and arenas by
 hand (the Mates helper and the small indexes of tests/test_gpu_pairs_edges.py), so every row of the rule, every list shape and both kernels'
 boundaries are chosen exactly. Everything is compared with the model (tests/strands_model.py) by CONTENT (which of reference / arena a
 result takes is the implementation's): all integers, equality."""
@@ -231,6 +231,21 @@ def test_small_batches(n):
     s.rec, s.arena, r.rec, r.arena = S.rec[lo:lo + n], S.arena, R.rec[lo:lo + n], R.arena
     want, res, arena, st, used, need = _check("synth", s, r)
     assert n == 0 or want[4][0] == "tie"
+
+
+def test_more_long_ties_than_the_grid_has_waves():
+    """a wave goes round its item loop a second time: the ids common to both lists, and those counted in the chunks done, start from zero for every item"""
+    host, al, a, T = _setup("synth")
+    n = 5000                                   # the wave kernel's grid is at most 4 blocks of 4 waves per CU: 4 096 waves on 256 CUs
+    rng = np.random.default_rng(9)
+    S, R = Mates(a), Mates(a)
+    for i in range(n):                         # two runs with an overlap that varies in size and in shape (every id, every other id)
+        base = int(rng.integers(0, T - 64))
+        S.ids(range(base, base + 24 + i % 5))
+        R.ids(range(base + 10 + i % 7, base + 50 + i % 3, 1 + i % 2))
+    want, res, arena, st, used, need = _check("synth", S, R)
+    assert want[4].count("tie") == n and (res["class_len"] > 32).all()    # every union is a wave's, whatever the cut at or below 32
+    assert st["ties"] == n and st["in_arena"] + st["by_reference"] == n
 
 
 def test_arena_full_and_rerun():

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Timing of the paired-end stage (csrc/pairs.hip) on device-resident pairs, and of pa_count_pairs from files in the page cache.
+"""Timing of the paired-end stage (csrc/pair_stage.hpp with the rule of csrc/pairs.hip) on device-resident pairs, and of pa_count_pairs from files in the page cache.
 
   python tools/bench_pairs.py [--pairs 10000000] [--index config3|17k] [--orient fr|un] [--out profiles/r10_pairs_bench.json]
 
@@ -9,7 +9,7 @@ the reverse complement of mate 2, the two map launches, combine without the tabl
 the stats vector; the ratio combine / map and the bytes the combine stage must move (32 bytes of records in and 16 out per pair plus the ids
 of the non-trivial pairs, counted on the host from the mates' records); and count_pairs pairs/s with its stage seconds. None is a gate.
 
---orient un: the same pairs as an UNSTRANDED library (the mates of every odd pair swapped) through the unstranded stage (csrc/strands.hip): the four
+--orient un: the same pairs as an UNSTRANDED library (the mates of every odd pair swapped) through the unstranded stage (the same skeleton with the rule of csrc/strands.hip): the four
 map launches, the two uncounted combines, the merge without the table and with the table and an overflow table attached, the merge against the
 two combines and against the four maps it follows, the merge's stats vector, and count_pairs pairs/s for "un" beside "fr" on the same files
 (default --out profiles/r13_strands_bench.json)."""
