@@ -132,6 +132,26 @@ def build_dictknobs_variant(force: bool = False) -> Path:
     return DICTKNOBS_SO
 
 
+IBKNOBS_SO = OBJ_DIR / "libpseudoaligner_amd_ibknobs.so"
+
+
+def build_ibknobs_variant(force: bool = False) -> Path:
+    """A TEST build of the product: index_build.hip compiled with -DPA_DEBUG_KNOBS, everything else the product's own objects. The GPU index builder
+    then reads PA_IB_WEAK_ATTEMPTS = n: on its first n attempts the colour stage keeps two bits of every addend of the set hash, so that different id
+    lists share a hash, the content check fails and the stage runs again with another seed — four times, then the build fails
+    (tests/test_gpu_index_edges.py loads it in a child process through PA_PRODUCT_SO)."""
+    build_product()
+    hipcc = hipcc_path()
+    src = CSRC / "index_build.hip"
+    obj = OBJ_DIR / "index_build.ibknobs.o"
+    if force or _stale(obj, _deps_of(src)):
+        _run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread", "-Wall", "-Wno-unused-function", "-DPA_DEBUG_KNOBS", "-x", "hip", "-c", str(src), "-o", str(obj)])
+    objs = [OBJ_DIR / (s + ".o") for s in HOST_SOURCES + HIP_SOURCES if s != "index_build.hip"] + [obj]
+    if force or _stale(IBKNOBS_SO, objs):
+        _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-pthread"] + [str(o) for o in objs] + ["-ldl", "-lz", "-o", str(IBKNOBS_SO)])
+    return IBKNOBS_SO
+
+
 UMIHBM_SO = OBJ_DIR / "libpseudoaligner_amd_umihbm.so"
 
 

@@ -91,8 +91,11 @@ __global__ __launch_bounds__(256) void pa_ib_heads_kernel(const KT* __restrict__
 }
 
 // seg[i] = 1-based index of record i's distinct k-mer. CountFilterEqClass::summarize (src/equiv_classes.rs:62-91): colour =
-// sorted dedup'd transcript list, extensions = union
-template <class KT>
+// sorted dedup'd transcript list, extensions = union.
+// WEAK (test builds only, -DPA_DEBUG_KNOBS: tests/test_gpu_index_edges.py) keeps PA_IB_WEAK_MASK of every addend of the set hash, so that
+// different id lists share a hash and the stage has to run again; the shipped library instantiates WEAK = false alone
+constexpr unsigned long long PA_IB_WEAK_MASK = 3;
+template <class KT, bool WEAK>
 __global__ __launch_bounds__(256) void pa_ib_segment_kernel(const KT* __restrict__ keys, const uint32_t* __restrict__ vals, const uint32_t* __restrict__ seg,
                                                             uint64_t n, uint64_t seed, KT* __restrict__ dkmer, uint32_t* __restrict__ dfirst,
                                                             uint32_t* __restrict__ dexts, uint32_t* __restrict__ dcnt,
@@ -106,9 +109,13 @@ __global__ __launch_bounds__(256) void pa_ib_segment_kernel(const KT* __restrict
     if (dexts) atomicOr(dexts + d, v & 0xFFu);
     if (head || (vals[i - 1] >> 8) != (v >> 8)) {
         if (dcnt) atomicAdd(dcnt + d, 1u);
-        atomicAdd(dhash + d, (unsigned long long)pa_mix64((uint64_t)(v >> 8) + seed));
+        const unsigned long long addend = pa_mix64((uint64_t)(v >> 8) + seed);
+        atomicAdd(dhash + d, WEAK ? addend & PA_IB_WEAK_MASK : addend);
     }
 }
+#ifdef PA_DEBUG_KNOBS   // attempts of the colour stage that run with the weak hash (the shipped library reads no such variable)
+static int weak_attempts() { return knob_int("PA_IB_WEAK_ATTEMPTS", 0); }
+#endif
 
 // ---- 4. colours ----
 __global__ __launch_bounds__(256) void pa_ib_iota_kernel(uint32_t* out, uint64_t n) {
@@ -403,7 +410,11 @@ int build_graph_device_t(const uint64_t* packed_in, const uint64_t* tx_start, ui
     uint64_t seed = 0x243f6a8885a308d3ull;
     for (int attempt = 0;; ++attempt) {
         PA_HIP_TRY(hipMemset(dhash.get(), 0, (size_t)D * 8));
-        hipLaunchKernelGGL(pa_ib_segment_kernel<KT>, dim3(grid_for(N)), dim3(256), 0, s, keys.get(), vals.get(), seg.get(), N, seed, dkmer.get(), dfirst.get(),
+        auto segment = pa_ib_segment_kernel<KT, false>;
+#ifdef PA_DEBUG_KNOBS
+        if (attempt < weak_attempts()) segment = pa_ib_segment_kernel<KT, true>;
+#endif
+        hipLaunchKernelGGL(segment, dim3(grid_for(N)), dim3(256), 0, s, keys.get(), vals.get(), seg.get(), N, seed, dkmer.get(), dfirst.get(),
                            attempt == 0 ? dexts.get() : nullptr, attempt == 0 ? dcnt.get() : nullptr, dhash.get());
         PA_HIP_TRY(hipGetLastError());
         DeviceBuffer<unsigned long long> hs;
