@@ -1,5 +1,5 @@
 """Test-side plumbing: loads the product package, and wraps the two CHECKERS (oracle/ C restatement, tests/emu lane
-emulator) and the probes of csrc/device_prims.hpp (tests/prims), of the text kernels (tests/text) and of the overflow table (tests/overflow) with ctypes. Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg use this module."""
+emulator) and the probes of csrc/device_prims.hpp (tests/prims), of the text kernels (tests/text) of the overflow table (tests/overflow) and of the resolve kernel (tests/resolve) with ctypes. Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg use this module."""
 from __future__ import annotations
 
 import ctypes as C
@@ -31,12 +31,13 @@ _emu_build = _load_recipe(ROOT / "tests" / "emu" / "build.py", "pa_emu_build")
 _prims_build = _load_recipe(ROOT / "tests" / "prims" / "build.py", "pa_prims_build")
 _text_build = _load_recipe(ROOT / "tests" / "text" / "build.py", "pa_text_build")
 _overflow_build = _load_recipe(ROOT / "tests" / "overflow" / "build.py", "pa_overflow_build")
+_resolve_build = _load_recipe(ROOT / "tests" / "resolve" / "build.py", "pa_resolve_build")
 
 
 def build_all(force: bool = False):
-    """product (hipcc, gfx950) + the two checkers (gcc / g++) + the device_prims probe, the text probe and the overflow probe (hipcc, gfx950)"""
+    """product (hipcc, gfx950) + the two checkers (gcc / g++) + the device_prims probe, the text probe, the overflow probe and the resolve probe (hipcc, gfx950)"""
     return (_build.build_product(force), _oracle_build.build_oracle(force), _emu_build.build_emu(force), _prims_build.build_probe(force),
-            _text_build.build_probe(force), _overflow_build.build_probe(force))
+            _text_build.build_probe(force), _overflow_build.build_probe(force), _resolve_build.build_probe(force))
 
 GOLDEN = ROOT / "tests" / "golden"
 FASTA = GOLDEN / "gencode_small.fa"
@@ -59,6 +60,7 @@ _emu_lib = None
 _prims_lib = None
 _text_lib = None
 _overflow_lib = None
+_resolve_lib = None
 
 
 def oracle_lib():
@@ -191,6 +193,24 @@ def overflow_lib():
         L.ovp_hash.argtypes = [vp, u64, vp, u64, vp, vp]
         _overflow_lib = L
     return _overflow_lib
+
+
+def resolve_lib():
+    """tests/resolve/resolve_probe.hip: csrc/resolve.hip itself (pa_resolve_kernel, launch_resolve) behind rsp_resolve — one validated launch on
+    host arrays, every output pre-filled and guarded — and rsp_tables, the read-back of the index's window table and class-list table.
+    PA_RESOLVE_PROBE_SO: another build of the probe to load (a mutated one, when the tests themselves are tested)."""
+    global _resolve_lib
+    if _resolve_lib is None:
+        import os
+        pa.lib()   # the host runtime the probe is linked against
+        L = C.CDLL(os.environ.get("PA_RESOLVE_PROBE_SO") or str(_resolve_build.build_probe()))
+        vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
+        L.rsp_fill.restype = L.rsp_arena_chunk.restype = u32
+        L.rsp_fill64.restype = L.rsp_guard.restype = u64
+        L.rsp_tables.argtypes = [vp, C.POINTER(u32), C.POINTER(u64), C.POINTER(u32), C.POINTER(C.c_int), vp, vp]
+        L.rsp_resolve.argtypes = [vp, vp, u64, u64, u64, vp, u64, u64, u64, u64, u64, u64, u64, u64, C.c_int, u32, u64, vp, vp, vp, vp, vp, vp, vp]
+        _resolve_lib = L
+    return _resolve_lib
 
 
 def pack_read(seq: str) -> np.ndarray:
